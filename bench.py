@@ -12,6 +12,10 @@ BASELINE config 4); the only collective is the scalar chi^2 all-reduce (RCCL).
 
     python bench.py --gpus N --steps K --warmup W
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds the secondary figures, each a run
+of its own after the timed region: the CPU oracle baseline, the reference-side Fortran wrapper, the template model and
+the full-sky / coarse index modes.  --dump-outputs DIR writes what the last timed step computed as DIR/*.npy.
 """
 import argparse
 import json
@@ -335,6 +339,50 @@ def index_mode_figures(config_name, nsample, steps=4, warmup=2):
     return out
 
 
+DUMP_BUDGET_BYTES = 48 << 20   # what --dump-outputs writes in all stays below 64 MB
+DUMP_SEED = 20240601
+
+
+def dump_outputs(outdir, comps, chisq, lo, hi, pix0, world, backend, dev):
+    """What a caller of the timed path receives after the last timed step: every component's amplitude map and index maps
+    (float64, as the engine holds them) and the two chi^2 values of the line.  The maps are sampled at a fixed, seeded set of
+    global pixels of [lo, hi) -- all of them when they fit DUMP_BUDGET_BYTES -- so the files do not depend on the build or
+    on the number of ranks: each rank contributes the sampled pixels of its shard, summed as bit patterns over the ranks."""
+    import numpy as np
+    nmaps = int(comps[0].amplitude.shape[0])
+    planes = sum(1 + c.nindices for c in comps) * nmaps
+    npix = hi - lo
+    nsel = min(npix, DUMP_BUDGET_BYTES // (8 * planes))
+    if nsel < npix:
+        sel = np.sort(np.random.default_rng(DUMP_SEED).choice(npix, size=nsel, replace=False)) + lo
+    else:
+        sel = np.arange(lo, hi)
+    arrays = {}
+    for l, c in enumerate(comps):
+        arrays["amplitude_%02d_%s" % (l, c.label)] = c.amplitude
+        if c.nindices:
+            arrays["indices_%02d_%s" % (l, c.label)] = c.indices
+    out = {}
+    for name, t in arrays.items():
+        n_local = int(t.shape[-1])
+        mine = (sel >= pix0) & (sel < pix0 + n_local)
+        buf = torch.zeros(tuple(t.shape[:-1]) + (nsel,), dtype=torch.float64, device=dev)
+        if mine.any():
+            pos = torch.from_numpy(np.nonzero(mine)[0]).to(dev)
+            buf[..., pos] = t[..., torch.from_numpy(sel[mine] - pix0).to(dev)].to(torch.float64)
+        if world > 1:   # every sampled pixel lives on exactly one rank: an integer sum of the bit patterns is exact
+            bits = buf.view(torch.int64) if backend == "nccl" else buf.view(torch.int64).cpu()
+            td.all_reduce(bits)
+            buf = bits.to(dev).view(torch.float64)
+        out[name] = buf.cpu().numpy()
+    out["chisq"] = np.asarray(chisq, dtype=np.float64)
+    if outdir is not None:
+        os.makedirs(outdir, exist_ok=True)
+        for name, a in out.items():
+            np.save(os.path.join(outdir, name + ".npy"), a)
+    return sum(a.nbytes for a in out.values())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -348,7 +396,7 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-template-model", action="store_true", help="skip the secondary figure: the workload with a fitted Q/U template")
     ap.add_argument("--no-fortran-seam", action="store_true", help="skip the it/s of the reference-side Fortran wrapper (two-call "
-                    "seam and gibbs_iteration_gpu), which bench.py otherwise reports beside the headline value at N=1")
+                    "seam and gibbs_iteration_gpu), which bench.py --full otherwise reports beside the headline value at N=1")
     ap.add_argument("--no-fuse", action="store_true", help="diagnostic: amplitude solve and first index sweep of a plane set as "
                     "two calls (two launches) instead of dangx_amp_index_sample")
     ap.add_argument("--bandpass", type=int, default=0, help="diagnostic (not a BASELINE config): integrate every second "
@@ -368,10 +416,18 @@ def main():
                     "T plane (the state after sample_calibrators and a fitted monopole): the plane-set launches must stay")
     ap.add_argument("--backend", default="nccl", help="process-group backend (nccl = RCCL; gloo only for rehearsing "
                                                       "the N>1 path with several ranks on ONE GPU)")
+    ap.add_argument("--full", action="store_true", help="after the timed region, also measure the secondary figures, each a run "
+                    "of its own: the CPU oracle baseline, the reference-side Fortran wrapper, the template model and the "
+                    "full-sky / coarse index modes (--no-* above switch single ones off).  Without it a run times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps: write what the last one computed "
+                    "-- every component's amplitude and index maps (float64; a fixed, seeded sample of pixels when the "
+                    "maps exceed 48 MB) and the two chi^2 values -- as DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if "RANK" not in os.environ and args.gpus > 1:
         # plain `python bench.py --gpus N`: this process becomes the launcher of N rank processes.  It has made
         # no GPU call (device_count() does not initialise the runtime) and never execs: children are spawned.
@@ -548,6 +604,10 @@ def main():
         td.all_reduce(ones)   # every rank contributes 1 through the same process group the chi^2 uses
         ranks_seen = int(round(float(ones.item())))
     chisq = (chisq_buf / nb / ddata.nump).tolist()
+    if args.dump_outputs:
+        lo, hi = (meta["pix0"], meta["pix0"] + meta["npix"]) if shard_of else (0, meta["npix_global"])
+        nbytes = dump_outputs(args.dump_outputs if rank == 0 else None, comps, chisq, lo, hi, meta["pix0"], world, args.backend, dev)
+        log("outputs of the last timed step: %.1f MB in %s" % (nbytes / 1e6, args.dump_outputs))
     gathered = None
     if args.gather:
         # map output (north_star: "a gather for map output"): the shards of two state maps to rank 0, reassembled with the SAME
@@ -653,7 +713,7 @@ def main():
                          "algorithmic bytes of that launch / its duration; traffic = counter-measured HBM bytes per launch")
         if gathered is not None:
             out["gather"] = gathered
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 log("timing the CPU oracle (cpu_baseline)")
                 out["cpu_baseline"] = cpu_baseline(args.config, args.nsample)
@@ -661,7 +721,7 @@ def main():
             except Exception as e:  # the oracle is optional infrastructure; never let it break the bench line
                 out["cpu_baseline"] = {"value": None, "unit": "it/s", "cores": os.cpu_count(), "kind": "port",
                                        "sample": "failed: %r" % (e,)}
-        if world == 1 and standard and not args.no_fortran_seam:
+        if world == 1 and args.full and standard and not args.no_fortran_seam:
             try:
                 log("timing the Fortran wrapper (fortran_seam)")
                 eng.close()
@@ -673,7 +733,7 @@ def main():
                 log("fortran_seam done")
             except Exception as e:  # flang absent / driver failed: say so in the line, never break it
                 out["fortran_seam"] = {"error": repr(e)[:500]}
-        if world == 1 and standard and not args.no_template_model:
+        if world == 1 and args.full and standard and not args.no_template_model:
             try:
                 log("timing the template model (template_model)")
                 if args.no_fortran_seam:   # (the seam branch above has released the headline's maps already)

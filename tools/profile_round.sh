@@ -11,9 +11,9 @@ R=$(pwd)
 out=$R/gpurun_out/prof_$tag
 mkdir -p "$out"
 export TMPDIR=/tmp
-B="python3 $R/bench.py --no-cpu-baseline --no-fortran-seam"
+B="python3 $R/bench.py --full --no-cpu-baseline --no-fortran-seam"
 echo "[profile] plain bench (the numbers the JSON line reports)"; 
-python3 $R/bench.py --steps 20 --warmup 3 > "$out/${tag}_bench.json" 2> "$out/bench.err"
+python3 $R/bench.py --full --steps 20 --warmup 3 > "$out/${tag}_bench.json" 2> "$out/bench.err"
 echo "[profile] kernel trace"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -o run -- $B --steps 20 --warmup 3 > "$out/${tag}_bench_under_rocprof.json" 2> "$out/trace.err"
 echo "[profile] FETCH_SIZE"
@@ -28,7 +28,7 @@ rocprofv3 --kernel-include-regex "k_(amp|index|plane|schur|sky|cg|Ax|rhs|reduce)
 rocprofv3 --kernel-include-regex "k_(amp|index|plane|schur|sky|cg|Ax|rhs|reduce)" --output-format csv --pmc WRITE_SIZE -d "$out/cal_write" -o run -- python3 $R/tools/pmc_calib.py >> "$out/cal.log" 2> "$out/cal_write.err"
 python3 $R/tools/prof_summary.py --stats "$out/trace" --pmc FETCH_SIZE="$out/pmc_fetch" --pmc WRITE_SIZE="$out/pmc_write" \
     --sq "$out/sq" --traffic-json "$out/${tag}_traffic.json" --valu-json "$out/${tag}_valu.json" -o "$out/${tag}_profile.md" \
-    --title "$tag: python3 bench.py --steps 20 --warmup 3 (C3, 1x MI355X); PMC passes: --steps 2 --warmup 1" > /dev/null
+    --title "$tag: python3 bench.py --full --steps 20 --warmup 3 (C3, 1x MI355X); PMC passes: --steps 2 --warmup 1" > /dev/null
 python3 $R/tools/prof_summary.py --only k_cg_vec --pmc FETCH_SIZE="$out/cal_fetch" --pmc WRITE_SIZE="$out/cal_write" \
     -o "$out/${tag}_calibration.md" --title "$tag: FETCH_SIZE / WRITE_SIZE on k_cg_vec (8 B per lane, coalesced, known byte count)" > /dev/null
 cp "$(find "$out/trace" -name '*kernel_stats.csv' | head -1)" "$out/${tag}_kernel_stats.csv"

@@ -5,7 +5,7 @@
 set -e -o pipefail
 tag=${1:-rXX}
 R=$(pwd); out=$R/gpurun_out/prof_${tag}_side; mkdir -p "$out"
-B="python3 $R/bench.py --no-cpu-baseline --no-fortran-seam"
+B="python3 $R/bench.py --full --no-cpu-baseline --no-fortran-seam"
 $B --nsample 100 --steps 5 --warmup 2            > "$out/${tag}_z_nsample100.json"   2> "$out/err.log"
 $B --config C5 --nsample 100 --steps 2 --warmup 1 > "$out/${tag}_c5z_nsample100.json" 2>> "$out/err.log"
 $B --shard-of 8 --steps 50 --warmup 5             > "$out/${tag}_z_shard_of_8.json"   2>> "$out/err.log"

@@ -7,7 +7,7 @@ set -e -o pipefail
 tag=$1; shift
 R=$(pwd); out=$R/gpurun_out/prof_$tag; mkdir -p "$out"
 export TMPDIR=/tmp
-B="python3 $R/bench.py --no-cpu-baseline --no-fortran-seam $*"
+B="python3 $R/bench.py --full --no-cpu-baseline --no-fortran-seam $*"
 RE="k_(amp|index|plane|schur|sky|cg|Ax|rhs|reduce)"
 echo "[$tag] plain bench"; $B > "$out/$tag.json" 2> "$out/bench.err"
 echo "[$tag] kernel trace"
@@ -20,7 +20,7 @@ rocprofv3 --kernel-include-regex "$RE" --output-format csv --pmc FETCH_SIZE -d "
 echo "[$tag] WRITE_SIZE"
 rocprofv3 --kernel-include-regex "$RE" --output-format csv --pmc WRITE_SIZE -d "$out/pmc_write" -o run -- $B > /dev/null 2> "$out/write.err"
 python3 $R/tools/prof_summary.py --stats "$out/trace" --pmc FETCH_SIZE="$out/pmc_fetch" --pmc WRITE_SIZE="$out/pmc_write" --sq "$out/sq" \
-    -o "$out/${tag}_profile.md" --title "$tag: python3 bench.py $* (1x MI355X); PMC passes: the same command" > /dev/null
+    -o "$out/${tag}_profile.md" --title "$tag: python3 bench.py --full $* (1x MI355X); PMC passes: the same command" > /dev/null
 cp "$(find "$out/trace" -name '*kernel_stats.csv' | head -1)" "$out/${tag}_kernel_stats.csv"
 rm -rf "$out/trace" "$out/sq" "$out/pmc_fetch" "$out/pmc_write"
 echo "[$tag] done: $(ls $out | tr '\n' ' ')"
