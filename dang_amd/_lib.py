@@ -20,6 +20,8 @@ ML_SAMPLE, ML_OPTIMIZE = 1, 2
 FLAG_T, FLAG_Q, FLAG_U, FLAG_QU = 1, 2, 4, 8
 SOLVER_DIRECT, SOLVER_CG = 0, 1
 FLUCT_CORRECT, FLUCT_REFERENCE = 0, 1
+COARSE_REFERENCE, COARSE_DEGRADED = 0, 1
+COARSE_MODEL_CODES = {"reference": COARSE_REFERENCE, "degraded": COARSE_DEGRADED}
 A2T, A2F, F2T = 0, 1, 2
 UNIT_CODES = {"uK_RJ": 0, "uK_cmb": 1, "MJy/sr": 2}
 K_AMP_DIRECT, K_INDEX_MH, K_SKY_CHISQ, K_REDUCE, K_CG_AX, K_CG_VEC, K_AMP_INDEX = range(7)
@@ -67,6 +69,10 @@ SYMBOLS = {
     "dangx_coarse_partials": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "dangx_coarse_chains": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_int, _P, _P]),
     "dangx_coarse_writeback": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "dangx_set_coarse_model": (C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
+    "dangx_coarse_model_size": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "dangx_coarse_model_partials": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "dangx_coarse_model_finish": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "dangx_udgrade": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_int]),
     "dangx_index_masked_sum": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "dangx_index_plain_sum": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),

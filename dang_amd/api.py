@@ -57,6 +57,9 @@ class DangComps:
     pol_flag: List[List[int]] = field(default_factory=list)  # per index: list of poltype bit flags
     tuned: List[bool] = field(default_factory=list)          # c%tuned (empty = all tuned)
     sample_nside: List[int] = field(default_factory=list)    # c%sample_nside(nind) (empty / 0 = nside)
+    # per index, with sample_nside < nside: 'reference' (default; the chain reads the full-resolution amplitude / indices / mask at the
+    # coarse pixel number, as the reference does) or 'degraded' (they are degraded like the data; dangx_set_coarse_model)
+    coarse_model: List[str] = field(default_factory=list)
     # global-amplitude types ('template', 'monopole', 'hi_fit'), src/dang_component_mod.f90:17-33
     nfit: int = 0
     corr: List[bool] = field(default_factory=list)           # c%corr(j): is band j fitted?
@@ -175,7 +178,7 @@ class Engine:
         if tcmb is not None:
             self._chk(self.lib.dangx_set_tcmb(self.h, float(tcmb)))
         for l, c in enumerate(component_list):
-            self._chk(self.lib.dangx_set_component(self.h, l, C.byref(comp_desc(c))))
+            self.set_component(l, c)
         gain = np.ones(nb) if ddata.gain is None else np.ascontiguousarray(ddata.gain, dtype=np.float64)
         off = np.zeros(nb) if ddata.offset is None else np.ascontiguousarray(ddata.offset, dtype=np.float64)
         self._chk(self.lib.dangx_set_calibration(self.h, gain.ctypes.data, off.ctypes.data))
@@ -237,6 +240,38 @@ class Engine:
                 return 1
         self._allreduce_cb = L.ALLREDUCE_FN(cb)   # keep the trampoline alive as long as the context
         self._chk(self.lib.dangx_set_allreduce(self.h, C.cast(self._allreduce_cb, C.c_void_p), None, 1 if is_root else 0))
+
+    def set_component(self, l, c=None):
+        """Push component l's descriptor (default: self.component_list[l]) and its coarse model (DangComps.coarse_model)."""
+        c = self.component_list[l] if c is None else c
+        codes = coarse_model_codes(c)
+        self._chk(self.lib.dangx_set_component(self.h, l, C.byref(comp_desc(c))))
+        for q, m in enumerate(codes):
+            self._chk(self.lib.dangx_set_coarse_model(self.h, l, q, m))
+
+    def set_coarse_model(self, l, nind, model):
+        """The coarse model of index nind of component l on this context: 'reference' or 'degraded' (see DangComps.coarse_model)."""
+        if model not in L.COARSE_MODEL_CODES:
+            raise DangxError("unknown coarse model %r (expected 'reference' or 'degraded')" % (model,))
+        self._chk(self.lib.dangx_set_coarse_model(self.h, l, nind, L.COARSE_MODEL_CODES[model]))
+        c = self.component_list[l]
+        c.coarse_model = (list(c.coarse_model) + ["reference"] * c.nindices)[:c.nindices]
+        c.coarse_model[nind] = model
+
+    def coarse_model_size(self, comp, map_n, sample_nside):
+        n = C.c_int64(0)
+        self._chk(self.lib.dangx_coarse_model_size(self.h, comp, map_n, int(sample_nside), C.byref(n)))
+        return n.value
+
+    def coarse_model_partials(self, comp, map_n, sample_nside):
+        buf = np.empty(self.coarse_model_size(comp, map_n, sample_nside))
+        self._chk(self.lib.dangx_coarse_model_partials(self.h, comp, map_n, self.nside, int(sample_nside), buf.ctypes.data))
+        return buf
+
+    def coarse_model_finish(self, comp, map_n, sample_nside, model_sum):
+        x = np.ascontiguousarray(model_sum, dtype=np.float64)
+        assert x.size == self.coarse_model_size(comp, map_n, sample_nside)
+        self._chk(self.lib.dangx_coarse_model_finish(self.h, comp, map_n, self.nside, int(sample_nside), x.ctypes.data))
 
     # -- plumbing
     def _chk(self, rc):
@@ -602,6 +637,17 @@ class Engine:
         return out
 
 
+def coarse_model_codes(c: DangComps):
+    """c.coarse_model as library codes, one per index (missing entries: 'reference'); an unknown name raises DangxError."""
+    names = list(c.coarse_model or [])
+    if len(names) > max(c.nindices, 0):
+        raise DangxError("component '%s': %d coarse_model entries for %d indices" % (c.label, len(names), c.nindices))
+    for m in names:
+        if m not in L.COARSE_MODEL_CODES:
+            raise DangxError("component '%s': unknown coarse model %r (expected 'reference' or 'degraded')" % (c.label, m))
+    return [L.COARSE_MODEL_CODES[m] for m in names] + [L.COARSE_REFERENCE] * (c.nindices - len(names))
+
+
 def comp_desc(c: DangComps):
     d = L.CompDesc()
     if c.type not in L.TYPE_CODES:
@@ -696,11 +742,19 @@ def refresh_host_state(ddata):
 def index_sample_coarse_multi(engines, comp, nind, map_n, nsample, ml_mode, seed, stream, sample_nside):
     """sample_index_mh with sample_nside < nside over several pixel-shard contexts of ONE process (e.g. one per GPU):
     the three phases of dangx_index_sample_coarse with the shards' buffers added in shard order between them.
+    When an index of the component runs the 'degraded' coarse model, the model channels' child sums are added and finished too.
     Returns the number of accepted proposals."""
     part = None
     for e in engines:
         b = e.coarse_partials(comp, map_n, sample_nside)
         part = b if part is None else part + b
+    if engines[0].coarse_model_size(comp, map_n, sample_nside) > 0:
+        msum = None
+        for e in engines:
+            b = e.coarse_model_partials(comp, map_n, sample_nside)
+            msum = b if msum is None else msum + b
+        for e in engines:
+            e.coarse_model_finish(comp, map_n, sample_nside, msum)
     idx = None
     for e in engines:
         b = e.coarse_chains(comp, nind, map_n, nsample, ml_mode, seed, stream, sample_nside, part)

@@ -64,11 +64,12 @@ __global__ __launch_bounds__(BLOCK) void k_fullsky_prepare(const Model* __restri
 // partial[row][gridDim.x]
 // With sample_nside /= nside (crms /= nullptr) the sums run over the npix_c pixels of the DEGRADED data / rms / mask
 // ([kk][j][npix_c] and [npix_c]) while eval_signal reads c%amplitude at the coarse pixel number in the full-resolution
-// array, as the reference does (src/dang_sample_mod.f90:199-217, 548-563).
+// array, as the reference does (src/dang_sample_mod.f90:199-217, 548-563) -- or, DANGX_COARSE_DEGRADED (camp /= nullptr),
+// the degraded amplitude planes camp[kk][npix_c].
 __global__ __launch_bounds__(BLOCK) void k_fullsky_rows(const Model* __restrict__ Mp, int comp, int s1, int s2, int what,
                                                         double th0, double th1, const double* __restrict__ data,
                                                         const double* __restrict__ crms, const double* __restrict__ cmask,
-                                                        long long npix_c, double* __restrict__ partial) {
+                                                        const double* __restrict__ camp, long long npix_c, double* __restrict__ partial) {
     __shared__ double sh[BLOCK / 64];
     const Model& M = *Mp;
     const Comp& c = M.comp[comp];
@@ -88,7 +89,7 @@ __global__ __launch_bounds__(BLOCK) void k_fullsky_rows(const Model* __restrict_
     __syncthreads();
     const int nrows = (what == 1) ? 2 * nb * Sp : (what == 3) ? 3 * nb * Sp : 1;
     double amp[2] = {0.0, 0.0};
-    if (in) for (int kk = 0; kk < Sp; ++kk) amp[kk] = c.amp[(long long)(s1 + kk - 1) * M.npix + il];
+    if (in) for (int kk = 0; kk < Sp; ++kk) amp[kk] = camp ? camp[(long long)kk * npix + i] : c.amp[(long long)(s1 + kk - 1) * M.npix + il];
     auto rms_at = [&](int kk, int j) -> double {
         return coarse ? crms[((long long)kk * nb + j) * npix + i] : M.rms[((long long)j * M.nmaps + (s1 + kk - 1)) * npix + i];
     };
@@ -143,11 +144,14 @@ __global__ __launch_bounds__(BLOCK) void k_fullsky_rows(const Model* __restrict_
 // plane) reduced over the wave at once, the block's four wave sums added in order after ONE barrier.  `fused`: the data are formed
 // here -- data_raw minus every other component in dangx_fullsky_prepare's order (:173-196), a plane's bands in the thread's LDS
 // column, each other component's index values / amplitude read once per plane -- instead of read from the staging buffer, which is
-// then never written.  Dynamic LDS: nb * BLOCK doubles (the column) + 3 * nb * Sp * (BLOCK / 64) (the wave sums).
+// then never written.  Dynamic LDS: nb * BLOCK doubles (the column) + 3 * nb * Sp * (BLOCK / 64) (the wave sums).  `fused` is a
+// full-resolution form only (the launch site refuses it with the degraded maps); model state is read at (M.npix, il) throughout.
+// DEGRADED (coarse, DANGX_COARSE_DEGRADED): the swept component's amplitude is the degraded plane camp[kk][npix_c].
+template <bool DEGRADED>
 __global__ __launch_bounds__(BLOCK, 6) void k_fullsky_stats(const Model* __restrict__ Mp, int comp, int s1, int s2, double th0, double th1,
                                                          const double* __restrict__ data, unsigned others, int fused,
                                                          const double* __restrict__ crms, const double* __restrict__ cmask,
-                                                         long long npix_c, double* __restrict__ partial) {
+                                                         const double* __restrict__ camp, long long npix_c, double* __restrict__ partial) {
     extern __shared__ double fs_lds[];
     const Model& M = *Mp;
     const Comp& c = M.comp[comp];
@@ -179,14 +183,14 @@ __global__ __launch_bounds__(BLOCK, 6) void k_fullsky_stats(const Model* __restr
     const int wave = threadIdx.x >> 6;
     for (int kk = 0; kk < Sp; ++kk) {
         const int k = s1 + kk;
-        const double amp = in ? c.amp[(long long)(k - 1) * M.npix + il] : 0.0;
+        const double amp = !in ? 0.0 : DEGRADED ? camp[(long long)kk * npix + i] : c.amp[(long long)(k - 1) * M.npix + il];
         // ---- the plane's cleaned data -> the column
         for (int j0 = 0; j0 < nb; j0 += FS_B) {   // FS_B bands' maps in flight
             double d[FS_B];
 #pragma unroll
             for (int t = 0; t < FS_B; ++t) {
                 const int j = (j0 + t < nb) ? j0 + t : nb - 1;
-                d[t] = fused ? M.sig[((long long)j * M.nmaps + (k - 1)) * npix + ic] : data[((long long)kk * nb + j) * npix + ic];
+                d[t] = fused ? M.sig[((long long)j * M.nmaps + (k - 1)) * M.npix + ic] : data[((long long)kk * nb + j) * npix + ic];
             }
 #pragma unroll
             for (int t = 0; t < FS_B; ++t) {
@@ -201,16 +205,16 @@ __global__ __launch_bounds__(BLOCK, 6) void k_fullsky_stats(const Model* __restr
             int oi = 0;
             for (unsigned om = others; om; om &= om - 1, ++oi) {
                 const Comp& c2 = M.comp[__builtin_ctz(om)];
-                const double a2 = c2.amp[(long long)(k - 1) * npix + i];
+                const double a2 = c2.amp[(long long)(k - 1) * M.npix + il];
                 if (c2.type >= DANGX_POWERLAW && c2.type <= DANGX_CMB && ((c2.const_planes >> (k - 1)) & 1)) {
                     // comp_signal of a diffuse component with constant indices: amplitude * the host-evaluated row
                     const double* row = ocs + (oi * Sp + kk) * nb;
                     for (int j = 0; j < nb; ++j) col[j * BLOCK] = col[j * BLOCK] - a2 * row[j];
                 } else {
                     double t0, t1;
-                    load_theta(M, c2, i, k, t0, t1);
+                    load_theta(M, c2, (int)il, k, t0, t1);
                     const Prep p2 = sed_prep(c2, t0, t1);
-                    for (int j = 0; j < nb; ++j) col[j * BLOCK] = col[j * BLOCK] - comp_signal(M, c2, i, k, j, a2, p2);
+                    for (int j = 0; j < nb; ++j) col[j * BLOCK] = col[j * BLOCK] - comp_signal(M, c2, (int)il, k, j, a2, p2);
                 }
             }
         }
@@ -338,40 +342,57 @@ __global__ __launch_bounds__(BLOCK) void k_udgrade_planes(const double* __restri
 // touches far fewer lines than with one thread per coarse pixel (64 children: 0.5 ms against 2.07 ms per sweep at C3).  The values
 // go through LDS ([wave][plane][lane], one pad word per row) and one thread per (coarse pixel, plane) adds its children in NESTED
 // order as before.  ratio: a power of four.
-constexpr int UDG_QW = 10, UDG_G = BLOCK / 64;
-template <bool FUSED>
+// Extra channels (DANGX_COARSE_DEGRADED; mode 0 only): after the nplanes maps of `in` come nxa maps xa[e * npix_in] (the swept
+// component's amplitude planes) and nxi maps xi[e * xi_stride] (its index maps at plane s1) -> xout[e][npix_out], the same gather
+// and NESTED-order sum, i.e. dangx_udgrade mode 0.  MODEL = false (no extra channels) is the kernel as it was; MODEL = true takes
+// UDG_QW_MODEL maps per block, so that the extra channels of a ten-band plane set ride in the data's blocks (10 + 3, 20 + 4 in two)
+// instead of a block row of their own, which costs as much as a full one.
+constexpr int UDG_QW = 10, UDG_QW_MODEL = 13, UDG_G = BLOCK / 64;
+template <bool MODEL> constexpr int udg_qw() { return MODEL ? UDG_QW_MODEL : UDG_QW; }
+template <bool FUSED, bool MODEL>
 __global__ __launch_bounds__(BLOCK) void k_udgrade_wave(const Model* __restrict__ Mp, int comp_unused, unsigned others, int Sp,
                                                         const double* __restrict__ in, double* __restrict__ out,
                                                         const int* __restrict__ n2r_in, const int* __restrict__ r2n_out,
                                                         long long npix_in, long long npix_out, int ratio, int mode, double scale,
-                                                        int layout, int nb, int nmaps, int s1, int nplanes) {
-    __shared__ double sh[UDG_G][UDG_QW][65];
+                                                        int layout, int nb, int nmaps, int s1, int nplanes,
+                                                        const double* __restrict__ xa, int nxa, const double* __restrict__ xi,
+                                                        long long xi_stride, int nxi, double* __restrict__ xout) {
+    constexpr int QW = udg_qw<MODEL>(), SLOTS = (UDG_G * 16 * QW + BLOCK - 1) / BLOCK;   // (16: coarse pixels per wave at ratio 4)
+    __shared__ double sh[UDG_G][QW][65];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int cpw = (ratio < 64) ? 64 / ratio : 1, rounds = (ratio > 64) ? ratio / 64 : 1, per = (ratio < 64) ? ratio : 64;
-    const int q0 = blockIdx.y * UDG_QW;
+    const int q0 = blockIdx.y * QW, ntot = MODEL ? nplanes + nxa + nxi : nplanes;
     const long long o0 = ((long long)blockIdx.x * UDG_G + wave) * cpw;          // first coarse pixel of the wave
     const long long ol = o0 + lane / per;                                        // the lane's coarse pixel
     // the summing threads: (wave g, pixel u of the wave, plane t), several rounds of the block when there are more than BLOCK of them
-    const int nsum = UDG_G * cpw * UDG_QW;
-    double total[3] = {0.0, 0.0, 0.0};
-    int nobs[3] = {0, 0, 0};
+    const int nsum = UDG_G * cpw * QW;
+    double total[SLOTS];
+    int nobs[SLOTS];
+#pragma unroll
+    for (int t = 0; t < SLOTS; ++t) { total[t] = 0.0; nobs[t] = 0; }
     for (int rd = 0; rd < rounds; ++rd) {
         if (ol < npix_out) {
             const long long c = n2r_in[(long long)r2n_out[ol] * ratio + rd * 64 + lane % per];
-            double x[UDG_QW];
+            double x[QW];
 #pragma unroll
-            for (int t = 0; t < UDG_QW; ++t) {
-                const int q = (q0 + t < nplanes) ? q0 + t : nplanes - 1;
-                // FUSED: the raw maps (plane q = Stokes q / nb, band q % nb), cleaned below; else the staged / rms maps
-                const long long off = (FUSED || layout != 0) ? ((long long)(q % nb) * nmaps + (s1 + q / nb - 1)) * npix_in : (long long)q * npix_in;
-                x[t] = in[off + c];
+            for (int t = 0; t < QW; ++t) {
+                const int q = (q0 + t < ntot) ? q0 + t : ntot - 1;
+                if (!MODEL || q < nplanes) {
+                    // FUSED: the raw maps (plane q = Stokes q / nb, band q % nb), cleaned below; else the staged / rms maps
+                    const long long off = (FUSED || layout != 0) ? ((long long)(q % nb) * nmaps + (s1 + q / nb - 1)) * npix_in : (long long)q * npix_in;
+                    x[t] = in[off + c];
+                } else if (q < nplanes + nxa) {
+                    x[t] = xa[(long long)(q - nplanes) * npix_in + c];
+                } else {
+                    x[t] = xi[(long long)(q - nplanes - nxa) * xi_stride + c];
+                }
             }
             if (FUSED) {   // data_raw minus every other component at the child pixel, dangx_fullsky_prepare's expression and order (:173-196)
                 const Model& M = *Mp;
 #pragma unroll
-                for (int t = 0; t < UDG_QW; ++t) {
+                for (int t = 0; t < QW; ++t) {
                     const int q = (q0 + t < nplanes) ? q0 + t : nplanes - 1, j = q % nb;
-                    if (s1 + q / nb == 1) x[t] = (x[t] - M.offset[j]) / M.gain[j];
+                    if ((!MODEL || q0 + t < nplanes) && s1 + q / nb == 1) x[t] = (x[t] - M.offset[j]) / M.gain[j];
                 }
                 for (unsigned om = others; om; om &= om - 1) {
                     const Comp& c2 = M.comp[__builtin_ctz(om)];
@@ -384,21 +405,21 @@ __global__ __launch_bounds__(BLOCK) void k_udgrade_wave(const Model* __restrict_
                         a2[kk] = c2.amp[(long long)(s1 + kk - 1) * npix_in + c];
                     }
 #pragma unroll
-                    for (int t = 0; t < UDG_QW; ++t) {
+                    for (int t = 0; t < QW; ++t) {
                         const int q = (q0 + t < nplanes) ? q0 + t : nplanes - 1, kk = q / nb, j = q - kk * nb;
-                        x[t] = x[t] - comp_signal(M, c2, (int)c, s1 + kk, j, a2[kk], p2[kk]);
+                        if (!MODEL || q0 + t < nplanes) x[t] = x[t] - comp_signal(M, c2, (int)c, s1 + kk, j, a2[kk], p2[kk]);
                     }
                 }
             }
 #pragma unroll
-            for (int t = 0; t < UDG_QW; ++t) sh[wave][t][lane] = x[t];
+            for (int t = 0; t < QW; ++t) sh[wave][t][lane] = x[t];
         }
         __syncthreads();
         int slot = 0;
         for (int a = threadIdx.x; a < nsum; a += BLOCK, ++slot) {
-            const int g = a / (cpw * UDG_QW), r = a - g * cpw * UDG_QW, u = r / UDG_QW, t = r - u * UDG_QW;
+            const int g = a / (cpw * QW), r = a - g * cpw * QW, u = r / QW, t = r - u * QW;
             const long long og = ((long long)blockIdx.x * UDG_G + g) * cpw + u;
-            if (og < npix_out && q0 + t < nplanes)
+            if (og < npix_out && q0 + t < ntot)
                 for (int ip = 0; ip < per; ++ip) {
                     double v = sh[g][t][u * per + ip];
                     if (mode == 1) v = v * v;
@@ -409,12 +430,13 @@ __global__ __launch_bounds__(BLOCK) void k_udgrade_wave(const Model* __restrict_
     }
     int slot = 0;
     for (int a = threadIdx.x; a < nsum; a += BLOCK, ++slot) {
-        const int g = a / (cpw * UDG_QW), r = a - g * cpw * UDG_QW, u = r / UDG_QW, t = r - u * UDG_QW;
+        const int g = a / (cpw * QW), r = a - g * cpw * QW, u = r / QW, t = r - u * QW;
         const long long og = ((long long)blockIdx.x * UDG_G + g) * cpw + u;
-        if (og < npix_out && q0 + t < nplanes) {
+        if (og < npix_out && q0 + t < ntot) {
             double v = nobs[slot] ? total[slot] / nobs[slot] : MISSVAL;
             if (mode == 1) v = sqrt(v) * scale;
-            out[(long long)(q0 + t) * npix_out + og] = v;
+            if (!MODEL || q0 + t < nplanes) out[(long long)(q0 + t) * npix_out + og] = v;
+            else xout[(long long)(q0 + t - nplanes) * npix_out + og] = v;
         }
     }
 }
@@ -444,6 +466,38 @@ __global__ __launch_bounds__(BLOCK) void k_udgrade_part(const double* __restrict
     tot[(long long)q * npix_out + o] = total;
     cnt[(long long)q * npix_out + o] = (double)nobs;
 }
+// k_udgrade_part for the model channels of DANGX_COARSE_DEGRADED (blockIdx.y = channel: nxa amplitude planes xa[q * npix_loc], then
+// index maps xi[(q - nxa) * xi_stride]): amplitudes and indices are never MISSVAL, so every channel counts the same children and
+// the count is written once (cnt[npix_out], by channel 0).  With one shard k_udgrade_finish_shared makes it k_udgrade_wave's
+// extra channels bit for bit.
+__global__ __launch_bounds__(BLOCK) void k_udgrade_part_model(const double* __restrict__ xa, int nxa, const double* __restrict__ xi,
+                                                              long long xi_stride, double* __restrict__ tot, double* __restrict__ cnt,
+                                                              const int* __restrict__ n2r_in, const int* __restrict__ r2n_out,
+                                                              long long pix0, long long npix_loc, long long npix_out, int ratio) {
+    const long long o = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    if (o >= npix_out) return;
+    const int q = blockIdx.y;
+    const double* src = (q < nxa) ? xa + (long long)q * npix_loc : xi + (long long)(q - nxa) * xi_stride;
+    const long long nest = r2n_out[o];
+    double total = 0.0;
+    int nobs = 0;
+    for (int ip = 0; ip < ratio; ++ip) {
+        const long long ring = n2r_in[nest * ratio + ip];
+        if (ring < pix0 || ring >= pix0 + npix_loc) continue;
+        total = total + src[ring - pix0];
+        ++nobs;
+    }
+    tot[(long long)q * npix_out + o] = total;
+    if (q == 0) cnt[o] = (double)nobs;
+}
+// the model channels from the summed buffer: out[q][o] = tot[q][o] / cnt[o]
+__global__ __launch_bounds__(BLOCK) void k_udgrade_finish_shared(const double* __restrict__ tot, const double* __restrict__ cnt,
+                                                                 double* __restrict__ out, long long npix_out, int nch) {
+    const long long t = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    if (t >= npix_out * nch) return;
+    const double nobs = cnt[t % npix_out];
+    out[t] = (nobs > 0.0) ? tot[t] / nobs : MISSVAL;
+}
 __global__ __launch_bounds__(BLOCK) void k_udgrade_finish(const double* __restrict__ tot, const double* __restrict__ cnt,
                                                           double* __restrict__ out, long long n, int mode, double scale) {
     const long long t = (long long)blockIdx.x * BLOCK + threadIdx.x;
@@ -461,25 +515,37 @@ __global__ __launch_bounds__(BLOCK) void k_udgrade_finish(const double* __restri
 // evaluate_marginal_lnL j outer, k inner (:113-122).  index_map(i) -> idxmap[i] (0 where the chain is skipped, :223).
 // On a pixel shard the chain of coarse pixel i runs where the full-resolution pixel i lives (M.pix0 <= i < M.pix0 + npix);
 // the other shards leave idxmap[i] = 0 and the caller adds the maps.
+// DEGRADED (DANGX_COARSE_DEGRADED): the chain reads the degraded model instead -- cmodel[kk][npix_c] the swept component's amplitude
+// planes s1..s2, then cmodel[(Sp + n)][npix_c] its index maps n at plane s1 -- and is skipped where the DEGRADED mask is masked.
+// Everything else (likelihoods and their orders, priors, bounds, draw slots, which shard runs pixel i) is the reference's.
+template <bool DEGRADED>
 __global__ __launch_bounds__(BLOCK) void k_index_mh_coarse(const Model* __restrict__ Mp, IndexArgs a, long long npix_c,
                                                            const double* __restrict__ cdata, const double* __restrict__ crms,
-                                                           const double* __restrict__ cmask, double* __restrict__ idxmap,
-                                                           unsigned long long* __restrict__ accepted) {
+                                                           const double* __restrict__ cmask, const double* __restrict__ cmodel,
+                                                           double* __restrict__ idxmap, unsigned long long* __restrict__ accepted) {
     const Model& M = *Mp;
     const long long i = (long long)blockIdx.x * BLOCK + threadIdx.x;
     unsigned long long nacc = 0;
     if (i < npix_c) {
         idxmap[i] = 0.0;
         const long long il = i - M.pix0;  // index of full-resolution pixel i in this shard's arrays
-        if (il >= 0 && il < M.npix && !is_masked(M.mask[il])) {
+        // DEGRADED, skipped (masked coarse pixel): the chain's starting value, udgrade_ring of the swept index -- the reference's 0
+        // (its index_map initialisation) is no usable index (a dust temperature of 0 makes every SED of the pixel's children NaN)
+        if (DEGRADED && il >= 0 && il < M.npix && is_masked(cmask[i])) idxmap[i] = cmodel[(long long)(a.s2 - a.s1 + 1 + a.nind) * npix_c + i];
+        if (il >= 0 && il < M.npix && !is_masked(DEGRADED ? cmask[i] : M.mask[il])) {
             const Comp& c = M.comp[a.comp];
             const int nb = M.nbands, Sp = a.s2 - a.s1 + 1, q = a.nind;
             double sample0, sample1;
-            load_theta(M, c, (int)il, a.s1, sample0, sample1);
+            if (DEGRADED) {
+                sample0 = (c.nind > 0) ? cmodel[(long long)Sp * npix_c + i] : 0.0;
+                sample1 = (c.nind > 1) ? cmodel[(long long)(Sp + 1) * npix_c + i] : 0.0;
+            } else {
+                load_theta(M, c, (int)il, a.s1, sample0, sample1);
+            }
             const bool first = (q == 0);
             const double other = first ? sample1 : sample0;
             double amp[2] = {0.0, 0.0};
-            for (int kk = 0; kk < Sp; ++kk) amp[kk] = c.amp[(long long)(a.s1 + kk - 1) * M.npix + il];
+            for (int kk = 0; kk < Sp; ++kk) amp[kk] = DEGRADED ? cmodel[(long long)kk * npix_c + i] : c.amp[(long long)(a.s1 + kk - 1) * M.npix + il];
             const int lnl_type = c.lnl_type[q];
             const bool cmasked = is_masked(cmask[i]);
             auto lnl_of = [&](double th) -> double {
@@ -603,7 +669,7 @@ static int fullsky_prepare_impl(dangx_ctx* ctx, int comp, int map_n, bool lazy) 
     ctx->fs_lazy = lazy && lazy_on;
     if (!ctx->fs_lazy) hipLaunchKernelGGL(k_fullsky_prepare, dim3(nblocks(ctx->hm.npix)), dim3(BLOCK), (size_t)ctx->hm.nbands * BLOCK * sizeof(double), ctx->stream, ctx->dm, comp, s1, s2, others, ctx->fs_data);
     HIPCHK(ctx, hipGetLastError());
-    ctx->fs_comp = comp; ctx->fs_s1 = s1; ctx->fs_s2 = s2; ctx->fs_npc = 0;
+    ctx->fs_comp = comp; ctx->fs_s1 = s1; ctx->fs_s2 = s2; ctx->fs_npc = 0; ctx->fs_camp = nullptr;
     return 0;
 }
 int dangx_fullsky_prepare(dangx_ctx* ctx, int comp, int map_n) { return fullsky_prepare_impl(ctx, comp, map_n, false); }
@@ -621,15 +687,22 @@ int dangx_fullsky_sums(dangx_ctx* ctx, int what, const double* theta, double* ou
     const int rows = (what == 1) ? 2 * ctx->hm.nbands * Sp : (what == 3) ? 3 * ctx->hm.nbands * Sp : 1;
     if (nout < rows) return fail(ctx, "output buffer too small");
     const bool coarse = ctx->fs_npc > 0;
+    // the fused statistics pass forms the cleaned data at full resolution: never over the degraded maps
+    if (coarse && ctx->fs_lazy) return fail(ctx, "internal: a lazily staged full-sky prepare with the degraded maps");
+    const double* camp = coarse ? ctx->fs_camp : nullptr;
     const unsigned nblk = nblocks(coarse ? ctx->fs_npc : ctx->hm.npix);
     if (what == 3) {   // the chisq statistics: one pass
         const long long nwp = nblk;
         const size_t ldsz = ((size_t)ctx->hm.nbands * BLOCK + (size_t)rows * (BLOCK / 64) + (size_t)MAXC * Sp * ctx->hm.nbands) * sizeof(double);
         if (ensure_partial(ctx, (long long)rows * nwp)) return 1;
-        hipLaunchKernelGGL(k_fullsky_stats, dim3(nblk), dim3(BLOCK), ldsz, ctx->stream, ctx->dm, ctx->fs_comp, ctx->fs_s1, ctx->fs_s2, theta[0], theta[1],
-                           coarse ? ctx->cs_data : ctx->fs_data, ctx->fs_others, (!coarse && ctx->fs_lazy) ? 1 : 0,
-                           coarse ? ctx->cs_rms : (const double*)nullptr, coarse ? ctx->cs_mask : (const double*)nullptr,
-                           coarse ? ctx->fs_npc : 0ll, ctx->partial);
+        if (camp)
+            hipLaunchKernelGGL(k_fullsky_stats<true>, dim3(nblk), dim3(BLOCK), ldsz, ctx->stream, ctx->dm, ctx->fs_comp, ctx->fs_s1, ctx->fs_s2, theta[0], theta[1],
+                               ctx->cs_data, ctx->fs_others, 0, ctx->cs_rms, ctx->cs_mask, camp, ctx->fs_npc, ctx->partial);
+        else
+            hipLaunchKernelGGL(k_fullsky_stats<false>, dim3(nblk), dim3(BLOCK), ldsz, ctx->stream, ctx->dm, ctx->fs_comp, ctx->fs_s1, ctx->fs_s2, theta[0], theta[1],
+                               coarse ? ctx->cs_data : ctx->fs_data, ctx->fs_others, ctx->fs_lazy ? 1 : 0,
+                               coarse ? ctx->cs_rms : (const double*)nullptr, coarse ? ctx->cs_mask : (const double*)nullptr,
+                               (const double*)nullptr, coarse ? ctx->fs_npc : 0ll, ctx->partial);
         dx_reduce_rows_to(ctx, ctx->partial, nwp, rows, ctx->rows_out);
         HIPCHK(ctx, hipGetLastError());
         HIPCHK(ctx, hipMemcpyAsync(out, ctx->rows_out, sizeof(double) * rows, hipMemcpyDeviceToHost, ctx->stream));
@@ -644,7 +717,7 @@ int dangx_fullsky_sums(dangx_ctx* ctx, int what, const double* theta, double* ou
     if (ensure_partial(ctx, (long long)rows * nblk)) return 1;
     hipLaunchKernelGGL(k_fullsky_rows, dim3(nblk), dim3(BLOCK), 0, ctx->stream, ctx->dm, ctx->fs_comp, ctx->fs_s1, ctx->fs_s2, what,
                        theta[0], theta[1], coarse ? ctx->cs_data : ctx->fs_data, coarse ? ctx->cs_rms : (const double*)nullptr,
-                       coarse ? ctx->cs_mask : (const double*)nullptr, coarse ? ctx->fs_npc : 0ll, ctx->partial);
+                       coarse ? ctx->cs_mask : (const double*)nullptr, camp, coarse ? ctx->fs_npc : 0ll, ctx->partial);
     dx_reduce_rows_to(ctx, ctx->partial, nblk, rows, ctx->rows_out);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(out, ctx->rows_out, sizeof(double) * rows, hipMemcpyDeviceToHost, ctx->stream));
@@ -724,9 +797,30 @@ int dangx_udgrade(dangx_ctx* ctx, int mode, const double* map_in, int nside_in, 
     return 0;
 }
 
+// ---- DANGX_COARSE_DEGRADED: the swept component's amplitude planes s1..s2 and index maps (plane s1), degraded like the data
+static bool cm_on(const dangx_ctx* ctx, int comp, int nind) { return (ctx->cm_degraded[comp] >> nind) & 1u; }
+static long long cm_channels(const dangx_ctx* ctx, int comp, int Sp) { return Sp + ctx->desc[comp].nindices; }
+static int cm_alloc(dangx_ctx* ctx, long long nch, long long npc) {
+    if (nch * npc > ctx->cm_cap) {
+        if (ctx->cs_model) (void)hipFree(ctx->cs_model);
+        ctx->cs_model = nullptr; ctx->cm_cap = 0;
+        HIPCHK(ctx, hipMalloc(&ctx->cs_model, sizeof(double) * nch * npc));
+        ctx->cm_cap = nch * npc;
+    }
+    return 0;
+}
+static void cm_done(dangx_ctx* ctx, int comp, int s1, int s2, int nside, int sample_nside) {
+    ctx->cm_ok = true; ctx->cm_comp = comp; ctx->cm_s1 = s1; ctx->cm_s2 = s2; ctx->cm_nside = nside; ctx->cm_cnside = sample_nside;
+}
+static bool cm_ready(const dangx_ctx* ctx, int comp, int s1, int s2, int nside, int sample_nside) {
+    return ctx->cm_ok && ctx->cm_comp == comp && ctx->cm_s1 == s1 && ctx->cm_s2 == s2 && ctx->cm_nside == nside && ctx->cm_cnside == sample_nside;
+}
+static const char* const CM_MISSING = "DANGX_COARSE_DEGRADED: the degraded amplitude / index maps of this sweep were not finished for the current state (dangx_coarse_model_partials, summed over the shards, then dangx_coarse_model_finish)";
+
 // data_raw minus every other component at full resolution (:173-196, the full-sky mode's staging kernel), degraded with
-// udgrade_ring; the rms with udgrade_rms, the mask with udgrade_mask (:199-217) -> cs_data / cs_rms / cs_mask
-static int coarse_stage(dangx_ctx* ctx, int comp, int map_n, int nside, int sample_nside) {
+// udgrade_ring; the rms with udgrade_rms, the mask with udgrade_mask (:199-217) -> cs_data / cs_rms / cs_mask.  model: also the
+// swept component's amplitude planes and index maps (udgrade_ring, extra channels of the data's launch) -> cs_model
+static int coarse_stage(dangx_ctx* ctx, int comp, int map_n, int nside, int sample_nside, bool model) {
     const long long npix = ctx->dims.npix;
     if (hp_tables(ctx, nside, sample_nside)) return 1;
     const int r1 = nside / sample_nside, ratio = r1 * r1;
@@ -755,16 +849,42 @@ static int coarse_stage(dangx_ctx* ctx, int comp, int map_n, int nside, int samp
     const dim3 gp(nblocks(npc), (Sp * nb + UDG_QC - 1) / UDG_QC);
     // (ratio 4: 16 pixels x 4 waves x 10 planes = 640 summing threads, three rounds of the block: the kernel's three slots)
     const long long per_block = (long long)UDG_G * ((ratio < 64) ? 64 / ratio : 1);
-    const dim3 gw((unsigned)((npc + per_block - 1) / per_block), (Sp * nb + UDG_QW - 1) / UDG_QW);
-    if (by_wave && fuse_stage)   // the cleaned data are formed at the child pixels: the staging pass above was skipped
-        hipLaunchKernelGGL(k_udgrade_wave<true>, gw, dim3(BLOCK), 0, ctx->stream, ctx->dm, comp, ctx->fs_others, Sp, ctx->sig, ctx->cs_data,
-                           ctx->hp_n2r_f, ctx->hp_r2n_c, npix, npc, ratio, 0, scale, 0, nb, ctx->hm.nmaps, s1, Sp * nb);
+    // the model channels: Sp amplitude planes (contiguous), then the nindices index maps at plane s1 (nmaps planes apart)
+    const int nxa = model ? Sp : 0, nxi = model ? ctx->desc[comp].nindices : 0;
+    if (model && cm_alloc(ctx, nxa + nxi, npc)) return 1;
+    const double* xa = model ? ctx->amp[comp] + (long long)(s1 - 1) * npix : nullptr;
+    const double* xi = (model && nxi) ? ctx->idx[comp] + (long long)(s1 - 1) * npix : nullptr;
+    const long long xi_stride = (long long)ctx->hm.nmaps * npix;
+    const int qw = model ? UDG_QW_MODEL : UDG_QW;
+    const dim3 gw((unsigned)((npc + per_block - 1) / per_block), (Sp * nb + nxa + nxi + qw - 1) / qw),
+               gr((unsigned)((npc + per_block - 1) / per_block), (Sp * nb + UDG_QW - 1) / UDG_QW);
+    if (by_wave && fuse_stage && model)   // the cleaned data are formed at the child pixels: the staging pass above was skipped
+        hipLaunchKernelGGL((k_udgrade_wave<true, true>), gw, dim3(BLOCK), 0, ctx->stream, ctx->dm, comp, ctx->fs_others, Sp, ctx->sig, ctx->cs_data,
+                           ctx->hp_n2r_f, ctx->hp_r2n_c, npix, npc, ratio, 0, scale, 0, nb, ctx->hm.nmaps, s1, Sp * nb,
+                           xa, nxa, xi, xi_stride, nxi, ctx->cs_model);
+    else if (by_wave && fuse_stage)
+        hipLaunchKernelGGL((k_udgrade_wave<true, false>), gw, dim3(BLOCK), 0, ctx->stream, ctx->dm, comp, ctx->fs_others, Sp, ctx->sig, ctx->cs_data,
+                           ctx->hp_n2r_f, ctx->hp_r2n_c, npix, npc, ratio, 0, scale, 0, nb, ctx->hm.nmaps, s1, Sp * nb,
+                           xa, nxa, xi, xi_stride, nxi, ctx->cs_model);
+    else if (by_wave && model)
+        hipLaunchKernelGGL((k_udgrade_wave<false, true>), gw, dim3(BLOCK), 0, ctx->stream, ctx->dm, comp, 0u, Sp, ctx->fs_data, ctx->cs_data, ctx->hp_n2r_f, ctx->hp_r2n_c, npix, npc,
+                           ratio, 0, scale, 0, nb, ctx->hm.nmaps, s1, Sp * nb, xa, nxa, xi, xi_stride, nxi, ctx->cs_model);
     else if (by_wave)
-        hipLaunchKernelGGL(k_udgrade_wave<false>, gw, dim3(BLOCK), 0, ctx->stream, ctx->dm, comp, 0u, Sp, ctx->fs_data, ctx->cs_data, ctx->hp_n2r_f, ctx->hp_r2n_c, npix, npc,
-                           ratio, 0, scale, 0, nb, ctx->hm.nmaps, s1, Sp * nb);
-    else
+        hipLaunchKernelGGL((k_udgrade_wave<false, false>), gw, dim3(BLOCK), 0, ctx->stream, ctx->dm, comp, 0u, Sp, ctx->fs_data, ctx->cs_data, ctx->hp_n2r_f, ctx->hp_r2n_c, npix, npc,
+                           ratio, 0, scale, 0, nb, ctx->hm.nmaps, s1, Sp * nb, xa, nxa, xi, xi_stride, nxi, ctx->cs_model);
+    else {
         hipLaunchKernelGGL(k_udgrade_planes, gp, dim3(BLOCK), 0, ctx->stream, ctx->fs_data, ctx->cs_data, ctx->hp_n2r_f, ctx->hp_r2n_c, npix, npc,
                            ratio, 0, scale, 0, nb, ctx->hm.nmaps, s1, Sp * nb);
+        if (model) {   // (DANGX_UDGRADE_WAVE=0) the amplitude planes as layout 0, the index maps as layout 1 with one "band" per index
+            hipLaunchKernelGGL(k_udgrade_planes, dim3(nblocks(npc), 1), dim3(BLOCK), 0, ctx->stream, xa, ctx->cs_model, ctx->hp_n2r_f, ctx->hp_r2n_c,
+                               npix, npc, ratio, 0, scale, 0, 1, ctx->hm.nmaps, s1, nxa);
+            if (nxi)
+                hipLaunchKernelGGL(k_udgrade_planes, dim3(nblocks(npc), 1), dim3(BLOCK), 0, ctx->stream, ctx->idx[comp], ctx->cs_model + (long long)nxa * npc,
+                                   ctx->hp_n2r_f, ctx->hp_r2n_c, npix, npc, ratio, 0, scale, 1, nxi, ctx->hm.nmaps, s1, nxi);
+        }
+    }
+    ctx->fs_lazy = false;   // the staging buffer is consumed (or, fused, never needed)
+    if (model) cm_done(ctx, comp, s1, s2, nside, sample_nside);
     // the degraded rms and mask: the kept copy of this plane set if the maps have not changed since, else degraded and kept
     static const bool keep_on = [] { const char* e = getenv("DANGX_COARSE_KEEP"); return !(e && e[0] == '0'); }();  // A/B switch
     dangx_ctx::CsKept* hit = nullptr;
@@ -777,8 +897,9 @@ static int coarse_stage(dangx_ctx* ctx, int comp, int map_n, int nside, int samp
         return 0;
     }
     if (by_wave)
-        hipLaunchKernelGGL(k_udgrade_wave<false>, gw, dim3(BLOCK), 0, ctx->stream, ctx->dm, comp, 0u, Sp, ctx->rms, ctx->cs_rms, ctx->hp_n2r_f, ctx->hp_r2n_c, npix, npc,
-                           ratio, 1, scale, 1, nb, ctx->hm.nmaps, s1, Sp * nb);
+        hipLaunchKernelGGL((k_udgrade_wave<false, false>), gr, dim3(BLOCK), 0, ctx->stream, ctx->dm, comp, 0u, Sp, ctx->rms, ctx->cs_rms, ctx->hp_n2r_f, ctx->hp_r2n_c, npix, npc,
+                           ratio, 1, scale, 1, nb, ctx->hm.nmaps, s1, Sp * nb, (const double*)nullptr, 0, (const double*)nullptr, 0ll, 0,
+                           (double*)nullptr);
     else
         hipLaunchKernelGGL(k_udgrade_planes, gp, dim3(BLOCK), 0, ctx->stream, ctx->rms, ctx->cs_rms, ctx->hp_n2r_f, ctx->hp_r2n_c, npix, npc,
                            ratio, 1, scale, 1, nb, ctx->hm.nmaps, s1, Sp * nb);
@@ -898,7 +1019,91 @@ int dangx_fullsky_finish_coarse(dangx_ctx* ctx, int comp, int map_n, int nside, 
     if (map_planes(ctx, map_n, s1, s2) || sync_model(ctx)) return 1;
     const long long npc = 12LL * sample_nside * sample_nside;
     if (coarse_finish(ctx, s2 - s1 + 1, npc, nside, sample_nside, partials_sum)) return 1;
-    ctx->fs_comp = comp; ctx->fs_s1 = s1; ctx->fs_s2 = s2; ctx->fs_npc = npc;
+    ctx->fs_comp = comp; ctx->fs_s1 = s1; ctx->fs_s2 = s2; ctx->fs_npc = npc; ctx->fs_camp = nullptr; ctx->fs_lazy = false;
+    return 0;
+}
+
+// ---- DANGX_COARSE_DEGRADED on a pixel shard: the model channels' child sums (one count for all of them), added over the
+// shards, then finished on every shard -> cs_model, valid for the state as it is now.  The buffer exists only for a component
+// with a DEGRADED index (n_model = 0 otherwise, and the two phases refuse): a caller can size it, and skip it, without knowing
+// which indices run which model.
+int dangx_coarse_model_size(dangx_ctx* ctx, int comp, int map_n, int sample_nside, int64_t* n_model) {
+    if (!ctx || !n_model || check_comp(ctx, comp)) return 1;
+    int s1, s2;
+    if (map_planes(ctx, map_n, s1, s2)) return 1;
+    if (!hp_valid_nside(sample_nside)) return fail(ctx, "nside must be a power of two in 1..8192");
+    const long long npc = 12LL * sample_nside * sample_nside;
+    *n_model = ctx->cm_degraded[comp] ? (cm_channels(ctx, comp, s2 - s1 + 1) + 1) * npc : 0;
+    return 0;
+}
+static int cm_check(dangx_ctx* ctx, int comp) {
+    if (!ctx->cm_degraded[comp]) return fail(ctx, "no index of this component runs DANGX_COARSE_DEGRADED: there is no model buffer (dangx_coarse_model_size = 0)");
+    return 0;
+}
+
+static int cm_part_alloc(dangx_ctx* ctx, long long n) {
+    if (n > ctx->cm_part_cap) {
+        if (ctx->cm_part) (void)hipFree(ctx->cm_part);
+        ctx->cm_part = nullptr; ctx->cm_part_cap = 0;
+        HIPCHK(ctx, hipMalloc(&ctx->cm_part, sizeof(double) * n));
+        ctx->cm_part_cap = n;
+    }
+    return 0;
+}
+
+int dangx_coarse_model_partials(dangx_ctx* ctx, int comp, int map_n, int nside, int sample_nside, double* buf) {
+    if (!ctx || !buf || coarse_check(ctx, comp, nside, sample_nside) || cm_check(ctx, comp)) return 1;
+    (void)hipSetDevice(ctx->device);
+    int s1, s2;
+    if (map_planes(ctx, map_n, s1, s2) || hp_tables(ctx, nside, sample_nside) || sync_model(ctx)) return 1;
+    const int Sp = s2 - s1 + 1, nxi = ctx->desc[comp].nindices;
+    const long long npc = 12LL * sample_nside * sample_nside, npl = ctx->dims.npix, nch = cm_channels(ctx, comp, Sp), n = (nch + 1) * npc;
+    const int r1 = nside / sample_nside, ratio = r1 * r1;
+    if (cm_part_alloc(ctx, n)) return 1;
+    hipLaunchKernelGGL(k_udgrade_part_model, dim3(nblocks(npc), (unsigned)nch), dim3(BLOCK), 0, ctx->stream, ctx->amp[comp] + (long long)(s1 - 1) * npl, Sp,
+                       nxi ? ctx->idx[comp] + (long long)(s1 - 1) * npl : (const double*)nullptr, (long long)ctx->hm.nmaps * npl, ctx->cm_part,
+                       ctx->cm_part + nch * npc, ctx->hp_n2r_f, ctx->hp_r2n_c, ctx->dims.pix0, npl, npc, ratio);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(buf, ctx->cm_part, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+int dangx_coarse_model_finish(dangx_ctx* ctx, int comp, int map_n, int nside, int sample_nside, const double* model_sum) {
+    if (!ctx || !model_sum || coarse_check(ctx, comp, nside, sample_nside) || cm_check(ctx, comp)) return 1;
+    (void)hipSetDevice(ctx->device);
+    int s1, s2;
+    if (map_planes(ctx, map_n, s1, s2)) return 1;
+    const long long npc = 12LL * sample_nside * sample_nside, nch = cm_channels(ctx, comp, s2 - s1 + 1), n = (nch + 1) * npc;
+    if (cm_part_alloc(ctx, n) || cm_alloc(ctx, nch, npc)) return 1;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->cm_part, model_sum, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_udgrade_finish_shared, dim3(nblocks(nch * npc)), dim3(BLOCK), 0, ctx->stream, ctx->cm_part, ctx->cm_part + nch * npc,
+                       ctx->cs_model, npc, (int)nch);
+    HIPCHK(ctx, hipGetLastError());
+    cm_done(ctx, comp, s1, s2, nside, sample_nside);
+    return 0;
+}
+
+int dangx_set_coarse_model(dangx_ctx* ctx, int comp, int nind, int model) {
+    if (!ctx || check_comp(ctx, comp)) return 1;
+    if (!ctx->comp_set[comp]) return fail(ctx, "component not set");
+    if (nind < 0 || nind >= ctx->desc[comp].nindices) return fail(ctx, "index number out of range");
+    if (model != DANGX_COARSE_REFERENCE && model != DANGX_COARSE_DEGRADED)
+        return fail(ctx, "coarse model must be DANGX_COARSE_REFERENCE (0) or DANGX_COARSE_DEGRADED (1)");
+    if (model == DANGX_COARSE_DEGRADED) ctx->cm_degraded[comp] |= 1u << nind;
+    else ctx->cm_degraded[comp] &= ~(1u << nind);
+    return 0;
+}
+
+// the sky-wide chains (dangx_sky.hip) before their sums: with the degraded maps and DANGX_COARSE_DEGRADED for (comp, nind), the
+// full-sky sums read the degraded amplitude (cs_model), which must have been made for the prepared planes and the current state
+int dx_fullsky_coarse_model(dangx_ctx* ctx, int comp, int nind) {
+    ctx->fs_camp = nullptr;
+    if (ctx->fs_npc <= 0 || !cm_on(ctx, comp, nind)) return 0;
+    if (!(ctx->cm_ok && ctx->cm_comp == comp && ctx->cm_s1 == ctx->fs_s1 && ctx->cm_s2 == ctx->fs_s2 &&
+          12LL * ctx->cm_cnside * ctx->cm_cnside == ctx->fs_npc))
+        return fail(ctx, CM_MISSING);
+    ctx->fs_camp = ctx->cs_model;
     return 0;
 }
 
@@ -914,6 +1119,8 @@ int dangx_coarse_chains(dangx_ctx* ctx, int comp, int nind, int map_n, int nsamp
     if (map_planes(ctx, map_n, s1, s2) || sync_model(ctx)) return 1;
     const int Sp = s2 - s1 + 1, nb = ctx->hm.nbands;
     const long long npc = 12LL * sample_nside * sample_nside, nq = (long long)Sp * nb * npc;
+    const bool deg = cm_on(ctx, comp, nind);
+    if (deg && !cm_ready(ctx, comp, s1, s2, nside, sample_nside)) return fail(ctx, CM_MISSING);
     if (coarse_finish(ctx, Sp, npc, nside, sample_nside, partials_sum)) return 1;
     (void)nq;
     IndexArgs a{};
@@ -922,8 +1129,12 @@ int dangx_coarse_chains(dangx_ctx* ctx, int comp, int nind, int map_n, int nsamp
     HIPCHK(ctx, hipMemsetAsync(ctx->counters + 1, 0, sizeof(unsigned long long), ctx->stream));
     {
         Timed t(ctx, DANGX_K_INDEX_MH);
-        hipLaunchKernelGGL(k_index_mh_coarse, dim3(nblocks(npc)), dim3(BLOCK), 0, ctx->stream, ctx->dm, a, npc, ctx->cs_data, ctx->cs_rms,
-                           ctx->cs_mask, ctx->cs_index, ctx->counters + 1);
+        if (deg)
+            hipLaunchKernelGGL(k_index_mh_coarse<true>, dim3(nblocks(npc)), dim3(BLOCK), 0, ctx->stream, ctx->dm, a, npc, ctx->cs_data, ctx->cs_rms,
+                               ctx->cs_mask, (const double*)ctx->cs_model, ctx->cs_index, ctx->counters + 1);
+        else
+            hipLaunchKernelGGL(k_index_mh_coarse<false>, dim3(nblocks(npc)), dim3(BLOCK), 0, ctx->stream, ctx->dm, a, npc, ctx->cs_data, ctx->cs_rms,
+                               ctx->cs_mask, (const double*)nullptr, ctx->cs_index, ctx->counters + 1);
     }
     HIPCHK(ctx, hipGetLastError());
     unsigned long long v = 0;
@@ -971,7 +1182,8 @@ int dangx_fullsky_prepare_coarse(dangx_ctx* ctx, int comp, int map_n, int nside,
         return fail(ctx, "coarse-Nside sampling needs ONE whole-sky context (npix = 12*nside^2): the children of a coarse pixel are scattered over the RING ranges of a sharded run");
     if (!(sample_nside < nside)) return fail(ctx, "sample_nside must be smaller than nside (equal: dangx_fullsky_prepare)");
     if (ctx->desc[comp].type > DANGX_TCMB) return fail(ctx, "coarse-Nside sampling is built for the diffuse component types and T_cmb");
-    if (coarse_stage(ctx, comp, map_n, nside, sample_nside)) return 1;
+    // the degraded amplitude too when an index of the component runs DANGX_COARSE_DEGRADED (the chain's entry picks it per index)
+    if (coarse_stage(ctx, comp, map_n, nside, sample_nside, ctx->cm_degraded[comp] != 0)) return 1;
     ctx->fs_comp = comp;
     ctx->fs_npc = 12LL * sample_nside * sample_nside;
     return 0;
@@ -991,6 +1203,14 @@ int dangx_index_sample_coarse(dangx_ctx* ctx, int comp, int nind, int map_n, int
         if (dangx_coarse_sizes(ctx, map_n, sample_nside, &np, &ni)) return 1;
         std::vector<double> part((size_t)np), idx((size_t)ni);
         if (dangx_coarse_partials(ctx, comp, map_n, nside, sample_nside, part.data()) || rank_sum(ctx, part.data(), np)) return 1;
+        if (nind >= 0 && nind < ctx->desc[comp].nindices && cm_on(ctx, comp, nind)) {   // DANGX_COARSE_DEGRADED: the model channels too
+            int64_t nm = 0;
+            if (dangx_coarse_model_size(ctx, comp, map_n, sample_nside, &nm)) return 1;
+            std::vector<double> msum((size_t)nm);
+            if (dangx_coarse_model_partials(ctx, comp, map_n, nside, sample_nside, msum.data()) || rank_sum(ctx, msum.data(), nm) ||
+                dangx_coarse_model_finish(ctx, comp, map_n, nside, sample_nside, msum.data()))
+                return 1;
+        }
         if (dangx_coarse_chains(ctx, comp, nind, map_n, nsample, ml_mode, seed, stream, nside, sample_nside, part.data(), idx.data()) ||
             rank_sum(ctx, idx.data(), ni))
             return 1;
@@ -1003,7 +1223,8 @@ int dangx_index_sample_coarse(dangx_ctx* ctx, int comp, int nind, int map_n, int
     if (d.type > DANGX_TCMB) return fail(ctx, "coarse-Nside sampling is built for the diffuse component types and T_cmb");
     if (d.lnl_type[nind] < DANGX_LNL_CHISQ || d.lnl_type[nind] > DANGX_LNL_PRIOR) return fail(ctx, "bad lnl_type");
     if (ml_mode != DANGX_ML_SAMPLE && ml_mode != DANGX_ML_OPTIMIZE) return fail(ctx, "bad ml_mode");
-    if (coarse_stage(ctx, comp, map_n, nside, sample_nside)) return 1;
+    const bool deg = cm_on(ctx, comp, nind);
+    if (coarse_stage(ctx, comp, map_n, nside, sample_nside, deg)) return 1;
     const int s1 = ctx->fs_s1, s2 = ctx->fs_s2;
     const long long npc = 12LL * sample_nside * sample_nside;
     const int r1 = nside / sample_nside, ratio = r1 * r1;
@@ -1013,8 +1234,12 @@ int dangx_index_sample_coarse(dangx_ctx* ctx, int comp, int nind, int map_n, int
     if (accepted) HIPCHK(ctx, hipMemsetAsync(ctx->counters + 1, 0, sizeof(unsigned long long), ctx->stream));
     {
         Timed t(ctx, DANGX_K_INDEX_MH);
-        hipLaunchKernelGGL(k_index_mh_coarse, dim3(nblocks(npc)), dim3(BLOCK), 0, ctx->stream, ctx->dm, a, npc, ctx->cs_data, ctx->cs_rms,
-                           ctx->cs_mask, ctx->cs_index, accepted ? ctx->counters + 1 : nullptr);
+        if (deg)
+            hipLaunchKernelGGL(k_index_mh_coarse<true>, dim3(nblocks(npc)), dim3(BLOCK), 0, ctx->stream, ctx->dm, a, npc, ctx->cs_data, ctx->cs_rms,
+                               ctx->cs_mask, (const double*)ctx->cs_model, ctx->cs_index, accepted ? ctx->counters + 1 : nullptr);
+        else
+            hipLaunchKernelGGL(k_index_mh_coarse<false>, dim3(nblocks(npc)), dim3(BLOCK), 0, ctx->stream, ctx->dm, a, npc, ctx->cs_data, ctx->cs_rms,
+                               ctx->cs_mask, (const double*)nullptr, ctx->cs_index, accepted ? ctx->counters + 1 : nullptr);
     }
     hipLaunchKernelGGL(k_coarse_writeback, dim3(nblocks(npix)), dim3(BLOCK), 0, ctx->stream, ctx->dm, comp, nind, s1, s2, ctx->cs_index,
                        ctx->hp_r2n_f, ctx->hp_n2r_c, ratio);

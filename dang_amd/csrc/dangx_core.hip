@@ -1259,6 +1259,8 @@ int dangx_destroy(dangx_ctx* ctx) {
     for (auto& kq : ctx->cs_kept) { if (kq.rms) (void)hipFree(kq.rms); if (kq.mask) (void)hipFree(kq.mask); kq.rms = kq.mask = nullptr; kq.cap = kq.capm = 0; kq.gen = -1; }
     if (ctx->cs_part) (void)hipFree(ctx->cs_part);
     ctx->cs_part = nullptr; ctx->cs_part_cap = 0;
+    for (double** b : {&ctx->cs_model, &ctx->cm_part}) { if (*b) (void)hipFree(*b); *b = nullptr; }
+    ctx->cm_cap = ctx->cm_part_cap = 0;
     ctx->hp_nside = ctx->hp_cnside = 0; ctx->cs_cap = 0;
     (void)hipFree(ctx->rows_out);
     (void)hipFree(ctx->dm); (void)hipFree(ctx->scalars); (void)hipFree(ctx->counters); (void)hipFree(ctx->chi_cache);

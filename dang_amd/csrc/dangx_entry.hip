@@ -129,6 +129,7 @@ int dangx_amp_sample(dangx_ctx* ctx, int group, int flag, int ml_mode, int solve
     for (int pl = 0; pl < flag_planes_h(flag); ++pl) {  // the planes' cached chi^2 is stale now
         const int k = (flag & DANGX_FLAG_QU) ? 2 + pl : (flag & DANGX_FLAG_T) ? 1 : (flag & DANGX_FLAG_Q) ? 2 : 3;
         ctx->chi_before_valid[k - 1] = ctx->chi_after_valid[k - 1] = ctx->touched_since_amp[k - 1] = false;
+        ctx->cm_ok = false;   // amplitudes about to be written
         for (int g = 0; g < a.ng; ++g) ctx->plane_nz[a.gc[g]] |= 1u << (k - 1);  // about to be written
     }
     if (cg_iters) *cg_iters = 0;
@@ -230,6 +231,7 @@ int dangx_sky_amp_sample(dangx_ctx* const* ctxs, int nctx, int group, int flag, 
         for (int pl = 0; pl < flag_planes_h(flag); ++pl) {
             const int k = (flag & DANGX_FLAG_QU) ? 2 + pl : (flag & DANGX_FLAG_T) ? 1 : (flag & DANGX_FLAG_Q) ? 2 : 3;
             c->chi_before_valid[k - 1] = c->chi_after_valid[k - 1] = c->touched_since_amp[k - 1] = false;
+            c->cm_ok = false;
             for (int g = 0; g < as[r].ng; ++g) c->plane_nz[as[r].gc[g]] |= 1u << (k - 1);
         }
         if (as[r].nglob != as[0].nglob || as[r].nt != as[0].nt) return fail(c0, "the contexts disagree on the group's global-amplitude members");
@@ -470,6 +472,7 @@ static int planeset_launch(dangx_ctx* ctx, const GroupArgs& g, const SweepList& 
     if (solve) {
         for (int k = sl.s1; k <= sl.s2; ++k) {
             ctx->chi_before_valid[k - 1] = ctx->chi_after_valid[k - 1] = ctx->touched_since_amp[k - 1] = false;
+            ctx->cm_ok = false;   // amplitudes about to be written
             for (int q = 0; q < g.ng; ++q) ctx->plane_nz[g.gc[q]] |= 1u << (k - 1);
         }
     } else {
@@ -724,6 +727,7 @@ int dangx_sky_plane_set_sample(dangx_ctx* const* ctxs, int nctx, int group, int 
         SNs[r] = (long long)flag_planes_h(flag) * c->hm.npix;
         for (int k = s1; k <= s2; ++k) {
             c->chi_before_valid[k - 1] = c->chi_after_valid[k - 1] = c->touched_since_amp[k - 1] = false;
+            c->cm_ok = false;
             for (int g = 0; g < as[r].ng; ++g) c->plane_nz[as[r].gc[g]] |= 1u << (k - 1);
         }
         if (as[r].nglob != as[0].nglob || as[r].nt != as[0].nt) return fail(c0, "the contexts disagree on the group's global-amplitude members");

@@ -280,6 +280,25 @@ int prepare(const Sky& s, int comp, int map_n, int nside, int sample_nside) {
     if (sky_ranks(s, sum.data(), (int)np)) return 1;
     for (int r = 0; r < s.n; ++r)
         if (dangx_fullsky_finish_coarse(s.c[r], comp, map_n, nside, sample_nside, sum.data())) return sky_err(s, s.c[r]);
+    if (c0->cm_degraded[comp]) {   // DANGX_COARSE_DEGRADED: the degraded amplitude as well, the shards' child sums added the same way
+        int64_t nm = 0;
+        if (dangx_coarse_model_size(c0, comp, map_n, sample_nside, &nm)) return 1;
+        std::vector<double> msum((size_t)nm, 0.0), mpart((size_t)nm);
+        for (int r = 0; r < s.n; ++r) {
+            if (dangx_coarse_model_partials(s.c[r], comp, map_n, nside, sample_nside, mpart.data())) return sky_err(s, s.c[r]);
+            for (int64_t q = 0; q < nm; ++q) msum[(size_t)q] += mpart[(size_t)q];
+        }
+        if (sky_ranks(s, msum.data(), (int)nm)) return 1;
+        for (int r = 0; r < s.n; ++r)
+            if (dangx_coarse_model_finish(s.c[r], comp, map_n, nside, sample_nside, msum.data())) return sky_err(s, s.c[r]);
+    }
+    return 0;
+}
+
+// the coarse model of (comp, nind) on every context before the chain's sums (dangx_set_coarse_model)
+int coarse_model(const Sky& s, int comp, int nind) {
+    for (int r = 0; r < s.n; ++r)
+        if (dx_fullsky_coarse_model(s.c[r], comp, nind)) return sky_err(s, s.c[r]);
     return 0;
 }
 
@@ -307,7 +326,7 @@ int dangx_fullsky_sample(dangx_ctx* const* ctxs, int nctx, int comp, int nind, i
     const dangx_comp_desc& d = c0->desc[comp];
     int32_t all_tuned[DANGX_MAX_IND] = {1, 1};
     if (!tuned) tuned = all_tuned;
-    if (prepare(s, comp, map_n, nside, sample_nside)) return 1;
+    if (prepare(s, comp, map_n, nside, sample_nside) || coarse_model(s, comp, nind)) return 1;
     double first[2], sample[2], theta[2];
     if (first_pixel(s, comp, s1, first)) return 1;
     sample[0] = theta[0] = first[0]; sample[1] = theta[1] = first[1];
@@ -381,6 +400,7 @@ int dangx_tune_step_size(dangx_ctx* const* ctxs, int nctx, int comp, int nind, i
     if (check_index(c0, comp, nind)) return 1;
     for (int r = 0; r < nctx; ++r)
         if (ctxs[r]->fs_comp != comp) return fail(c0, "dangx_fullsky_prepare has not been called for this component");
+    if (coarse_model(s, comp, nind)) return 1;
     if (tune(s, comp, nind, c0->fs_s2 - c0->fs_s1 + 1, nsample, ml_mode, seed, stream, theta_init, draw, tuned)) return 1;
     if (step_size) *step_size = c0->desc[comp].step_size[nind];
     return 0;

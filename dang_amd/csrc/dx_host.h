@@ -99,6 +99,18 @@ struct dangx_ctx {
     long long data_gen = 0, cs_stamp = 0;   // data_gen: bumped whenever sig / rms / mask are replaced or rescaled
     double* cs_part = nullptr;              // per-shard sums / counts of the degrade step (pixel-sharded coarse sampling)
     long long cs_part_cap = 0;
+    // coarse model (dangx_set_coarse_model): bit q of cm_degraded[l] = index q of component l runs DANGX_COARSE_DEGRADED -- its chains
+    // read the degraded amplitude planes and index maps of the swept component (cs_model: [Sp][npc] amplitudes, then [nindices][npc]
+    // indices at plane s1).  cm_ok: cs_model holds them for the state as it is now, for cm_comp / cm_s1..cm_s2 / cm_nside -> cm_cnside;
+    // anything that writes amplitudes, indices, the mask or the model through the library drops it (state_written)
+    unsigned cm_degraded[MAXC] = {};
+    double* cs_model = nullptr;
+    long long cm_cap = 0;
+    double* cm_part = nullptr;              // per-shard child sums of the model channels + the shared child count
+    long long cm_part_cap = 0;
+    bool cm_ok = false;
+    int cm_comp = -1, cm_s1 = 0, cm_s2 = 0, cm_nside = 0, cm_cnside = 0;
+    const double* fs_camp = nullptr;        // non-null: the coarse full-sky sums read the swept component's amplitude here ([Sp][fs_npc])
     long long work_cap = 0;
     // last DANGX_SOLVER_DIRECT solve of a group with global-amplitude members: largest |b - A x| of a global row relative
     // to that row of b after the last refinement, and the number of refinement steps taken
@@ -155,6 +167,7 @@ const char* dx_kernel_family(int kid);
 // the chi^2 sums cached by the index sweeps describe a model that no longer exists: every setter that changes the
 // model (T_CMB, calibration, host pushes of state, new data, new descriptors) calls this
 inline void invalidate_chi(dangx_ctx* ctx) {
+    ctx->cm_ok = false;   // the degraded model channels describe that model too
     for (int k = 0; k < 3; ++k) ctx->chi_before_valid[k] = ctx->chi_after_valid[k] = false;
     if (ctx->chi_npend) {   // the dropped entries carry the index sums of their launches too: those fall back to the explicit pass
         for (int l = 0; l < MAXC; ++l)
@@ -165,6 +178,7 @@ inline void invalidate_chi(dangx_ctx* ctx) {
 
 // an index map of component `comp` (comp < 0: any map, or the mask) is about to change: its cached masked sums are stale
 inline void idx_written(dangx_ctx* ctx, int comp) {
+    ctx->cm_ok = false;
     for (int l = 0; l < MAXC; ++l)
         if (comp < 0 || l == comp)
             for (int q = 0; q < MAXI; ++q) for (int k = 0; k < 3; ++k) ctx->idxsum_ok[l][q][k] = ctx->idxsum_dev[l][q][k] = false;
@@ -232,6 +246,7 @@ int reduce_to_host(dangx_ctx* ctx, long long nblk, double* out);
 int rank_sum(dangx_ctx* ctx, double* buf, int64_t n);
 int device_cg(dangx_ctx* ctx, const GroupArgs& a, int i_max, double converge, int* iters);
 extern "C" int dx_fullsky_prepare_lazy(dangx_ctx* ctx, int comp, int map_n);   // dangx_fullsky_prepare without the staging pass (dangx_coarse.hip)
+extern "C" int dx_fullsky_coarse_model(dangx_ctx* ctx, int comp, int nind);   // DANGX_COARSE_DEGRADED: the coarse full-sky sums on the degraded amplitude (dangx_coarse.hip)
 double dx_host_band_sed(dangx_ctx* ctx, int comp, int j, double t0, double t1);   // eval_sed of a diffuse component, host side
 int device_schur(dangx_ctx* const* cs, int nc, const GroupArgs* as, const long long* SNs, int64_t* n_not_spd, int* nullity, int* defer = nullptr);
 // map_n of sample_index_mh (src/dang_sample_mod.f90:53-64) -> first and last map plane

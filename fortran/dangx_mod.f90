@@ -22,6 +22,7 @@ module dangx_mod
   integer(c_int), parameter :: DANGX_FLAG_T = 1, DANGX_FLAG_Q = 2, DANGX_FLAG_U = 4, DANGX_FLAG_QU = 8
   integer(c_int), parameter :: DANGX_SOLVER_DIRECT = 0, DANGX_SOLVER_CG = 1
   integer(c_int), parameter :: DANGX_FLUCT_CORRECT = 0, DANGX_FLUCT_REFERENCE = 1
+  integer(c_int), parameter :: DANGX_COARSE_REFERENCE = 0, DANGX_COARSE_DEGRADED = 1
   integer(c_int), parameter :: DANGX_A2T = 0, DANGX_A2F = 1, DANGX_F2T = 2
   integer(c_int), parameter :: DANGX_UNIT_UK_RJ = 0, DANGX_UNIT_UK_CMB = 1, DANGX_UNIT_MJY_SR = 2
 
@@ -268,6 +269,31 @@ module dangx_mod
        import :: c_int, c_ptr
        type(c_ptr), value :: ctx, index_sum
        integer(c_int), value :: comp, nind, map_n, nside, sample_nside
+     end function
+     ! the coarse model of (comp, nind), both 0-based: DANGX_COARSE_REFERENCE (default) or DANGX_COARSE_DEGRADED, on every context
+     integer(c_int) function dangx_set_coarse_model(ctx, comp, nind, model) bind(C, name='dangx_set_coarse_model')
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: comp, nind, model
+     end function
+     ! DANGX_COARSE_DEGRADED on pixel shards: the model buffer, added over the shards between phases A and B
+     integer(c_int) function dangx_coarse_model_size(ctx, comp, map_n, sample_nside, n_model) bind(C, name='dangx_coarse_model_size')
+       import :: c_int, c_ptr, c_int64_t
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: comp, map_n, sample_nside
+       integer(c_int64_t), intent(out) :: n_model
+     end function
+     integer(c_int) function dangx_coarse_model_partials(ctx, comp, map_n, nside, sample_nside, buf) &
+          bind(C, name='dangx_coarse_model_partials')
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx, buf
+       integer(c_int), value :: comp, map_n, nside, sample_nside
+     end function
+     integer(c_int) function dangx_coarse_model_finish(ctx, comp, map_n, nside, sample_nside, model_sum) &
+          bind(C, name='dangx_coarse_model_finish')
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx, model_sum
+       integer(c_int), value :: comp, map_n, nside, sample_nside
      end function
      integer(c_int) function dangx_udgrade(ctx, mode, map_in, nside_in, map_out, nside_out) bind(C, name='dangx_udgrade')
        import :: c_int, c_ptr

@@ -379,8 +379,8 @@ contains
     integer, intent(in) :: comp, nind, map_n, nsample, ml_mode, nside, sample_nside
     integer(c_int64_t), intent(in) :: seed, stream
     integer(c_int64_t), intent(out) :: accepted
-    integer(c_int64_t) :: np, ni
-    real(c_double), allocatable, target :: part(:), psum(:), idx(:), isum(:)
+    integer(c_int64_t) :: np, ni, nm
+    real(c_double), allocatable, target :: part(:), psum(:), idx(:), isum(:), mpart(:), msum(:)
     integer :: r
     if (sky%nctx == 1 .and. sky%npix(1) == sky%npix_global) then     ! one whole-sky context: the direct form
        call dangx_check(sky%ctx(1), dangx_index_sample_coarse(sky%ctx(1), comp, nind, map_n, nsample, ml_mode, seed, stream, &
@@ -395,6 +395,22 @@ contains
             'dangx_coarse_partials')
        psum = psum + part
     end do
+    ! DANGX_COARSE_DEGRADED (dangx_set_coarse_model on every context): the degraded amplitude / index maps, summed the same way;
+    ! nm = 0 when no index of the component runs it
+    call dangx_check(sky%ctx(1), dangx_coarse_model_size(sky%ctx(1), comp, map_n, sample_nside, nm), 'dangx_coarse_model_size')
+    if (nm > 0) then
+       allocate(mpart(nm), msum(nm))
+       msum = 0.d0
+       do r = 1, sky%nctx
+          call dangx_check(sky%ctx(r), dangx_coarse_model_partials(sky%ctx(r), comp, map_n, nside, sample_nside, c_loc(mpart)), &
+               'dangx_coarse_model_partials')
+          msum = msum + mpart
+       end do
+       do r = 1, sky%nctx
+          call dangx_check(sky%ctx(r), dangx_coarse_model_finish(sky%ctx(r), comp, map_n, nside, sample_nside, c_loc(msum)), &
+               'dangx_coarse_model_finish')
+       end do
+    end if
     do r = 1, sky%nctx
        call dangx_check(sky%ctx(r), dangx_coarse_chains(sky%ctx(r), comp, nind, map_n, nsample, ml_mode, seed, stream, nside, &
             sample_nside, c_loc(psum), c_loc(idx)), 'dangx_coarse_chains')

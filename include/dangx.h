@@ -65,6 +65,11 @@ enum { DANGX_SOLVER_DIRECT = 0, DANGX_SOLVER_CG = 1 };
  * its two quirks (src/dang_cg_mod.f90:1008-1015 one eta for all bands; :1033-1040 no
  * component offset); CORRECT draws the textbook sum_nu T^t N^-1/2 eta_nu. */
 enum { DANGX_FLUCT_CORRECT = 0, DANGX_FLUCT_REFERENCE = 1 };
+/* what a chain at a coarser Nside (sample_nside < nside) reads of the swept component (dangx_set_coarse_model):
+ * REFERENCE reproduces the reference -- c%amplitude(i,k), c%indices(i,..) and ddata%masks(i,1) of the FULL-resolution
+ * arrays at the coarse pixel number i (src/dang_sample_mod.f90:362, 372-377, 548-563); DEGRADED reads the component's
+ * amplitude planes and index maps degraded like the data (udgrade_ring) and skips where the degraded mask is masked. */
+enum { DANGX_COARSE_REFERENCE = 0, DANGX_COARSE_DEGRADED = 1 };
 
 /* kernel ids for dangx_profile_get / dangx_profile_get_planes */
 enum {
@@ -287,7 +292,8 @@ int dangx_chisq_current(dangx_ctx *ctx, int pol_lo, int pol_hi, double *chisq_su
  * (mean >= 0.5); one chain per COARSE pixel i; the coarse index map is upgraded (children take the parent's value) and
  * written to c%indices(:, s1:s2, nind) for EVERY pixel.  Also as in the reference, the chain of coarse pixel i reads
  * the FULL-resolution arrays at the same index i (ddata%masks(i,1), c%indices(i,...), and eval_signal's
- * c%amplitude(i,k): src/dang_sample_mod.f90:362, 372-377, 548-553): reproduced literally, see DESIGN.md section 7.
+ * c%amplitude(i,k): src/dang_sample_mod.f90:362, 372-377, 548-553): reproduced literally, see DESIGN.md section 7 -- unless
+ * dangx_set_coarse_model chose DANGX_COARSE_DEGRADED for (comp, nind), below.
  * HEALPix itself is absent from the reference tree (an external library): udgrade_ring / nest2ring are restated from
  * the published algorithm (Gorski et al. 2005, ApJ 622, 759; HEALPix 3.x pix_tools / udgrade_nr).
  * Likelihoods: chisq / marginal / prior; priors: gaussian / uniform / jeffreys; diffuse component types and T_cmb. */
@@ -312,6 +318,28 @@ int dangx_coarse_partials(dangx_ctx *ctx, int comp, int map_n, int nside, int sa
 int dangx_coarse_chains(dangx_ctx *ctx, int comp, int nind, int map_n, int nsample, int ml_mode, uint64_t seed, uint64_t stream,
                         int nside, int sample_nside, const double *partials_sum, double *index_out);
 int dangx_coarse_writeback(dangx_ctx *ctx, int comp, int nind, int map_n, int nside, int sample_nside, const double *index_sum);
+/* The coarse model of index nind (0-based) of component comp: DANGX_COARSE_REFERENCE (the default) or DANGX_COARSE_DEGRADED.
+ * Sticky per context; set it on EVERY context of a sky.  With DEGRADED the chain of coarse pixel p reads
+ *   amp_c[k](p) = udgrade_ring(c%amplitude(:,k)), k = s1..s2 (mean of the children in NESTED order, dangx_udgrade mode 0),
+ *   idx_c[n](p) = udgrade_ring(c%indices(:,s1,n)) for every index n (the swept one is the chain's start, the others enter the SED),
+ * and is skipped where the degraded mask is masked -- a skipped pixel keeps its starting value idx_c (the reference's 0 is
+ * no usable index: a dust temperature of 0 makes the children's SEDs NaN); data / rms / mask, likelihoods, priors, bounds,
+ * draw slots and the write-back (children take the parent's value) are unchanged.  The full-sky chain at a coarser Nside and
+ * its tuner use amp_c.  Honoured by dangx_index_sample_coarse (whole sky, and shards through dangx_set_allreduce),
+ * dangx_fullsky_sample, dangx_tune_step_size and the dangx_sky_* wrappers.
+ * Several contexts of one process drive DEGRADED with three more entries between phases A and B (the three-phase entries
+ * above keep their buffers and results):
+ *   dangx_coarse_model_size     : length of the model buffer, (Sp + nindices + 1) * 12*sample_nside^2 -- 0 when no index of
+ *                                 comp runs DEGRADED (then there is nothing to add, and the two calls below refuse)
+ *   dangx_coarse_model_partials : per coarse pixel this shard's child sums of the Sp amplitude planes and nindices index
+ *                                 maps, then the number of those children (one count: amplitudes are never MISSVAL)
+ *   dangx_coarse_model_finish   : the degraded amplitudes / indices from the SUMMED buffer, valid until the state changes;
+ *                                 also before dangx_tune_step_size on shards prepared by dangx_fullsky_finish_coarse
+ * dangx_coarse_chains (and dangx_tune_step_size) of a DEGRADED index without finished model sums for the current state fail. */
+int dangx_set_coarse_model(dangx_ctx *ctx, int comp, int nind, int model);
+int dangx_coarse_model_size(dangx_ctx *ctx, int comp, int map_n, int sample_nside, int64_t *n_model);
+int dangx_coarse_model_partials(dangx_ctx *ctx, int comp, int map_n, int nside, int sample_nside, double *buf);
+int dangx_coarse_model_finish(dangx_ctx *ctx, int comp, int map_n, int nside, int sample_nside, const double *model_sum);
 /* the degrade / upgrade primitives on their own (whole-sky context): mode 0 = udgrade_ring, 1 = udgrade_rms,
  * 2 = udgrade_mask(threshold 0.5); host pointers, one map each ([12*nside_in^2] -> [12*nside_out^2]) */
 int dangx_udgrade(dangx_ctx *ctx, int mode, const double *map_in, int nside_in, double *map_out, int nside_out);
@@ -347,7 +375,8 @@ int dangx_fullsky_prepare(dangx_ctx *ctx, int comp, int map_n);
 /* the same mode with c%sample_nside(nind) /= nside (:199-217): the cleaned data, the rms and the mask are degraded first
  * (udgrade_ring / udgrade_rms / udgrade_mask), dangx_fullsky_sums then runs over the 12*sample_nside^2 coarse pixels --
  * with eval_signal's c%amplitude read from the full-resolution array at the coarse pixel number, as in the reference
- * (see dangx_index_sample_coarse).  One whole-sky context. */
+ * (see dangx_index_sample_coarse; with DANGX_COARSE_DEGRADED for any index of comp the degraded amplitude is made too, and
+ * dangx_fullsky_sample / dangx_tune_step_size read it for those indices).  One whole-sky context. */
 int dangx_fullsky_prepare_coarse(dangx_ctx *ctx, int comp, int map_n, int nside, int sample_nside);
 int dangx_fullsky_sums(dangx_ctx *ctx, int what, const double *theta, double *out, int nout);
 int dangx_fill_index(dangx_ctx *ctx, int comp, int nind, int map_n, double value);
