@@ -24,9 +24,10 @@ COARSE_REFERENCE, COARSE_DEGRADED = 0, 1
 COARSE_MODEL_CODES = {"reference": COARSE_REFERENCE, "degraded": COARSE_DEGRADED}
 A2T, A2F, F2T = 0, 1, 2
 UNIT_CODES = {"uK_RJ": 0, "uK_cmb": 1, "MJy/sr": 2}
-K_AMP_DIRECT, K_INDEX_MH, K_SKY_CHISQ, K_REDUCE, K_CG_AX, K_CG_VEC, K_AMP_INDEX = range(7)
+K_AMP_DIRECT, K_INDEX_MH, K_SKY_CHISQ, K_REDUCE, K_CG_AX, K_CG_VEC, K_AMP_INDEX, K_MOMENTS = range(8)
 KERNEL_NAMES = {K_AMP_DIRECT: "k_amp_direct", K_INDEX_MH: "k_index_mh", K_SKY_CHISQ: "k_sky_chisq",
-                K_REDUCE: "k_reduce", K_CG_AX: "k_Ax", K_CG_VEC: "k_cg_vec", K_AMP_INDEX: "k_amp_index"}
+                K_REDUCE: "k_reduce", K_CG_AX: "k_Ax", K_CG_VEC: "k_cg_vec", K_AMP_INDEX: "k_amp_index", K_MOMENTS: "k_moments"}
+STAT_CODES = {"mean": 0, "std": 1}
 
 TYPE_CODES = {"power-law": POWERLAW, "mbb": MBB, "freefree": FREEFREE, "lognormal": LOGNORMAL, "cmb": CMB, "T_cmb": TCMB,
               "template": TEMPLATE, "monopole": MONOPOLE, "hi_fit": HIFIT}
@@ -143,6 +144,13 @@ SYMBOLS = {
     "dangx_eval_sed": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
     "dangx_rtc_kernels": (C.c_int, [_P, C.POINTER(C.c_int), C.c_char_p, C.c_int]),
     "dangx_rtc_compile": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int]),
+    "dangx_moments_begin": (C.c_int, [_P, _P]),
+    "dangx_moments_accumulate": (C.c_int, [_P]),
+    "dangx_moments_count": (C.c_int, [_P, C.POINTER(C.c_int64)]),
+    "dangx_moments_get": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "dangx_moments_get_dev": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "dangx_moments_get_template": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
+    "dangx_moments_end": (C.c_int, [_P]),
     "dangx_profile_enable": (C.c_int, [_P, C.c_int]),
     "dangx_profile_reset": (C.c_int, [_P]),
     "dangx_profile_get": (C.c_int, [_P, C.c_int, _D, C.POINTER(C.c_int64)]),

@@ -160,6 +160,7 @@ class Engine:
         self.pix0 = int(pix0)
         self.npix_global = int(npix_global if npix_global is not None else npix)
         self._keep = []
+        self._device = device
         dims = L.Dims(npix, nmaps, nb, self.ncomp, self.pix0, self.npix_global, device, 0)
         h = C.c_void_p()
         rc = self.lib.dangx_create(C.byref(h), C.byref(dims))
@@ -616,6 +617,61 @@ class Engine:
         assert len(names) == n.value or len(buf.value) >= len(buf) - 1
         return names
 
+    # -- posterior moments (dangx_moments_*: the chain's running mean / second moment, accumulated in HBM)
+    def moments_begin(self, sel=None):
+        """Start (or restart) accumulating: sel[l] = selection word of component l (include/dangx.h; None = every plane)."""
+        if sel is None:
+            self._chk(self.lib.dangx_moments_begin(self.h, None))
+            full = (1 << self.nmaps) - 1
+            self._moment_sel = np.array([full | sum(full << (3 + 3 * j) for j in range(c.nindices)) for c in self.component_list],
+                                        dtype=np.int32)
+            return
+        s = np.ascontiguousarray(sel, dtype=np.int32)
+        assert s.shape == (self.ncomp,)
+        self._chk(self.lib.dangx_moments_begin(self.h, s.ctypes.data))
+        self._moment_sel = s.copy()
+
+    def moments_accumulate(self):
+        """One sample of the current state, enqueued on the context's stream (no host wait)."""
+        self._chk(self.lib.dangx_moments_accumulate(self.h))
+
+    def moments_count(self):
+        n = C.c_int64(0)
+        self._chk(self.lib.dangx_moments_count(self.h, C.byref(n)))
+        return n.value
+
+    def moments_get(self, l, what, stat, ddof=0, device=False, out=None):
+        """Mean (stat 'mean' / 0) or standard deviation ('std' / 1, sqrt(m2 / (n - ddof))) of component l's amplitude (what 0)
+        or index j (what 1 + j) as [nmaps][npix].  Planes that are not selected keep what `out` holds (default zeros).
+        device=True: a torch cuda tensor filled on the device (no host round trip)."""
+        st = L.STAT_CODES[stat] if isinstance(stat, str) else int(stat)
+        if device:
+            import torch
+            if out is None:
+                dev = self._device if self._device is not None and self._device >= 0 else torch.cuda.current_device()
+                out = torch.zeros((self.nmaps, self.npix), dtype=torch.float64, device=torch.device("cuda", dev))
+            assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float64 and tuple(out.shape) == (self.nmaps, self.npix)
+            self._chk(self.lib.dangx_moments_get_dev(self.h, l, int(what), st, int(ddof), out.data_ptr()))
+            self.synchronize()
+            return out
+        if out is None:
+            out = np.zeros((self.nmaps, self.npix))
+        assert isinstance(out, np.ndarray) and out.dtype == np.float64 and out.flags.c_contiguous and out.shape == (self.nmaps, self.npix)
+        self._chk(self.lib.dangx_moments_get(self.h, l, int(what), st, int(ddof), out.ctypes.data))
+        return out
+
+    def moments_get_template(self, l, stat, ddof=0, out=None):
+        """Moments of c%template_amplitudes of a template / monopole / hi_fit member, [nmaps][nbands]."""
+        st = L.STAT_CODES[stat] if isinstance(stat, str) else int(stat)
+        if out is None:
+            out = np.zeros((self.nmaps, self.nbands))
+        assert out.dtype == np.float64 and out.flags.c_contiguous and out.shape == (self.nmaps, self.nbands)
+        self._chk(self.lib.dangx_moments_get_template(self.h, l, st, int(ddof), out.ctypes.data))
+        return out
+
+    def moments_end(self):
+        self._chk(self.lib.dangx_moments_end(self.h))
+
     # -- profiling
     def profile(self, on=True):
         self._chk(self.lib.dangx_profile_enable(self.h, 1 if on else 0))
@@ -984,6 +1040,94 @@ def gibbs_iteration(dpar: DangParams, ddata: DangData, it, verbose=False, want_c
     a = sample_cg_groups(dpar, ddata, it=it, verbose=False, defer_chisq=True, fuse_first=done, it_index=it, want_counts=want_counts)
     b = sample_spectral_parameters(dpar, ddata, it=it, verbose=verbose, skip=done, want_counts=want_counts)
     return a, b
+
+
+# --------------------------------------------------------------------------- posterior moments
+# The reference writes every sample (write_maps every iter_out iterations, src/dang.f90:119-121) and averages the files afterwards
+# (scripts/make_mean_maps.py: return_mean_map, return_std_map = np.std).  Here the moments accumulate on the device and are read once.
+
+_FLAG_PLANES = ((L.FLAG_T, 1), (L.FLAG_Q, 2), (L.FLAG_U, 4), (L.FLAG_QU, 6))   # poltype bit -> plane bits T=1, Q=2, U=4
+GLOBAL_TYPES = ("template", "monopole", "hi_fit")
+
+
+def _flag_planes(flag):
+    return sum(bits for f, bits in _FLAG_PLANES if flag & f) & 7
+
+
+def default_moment_selection(dpar, component_list):
+    """Selection words (include/dangx.h, dangx_moments_begin) of what a run samples: amplitude plane k of component l when
+    c.sample_amplitude holds and a CG group with c's cg_group has a pol_flag covering k; index plane k of index j when
+    c.sample_index[j] holds and a flag of c.pol_flag[j] covers k.  Pure Python: needs no device."""
+    sel = np.zeros(len(component_list), dtype=np.int32)
+    for l, c in enumerate(component_list):
+        if c.sample_amplitude:
+            for g in dpar.cg_groups:
+                if g.cg_group == c.cg_group:
+                    for f in g.pol_flag:
+                        sel[l] |= _flag_planes(f)
+        for j in range(c.nindices):
+            if j < len(c.sample_index) and c.sample_index[j]:
+                for f in (c.pol_flag[j] if j < len(c.pol_flag) else []):
+                    sel[l] |= _flag_planes(f) << (3 + 3 * j)
+    return sel
+
+
+def moments_begin(dpar, ddata, sel=None, engines=None):
+    """dangx_moments_begin on every context of this process; sel=None: default_moment_selection(dpar, ...).  Returns the selection."""
+    engs = _engines_of(ddata, engines)
+    if sel is None:
+        sel = default_moment_selection(dpar, engs[0].component_list)
+    sel = np.ascontiguousarray(sel, dtype=np.int32)
+    for e in engs:
+        e.moments_begin(sel)
+    return sel
+
+
+def moments_accumulate(ddata, engines=None):
+    """One sample of the current state on every context (asynchronous on each context's stream)."""
+    for e in _engines_of(ddata, engines):
+        e.moments_accumulate()
+
+
+def _mask_fill(m, mask, value):
+    """Pixels whose mask (plane 1, as the reference tests it; make_mean_maps.py's mask[i] == 0) is 0 get `value` on every plane."""
+    mask1 = np.asarray(mask.cpu().numpy() if _is_torch(mask) else mask)[0]
+    out = np.array(m, dtype=np.float64, copy=True)
+    out[..., mask1 == 0] = value
+    return out
+
+
+def posterior_maps(ddata, ddof=0, masked_value=None, engines=None):
+    """{(label, 'amplitude' | ind_label): {'mean', 'std', 'n'}} of what moments_begin selected, as host arrays ([nmaps][npix]; template
+    / monopole / hi_fit amplitudes [nmaps][nbands]).  Several contexts of this process (shard order): their shards side by side.
+    masked_value (e.g. MISSVAL, healpy's UNSEEN, as make_mean_maps.py writes): pixels masked in ddata.masks plane 1 get it.
+    With several ranks each rank returns its shard: dist.gather_maps(..., bounds) assembles the sky, as for the state."""
+    engs = _engines_of(ddata, engines)
+    counts = {e.moments_count() for e in engs}
+    if len(counts) != 1:
+        raise DangxError("posterior_maps: the contexts hold different sample counts %s" % sorted(counts))
+    n = counts.pop()
+    sel = getattr(engs[0], "_moment_sel", None)
+    if sel is None:
+        raise DangxError("posterior_maps: moments_begin was not called")
+    out = {}
+    for l, c in enumerate(engs[0].component_list):
+        for what in range(1 + c.nindices):
+            if not (int(sel[l]) >> (0 if what == 0 else 3 + 3 * (what - 1))) & 7:
+                continue
+            key = (c.label, "amplitude" if what == 0 else (c.ind_label[what - 1] if what - 1 < len(c.ind_label) else "index%d" % what))
+            entry = {"n": n}
+            for stat in ("mean", "std"):
+                if what == 0 and c.type in GLOBAL_TYPES:
+                    entry[stat] = engs[0].moments_get_template(l, stat, ddof)
+                    continue
+                parts = []
+                for e in engs:
+                    m = e.moments_get(l, what, stat, ddof)
+                    parts.append(_mask_fill(m, e.ddata.masks, masked_value) if masked_value is not None else m)
+                entry[stat] = np.concatenate(parts, axis=-1) if len(parts) > 1 else parts[0]
+            out[key] = entry
+    return out
 
 
 # --------------------------------------------------------------------------- full-sky mode, tuner, calibrators

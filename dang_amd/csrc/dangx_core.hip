@@ -31,7 +31,7 @@ const DxRoctx& dx_roctx() {
 }
 const char* dx_kernel_family(int kid) {
     static const char* const names[DANGX_K_COUNT] = {"dangx:amplitude_solve", "dangx:index_sweep", "dangx:sky_chisq", "dangx:reduce",
-                                                     "dangx:cg_Ax", "dangx:cg_vec", "dangx:solve+sweeps", "dangx:other"};
+                                                     "dangx:cg_Ax", "dangx:cg_vec", "dangx:solve+sweeps", "dangx:moments"};
     return (kid >= 0 && kid < DANGX_K_COUNT) ? names[kid] : "dangx:?";
 }
 
@@ -1243,6 +1243,7 @@ int dangx_destroy(dangx_ctx* ctx) {
     if (!ctx) return 0;
     (void)hipSetDevice(ctx->device);
     (void)hipDeviceSynchronize();
+    dx_moments_free(ctx);
     if (ctx->own_data) { (void)hipFree(ctx->sig); (void)hipFree(ctx->rms); (void)hipFree(ctx->mask); }
     for (int l = 0; l < MAXC; ++l) {
         if (ctx->amp[l] && ctx->own_amp[l]) (void)hipFree(ctx->amp[l]);

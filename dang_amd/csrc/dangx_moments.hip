@@ -1,0 +1,342 @@
+// dangx_moments.hip -- posterior moments of the chain state, accumulated in HBM (dangx_moments_*): the mean and standard deviation
+// of every selected amplitude / index plane over the samples the driver hands in, without a map leaving the device until the end.
+// The reference writes every sample with write_maps (src/dang.f90:119-121) and averages the FITS files afterwards
+// (scripts/make_mean_maps.py: return_mean_map, return_std_map = np.std, ddof 0).
+//
+// k_moments_accum is one pass over every selected plane: Welford's update with the new sample count n (inv_n = 1/n from the host),
+//     d = x - mean;  mean += d * inv_n;  m2 += d * (x - mean)
+// in f64 accumulators [plane][npix] that dangx_moments_begin allocates.  It is a pure stream of 5 x 8 B per element (read x, mean,
+// m2; write mean, m2) with 16-byte accesses; a plane whose x, mean and m2 do not share their 16-byte phase (an adopted buffer
+// adopted again at another alignment) takes the scalar path, and so do the odd first / last element of every plane.  Both paths
+// evaluate the same expression with explicit fma: results do not depend on which path an element takes, i.e. on the shard
+// boundaries or the alignment of the caller's buffers.
+//
+// Template amplitudes of global-amplitude members (<= 3 x nbands values) live on the host (ctx->tamp, current after every call
+// that samples them) and get the same update there: accumulation adds no device-to-host synchronisation.
+#include "dx_host.h"
+
+#include <cstdint>
+
+struct MomSeg {           // one selected plane: the chain's plane (resolved at accumulate time) and its two accumulators
+    const double* x;
+    double* mean;
+    double* m2;
+    long long n;
+};
+
+struct DxMoments {
+    int32_t sel[MAXC] = {};          // effective selection (bits as in include/dangx.h)
+    int type[MAXC] = {}, nind[MAXC] = {};  // shape key recorded at begin
+    struct Seg { int comp, what, plane; long long off; };
+    std::vector<Seg> segs;
+    std::vector<MomSeg> table;       // the table as last uploaded
+    MomSeg* d_table = nullptr;
+    double* acc = nullptr;           // [mean: acc_half doubles | m2: acc_half doubles]
+    long long acc_half = 0;
+    long long count = 0;
+    double tm_mean[MAXC][3][MAXB] = {}, tm_m2[MAXC][3][MAXB] = {};
+    double* scratch = nullptr;       // [nmaps][npix]: what the host getter copies from
+    unsigned grid_target = 0;        // blocks of a full-machine launch
+};
+
+namespace {
+
+typedef double dbl2 __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(1))) dbl2 GD2;   // two doubles in global memory
+
+__device__ __forceinline__ void welford(double x, double& mean, double& m2, double inv_n) {
+    const double d = x - mean;
+    mean = fma(d, inv_n, mean);
+    m2 = fma(d, x - mean, m2);
+}
+
+// blockIdx.y = segment; the blocks of a segment stride over its pairs of doubles
+__global__ __launch_bounds__(BLOCK) void k_moments_accum(const MomSeg* __restrict__ segs, double inv_n) {
+    const MomSeg s = segs[blockIdx.y];
+    const long long n = s.n;
+    const long long gid = (long long)blockIdx.x * BLOCK + threadIdx.x, stride = (long long)gridDim.x * BLOCK;
+    const uintptr_t ax = reinterpret_cast<uintptr_t>(s.x), am = reinterpret_cast<uintptr_t>(s.mean), a2 = reinterpret_cast<uintptr_t>(s.m2);
+    if (((ax ^ am) & 15) != 0 || ((am ^ a2) & 15) != 0) {   // no common 16-byte phase: element by element
+        for (long long i = gid; i < n; i += stride) {
+            double m = s.mean[i], q = s.m2[i];
+            welford(s.x[i], m, q, inv_n);
+            s.mean[i] = m; s.m2[i] = q;
+        }
+        return;
+    }
+    const long long head = ((ax & 15) != 0 && n > 0) ? 1 : 0;
+    const long long npair = (n - head) / 2, tail = head + 2 * npair;   // tail < n: one element after the last pair
+    if (gid == 0 && head) {
+        double m = s.mean[0], q = s.m2[0];
+        welford(s.x[0], m, q, inv_n);
+        s.mean[0] = m; s.m2[0] = q;
+    }
+    if (gid == 1 && tail < n) {
+        double m = s.mean[tail], q = s.m2[tail];
+        welford(s.x[tail], m, q, inv_n);
+        s.mean[tail] = m; s.m2[tail] = q;
+    }
+    // the table's pointers are generic: named global, the pairs load and store as global_load / global_store_dwordx4
+    const GD2* __restrict__ x2 = (const GD2*)(s.x + head);
+    GD2* __restrict__ m2v = (GD2*)(s.mean + head);
+    GD2* __restrict__ q2v = (GD2*)(s.m2 + head);
+    for (long long p = gid; p < npair; p += stride) {
+        const dbl2 x = x2[p], m = m2v[p], q = q2v[p];
+        double m0 = m.x, m1 = m.y, q0 = q.x, q1 = q.y;
+        welford(x.x, m0, q0, inv_n);
+        welford(x.y, m1, q1, inv_n);
+        m2v[p] = dbl2{m0, m1}; q2v[p] = dbl2{q0, q1};
+    }
+}
+
+struct FinishArgs {
+    const double* mean[3];
+    const double* m2[3];
+    double* out[3];
+    long long n;
+    int stat;
+    double dn;   // n - ddof
+};
+
+// blockIdx.y = plane: out = mean, or sqrt(m2 / (n - ddof))
+__global__ __launch_bounds__(BLOCK) void k_moments_finish(FinishArgs a) {
+    const int p = blockIdx.y;
+    const double* __restrict__ mean = a.mean[p];
+    const double* __restrict__ m2 = a.m2[p];
+    double* __restrict__ out = a.out[p];
+    for (long long i = (long long)blockIdx.x * BLOCK + threadIdx.x; i < a.n; i += (long long)gridDim.x * BLOCK)
+        out[i] = a.stat == 0 ? mean[i] : sqrt(m2[i] / a.dn);
+}
+
+void host_welford(double x, double& mean, double& m2, double inv_n) {
+    const double d = x - mean;
+    mean = std::fma(d, inv_n, mean);
+    m2 = std::fma(d, x - mean, m2);
+}
+
+int sel_bits(const dangx_ctx* ctx, int comp) {   // every plane the component has
+    if (is_global_type(ctx->desc[comp].type)) return (1 << ctx->dims.nmaps) - 1;
+    int b = (1 << ctx->dims.nmaps) - 1;
+    for (int j = 0; j < ctx->desc[comp].nindices; ++j) b |= ((1 << ctx->dims.nmaps) - 1) << (3 + 3 * j);
+    return b;
+}
+
+int need(dangx_ctx* ctx) {
+    if (!ctx->mom) return fail(ctx, "posterior moments: dangx_moments_begin was not called");
+    return 0;
+}
+
+void release(DxMoments* m) {
+    if (!m) return;
+    if (m->d_table) (void)hipFree(m->d_table);
+    if (m->acc) (void)hipFree(m->acc);
+    if (m->scratch) (void)hipFree(m->scratch);
+    delete m;
+}
+
+// the resident plane of a segment as it is now (adopted buffers may have been replaced since begin)
+const double* seg_plane(const dangx_ctx* ctx, const DxMoments::Seg& s) {
+    const long long np = ctx->dims.npix;
+    if (s.what == 0) return ctx->amp[s.comp] + (long long)s.plane * np;
+    return ctx->idx[s.comp] + ((long long)(s.what - 1) * ctx->dims.nmaps + s.plane) * np;
+}
+
+// checks of a get: planes of (comp, what) that are selected -> bit k = plane k+1
+int get_planes(dangx_ctx* ctx, int comp, int what, int stat, int ddof, unsigned& planes) {
+    if (need(ctx)) return 1;
+    DxMoments* m = ctx->mom;
+    if (comp < 0 || comp >= ctx->dims.ncomp) return fail(ctx, "posterior moments: component index out of range");
+    if (what < 0 || what > DANGX_MAX_IND) return fail(ctx, "posterior moments: what must be 0 (amplitude) or 1 + index number");
+    if (stat != 0 && stat != 1) return fail(ctx, "posterior moments: stat must be 0 (mean) or 1 (standard deviation)");
+    if (m->count == 0) return fail(ctx, "posterior moments: no sample accumulated");
+    if (stat == 1 && (ddof < 0 || m->count - ddof <= 0)) return fail(ctx, "posterior moments: standard deviation needs 0 <= ddof < n");
+    planes = (unsigned)(m->sel[comp] >> (what == 0 ? 0 : 3 + 3 * (what - 1))) & 7u;
+    if (!planes) return fail(ctx, "posterior moments: nothing selected for this component and what");
+    return 0;
+}
+
+// k_moments_finish of the selected planes of (comp, what) into dst ([nmaps][npix], device)
+int finish(dangx_ctx* ctx, int comp, int what, int stat, int ddof, unsigned planes, double* dst) {
+    DxMoments* m = ctx->mom;
+    FinishArgs a{};
+    int np = 0;
+    for (const auto& s : m->segs) {
+        if (s.comp != comp || s.what != what || !((planes >> s.plane) & 1u)) continue;
+        a.mean[np] = m->acc + s.off;
+        a.m2[np] = m->acc + m->acc_half + s.off;
+        a.out[np] = dst + (long long)s.plane * ctx->dims.npix;
+        ++np;
+    }
+    a.n = ctx->dims.npix;
+    a.stat = stat;
+    a.dn = (double)(m->count - ddof);
+    const unsigned gx = std::max(1u, std::min(nblocks(a.n), 1024u));
+    hipLaunchKernelGGL(k_moments_finish, dim3(gx, np), dim3(BLOCK), 0, ctx->stream, a);
+    HIPCHK(ctx, hipGetLastError());
+    return 0;
+}
+
+}  // namespace
+
+void dx_moments_free(dangx_ctx* ctx) {
+    release(ctx->mom);
+    ctx->mom = nullptr;
+}
+
+extern "C" {
+
+int dangx_moments_begin(dangx_ctx* ctx, const int32_t* sel) {
+    if (!ctx) return 1;
+    (void)hipSetDevice(ctx->device);
+    const int ncomp = ctx->dims.ncomp, nmaps = ctx->dims.nmaps;
+    int32_t eff[MAXC] = {};
+    for (int l = 0; l < ncomp; ++l) {
+        if (!sel) { eff[l] = ctx->comp_set[l] ? sel_bits(ctx, l) : 0; continue; }
+        if (!sel[l]) continue;
+        if (!ctx->comp_set[l]) return fail(ctx, "posterior moments: a selected component is not set");
+        if (sel[l] & ~sel_bits(ctx, l))
+            return fail(ctx, "posterior moments: the selection of component " + std::to_string(l) + " names planes it does not have");
+        eff[l] = sel[l];
+    }
+    for (int l = 0; l < ncomp; ++l)   // the chain's maps exist from here on (what dangx_get_amplitude does on first use)
+        if (eff[l] && !is_global_type(ctx->desc[l].type) && ensure_state(ctx, l)) return 1;
+    DxMoments* m = new DxMoments();
+    for (int l = 0; l < ncomp; ++l) {
+        m->sel[l] = eff[l];
+        m->type[l] = ctx->desc[l].type;
+        m->nind[l] = ctx->desc[l].nindices;
+    }
+    // accumulators: every plane at the 16-byte phase of the chain's plane, so that the three streams line up
+    long long off = 0;
+    for (int l = 0; l < ncomp; ++l) {
+        if (is_global_type(ctx->desc[l].type)) continue;
+        for (int w = 0; w <= ctx->desc[l].nindices; ++w)
+            for (int k = 0; k < nmaps; ++k) {
+                if (!((eff[l] >> (w == 0 ? k : 3 + 3 * (w - 1) + k)) & 1)) continue;
+                DxMoments::Seg s{l, w, k, 0};
+                const long long phase = (long long)((reinterpret_cast<uintptr_t>(seg_plane(ctx, s)) >> 3) & 1);
+                if ((off & 1) != phase) ++off;
+                s.off = off;
+                off += ctx->dims.npix;
+                m->segs.push_back(s);
+            }
+    }
+    m->acc_half = off + (off & 1);   // even: the m2 half has the phases of the mean half
+    int ncu = 0;
+    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || ncu <= 0) ncu = 256;
+    m->grid_target = 8u * (unsigned)ncu;
+    auto bail = [&](hipError_t e, const char* what) {
+        ctx->err = std::string("posterior moments: ") + what + ": " + hipGetErrorString(e);
+        release(m);
+        return 1;
+    };
+    hipError_t e;
+    if (!m->segs.empty()) {
+        if ((e = hipMalloc(&m->acc, sizeof(double) * 2 * (size_t)m->acc_half)) != hipSuccess) return bail(e, "hipMalloc");
+        if ((e = hipMemsetAsync(m->acc, 0, sizeof(double) * 2 * (size_t)m->acc_half, ctx->stream)) != hipSuccess) return bail(e, "hipMemsetAsync");
+        if ((e = hipMalloc(&m->d_table, sizeof(MomSeg) * m->segs.size())) != hipSuccess) return bail(e, "hipMalloc");
+        if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return bail(e, "hipStreamSynchronize");
+    }
+    dx_moments_free(ctx);   // calling begin again starts over
+    ctx->mom = m;
+    return 0;
+}
+
+int dangx_moments_accumulate(dangx_ctx* ctx) {
+    if (!ctx || need(ctx)) return 1;
+    DxMoments* m = ctx->mom;
+    for (int l = 0; l < ctx->dims.ncomp; ++l)
+        if (m->sel[l] && (!ctx->comp_set[l] || ctx->desc[l].type != m->type[l] || ctx->desc[l].nindices != m->nind[l]))
+            return fail(ctx, "posterior moments: component " + std::to_string(l) + " changed type or nindices since dangx_moments_begin");
+    if (ctx->have_pending) return fail(ctx, "posterior moments: an amplitude solve is still pending");   // not at a call boundary
+    (void)hipSetDevice(ctx->device);
+    const double inv_n = 1.0 / (double)(m->count + 1);
+    if (!m->segs.empty()) {
+        std::vector<MomSeg> t(m->segs.size());
+        for (size_t i = 0; i < t.size(); ++i) {
+            const auto& s = m->segs[i];
+            t[i] = MomSeg{seg_plane(ctx, s), m->acc + s.off, m->acc + m->acc_half + s.off, (long long)ctx->dims.npix};
+        }
+        bool same = t.size() == m->table.size();
+        for (size_t i = 0; same && i < t.size(); ++i) same = t[i].x == m->table[i].x;
+        if (!same) {   // first accumulation, or a component's buffers were adopted again: one upload (and a host wait) here only
+            HIPCHK(ctx, hipMemcpyAsync(m->d_table, t.data(), sizeof(MomSeg) * t.size(), hipMemcpyHostToDevice, ctx->stream));
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+            m->table = t;
+        }
+        const unsigned nseg = (unsigned)t.size();
+        const long long pairs = (ctx->dims.npix + 1) / 2;
+        const unsigned gx = std::max(1u, std::min(nblocks(pairs), (m->grid_target + nseg - 1) / nseg));
+        Timed tm(ctx, DANGX_K_MOMENTS);
+        hipLaunchKernelGGL(k_moments_accum, dim3(gx, nseg), dim3(BLOCK), 0, ctx->stream, (const MomSeg*)m->d_table, inv_n);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    for (int l = 0; l < ctx->dims.ncomp; ++l) {
+        if (!m->sel[l] || !is_global_type(ctx->desc[l].type)) continue;
+        for (int k = 0; k < ctx->dims.nmaps; ++k)
+            if ((m->sel[l] >> k) & 1)
+                for (int j = 0; j < ctx->dims.nbands; ++j) host_welford(ctx->tamp[l][k][j], m->tm_mean[l][k][j], m->tm_m2[l][k][j], inv_n);
+    }
+    ++m->count;
+    return 0;
+}
+
+int dangx_moments_count(dangx_ctx* ctx, int64_t* n) {
+    if (!ctx || !n || need(ctx)) return 1;
+    *n = ctx->mom->count;
+    return 0;
+}
+
+int dangx_moments_get_dev(dangx_ctx* ctx, int comp, int what, int stat, int ddof, double* out_dev) {
+    if (!ctx || !out_dev) return 1;
+    unsigned planes = 0;
+    if (get_planes(ctx, comp, what, stat, ddof, planes)) return 1;
+    if (what == 0 && is_global_type(ctx->desc[comp].type))
+        return fail(ctx, "posterior moments: a template / monopole / hi_fit amplitude is read with dangx_moments_get_template");
+    (void)hipSetDevice(ctx->device);
+    return finish(ctx, comp, what, stat, ddof, planes, out_dev);
+}
+
+int dangx_moments_get(dangx_ctx* ctx, int comp, int what, int stat, int ddof, double* out) {
+    if (!ctx || !out) return 1;
+    unsigned planes = 0;
+    if (get_planes(ctx, comp, what, stat, ddof, planes)) return 1;
+    if (what == 0 && is_global_type(ctx->desc[comp].type))
+        return fail(ctx, "posterior moments: a template / monopole / hi_fit amplitude is read with dangx_moments_get_template");
+    (void)hipSetDevice(ctx->device);
+    DxMoments* m = ctx->mom;
+    const long long np = ctx->dims.npix;
+    if (!m->scratch) HIPCHK(ctx, hipMalloc(&m->scratch, sizeof(double) * (size_t)np * ctx->dims.nmaps));
+    if (finish(ctx, comp, what, stat, ddof, planes, m->scratch)) return 1;
+    const long long hs = ctx->host_stride > 0 ? ctx->host_stride : np;
+    for (int k = 0; k < ctx->dims.nmaps; ++k)
+        if ((planes >> k) & 1u)
+            HIPCHK(ctx, hipMemcpyAsync(out + (long long)k * hs, m->scratch + (long long)k * np, sizeof(double) * (size_t)np,
+                                       hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+int dangx_moments_get_template(dangx_ctx* ctx, int comp, int stat, int ddof, double* ta) {
+    if (!ctx || !ta) return 1;
+    unsigned planes = 0;
+    if (get_planes(ctx, comp, 0, stat, ddof, planes)) return 1;
+    if (!is_global_type(ctx->desc[comp].type)) return fail(ctx, "posterior moments: not a template / monopole / hi_fit component");
+    const DxMoments* m = ctx->mom;
+    const double dn = (double)(m->count - ddof);
+    for (int k = 0; k < ctx->dims.nmaps; ++k)
+        if ((planes >> k) & 1u)
+            for (int j = 0; j < ctx->dims.nbands; ++j)
+                ta[k * ctx->dims.nbands + j] = stat == 0 ? m->tm_mean[comp][k][j] : std::sqrt(m->tm_m2[comp][k][j] / dn);
+    return 0;
+}
+
+int dangx_moments_end(dangx_ctx* ctx) {
+    if (!ctx) return 1;
+    (void)hipSetDevice(ctx->device);
+    if (ctx->mom) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // no launch may still read the accumulators
+    dx_moments_free(ctx);
+    return 0;
+}
+
+}  // extern "C"

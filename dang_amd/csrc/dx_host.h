@@ -17,6 +17,8 @@
 #include "../../include/dangx.h"
 #include "dx_args.h"
 
+struct DxMoments;   // posterior-moment accumulators (dangx_moments.hip)
+
 struct dangx_ctx {
     dangx_dims dims{};
     int device = 0;
@@ -135,6 +137,7 @@ struct dangx_ctx {
     long long prof_n[DANGX_K_COUNT] = {};
     double prof_ms_pl[DANGX_K_COUNT][3] = {};      // the same by the number of planes the launch worked on (0: not recorded)
     long long prof_n_pl[DANGX_K_COUNT][3] = {};
+    DxMoments* mom = nullptr;  // dangx_moments_begin .. dangx_moments_end
 };
 
 // roctx ranges around every timed launch group and the entry points that issue them ("rocprof/roctx ranges
@@ -234,6 +237,7 @@ void dx_reduce_two_stage(dangx_ctx* ctx, const double* partial, long long n, dou
 // ---- host helpers of dangx_core.hip used by the other translation units of the ABI
 int sync_model(dangx_ctx* ctx);                 // host model -> device copy when something changed (constant-index rows, bandpass tables)
 int prof_collect(dangx_ctx* ctx);
+void dx_moments_free(dangx_ctx* ctx);           // dangx_moments.hip: release the posterior-moment accumulators
 int ensure_work(dangx_ctx* ctx, long long n);
 int ensure_state(dangx_ctx* ctx, int comp);     // allocate a component's maps on first use
 int check_comp(dangx_ctx* ctx, int comp);

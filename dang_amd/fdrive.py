@@ -62,7 +62,9 @@ def write_problem(path, dpar, ddata, comps, meta, niter, nsample=None, seed=None
                 f.write(np.ones(nmaps, dtype="<f8").tobytes())          # c%temp_norm
 
 
-def read_result(path, comps, meta, maps=True):
+def read_result(path, comps, meta, maps=True, posterior=False):
+    """posterior: the run had DANG_POSTERIOR set -- res["post"] = {"n", "mean", "std"}, each of mean / std a dict of "amp", "ind",
+    "tamp" lists laid out as the state's."""
     npix, nb, nmaps = meta["npix"], meta["nbands"], meta["nmaps"]
     out = np.fromfile(path, dtype="<f8")
     res = dict(chisq=out[0], tcmb=out[1], secs=out[2], gain=out[3:3 + nb], offset=out[3 + nb:3 + 2 * nb])
@@ -76,25 +78,40 @@ def read_result(path, comps, meta, maps=True):
     res["sky"], res["res"], res["chi"] = (out[p:p + n3].reshape(nb, nmaps, npix), out[p + n3:p + 2 * n3].reshape(nb, nmaps, npix),
                                           out[p + 2 * n3:p + 2 * n3 + n2].reshape(nmaps, npix))
     p += 2 * n3 + n2
-    res["amp"], res["ind"], res["tamp"] = [], [], []
-    for c in comps:
-        res["amp"].append(out[p:p + n2].reshape(nmaps, npix)); p += n2
-        res["ind"].append(out[p:p + c.nindices * n2].reshape(c.nindices, nmaps, npix) if c.nindices else None)
-        p += c.nindices * n2
-        if c.type in ("template", "monopole", "hi_fit"):
-            res["tamp"].append(out[p:p + nmaps * nb].reshape(nmaps, nb)); p += nmaps * nb
-        else:
-            res["tamp"].append(None)
+
+    def state(p):
+        st = {"amp": [], "ind": [], "tamp": []}
+        for c in comps:
+            st["amp"].append(out[p:p + n2].reshape(nmaps, npix)); p += n2
+            st["ind"].append(out[p:p + c.nindices * n2].reshape(c.nindices, nmaps, npix) if c.nindices else None)
+            p += c.nindices * n2
+            if c.type in ("template", "monopole", "hi_fit"):
+                st["tamp"].append(out[p:p + nmaps * nb].reshape(nmaps, nb)); p += nmaps * nb
+            else:
+                st["tamp"].append(None)
+        return st, p
+
+    st, p = state(p)
+    res.update(st)
+    if posterior:
+        res["post"] = {"n": int(out[p])}
+        p += 1
+        res["post"]["mean"], p = state(p)
+        res["post"]["std"], p = state(p)
     assert p == out.size, (p, out.size)
     return res
 
 
-def run(problem, result, nctx=1, mode="twocall", tile=1, timeout=900):
-    """Run the driver; returns its stdout.  Raises when flang is absent or the run fails (no fallback)."""
+def run(problem, result, nctx=1, mode="twocall", tile=1, timeout=900, posterior=None):
+    """Run the driver; returns its stdout.  Raises when flang is absent or the run fails (no fallback).
+    posterior=(burn_in, thin): accumulate the posterior moments (DANG_POSTERIOR) and append them to the result file."""
     exe = _build.build_reference_drive()
     if exe is None:
         raise RuntimeError("flang is not available: the Fortran driver cannot be built")
     env = dict(os.environ)
+    env.pop("DANG_POSTERIOR", None)
+    if posterior is not None:
+        env["DANG_POSTERIOR"] = "%d,%d" % tuple(posterior)
     r = subprocess.run([exe, problem, result, str(nctx), mode, str(tile)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
                        text=True, timeout=timeout, env=env)
     if r.returncode != 0 or "dang_gpu_drive ok" not in r.stdout:

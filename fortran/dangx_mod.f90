@@ -513,6 +513,42 @@ module dangx_mod
        character(kind=c_char), intent(out) :: log(*)
        integer(c_int), value :: log_len
      end function
+     ! posterior moments (write_maps every iteration + scripts/make_mean_maps.py, on the device).  sel(ncomp) (c_null_ptr = every
+     ! plane): bits 0-2 amplitude planes T,Q,U (template_amplitudes rows of global-amplitude members), bits 3+3j..5+3j index j+1
+     integer(c_int) function dangx_moments_begin(ctx, sel) bind(C, name='dangx_moments_begin')
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx, sel               ! sel: integer(c_int32_t)(ncomp) or c_null_ptr
+     end function
+     integer(c_int) function dangx_moments_accumulate(ctx) bind(C, name='dangx_moments_accumulate')
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+     end function
+     integer(c_int) function dangx_moments_count(ctx, n) bind(C, name='dangx_moments_count')
+       import :: c_int, c_ptr, c_int64_t
+       type(c_ptr), value :: ctx
+       integer(c_int64_t), intent(out) :: n
+     end function
+     ! what: 0 = c%amplitude, j = c%indices(:,:,j); stat: 0 = mean, 1 = std with ddof; out: (0:npix-1, nmaps) under the host stride,
+     ! planes that are not selected are left as they are
+     integer(c_int) function dangx_moments_get(ctx, comp, what, stat, ddof, out) bind(C, name='dangx_moments_get')
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx, out
+       integer(c_int), value :: comp, what, stat, ddof
+     end function
+     integer(c_int) function dangx_moments_get_dev(ctx, comp, what, stat, ddof, out_dev) bind(C, name='dangx_moments_get_dev')
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx, out_dev
+       integer(c_int), value :: comp, what, stat, ddof
+     end function
+     integer(c_int) function dangx_moments_get_template(ctx, comp, stat, ddof, ta) bind(C, name='dangx_moments_get_template')
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx, ta                ! real(c_double)(nbands, nmaps) == C [map][band]
+       integer(c_int), value :: comp, stat, ddof
+     end function
+     integer(c_int) function dangx_moments_end(ctx) bind(C, name='dangx_moments_end')
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+     end function
      integer(c_int) function dangx_profile_enable(ctx, on) bind(C, name='dangx_profile_enable')
        import :: c_int, c_ptr
        type(c_ptr), value :: ctx
@@ -567,6 +603,16 @@ contains
     end if
     stop 1
   end subroutine dangx_check
+
+  ! bit of plane `map` (1..3) of `what` (0 = amplitude, j = index j) in a dangx_moments_begin selection word
+  integer(c_int32_t) function dangx_moments_bit(what, map) result(b)
+    integer, intent(in) :: what, map
+    if (what == 0) then
+       b = shiftl(1_c_int32_t, map - 1)
+    else
+       b = shiftl(1_c_int32_t, 3 + 3 * (what - 1) + map - 1)
+    end if
+  end function dangx_moments_bit
 
   ! 64-bit random-stream label: Gibbs iteration, phase (0 amp / 1 index), three small ids
   ! (same packing as dang_amd.api.stream_id)

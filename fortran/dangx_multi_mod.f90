@@ -211,6 +211,66 @@ contains
     end do
   end subroutine dangx_sky_set_template
 
+  ! ---- posterior moments over the sky (write_maps every iteration + scripts/make_mean_maps.py, on the devices): every context
+  ! accumulates its shard; a get fills each context's window of the FULL-SKY host array (c%amplitude / one index of c%indices)
+  subroutine dangx_sky_moments_begin(sky, sel)
+    type(dangx_sky), intent(in) :: sky
+    integer(c_int32_t), intent(in), target :: sel(:)     ! (ncomp) selection words, include/dangx.h
+    integer :: r
+    do r = 1, sky%nctx
+       call dangx_check(sky%ctx(r), dangx_moments_begin(sky%ctx(r), c_loc(sel)), 'dangx_moments_begin')
+    end do
+  end subroutine dangx_sky_moments_begin
+
+  subroutine dangx_sky_moments_accumulate(sky)
+    type(dangx_sky), intent(in) :: sky
+    integer :: r
+    do r = 1, sky%nctx
+       call dangx_check(sky%ctx(r), dangx_moments_accumulate(sky%ctx(r)), 'dangx_moments_accumulate')
+    end do
+  end subroutine dangx_sky_moments_accumulate
+
+  ! out: c_loc of a full-sky (0:npix-1, nmaps) array; planes that are not selected are left as they are
+  subroutine dangx_sky_moments_get(sky, comp, what, stat, ddof, out)
+    type(dangx_sky), intent(in) :: sky
+    integer, intent(in) :: comp, what, stat, ddof
+    type(c_ptr), intent(in) :: out
+    integer :: r
+    do r = 1, sky%nctx
+       call dangx_check(sky%ctx(r), dangx_moments_get(sky%ctx(r), comp, what, stat, ddof, at_pix(out, sky%pix0(r))), 'dangx_moments_get')
+    end do
+  end subroutine dangx_sky_moments_get
+
+  ! template amplitudes are global: every context holds the same moments, the first one answers
+  subroutine dangx_sky_moments_get_template(sky, comp, stat, ddof, ta)
+    type(dangx_sky), intent(in) :: sky
+    integer, intent(in) :: comp, stat, ddof
+    type(c_ptr), intent(in) :: ta
+    call dangx_check(sky%ctx(1), dangx_moments_get_template(sky%ctx(1), comp, stat, ddof, ta), 'dangx_moments_get_template')
+  end subroutine dangx_sky_moments_get_template
+
+  function dangx_sky_moments_count(sky) result(n)
+    type(dangx_sky), intent(in) :: sky
+    integer(c_int64_t) :: n, m
+    integer :: r
+    call dangx_check(sky%ctx(1), dangx_moments_count(sky%ctx(1), n), 'dangx_moments_count')
+    do r = 2, sky%nctx
+       call dangx_check(sky%ctx(r), dangx_moments_count(sky%ctx(r), m), 'dangx_moments_count')
+       if (m /= n) then
+          write(*,*) 'dangx_sky_moments_count: the contexts hold different sample counts', n, m
+          stop 1
+       end if
+    end do
+  end function dangx_sky_moments_count
+
+  subroutine dangx_sky_moments_end(sky)
+    type(dangx_sky), intent(in) :: sky
+    integer :: r
+    do r = 1, sky%nctx
+       call dangx_check(sky%ctx(r), dangx_moments_end(sky%ctx(r)), 'dangx_moments_end')
+    end do
+  end subroutine dangx_sky_moments_end
+
   ! ---- the two per-pixel phases: enqueue on every device, then wait for all
   subroutine dangx_sky_wait(sky)
     type(dangx_sky), intent(in) :: sky

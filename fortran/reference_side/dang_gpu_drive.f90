@@ -14,6 +14,10 @@
 !           the global pixel, so every pixel still runs its own chain); no maps are written back
 ! Every iteration ends with write_data_gpu (the ASCII traces, into the directory of <result>) as in src/dang.f90:116-118; the
 ! run ends with dangx_refresh_host_state (what precedes write_maps, :119-121).
+! DANG_POSTERIOR="<burn_in>,<thin>" in the environment (no existing run sets it; without it the result file is unchanged): the
+! posterior summaries as INTEGRATION.md shows them -- posterior_begin_gpu before the loop, posterior_accumulate_gpu after
+! write_data_gpu -- and, after the state, the result file gets the sample count and, for the mean and then the standard
+! deviation (ddof 0), every component's c%amplitude, c%indices and c%template_amplitudes as posterior_to_host_gpu leaves them.
 subroutine mpi_allreduce(sendbuf, recvbuf, count, datatype, op, comm, ierror)
   ! the wrapper's MPI branch is never taken here (numprocs = 1); the symbol only has to exist
   integer :: sendbuf, recvbuf(*), count, datatype, op, comm, ierror
@@ -46,6 +50,8 @@ program dang_gpu_drive
   character(len=16) :: clabel, ilabel(2)
   character(len=512) :: fin, fout, arg, mode
   integer :: u, i, j, l, k, npix0, niter, ngroups, nctx, tile, t, it_first
+  integer :: post_burn, post_thin, post_len, post_stat
+  logical :: post
   integer(i8b) :: c0, c1, crate
   real(dp) :: secs
 
@@ -142,6 +148,12 @@ program dang_gpu_drive
 
   ! ---- program dang from here on (src/dang.f90:79-126), through the wrapper
   call dangx_init(dpar, ddata, nctx)
+  call get_environment_variable('DANG_POSTERIOR', arg, post_len)
+  post = post_len > 0 .and. tile == 1
+  if (post) then
+     read(arg(1:post_len), *) post_burn, post_thin
+     call posterior_begin_gpu(dpar)
+  end if
   secs = 0.d0; it_first = 3
   do iter = 1, niter
      if (iter == it_first + 1) then                       ! time iterations it_first+1 .. niter: the first two full ones warm up (index maps that start spatially constant take the generic launches once, kernels specialised at run time are compiled on first use)
@@ -162,6 +174,7 @@ program dang_gpu_drive
         do k = dpar%pol_type(1), dpar%pol_type(size(dpar%pol_type))
            call write_data_gpu(ddata, dpar, k)
         end do
+        if (post) call posterior_accumulate_gpu(iter, post_burn, post_thin)
      end if
   end do
   call dangx_sky_wait(gpu_sky)
@@ -185,6 +198,18 @@ program dang_gpu_drive
         write(u) cc%amplitude
         if (cc%nindices > 0) write(u) cc%indices
         if (allocated(cc%template_amplitudes)) write(u) cc%template_amplitudes
+     end do
+  end if
+  if (post) then
+     write(u) real(dangx_sky_moments_count(gpu_sky), c_double)
+     do post_stat = 0, 1
+        call posterior_to_host_gpu(ddata, post_stat, 0)
+        do l = 1, ncomp
+           cc => component_list(l)%p
+           write(u) cc%amplitude
+           if (cc%nindices > 0) write(u) cc%indices
+           if (allocated(cc%template_amplitudes)) write(u) cc%template_amplitudes
+        end do
      end do
   end if
   close(u)

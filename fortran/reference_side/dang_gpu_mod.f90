@@ -37,6 +37,7 @@ module dang_gpu_mod
   type(dangx_sky), save :: gpu_sky
   integer(c_int64_t)    :: gpu_seed = 1234_c_int64_t   ! the reference calls RANDOM_SEED() unseeded (src/dang.f90:67)
   integer(i4b)          :: gpu_pix0 = 0                ! first pixel of this PROCESS (0 unless the driver is run under MPI)
+  integer(c_int32_t), allocatable, target :: gpu_post_sel(:)   ! posterior_begin_gpu's selection words, one per component
 
 contains
 
@@ -681,6 +682,113 @@ contains
        call mpi_allreduce(MPI_IN_PLACE, ddata%chi_map, size(ddata%chi_map), MPI_DOUBLE_PRECISION, MPI_SUM, MPI_COMM_WORLD, ierr_l)
     end if
   end subroutine dangx_refresh_host_state
+
+  ! ---- posterior summaries (mean / standard deviation over the chain after burn-in) accumulated on the device(s): what the
+  ! reference gets by writing every sample with write_maps (src/dang.f90:119-121, iter_out = 1) and averaging the FITS files
+  ! afterwards (scripts/make_mean_maps.py: return_mean_map, return_std_map = np.std with ddof 0).  The chain never leaves HBM;
+  ! iter_out can stay large.
+
+  ! plane bits (T = 1, Q = 2, U = 4) a poltype flag covers (T, Q, U, Q+U = 1, 2, 4, 8)
+  integer(c_int32_t) function flag_plane_bits(flag)
+    integer(i4b), intent(in) :: flag
+    flag_plane_bits = int(ior(iand(flag, 7), merge(6, 0, iand(flag, 8) /= 0)), c_int32_t)
+  end function flag_plane_bits
+
+  ! before the loop: accumulate what the run samples (as dang_amd.api.default_moment_selection) -- amplitude plane k of a
+  ! component with c%sample_amplitude whose CG group has a pol_flag covering k (template / monopole / hi_fit members: row k of
+  ! c%template_amplitudes), and plane k of index j where c%sample_index(j) and a flag of c%pol_flag(j,:) covers k
+  subroutine posterior_begin_gpu(dpar)
+    type(dang_params) :: dpar
+    type(dang_comps), pointer :: cc
+    integer(i4b) :: i, j, k, g
+    if (allocated(gpu_post_sel)) deallocate(gpu_post_sel)
+    allocate(gpu_post_sel(ncomp)); gpu_post_sel = 0
+    do i = 1, ncomp
+       cc => component_list(i)%p
+       if (cc%sample_amplitude) then
+          do g = 1, ncg_groups
+             if (cg_groups(g)%p%cg_group /= cc%cg_group) cycle
+             do k = 1, cg_groups(g)%p%nflag
+                gpu_post_sel(i) = ior(gpu_post_sel(i), flag_plane_bits(cg_groups(g)%p%pol_flag(k)))
+             end do
+          end do
+       end if
+       do j = 1, cc%nindices
+          if (.not. cc%sample_index(j)) cycle
+          do k = 1, cc%nflag(j)
+             gpu_post_sel(i) = ior(gpu_post_sel(i), shiftl(flag_plane_bits(cc%pol_flag(j,k)), 3 + 3*(j-1)))
+          end do
+       end do
+    end do
+    call dangx_sky_moments_begin(gpu_sky, gpu_post_sel)
+  end subroutine posterior_begin_gpu
+
+  ! after write_data_gpu in the loop: one sample of the current state, every thin-th iteration after burn_in.  Enqueued on every
+  ! context's stream behind the iteration's launches: the host does not wait
+  subroutine posterior_accumulate_gpu(it, burn_in, thin)
+    integer(i4b), intent(in) :: it, burn_in, thin
+    if (it > burn_in .and. mod(it - burn_in, max(thin, 1)) == 0) call dangx_sky_moments_accumulate(gpu_sky)
+  end subroutine posterior_accumulate_gpu
+
+  ! after the loop: c%amplitude, c%indices and c%template_amplitudes become the mean (stat = 0) or the standard deviation (stat = 1,
+  ! sqrt(m2 / (n - ddof))) on the selected planes -- the other planes keep what they hold -- so that the reference's own
+  ! ddata%write_maps(dpar, 'mean') / (dpar, 'std') writes them.  This replaces the host copy of the chain state: the next
+  ! dangx_refresh_host_state restores it.  No routine of this wrapper uploads the host c%amplitude / c%indices /
+  ! c%template_amplitudes to the device except dangx_init (through dangx_push_state and dangx_sky_set_template), so the chain
+  ! on the device is not touched.  Under MPI every rank fills its own pixel range of the selected planes and the ranges are
+  ! merged as dangx_pull_state merges them (zero elsewhere, all-reduce), plane by plane.
+  subroutine posterior_to_host_gpu(ddata, stat, ddof)
+    type(dang_data) :: ddata
+    integer(i4b), intent(in) :: stat, ddof
+    type(dang_comps), pointer :: cc
+    integer(i4b) :: i, j, bits
+    if (.not. allocated(gpu_post_sel)) then
+       write(*,*) 'posterior_to_host_gpu: posterior_begin_gpu was not called'
+       stop 1
+    end if
+    do i = 1, ncomp
+       cc => component_list(i)%p
+       bits = iand(gpu_post_sel(i), 7)
+       if (trim(cc%type) == 'template' .or. trim(cc%type) == 'monopole' .or. trim(cc%type) == 'hi_fit') then
+          ! c%template_amplitudes(nbands,nmaps) is [map][band] in memory; global numbers, the same on every rank
+          if (bits /= 0) call dangx_sky_moments_get_template(gpu_sky, i-1, stat, ddof, c_loc(cc%template_amplitudes))
+          cycle
+       end if
+       if (bits /= 0) then
+          call rank_window(cc%amplitude, bits, .true.)
+          call dangx_sky_moments_get(gpu_sky, i-1, 0, stat, ddof, c_loc(cc%amplitude))
+          call rank_window(cc%amplitude, bits, .false.)
+       end if
+       do j = 1, cc%nindices
+          bits = iand(shiftr(gpu_post_sel(i), 3 + 3*(j-1)), 7)
+          if (bits == 0) cycle
+          call rank_window(cc%indices(:,:,j), bits, .true.)
+          call dangx_sky_moments_get(gpu_sky, i-1, j, stat, ddof, c_loc(cc%indices(0,1,j)))
+          call rank_window(cc%indices(:,:,j), bits, .false.)
+       end do
+    end do
+  end subroutine posterior_to_host_gpu
+
+  ! MPI: before a get, the selected planes (bits) of a (0:npix-1, nmaps) array are zeroed outside this rank's range; after it
+  ! they are summed over the ranks.  A single process does nothing here.
+  subroutine rank_window(a, bits, before)
+    real(dp), intent(inout) :: a(0:, :)
+    integer(i4b), intent(in) :: bits
+    logical, intent(in) :: before
+    integer :: k, ierr_l
+    integer(i4b) :: lo, hi
+    if (numprocs <= 1) return
+    lo = gpu_pix0; hi = gpu_pix0 + int(gpu_sky%npix(1), i4b) - 1
+    do k = 1, size(a, 2)
+       if (iand(bits, shiftl(1, k-1)) == 0) cycle
+       if (before) then
+          if (lo > 0) a(0:lo-1, k) = 0.d0
+          if (hi < npix-1) a(hi+1:npix-1, k) = 0.d0
+       else
+          call mpi_allreduce(MPI_IN_PLACE, a(:, k), npix, MPI_DOUBLE_PRECISION, MPI_SUM, MPI_COMM_WORLD, ierr_l)
+       end if
+    end do
+  end subroutine rank_window
 
   ! a trace file of the run: opened for appending, created by the first iteration that writes to it
   subroutine open_trace(unit, fname, created)

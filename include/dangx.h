@@ -74,7 +74,7 @@ enum { DANGX_COARSE_REFERENCE = 0, DANGX_COARSE_DEGRADED = 1 };
 /* kernel ids for dangx_profile_get / dangx_profile_get_planes */
 enum {
     DANGX_K_AMP_DIRECT = 0, DANGX_K_INDEX_MH = 1, DANGX_K_SKY_CHISQ = 2, DANGX_K_REDUCE = 3,
-    DANGX_K_CG_AX = 4, DANGX_K_CG_VEC = 5, DANGX_K_AMP_INDEX = 6, DANGX_K_COUNT = 8
+    DANGX_K_CG_AX = 4, DANGX_K_CG_VEC = 5, DANGX_K_AMP_INDEX = 6, DANGX_K_MOMENTS = 7, DANGX_K_COUNT = 8
 };
 
 typedef struct dangx_ctx dangx_ctx;
@@ -480,6 +480,36 @@ int dangx_eval_sed(dangx_ctx *ctx, int comp, int band, int map_n, double *out);
  *                      0 on success; log receives the compiler's messages (or the kernel's symbol). */
 int dangx_rtc_kernels(dangx_ctx *ctx, int *n, char *names, int names_len);
 int dangx_rtc_compile(const char *header, const char *name_expr, char *log, int log_len);
+
+/* ---- posterior moments: write_maps every iteration (src/dang.f90:119-121) + scripts/make_mean_maps.py (return_mean_map,
+ * return_std_map = np.std) on the device ----------------------------------------------------------------------------------
+ * Running means and second moments of the chain state, accumulated in HBM (f64 Welford update, k_moments_accum) so that no map
+ * leaves the device until the summaries are read once at the end.  Accumulation only READS the state: no chi^2 cache entry,
+ * kept coarse slot or index sum is dropped, and the chain's results do not change.
+ * sel[comp] (NULL = every plane of every component): bits 0-2 = amplitude planes T,Q,U (for template / monopole / hi_fit
+ * members: rows [map] of c%template_amplitudes); bits 3+3j .. 5+3j = planes T,Q,U of index j (j < DANGX_MAX_IND).  A bit for a
+ * plane or index the component does not have is an error.  Allocates the accumulators (two f64 planes per selected plane) and
+ * sets the count to 0; calling it again starts over. */
+int dangx_moments_begin(dangx_ctx *ctx, const int32_t *sel);
+/* one sample of the current state -- the resident planes as dangx_get_amplitude / _get_indices would read them after all
+ * issued work, caller-owned buffers of dangx_adopt_device_state included (resolved here, not at begin) -- enqueued on the
+ * context's stream like the sampler's launches: no host wait (except once after a component's buffers were adopted again).
+ * Not capturable in a hipGraph: the new count's 1/n is a by-value kernel argument.  Fails when dangx_set_component changed a
+ * selected component's type or nindices since begin.  dangx_put_amplitude / _put_indices between calls are state: the next
+ * accumulation takes what they wrote. */
+int dangx_moments_accumulate(dangx_ctx *ctx);
+int dangx_moments_count(dangx_ctx *ctx, int64_t *n);
+/* what: 0 = amplitude, 1 + j = index j;  stat: 0 = mean, 1 = standard deviation sqrt(m2 / (n - ddof)) (ddof 0 = np.std).
+ * out: host array laid out as dangx_get_amplitude / _get_indices (one index) lay it out ([map][pix], host stride honoured);
+ * planes that are not selected are left untouched.  Errors (nothing written): n = 0, stat = 1 with n - ddof <= 0, comp or what
+ * out of range, nothing selected for (comp, what), a template / monopole / hi_fit amplitude (read by _get_template). */
+int dangx_moments_get(dangx_ctx *ctx, int comp, int what, int stat, int ddof, double *out);
+/* the same into a device array [map][pix] of this shard (packed), asynchronously on the context's stream */
+int dangx_moments_get_dev(dangx_ctx *ctx, int comp, int what, int stat, int ddof, double *out_dev);
+/* template / monopole / hi_fit members: the moments of c%template_amplitudes, [map][band] as dangx_get_template_amplitudes */
+int dangx_moments_get_template(dangx_ctx *ctx, int comp, int stat, int ddof, double *ta);
+/* frees the accumulators */
+int dangx_moments_end(dangx_ctx *ctx);
 
 /* ---- per-kernel timing with HIP events on the context's stream ----------------- */
 int dangx_profile_enable(dangx_ctx *ctx, int on);
