@@ -38,6 +38,30 @@ template <bool V> struct BoolTag { static constexpr bool value = V; };
 
 namespace {
 
+// The accept test of a Metropolis step (:443-454): diff >= 0 or exp(diff) > u3, u3 in [2^-33, 1).  The full-precision exp
+// decides only where a cheap estimate cannot: e = v_exp_f32(float(diff) * float(log2e)).  Where exp(diff) is near some u3,
+// the exponent t = diff log2e lies in [-34, 0), and the three roundings to float (diff, log2e, the product; 2^-24 each) move
+// it by at most 34 * 3 * 2^-24, so e is within 5e-6 of exp(diff) (with v_exp_f32's 1 ulp); exp_nr_v is within 2^-52 of it
+// and float(u3) within 2^-24 of u3.  Hence e > u3 (1 + 2^-12) and e < u3 (1 - 2^-12) decide exactly as the full comparison
+// does; beyond t = -34 both say reject (e <= 2^-34 (1 + 5e-6), 0 once it underflows), and a NaN diff fails both bounds.
+// The remaining lanes (|e / u3 - 1| <= 2^-12, a band of relative width 2^-11 around the threshold) take exp_nr_v, in a
+// branch that the wavefront skips unless one of its lanes needs it.  Decisions are bit for bit those of the full test
+// (tests/test_accept_certificate.py): C3 +2.4 %.  -DDX_ACCEPT_FULL restores the full test.
+__device__ __forceinline__ bool mh_accept(double diff, double u3) {
+#if defined(DX_ACCEPT_FULL) || defined(DX_CHAIN_LIBEXP)
+    return (diff >= 0.0) || (CEXP1(diff) > u3);
+#else
+    const float e = __builtin_amdgcn_exp2f((float)diff * 0x1.715476p+0f);
+    const float uf = (float)u3;
+    bool acc = (diff >= 0.0) || (e > uf * 0x1.001p+0f);
+    const bool unsure = !(acc || e < uf * 0x1.ffep-1f);
+    if (__builtin_amdgcn_ballot_w64(unsure) != 0ull) {
+        if (unsure) acc = CEXP1(diff) > u3;
+    }
+    return acc;
+#endif
+}
+
 
 // ---------------------------------------------------------------------------
 // Register-resident form of the same chain (chisq likelihood, delta bandpasses, CH_POW / CH_MBB_BETA /
@@ -405,7 +429,7 @@ __device__ __forceinline__ unsigned long long chain_finish(const Model& M, const
                 lnl = R.template lnl<B>(M, c, prop, other, c0, c1);
                 const double lnl_new = lnl + prior(prop);
                 const double diff = lnl_new - lnl_old;
-                const bool acc = (a.ml_mode == DANGX_ML_OPTIMIZE) ? (diff > 0.0) : ((diff >= 0.0) || (CEXP1(diff) > u3));  // :443-454
+                const bool acc = (a.ml_mode == DANGX_ML_OPTIMIZE) ? (diff > 0.0) : mh_accept(diff, u3);  // :443-454
                 if (acc) { cur = prop; lnl_old = lnl_new; a0 = c0; a1 = c1; ++nacc; }
             }
         } else {
@@ -418,7 +442,7 @@ __device__ __forceinline__ unsigned long long chain_finish(const Model& M, const
                 lnl = R.template lnl<B>(M, c, prop, other, c0, c1);
                 const double lnl_new = lnl + prior(prop);
                 const double diff = lnl_new - lnl_old;
-                const bool acc = (a.ml_mode == DANGX_ML_OPTIMIZE) ? (diff > 0.0) : ((diff >= 0.0) || (CEXP1(diff) > u3));  // :443-454
+                const bool acc = (a.ml_mode == DANGX_ML_OPTIMIZE) ? (diff > 0.0) : mh_accept(diff, u3);  // :443-454
                 if (acc) { cur = prop; lnl_old = lnl_new; a0 = c0; a1 = c1; ++nacc; }
             };
             for (int l = 1; l <= a.nsample; l += 2) {
