@@ -87,7 +87,7 @@ __global__ __launch_bounds__(BLOCK) void k_fullsky_rows(const Model* __restrict_
     __shared__ double sj[MAXB];
     if (threadIdx.x < nb) sj[threadIdx.x] = sed_eval(M, c, threadIdx.x, pr);
     __syncthreads();
-    const int nrows = (what == 1) ? 2 * nb * Sp : (what == 3) ? 3 * nb * Sp : 1;
+    const int nrows = (what == 1) ? 2 * nb * Sp : 1;
     double amp[2] = {0.0, 0.0};
     if (in) for (int kk = 0; kk < Sp; ++kk) amp[kk] = camp ? camp[(long long)kk * npix + i] : c.amp[(long long)(s1 + kk - 1) * M.npix + il];
     auto rms_at = [&](int kk, int j) -> double {
@@ -109,15 +109,6 @@ __global__ __launch_bounds__(BLOCK) void k_fullsky_rows(const Model* __restrict_
                 const double rms = rms_at(kk, j);
                 const double TN = m / (rms * rms);
                 v = (row & 1) ? TN * m : TN * data[((long long)kk * nb + j) * npix + i];
-            } else if (what == 3 && !msk) {
-                // the sufficient statistics of the chisq likelihood about theta (the index is one value for the whole sky, so the SED
-                // is one number per band): with r0 = (d - a s0) / sigma, rows 3q .. 3q+2 = sum r0^2, sum r0 a / sigma, sum a^2 / sigma^2
-                // -- chi^2 at any other theta is sum_q [W0 - 2 (s - s0) U + (s - s0)^2 V] (dangx_sky.hip)
-                const int q = row / 3, t3 = row - 3 * q, j = q / Sp, kk = q - j * Sp;
-                const double rr = 1.0 / rms_at(kk, j);
-                const double ar = amp[kk] * rr;
-                const double r0 = (data[((long long)kk * nb + j) * npix + i] - signal_of(c, amp[kk], sj[j])) * rr;
-                v = (t3 == 0) ? r0 * r0 : (t3 == 1) ? r0 * ar : ar * ar;
             } else if (what == 2 && !msk && c.is_synch) {
                 for (int kk = 0; kk < Sp; ++kk)
                     for (int j = 0; j < nb; ++j) {
@@ -260,10 +251,24 @@ __global__ __launch_bounds__(BLOCK, 6) void k_fullsky_stats(const Model* __restr
 // reference (absent from its tree); nest2ring and udgrade_ring are restated from the published algorithm
 // (Gorski et al. 2005, ApJ 622, 759; HEALPix pix_tools::nest2ring, udgrade_nr::udgrade_ring -> sub_udgrade_nest).
 
-// udgrade of one RING map per blockIdx.y: out pixel o (RING) -> NEST -> children (degrade: mean of the good ones, in
-// NEST child order; upgrade: the parent's value) -> RING.  mode 0: udgrade_ring; 1: udgrade_rms (input squared,
-// sqrt(mean)*nside_out/nside_in, src/dang_util_mod.f90:341-356); 2: udgrade_mask (mean < 0.5 -> 0 else 1 when
-// degrading, :358-376).  layout 0: plane q at q*npix_in; layout 1: plane q = kk*nb + j of M.rms ((j*nmaps + s1+kk-1)*npix_in)
+// The degrade rule, one statement for every degrade and finish kernel (the whole-sky and the shard forms agree bit for bit
+// because they share it).  mode 0: udgrade_ring; 1: udgrade_rms (input squared, sqrt(mean)*nside_out/nside_in,
+// src/dang_util_mod.f90:341-356); 2: udgrade_mask (mean < 0.5 -> 0 else 1, :358-376).  Children are added in NEST order.
+__device__ __forceinline__ void udg_add(double x, int mode, double& total, int& nobs) {
+    if (mode == 1) x = x * x;
+    if (fabs(x - MISSVAL) > fabs(1e-5 * MISSVAL)) { total = total + x; ++nobs; }  // bad pixels do not enter the mean
+}
+// the coarse value from the sum of the good children and their number (an int, or a double summed over the shards)
+template <typename N>
+__device__ __forceinline__ double udg_value(double total, N nobs, int mode, double scale) {
+    double v = nobs ? total / nobs : MISSVAL;
+    if (mode == 1) v = sqrt(v) * scale;
+    if (mode == 2) v = (v < 0.5) ? 0.0 : 1.0;
+    return v;
+}
+
+// udgrade of one RING map per blockIdx.y: out pixel o (RING) -> NEST -> children (degrade: udg_add / udg_value; upgrade: the
+// parent's value) -> RING.  layout 0: plane q at q*npix_in; layout 1: plane q = kk*nb + j of M.rms ((j*nmaps + s1+kk-1)*npix_in)
 __global__ __launch_bounds__(BLOCK) void k_udgrade(const double* __restrict__ in, double* __restrict__ out,
                                                    const int* __restrict__ n2r_in, const int* __restrict__ r2n_out,
                                                    long long npix_in, long long npix_out, int ratio, int degrade, int mode,
@@ -278,65 +283,16 @@ __global__ __launch_bounds__(BLOCK) void k_udgrade(const double* __restrict__ in
     if (degrade) {
         double total = 0.0;
         int nobs = 0;
-        for (int ip = 0; ip < ratio; ++ip) {
-            double x = src[n2r_in[nest * ratio + ip]];
-            if (mode == 1) x = x * x;
-            if (fabs(x - MISSVAL) > fabs(1e-5 * MISSVAL)) { total = total + x; ++nobs; }  // bad pixels do not enter the mean
-        }
-        v = nobs ? total / nobs : MISSVAL;
+        for (int ip = 0; ip < ratio; ++ip) udg_add(src[n2r_in[nest * ratio + ip]], mode, total, nobs);
+        v = udg_value(total, nobs, mode, scale);
     } else {
         v = src[n2r_in[nest / ratio]];
-        if (mode == 1) v = v * v;
+        if (mode == 1) v = sqrt(v * v) * scale;
     }
-    if (mode == 1) v = sqrt(v) * scale;
-    if (mode == 2 && degrade) v = (v < 0.5) ? 0.0 : 1.0;
     out[(long long)q * npix_out + o] = v;
 }
 
-// k_udgrade's degrade branch for several planes at once: the children's RING numbers are read once per QC planes (they are the
-// same for every plane; one thread reads 64 consecutive ints, 256 B apart from its neighbour's) and QC maps are in flight per
-// child.  Each plane's sum runs over its children in NESTED order as before.
-constexpr int UDG_QC = 10;
-__global__ __launch_bounds__(BLOCK) void k_udgrade_planes(const double* __restrict__ in, double* __restrict__ out,
-                                                          const int* __restrict__ n2r_in, const int* __restrict__ r2n_out,
-                                                          long long npix_in, long long npix_out, int ratio, int mode, double scale,
-                                                          int layout, int nb, int nmaps, int s1, int nplanes) {
-    const long long o = (long long)blockIdx.x * BLOCK + threadIdx.x;
-    if (o >= npix_out) return;
-    const int q0 = blockIdx.y * UDG_QC;
-    long long off[UDG_QC];
-    double total[UDG_QC];
-    int nobs[UDG_QC];
-#pragma unroll
-    for (int t = 0; t < UDG_QC; ++t) {
-        const int q = (q0 + t < nplanes) ? q0 + t : nplanes - 1;
-        off[t] = (layout == 0) ? (long long)q * npix_in : ((long long)(q % nb) * nmaps + (s1 + q / nb - 1)) * npix_in;
-        total[t] = 0.0; nobs[t] = 0;
-    }
-    const long long nest = r2n_out[o];
-    const int* kids = n2r_in + nest * ratio;
-    for (int ip = 0; ip < ratio; ++ip) {
-        const long long c = kids[ip];
-        double x[UDG_QC];
-#pragma unroll
-        for (int t = 0; t < UDG_QC; ++t) x[t] = in[off[t] + c];
-#pragma unroll
-        for (int t = 0; t < UDG_QC; ++t) {
-            double v = x[t];
-            if (mode == 1) v = v * v;
-            if (fabs(v - MISSVAL) > fabs(1e-5 * MISSVAL)) { total[t] = total[t] + v; ++nobs[t]; }
-        }
-    }
-#pragma unroll
-    for (int t = 0; t < UDG_QC; ++t)
-        if (q0 + t < nplanes) {
-            double v = nobs[t] ? total[t] / nobs[t] : MISSVAL;
-            if (mode == 1) v = sqrt(v) * scale;
-            out[(long long)(q0 + t) * npix_out + o] = v;
-        }
-}
-
-// The same degrade with the loads shared out over a wave: lane l of wave w reads one child of every plane (QW planes in flight) --
+// k_udgrade's degrade for many planes at once, with the loads shared out over a wave: lane l of wave w reads one child of every plane (QW planes in flight) --
 // ratio <= 64: the wave takes 64 / ratio coarse pixels, lane l = child l % ratio of its pixel l / ratio; ratio > 64: one coarse pixel,
 // its children in rounds of 64.  The children of a coarse pixel are a few runs of neighbouring RING pixels, so a load instruction
 // touches far fewer lines than with one thread per coarse pixel (64 children: 0.5 ms against 2.07 ms per sweep at C3).  The values
@@ -344,14 +300,13 @@ __global__ __launch_bounds__(BLOCK) void k_udgrade_planes(const double* __restri
 // order as before.  ratio: a power of four.
 // Extra channels (DANGX_COARSE_DEGRADED; mode 0 only): after the nplanes maps of `in` come nxa maps xa[e * npix_in] (the swept
 // component's amplitude planes) and nxi maps xi[e * xi_stride] (its index maps at plane s1) -> xout[e][npix_out], the same gather
-// and NESTED-order sum, i.e. dangx_udgrade mode 0.  MODEL = false (no extra channels) is the kernel as it was; MODEL = true takes
-// UDG_QW_MODEL maps per block, so that the extra channels of a ten-band plane set ride in the data's blocks (10 + 3, 20 + 4 in two)
-// instead of a block row of their own, which costs as much as a full one.
+// and NESTED-order sum, i.e. dangx_udgrade mode 0.  MODEL = true takes UDG_QW_MODEL maps per block, so that the extra channels
+// of a ten-band plane set ride in the data's blocks (10 + 3, 20 + 4 in two) instead of a block row of their own, which costs as
+// much as a full one.
 constexpr int UDG_QW = 10, UDG_QW_MODEL = 13, UDG_G = BLOCK / 64;
 template <bool MODEL> constexpr int udg_qw() { return MODEL ? UDG_QW_MODEL : UDG_QW; }
-template <bool FUSED, bool MODEL>
-__global__ __launch_bounds__(BLOCK) void k_udgrade_wave(const Model* __restrict__ Mp, int comp_unused, unsigned others, int Sp,
-                                                        const double* __restrict__ in, double* __restrict__ out,
+template <bool MODEL>
+__global__ __launch_bounds__(BLOCK) void k_udgrade_wave(const double* __restrict__ in, double* __restrict__ out,
                                                         const int* __restrict__ n2r_in, const int* __restrict__ r2n_out,
                                                         long long npix_in, long long npix_out, int ratio, int mode, double scale,
                                                         int layout, int nb, int nmaps, int s1, int nplanes,
@@ -359,6 +314,7 @@ __global__ __launch_bounds__(BLOCK) void k_udgrade_wave(const Model* __restrict_
                                                         long long xi_stride, int nxi, double* __restrict__ xout) {
     constexpr int QW = udg_qw<MODEL>(), SLOTS = (UDG_G * 16 * QW + BLOCK - 1) / BLOCK;   // (16: coarse pixels per wave at ratio 4)
     __shared__ double sh[UDG_G][QW][65];
+    __builtin_assume(mode != 2);   // data and rms only (the mask goes through k_udgrade): udg_value's threshold folds away
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int cpw = (ratio < 64) ? 64 / ratio : 1, rounds = (ratio > 64) ? ratio / 64 : 1, per = (ratio < 64) ? ratio : 64;
     const int q0 = blockIdx.y * QW, ntot = MODEL ? nplanes + nxa + nxi : nplanes;
@@ -378,37 +334,12 @@ __global__ __launch_bounds__(BLOCK) void k_udgrade_wave(const Model* __restrict_
             for (int t = 0; t < QW; ++t) {
                 const int q = (q0 + t < ntot) ? q0 + t : ntot - 1;
                 if (!MODEL || q < nplanes) {
-                    // FUSED: the raw maps (plane q = Stokes q / nb, band q % nb), cleaned below; else the staged / rms maps
-                    const long long off = (FUSED || layout != 0) ? ((long long)(q % nb) * nmaps + (s1 + q / nb - 1)) * npix_in : (long long)q * npix_in;
+                    const long long off = (layout != 0) ? ((long long)(q % nb) * nmaps + (s1 + q / nb - 1)) * npix_in : (long long)q * npix_in;
                     x[t] = in[off + c];
                 } else if (q < nplanes + nxa) {
                     x[t] = xa[(long long)(q - nplanes) * npix_in + c];
                 } else {
                     x[t] = xi[(long long)(q - nplanes - nxa) * xi_stride + c];
-                }
-            }
-            if (FUSED) {   // data_raw minus every other component at the child pixel, dangx_fullsky_prepare's expression and order (:173-196)
-                const Model& M = *Mp;
-#pragma unroll
-                for (int t = 0; t < QW; ++t) {
-                    const int q = (q0 + t < nplanes) ? q0 + t : nplanes - 1, j = q % nb;
-                    if ((!MODEL || q0 + t < nplanes) && s1 + q / nb == 1) x[t] = (x[t] - M.offset[j]) / M.gain[j];
-                }
-                for (unsigned om = others; om; om &= om - 1) {
-                    const Comp& c2 = M.comp[__builtin_ctz(om)];
-                    Prep p2[2];
-                    double a2[2];
-                    for (int kk = 0; kk < Sp; ++kk) {
-                        double t0, t1;
-                        load_theta(M, c2, (int)c, s1 + kk, t0, t1);
-                        p2[kk] = sed_prep(c2, t0, t1);
-                        a2[kk] = c2.amp[(long long)(s1 + kk - 1) * npix_in + c];
-                    }
-#pragma unroll
-                    for (int t = 0; t < QW; ++t) {
-                        const int q = (q0 + t < nplanes) ? q0 + t : nplanes - 1, kk = q / nb, j = q - kk * nb;
-                        if (!MODEL || q0 + t < nplanes) x[t] = x[t] - comp_signal(M, c2, (int)c, s1 + kk, j, a2[kk], p2[kk]);
-                    }
                 }
             }
 #pragma unroll
@@ -420,11 +351,7 @@ __global__ __launch_bounds__(BLOCK) void k_udgrade_wave(const Model* __restrict_
             const int g = a / (cpw * QW), r = a - g * cpw * QW, u = r / QW, t = r - u * QW;
             const long long og = ((long long)blockIdx.x * UDG_G + g) * cpw + u;
             if (og < npix_out && q0 + t < ntot)
-                for (int ip = 0; ip < per; ++ip) {
-                    double v = sh[g][t][u * per + ip];
-                    if (mode == 1) v = v * v;
-                    if (fabs(v - MISSVAL) > fabs(1e-5 * MISSVAL)) { total[slot] = total[slot] + v; ++nobs[slot]; }
-                }
+                for (int ip = 0; ip < per; ++ip) udg_add(sh[g][t][u * per + ip], mode, total[slot], nobs[slot]);
         }
         __syncthreads();
     }
@@ -433,8 +360,7 @@ __global__ __launch_bounds__(BLOCK) void k_udgrade_wave(const Model* __restrict_
         const int g = a / (cpw * QW), r = a - g * cpw * QW, u = r / QW, t = r - u * QW;
         const long long og = ((long long)blockIdx.x * UDG_G + g) * cpw + u;
         if (og < npix_out && q0 + t < ntot) {
-            double v = nobs[slot] ? total[slot] / nobs[slot] : MISSVAL;
-            if (mode == 1) v = sqrt(v) * scale;
+            const double v = udg_value(total[slot], nobs[slot], mode, scale);
             if (!MODEL || q0 + t < nplanes) out[(long long)(q0 + t) * npix_out + og] = v;
             else xout[(long long)(q0 + t - nplanes) * npix_out + og] = v;
         }
@@ -459,9 +385,7 @@ __global__ __launch_bounds__(BLOCK) void k_udgrade_part(const double* __restrict
     for (int ip = 0; ip < ratio; ++ip) {
         const long long ring = n2r_in[nest * ratio + ip];
         if (ring < pix0 || ring >= pix0 + npix_loc) continue;
-        double x = src[ring - pix0];
-        if (mode == 1) x = x * x;
-        if (fabs(x - MISSVAL) > fabs(1e-5 * MISSVAL)) { total = total + x; ++nobs; }
+        udg_add(src[ring - pix0], mode, total, nobs);
     }
     tot[(long long)q * npix_out + o] = total;
     cnt[(long long)q * npix_out + o] = (double)nobs;
@@ -495,18 +419,13 @@ __global__ __launch_bounds__(BLOCK) void k_udgrade_finish_shared(const double* _
                                                                  double* __restrict__ out, long long npix_out, int nch) {
     const long long t = (long long)blockIdx.x * BLOCK + threadIdx.x;
     if (t >= npix_out * nch) return;
-    const double nobs = cnt[t % npix_out];
-    out[t] = (nobs > 0.0) ? tot[t] / nobs : MISSVAL;
+    out[t] = udg_value(tot[t], cnt[t % npix_out], 0, 1.0);
 }
 __global__ __launch_bounds__(BLOCK) void k_udgrade_finish(const double* __restrict__ tot, const double* __restrict__ cnt,
                                                           double* __restrict__ out, long long n, int mode, double scale) {
     const long long t = (long long)blockIdx.x * BLOCK + threadIdx.x;
     if (t >= n) return;
-    const double nobs = cnt[t];
-    double v = (nobs > 0.0) ? tot[t] / nobs : MISSVAL;
-    if (mode == 1) v = sqrt(v) * scale;
-    if (mode == 2) v = (v < 0.5) ? 0.0 : 1.0;
-    out[t] = v;
+    out[t] = udg_value(tot[t], cnt[t], mode, scale);
 }
 
 // One Metropolis chain per COARSE pixel i, literally as the reference runs it: ddata%masks(i,1), c%indices(i,..) and
@@ -663,10 +582,9 @@ static int fullsky_prepare_impl(dangx_ctx* ctx, int comp, int map_n, bool lazy) 
         if (l != comp && ((ctx->plane_nz[l] & ((1u << (s1 - 1)) | (1u << (s2 - 1)))) || ctx->desc[l].type == DANGX_TCMB || is_global_type(ctx->desc[l].type))) others |= 1u << l;
     // lazy (the sky-wide chains, dangx_sky.hip): the staging pass is deferred -- the chisq chain needs the cleaned data once, inside
     // its statistics pass (k_fullsky_stats forms them itself); any other sum (marginal rows, the Jeffreys sum, selector 0) fills
-    // the buffer first (dangx_fullsky_sums).  DANGX_FULLSKY_LAZY=0: always staged (A/B).
-    static const bool lazy_on = [] { const char* e = getenv("DANGX_FULLSKY_LAZY"); return !(e && e[0] == '0'); }();
+    // the buffer first (dangx_fullsky_sums)
     ctx->fs_others = others;
-    ctx->fs_lazy = lazy && lazy_on;
+    ctx->fs_lazy = lazy;
     if (!ctx->fs_lazy) hipLaunchKernelGGL(k_fullsky_prepare, dim3(nblocks(ctx->hm.npix)), dim3(BLOCK), (size_t)ctx->hm.nbands * BLOCK * sizeof(double), ctx->stream, ctx->dm, comp, s1, s2, others, ctx->fs_data);
     HIPCHK(ctx, hipGetLastError());
     ctx->fs_comp = comp; ctx->fs_s1 = s1; ctx->fs_s2 = s2; ctx->fs_npc = 0; ctx->fs_camp = nullptr;
@@ -817,25 +735,9 @@ static bool cm_ready(const dangx_ctx* ctx, int comp, int s1, int s2, int nside, 
 }
 static const char* const CM_MISSING = "DANGX_COARSE_DEGRADED: the degraded amplitude / index maps of this sweep were not finished for the current state (dangx_coarse_model_partials, summed over the shards, then dangx_coarse_model_finish)";
 
-// data_raw minus every other component at full resolution (:173-196, the full-sky mode's staging kernel), degraded with
-// udgrade_ring; the rms with udgrade_rms, the mask with udgrade_mask (:199-217) -> cs_data / cs_rms / cs_mask.  model: also the
-// swept component's amplitude planes and index maps (udgrade_ring, extra channels of the data's launch) -> cs_model
-static int coarse_stage(dangx_ctx* ctx, int comp, int map_n, int nside, int sample_nside, bool model) {
-    const long long npix = ctx->dims.npix;
-    if (hp_tables(ctx, nside, sample_nside)) return 1;
-    const int r1 = nside / sample_nside, ratio = r1 * r1;
-    // the degrade with its loads shared out over a wave (k_udgrade_wave; DANGX_UDGRADE_WAVE=0: a thread per coarse pixel).  It CAN form
-    // the cleaned data at the child pixels itself (no staging pass, no staging buffer traffic: DANGX_COARSE_FUSE=1) -- measured SLOWER,
-    // 24.7 against 16.8 ms per iteration at C3 / Nside 128: the other components' SEDs are then evaluated in a gather-shaped launch,
-    // once per ten-plane chunk -- so the staging pass stays.
-    static const bool wave_on = [] { const char* e = getenv("DANGX_UDGRADE_WAVE"); return !(e && e[0] == '0'); }();
-    static const bool fuse_on = [] { const char* e = getenv("DANGX_COARSE_FUSE"); return e && e[0] == '1'; }();
-    const bool by_wave = wave_on && ratio >= 4, fuse_stage = by_wave && fuse_on;
-    if (fuse_stage ? fullsky_prepare_impl(ctx, comp, map_n, true) : dangx_fullsky_prepare(ctx, comp, map_n)) return 1;
-    const int s1 = ctx->fs_s1, s2 = ctx->fs_s2, Sp = s2 - s1 + 1, nb = ctx->hm.nbands;
-    ctx->fs_comp = -1;  // the staging buffer is ours now
-    const long long npc = 12LL * sample_nside * sample_nside;
-    const long long need = (long long)Sp * nb * npc;
+// the degraded data and rms ([Sp][nb][npc] each), mask and coarse index map ([npc] each)
+static int coarse_maps_alloc(dangx_ctx* ctx, int Sp, long long npc) {
+    const long long need = (long long)Sp * ctx->hm.nbands * npc;
     if (need > ctx->cs_cap) {
         for (double** b : {&ctx->cs_data, &ctx->cs_rms, &ctx->cs_mask, &ctx->cs_index}) { if (*b) (void)hipFree(*b); *b = nullptr; }
         HIPCHK(ctx, hipMalloc(&ctx->cs_data, sizeof(double) * need));
@@ -844,82 +746,72 @@ static int coarse_stage(dangx_ctx* ctx, int comp, int map_n, int nside, int samp
         HIPCHK(ctx, hipMalloc(&ctx->cs_index, sizeof(double) * npc));
         ctx->cs_cap = need;
     }
-    const dim3 gq(nblocks(npc), Sp * nb), g1(nblocks(npc), 1);
+    return 0;
+}
+
+// data_raw minus every other component at full resolution (:173-196, the full-sky mode's staging kernel), degraded with
+// udgrade_ring; the rms with udgrade_rms, the mask with udgrade_mask (:199-217) -> cs_data / cs_rms / cs_mask.  model: also the
+// swept component's amplitude planes and index maps (udgrade_ring, extra channels of the data's launch) -> cs_model
+static int coarse_stage(dangx_ctx* ctx, int comp, int map_n, int nside, int sample_nside, bool model) {
+    const long long npix = ctx->dims.npix;
+    if (hp_tables(ctx, nside, sample_nside)) return 1;
+    // both resolutions are powers of two with sample_nside < nside: ratio is a power of four, as k_udgrade_wave needs.  Forming the
+    // cleaned data inside the degrade instead of staging them was measured slower, so the staging pass stays.
+    const int r1 = nside / sample_nside, ratio = r1 * r1;
+    if (dangx_fullsky_prepare(ctx, comp, map_n)) return 1;
+    const int s1 = ctx->fs_s1, s2 = ctx->fs_s2, Sp = s2 - s1 + 1, nb = ctx->hm.nbands;
+    ctx->fs_comp = -1;  // the staging buffer is ours now
+    const long long npc = 12LL * sample_nside * sample_nside;
+    const long long need = (long long)Sp * nb * npc;
+    if (coarse_maps_alloc(ctx, Sp, npc)) return 1;
     const double scale = (double)sample_nside * 1.0 / nside;
-    const dim3 gp(nblocks(npc), (Sp * nb + UDG_QC - 1) / UDG_QC);
     // (ratio 4: 16 pixels x 4 waves x 10 planes = 640 summing threads, three rounds of the block: the kernel's three slots)
     const long long per_block = (long long)UDG_G * ((ratio < 64) ? 64 / ratio : 1);
+    const unsigned nbx = (unsigned)((npc + per_block - 1) / per_block);
     // the model channels: Sp amplitude planes (contiguous), then the nindices index maps at plane s1 (nmaps planes apart)
     const int nxa = model ? Sp : 0, nxi = model ? ctx->desc[comp].nindices : 0;
     if (model && cm_alloc(ctx, nxa + nxi, npc)) return 1;
     const double* xa = model ? ctx->amp[comp] + (long long)(s1 - 1) * npix : nullptr;
     const double* xi = (model && nxi) ? ctx->idx[comp] + (long long)(s1 - 1) * npix : nullptr;
     const long long xi_stride = (long long)ctx->hm.nmaps * npix;
-    const int qw = model ? UDG_QW_MODEL : UDG_QW;
-    const dim3 gw((unsigned)((npc + per_block - 1) / per_block), (Sp * nb + nxa + nxi + qw - 1) / qw),
-               gr((unsigned)((npc + per_block - 1) / per_block), (Sp * nb + UDG_QW - 1) / UDG_QW);
-    if (by_wave && fuse_stage && model)   // the cleaned data are formed at the child pixels: the staging pass above was skipped
-        hipLaunchKernelGGL((k_udgrade_wave<true, true>), gw, dim3(BLOCK), 0, ctx->stream, ctx->dm, comp, ctx->fs_others, Sp, ctx->sig, ctx->cs_data,
-                           ctx->hp_n2r_f, ctx->hp_r2n_c, npix, npc, ratio, 0, scale, 0, nb, ctx->hm.nmaps, s1, Sp * nb,
+    if (model)
+        hipLaunchKernelGGL(k_udgrade_wave<true>, dim3(nbx, (Sp * nb + nxa + nxi + UDG_QW_MODEL - 1) / UDG_QW_MODEL), dim3(BLOCK), 0, ctx->stream,
+                           ctx->fs_data, ctx->cs_data, ctx->hp_n2r_f, ctx->hp_r2n_c, npix, npc, ratio, 0, scale, 0, nb, ctx->hm.nmaps, s1, Sp * nb,
                            xa, nxa, xi, xi_stride, nxi, ctx->cs_model);
-    else if (by_wave && fuse_stage)
-        hipLaunchKernelGGL((k_udgrade_wave<true, false>), gw, dim3(BLOCK), 0, ctx->stream, ctx->dm, comp, ctx->fs_others, Sp, ctx->sig, ctx->cs_data,
-                           ctx->hp_n2r_f, ctx->hp_r2n_c, npix, npc, ratio, 0, scale, 0, nb, ctx->hm.nmaps, s1, Sp * nb,
+    else
+        hipLaunchKernelGGL(k_udgrade_wave<false>, dim3(nbx, (Sp * nb + UDG_QW - 1) / UDG_QW), dim3(BLOCK), 0, ctx->stream,
+                           ctx->fs_data, ctx->cs_data, ctx->hp_n2r_f, ctx->hp_r2n_c, npix, npc, ratio, 0, scale, 0, nb, ctx->hm.nmaps, s1, Sp * nb,
                            xa, nxa, xi, xi_stride, nxi, ctx->cs_model);
-    else if (by_wave && model)
-        hipLaunchKernelGGL((k_udgrade_wave<false, true>), gw, dim3(BLOCK), 0, ctx->stream, ctx->dm, comp, 0u, Sp, ctx->fs_data, ctx->cs_data, ctx->hp_n2r_f, ctx->hp_r2n_c, npix, npc,
-                           ratio, 0, scale, 0, nb, ctx->hm.nmaps, s1, Sp * nb, xa, nxa, xi, xi_stride, nxi, ctx->cs_model);
-    else if (by_wave)
-        hipLaunchKernelGGL((k_udgrade_wave<false, false>), gw, dim3(BLOCK), 0, ctx->stream, ctx->dm, comp, 0u, Sp, ctx->fs_data, ctx->cs_data, ctx->hp_n2r_f, ctx->hp_r2n_c, npix, npc,
-                           ratio, 0, scale, 0, nb, ctx->hm.nmaps, s1, Sp * nb, xa, nxa, xi, xi_stride, nxi, ctx->cs_model);
-    else {
-        hipLaunchKernelGGL(k_udgrade_planes, gp, dim3(BLOCK), 0, ctx->stream, ctx->fs_data, ctx->cs_data, ctx->hp_n2r_f, ctx->hp_r2n_c, npix, npc,
-                           ratio, 0, scale, 0, nb, ctx->hm.nmaps, s1, Sp * nb);
-        if (model) {   // (DANGX_UDGRADE_WAVE=0) the amplitude planes as layout 0, the index maps as layout 1 with one "band" per index
-            hipLaunchKernelGGL(k_udgrade_planes, dim3(nblocks(npc), 1), dim3(BLOCK), 0, ctx->stream, xa, ctx->cs_model, ctx->hp_n2r_f, ctx->hp_r2n_c,
-                               npix, npc, ratio, 0, scale, 0, 1, ctx->hm.nmaps, s1, nxa);
-            if (nxi)
-                hipLaunchKernelGGL(k_udgrade_planes, dim3(nblocks(npc), 1), dim3(BLOCK), 0, ctx->stream, ctx->idx[comp], ctx->cs_model + (long long)nxa * npc,
-                                   ctx->hp_n2r_f, ctx->hp_r2n_c, npix, npc, ratio, 0, scale, 1, nxi, ctx->hm.nmaps, s1, nxi);
-        }
-    }
-    ctx->fs_lazy = false;   // the staging buffer is consumed (or, fused, never needed)
     if (model) cm_done(ctx, comp, s1, s2, nside, sample_nside);
     // the degraded rms and mask: the kept copy of this plane set if the maps have not changed since, else degraded and kept
-    static const bool keep_on = [] { const char* e = getenv("DANGX_COARSE_KEEP"); return !(e && e[0] == '0'); }();  // A/B switch
     dangx_ctx::CsKept* hit = nullptr;
     for (auto& kq : ctx->cs_kept)
-        if (keep_on && kq.rms && kq.gen == ctx->data_gen && kq.s1 == s1 && kq.s2 == s2 && kq.nside == nside && kq.sample_nside == sample_nside) hit = &kq;
+        if (kq.rms && kq.gen == ctx->data_gen && kq.s1 == s1 && kq.s2 == s2 && kq.nside == nside && kq.sample_nside == sample_nside) hit = &kq;
     if (hit) {
         hit->stamp = ++ctx->cs_stamp;
         HIPCHK(ctx, hipMemcpyAsync(ctx->cs_rms, hit->rms, sizeof(double) * need, hipMemcpyDeviceToDevice, ctx->stream));
         HIPCHK(ctx, hipMemcpyAsync(ctx->cs_mask, hit->mask, sizeof(double) * npc, hipMemcpyDeviceToDevice, ctx->stream));
         return 0;
     }
-    if (by_wave)
-        hipLaunchKernelGGL((k_udgrade_wave<false, false>), gr, dim3(BLOCK), 0, ctx->stream, ctx->dm, comp, 0u, Sp, ctx->rms, ctx->cs_rms, ctx->hp_n2r_f, ctx->hp_r2n_c, npix, npc,
-                           ratio, 1, scale, 1, nb, ctx->hm.nmaps, s1, Sp * nb, (const double*)nullptr, 0, (const double*)nullptr, 0ll, 0,
-                           (double*)nullptr);
-    else
-        hipLaunchKernelGGL(k_udgrade_planes, gp, dim3(BLOCK), 0, ctx->stream, ctx->rms, ctx->cs_rms, ctx->hp_n2r_f, ctx->hp_r2n_c, npix, npc,
-                           ratio, 1, scale, 1, nb, ctx->hm.nmaps, s1, Sp * nb);
-    hipLaunchKernelGGL(k_udgrade, g1, dim3(BLOCK), 0, ctx->stream, ctx->mask, ctx->cs_mask, ctx->hp_n2r_f, ctx->hp_r2n_c, npix, npc,
+    hipLaunchKernelGGL(k_udgrade_wave<false>, dim3(nbx, (Sp * nb + UDG_QW - 1) / UDG_QW), dim3(BLOCK), 0, ctx->stream, ctx->rms, ctx->cs_rms,
+                       ctx->hp_n2r_f, ctx->hp_r2n_c, npix, npc, ratio, 1, scale, 1, nb, ctx->hm.nmaps, s1, Sp * nb, (const double*)nullptr, 0,
+                       (const double*)nullptr, 0ll, 0, (double*)nullptr);
+    hipLaunchKernelGGL(k_udgrade, dim3(nblocks(npc), 1), dim3(BLOCK), 0, ctx->stream, ctx->mask, ctx->cs_mask, ctx->hp_n2r_f, ctx->hp_r2n_c, npix, npc,
                        ratio, 1, 2, scale, 0, nb, ctx->hm.nmaps, s1);
     HIPCHK(ctx, hipGetLastError());
-    if (keep_on) {   // into the slot used longest ago
-        dangx_ctx::CsKept& kq = (ctx->cs_kept[0].stamp <= ctx->cs_kept[1].stamp) ? ctx->cs_kept[0] : ctx->cs_kept[1];
-        if (kq.cap < need || kq.capm < npc) {
-            if (kq.rms) (void)hipFree(kq.rms);
-            if (kq.mask) (void)hipFree(kq.mask);
-            kq.rms = kq.mask = nullptr; kq.cap = kq.capm = 0; kq.gen = -1;
-            HIPCHK(ctx, hipMalloc(&kq.rms, sizeof(double) * need));
-            HIPCHK(ctx, hipMalloc(&kq.mask, sizeof(double) * npc));
-            kq.cap = need; kq.capm = npc;
-        }
-        HIPCHK(ctx, hipMemcpyAsync(kq.rms, ctx->cs_rms, sizeof(double) * need, hipMemcpyDeviceToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(kq.mask, ctx->cs_mask, sizeof(double) * npc, hipMemcpyDeviceToDevice, ctx->stream));
-        kq.s1 = s1; kq.s2 = s2; kq.nside = nside; kq.sample_nside = sample_nside; kq.gen = ctx->data_gen; kq.stamp = ++ctx->cs_stamp;
+    // into the slot used longest ago
+    dangx_ctx::CsKept& kq = (ctx->cs_kept[0].stamp <= ctx->cs_kept[1].stamp) ? ctx->cs_kept[0] : ctx->cs_kept[1];
+    if (kq.cap < need || kq.capm < npc) {
+        if (kq.rms) (void)hipFree(kq.rms);
+        if (kq.mask) (void)hipFree(kq.mask);
+        kq.rms = kq.mask = nullptr; kq.cap = kq.capm = 0; kq.gen = -1;
+        HIPCHK(ctx, hipMalloc(&kq.rms, sizeof(double) * need));
+        HIPCHK(ctx, hipMalloc(&kq.mask, sizeof(double) * npc));
+        kq.cap = need; kq.capm = npc;
     }
+    HIPCHK(ctx, hipMemcpyAsync(kq.rms, ctx->cs_rms, sizeof(double) * need, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(kq.mask, ctx->cs_mask, sizeof(double) * npc, hipMemcpyDeviceToDevice, ctx->stream));
+    kq.s1 = s1; kq.s2 = s2; kq.nside = nside; kq.sample_nside = sample_nside; kq.gen = ctx->data_gen; kq.stamp = ++ctx->cs_stamp;
     return 0;
 }
 
@@ -939,6 +831,49 @@ static int coarse_check(dangx_ctx* ctx, int comp, int nside, int sample_nside) {
     if (ctx->desc[comp].type > DANGX_TCMB) return fail(ctx, "coarse-Nside sampling is built for the diffuse component types and T_cmb");
     return 0;
 }
+// what a chain of index nind needs beyond coarse_check
+static int coarse_chain_check(dangx_ctx* ctx, int comp, int nind, int ml_mode) {
+    const dangx_comp_desc& d = ctx->desc[comp];
+    if (nind < 0 || nind >= d.nindices) return fail(ctx, "index number out of range");
+    if (d.lnl_type[nind] < DANGX_LNL_CHISQ || d.lnl_type[nind] > DANGX_LNL_PRIOR) return fail(ctx, "bad lnl_type");
+    if (ml_mode != DANGX_ML_SAMPLE && ml_mode != DANGX_ML_OPTIMIZE) return fail(ctx, "bad ml_mode");
+    return 0;
+}
+// the context holds the whole sky at nside: the coarse degrade can run in one pass (on a shard, a coarse pixel's children are
+// scattered over the RING ranges of the others)
+static bool whole_sky(const dangx_ctx* ctx, int nside) {
+    return ctx->dims.pix0 == 0 && ctx->dims.npix == 12LL * nside * nside && ctx->dims.npix_global == ctx->dims.npix;
+}
+
+// one chain per coarse pixel over cs_data / cs_rms / cs_mask -- and cs_model when index nind runs DANGX_COARSE_DEGRADED -> cs_index;
+// the accepted proposals are counted into *accp (zeroed first) unless it is null
+static int coarse_chains_launch(dangx_ctx* ctx, int comp, int nind, int s1, int s2, int nsample, int ml_mode, uint64_t seed,
+                                uint64_t stream, long long npc, unsigned long long* accp) {
+    IndexArgs a{};
+    a.comp = comp; a.nind = nind; a.nsample = nsample; a.ml_mode = ml_mode; a.seed = seed; a.stream = stream;
+    a.s1 = s1; a.s2 = s2; a.mode = CH_GENERIC;
+    if (accp) HIPCHK(ctx, hipMemsetAsync(accp, 0, sizeof(unsigned long long), ctx->stream));
+    Timed t(ctx, DANGX_K_INDEX_MH);
+    if (cm_on(ctx, comp, nind))
+        hipLaunchKernelGGL(k_index_mh_coarse<true>, dim3(nblocks(npc)), dim3(BLOCK), 0, ctx->stream, ctx->dm, a, npc, ctx->cs_data, ctx->cs_rms,
+                           ctx->cs_mask, (const double*)ctx->cs_model, ctx->cs_index, accp);
+    else
+        hipLaunchKernelGGL(k_index_mh_coarse<false>, dim3(nblocks(npc)), dim3(BLOCK), 0, ctx->stream, ctx->dm, a, npc, ctx->cs_data, ctx->cs_rms,
+                           ctx->cs_mask, (const double*)nullptr, ctx->cs_index, accp);
+    return 0;
+}
+
+// index nind of comp was written on planes s1..s2 (k_coarse_writeback): cached chi^2 and the constant-index bookkeeping are stale
+static void coarse_written(dangx_ctx* ctx, int comp, int nind, int map_n, int s1, int s2) {
+    for (int k = s1; k <= s2; ++k) {
+        ctx->chi_before_valid[k - 1] = ctx->chi_after_valid[k - 1] = false;
+        ctx->touched_since_amp[k - 1] = true;
+        ctx->idx_const[comp] &= ~(1u << (k - 1));
+    }
+    idx_written(ctx, comp);
+    qu_written(ctx, comp, nind, map_n);
+    ctx->dirty = true;
+}
 
 int dangx_coarse_sizes(dangx_ctx* ctx, int map_n, int sample_nside, int64_t* n_partials, int64_t* n_index) {
     if (!ctx || !n_partials || !n_index) return 1;
@@ -951,15 +886,7 @@ int dangx_coarse_sizes(dangx_ctx* ctx, int map_n, int sample_nside, int64_t* n_p
 }
 
 static int coarse_alloc(dangx_ctx* ctx, int Sp, long long npc) {
-    const long long need = (long long)Sp * ctx->hm.nbands * npc;
-    if (need > ctx->cs_cap) {
-        for (double** b : {&ctx->cs_data, &ctx->cs_rms, &ctx->cs_mask, &ctx->cs_index}) { if (*b) (void)hipFree(*b); *b = nullptr; }
-        HIPCHK(ctx, hipMalloc(&ctx->cs_data, sizeof(double) * need));
-        HIPCHK(ctx, hipMalloc(&ctx->cs_rms, sizeof(double) * need));
-        HIPCHK(ctx, hipMalloc(&ctx->cs_mask, sizeof(double) * npc));
-        HIPCHK(ctx, hipMalloc(&ctx->cs_index, sizeof(double) * npc));
-        ctx->cs_cap = need;
-    }
+    if (coarse_maps_alloc(ctx, Sp, npc)) return 1;
     const long long np = coarse_partials_len(ctx, Sp, npc);
     if (np > ctx->cs_part_cap) {
         if (ctx->cs_part) (void)hipFree(ctx->cs_part);
@@ -1109,33 +1036,16 @@ int dx_fullsky_coarse_model(dangx_ctx* ctx, int comp, int nind) {
 
 int dangx_coarse_chains(dangx_ctx* ctx, int comp, int nind, int map_n, int nsample, int ml_mode, uint64_t seed, uint64_t stream,
                         int nside, int sample_nside, const double* partials_sum, double* index_out) {
-    if (!ctx || !partials_sum || !index_out || coarse_check(ctx, comp, nside, sample_nside)) return 1;
+    if (!ctx || !partials_sum || !index_out || coarse_check(ctx, comp, nside, sample_nside) || coarse_chain_check(ctx, comp, nind, ml_mode))
+        return 1;
     (void)hipSetDevice(ctx->device);
-    const dangx_comp_desc& d = ctx->desc[comp];
-    if (nind < 0 || nind >= d.nindices) return fail(ctx, "index number out of range");
-    if (d.lnl_type[nind] < DANGX_LNL_CHISQ || d.lnl_type[nind] > DANGX_LNL_PRIOR) return fail(ctx, "bad lnl_type");
-    if (ml_mode != DANGX_ML_SAMPLE && ml_mode != DANGX_ML_OPTIMIZE) return fail(ctx, "bad ml_mode");
     int s1, s2;
     if (map_planes(ctx, map_n, s1, s2) || sync_model(ctx)) return 1;
-    const int Sp = s2 - s1 + 1, nb = ctx->hm.nbands;
-    const long long npc = 12LL * sample_nside * sample_nside, nq = (long long)Sp * nb * npc;
-    const bool deg = cm_on(ctx, comp, nind);
-    if (deg && !cm_ready(ctx, comp, s1, s2, nside, sample_nside)) return fail(ctx, CM_MISSING);
-    if (coarse_finish(ctx, Sp, npc, nside, sample_nside, partials_sum)) return 1;
-    (void)nq;
-    IndexArgs a{};
-    a.comp = comp; a.nind = nind; a.nsample = nsample; a.ml_mode = ml_mode; a.seed = seed; a.stream = stream;
-    a.s1 = s1; a.s2 = s2; a.mode = CH_GENERIC;
-    HIPCHK(ctx, hipMemsetAsync(ctx->counters + 1, 0, sizeof(unsigned long long), ctx->stream));
-    {
-        Timed t(ctx, DANGX_K_INDEX_MH);
-        if (deg)
-            hipLaunchKernelGGL(k_index_mh_coarse<true>, dim3(nblocks(npc)), dim3(BLOCK), 0, ctx->stream, ctx->dm, a, npc, ctx->cs_data, ctx->cs_rms,
-                               ctx->cs_mask, (const double*)ctx->cs_model, ctx->cs_index, ctx->counters + 1);
-        else
-            hipLaunchKernelGGL(k_index_mh_coarse<false>, dim3(nblocks(npc)), dim3(BLOCK), 0, ctx->stream, ctx->dm, a, npc, ctx->cs_data, ctx->cs_rms,
-                               ctx->cs_mask, (const double*)nullptr, ctx->cs_index, ctx->counters + 1);
-    }
+    const long long npc = 12LL * sample_nside * sample_nside;
+    if (cm_on(ctx, comp, nind) && !cm_ready(ctx, comp, s1, s2, nside, sample_nside)) return fail(ctx, CM_MISSING);
+    if (coarse_finish(ctx, s2 - s1 + 1, npc, nside, sample_nside, partials_sum) ||
+        coarse_chains_launch(ctx, comp, nind, s1, s2, nsample, ml_mode, seed, stream, npc, ctx->counters + 1))
+        return 1;
     HIPCHK(ctx, hipGetLastError());
     unsigned long long v = 0;
     HIPCHK(ctx, hipMemcpyAsync(index_out, ctx->cs_index, sizeof(double) * npc, hipMemcpyDeviceToHost, ctx->stream));
@@ -1159,15 +1069,7 @@ int dangx_coarse_writeback(dangx_ctx* ctx, int comp, int nind, int map_n, int ns
                        ctx->hp_r2n_f, ctx->hp_n2r_c, ratio);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    for (int k = s1; k <= s2; ++k) {
-        ctx->chi_before_valid[k - 1] = ctx->chi_after_valid[k - 1] = false;
-        ctx->touched_since_amp[k - 1] = true;
-        ctx->idx_const[comp] &= ~(1u << (k - 1));
-    }
-    idx_written(ctx, comp);
-    if (map_n == -1) ctx->qu_equal[comp] |= 1u << nind;
-    else if (map_n == 2 || map_n == 3) ctx->qu_equal[comp] &= ~(1u << nind);
-    ctx->dirty = true;
+    coarse_written(ctx, comp, nind, map_n, s1, s2);
     return 0;
 }
 
@@ -1177,11 +1079,9 @@ int dangx_coarse_writeback(dangx_ctx* ctx, int comp, int nind, int map_n, int ns
 int dangx_fullsky_prepare_coarse(dangx_ctx* ctx, int comp, int map_n, int nside, int sample_nside) {
     if (!ctx || check_comp(ctx, comp)) return 1;
     (void)hipSetDevice(ctx->device);
-    const long long npix = ctx->dims.npix;
-    if (ctx->dims.pix0 != 0 || npix != 12LL * nside * nside || ctx->dims.npix_global != npix)
+    if (!whole_sky(ctx, nside))
         return fail(ctx, "coarse-Nside sampling needs ONE whole-sky context (npix = 12*nside^2): the children of a coarse pixel are scattered over the RING ranges of a sharded run");
-    if (!(sample_nside < nside)) return fail(ctx, "sample_nside must be smaller than nside (equal: dangx_fullsky_prepare)");
-    if (ctx->desc[comp].type > DANGX_TCMB) return fail(ctx, "coarse-Nside sampling is built for the diffuse component types and T_cmb");
+    if (coarse_check(ctx, comp, nside, sample_nside)) return 1;
     // the degraded amplitude too when an index of the component runs DANGX_COARSE_DEGRADED (the chain's entry picks it per index)
     if (coarse_stage(ctx, comp, map_n, nside, sample_nside, ctx->cm_degraded[comp] != 0)) return 1;
     ctx->fs_comp = comp;
@@ -1194,8 +1094,7 @@ int dangx_index_sample_coarse(dangx_ctx* ctx, int comp, int nind, int map_n, int
     DxRange rg_("dangx_index_sample_coarse");
     if (!ctx || check_comp(ctx, comp)) return 1;
     (void)hipSetDevice(ctx->device);
-    const long long npix = ctx->dims.npix;
-    if (ctx->dims.pix0 != 0 || npix != 12LL * nside * nside || ctx->dims.npix_global != npix) {
+    if (!whole_sky(ctx, nside)) {
         // a pixel shard: the three phases, with the sum over the ranks between them
         if (!ctx->allreduce)
             return fail(ctx, "coarse-Nside sampling on a pixel shard needs the sum over the shards: register dangx_set_allreduce (one process per GPU), or call dangx_coarse_partials / _chains / _writeback and add the buffers (several contexts in one process)");
@@ -1217,42 +1116,17 @@ int dangx_index_sample_coarse(dangx_ctx* ctx, int comp, int nind, int map_n, int
         if (accepted) *accepted = (int64_t)idx[(size_t)ni - 1];   // all ranks' chains
         return dangx_coarse_writeback(ctx, comp, nind, map_n, nside, sample_nside, idx.data());
     }
-    if (!(sample_nside < nside)) return fail(ctx, "sample_nside must be smaller than nside (equal: dangx_index_sample)");
-    const dangx_comp_desc& d = ctx->desc[comp];
-    if (nind < 0 || nind >= d.nindices) return fail(ctx, "index number out of range");
-    if (d.type > DANGX_TCMB) return fail(ctx, "coarse-Nside sampling is built for the diffuse component types and T_cmb");
-    if (d.lnl_type[nind] < DANGX_LNL_CHISQ || d.lnl_type[nind] > DANGX_LNL_PRIOR) return fail(ctx, "bad lnl_type");
-    if (ml_mode != DANGX_ML_SAMPLE && ml_mode != DANGX_ML_OPTIMIZE) return fail(ctx, "bad ml_mode");
-    const bool deg = cm_on(ctx, comp, nind);
-    if (coarse_stage(ctx, comp, map_n, nside, sample_nside, deg)) return 1;
+    if (coarse_check(ctx, comp, nside, sample_nside) || coarse_chain_check(ctx, comp, nind, ml_mode) ||
+        coarse_stage(ctx, comp, map_n, nside, sample_nside, cm_on(ctx, comp, nind)))
+        return 1;
     const int s1 = ctx->fs_s1, s2 = ctx->fs_s2;
     const long long npc = 12LL * sample_nside * sample_nside;
     const int r1 = nside / sample_nside, ratio = r1 * r1;
-    IndexArgs a{};
-    a.comp = comp; a.nind = nind; a.nsample = nsample; a.ml_mode = ml_mode; a.seed = seed; a.stream = stream;
-    a.s1 = s1; a.s2 = s2; a.mode = CH_GENERIC;
-    if (accepted) HIPCHK(ctx, hipMemsetAsync(ctx->counters + 1, 0, sizeof(unsigned long long), ctx->stream));
-    {
-        Timed t(ctx, DANGX_K_INDEX_MH);
-        if (deg)
-            hipLaunchKernelGGL(k_index_mh_coarse<true>, dim3(nblocks(npc)), dim3(BLOCK), 0, ctx->stream, ctx->dm, a, npc, ctx->cs_data, ctx->cs_rms,
-                               ctx->cs_mask, (const double*)ctx->cs_model, ctx->cs_index, accepted ? ctx->counters + 1 : nullptr);
-        else
-            hipLaunchKernelGGL(k_index_mh_coarse<false>, dim3(nblocks(npc)), dim3(BLOCK), 0, ctx->stream, ctx->dm, a, npc, ctx->cs_data, ctx->cs_rms,
-                               ctx->cs_mask, (const double*)nullptr, ctx->cs_index, accepted ? ctx->counters + 1 : nullptr);
-    }
-    hipLaunchKernelGGL(k_coarse_writeback, dim3(nblocks(npix)), dim3(BLOCK), 0, ctx->stream, ctx->dm, comp, nind, s1, s2, ctx->cs_index,
+    if (coarse_chains_launch(ctx, comp, nind, s1, s2, nsample, ml_mode, seed, stream, npc, accepted ? ctx->counters + 1 : nullptr)) return 1;
+    hipLaunchKernelGGL(k_coarse_writeback, dim3(nblocks(ctx->dims.npix)), dim3(BLOCK), 0, ctx->stream, ctx->dm, comp, nind, s1, s2, ctx->cs_index,
                        ctx->hp_r2n_f, ctx->hp_n2r_c, ratio);
     HIPCHK(ctx, hipGetLastError());
-    for (int k = s1; k <= s2; ++k) {  // the planes changed: cached chi^2 and constant-index bookkeeping are stale
-        ctx->chi_before_valid[k - 1] = ctx->chi_after_valid[k - 1] = false;
-        ctx->touched_since_amp[k - 1] = true;
-        ctx->idx_const[comp] &= ~(1u << (k - 1));
-    }
-    idx_written(ctx, comp);
-    if (map_n == -1) ctx->qu_equal[comp] |= 1u << nind;
-    else if (map_n == 2 || map_n == 3) ctx->qu_equal[comp] &= ~(1u << nind);
-    ctx->dirty = true;
+    coarse_written(ctx, comp, nind, map_n, s1, s2);
     if (accepted) {
         unsigned long long v = 0;
         HIPCHK(ctx, hipMemcpyAsync(&v, ctx->counters + 1, sizeof(v), hipMemcpyDeviceToHost, ctx->stream));
@@ -1261,7 +1135,5 @@ int dangx_index_sample_coarse(dangx_ctx* ctx, int comp, int nind, int map_n, int
     }
     return 0;
 }
-
-
 
 }  // extern "C"

@@ -1791,8 +1791,7 @@ int dangx_fill_index(dangx_ctx* ctx, int comp, int nind, int map_n, double value
         ctx->chi_before_valid[k - 1] = ctx->chi_after_valid[k - 1] = false;
     }
     idx_written(ctx, comp);
-    if (map_n == -1) ctx->qu_equal[comp] |= 1u << nind;
-    else if (map_n == 2 || map_n == 3) ctx->qu_equal[comp] &= ~(1u << nind);
+    qu_written(ctx, comp, nind, map_n);
     ctx->dirty = true;
     return 0;
 }

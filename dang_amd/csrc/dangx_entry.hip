@@ -252,10 +252,7 @@ int dangx_index_sample(dangx_ctx* ctx, int comp, int nind, int map_n, int nsampl
         if (map_n == -1) touched = 6u; else if (map_n >= 1 && map_n <= 3) touched = 1u << (map_n - 1);
         if (ctx->idx_const[comp] & touched) { ctx->idx_const[comp] &= ~touched; ctx->dirty = true; }
         idx_written(ctx, comp);
-        if (nind >= 0 && nind < DANGX_MAX_IND) {  // a Q+U sweep writes one value to both planes (:465); a Q or U sweep to one
-            if (map_n == -1) ctx->qu_equal[comp] |= 1u << nind;
-            else if (map_n == 2 || map_n == 3) ctx->qu_equal[comp] &= ~(1u << nind);
-        }
+        if (nind >= 0 && nind < DANGX_MAX_IND) qu_written(ctx, comp, nind, map_n);
     }
     if (sync_model(ctx)) return 1;
     const dangx_comp_desc& d = ctx->desc[comp];
@@ -387,10 +384,7 @@ int dangx_index_sample_pair(dangx_ctx* ctx, int comp, int nind, int map_n, int n
     if (accepted_first) *accepted_first = acc1;
     if (!ctx->pair_done) return dangx_index_sample(ctx, comp, nind + 1, map_n, nsample, ml_mode, seed, stream_second, accepted_second);
     ctx->pair_done = false;
-    if (nind + 1 < DANGX_MAX_IND) {
-        if (map_n == -1) ctx->qu_equal[comp] |= 1u << (nind + 1);
-        else if (map_n == 2 || map_n == 3) ctx->qu_equal[comp] &= ~(1u << (nind + 1));
-    }
+    if (nind + 1 < DANGX_MAX_IND) qu_written(ctx, comp, nind + 1, map_n);
     if (accepted_second) {
         unsigned long long v = 0;
         HIPCHK(ctx, hipMemcpyAsync(&v, ctx->counters + 2, sizeof(v), hipMemcpyDeviceToHost, ctx->stream));

@@ -105,7 +105,7 @@ int sky_rows(const Sky& s, int what, const double* theta, double* rows, int nrow
 // band j on plane k is a(p) s_j(theta) with a pixel-independent s_j: about the chain's starting point theta0, with r0 = (d - a
 // s_j(theta0)) / sigma,
 //   -2 lnL(theta) = sum_jk [ W0_jk - 2 ds_j U_jk + ds_j^2 V_jk ],  ds_j = s_j(theta) - s_j(theta0),
-//   W0 = sum_p r0^2, U = sum_p r0 a / sigma, V = sum_p a^2 / sigma^2  (unmasked pixels; k_fullsky_rows, selector 3).
+//   W0 = sum_p r0^2, U = sum_p r0 a / sigma, V = sum_p a^2 / sigma^2  (unmasked pixels; k_fullsky_stats).
 // Exact algebra, no cancellation near theta0 (W0 is chi^2 itself, the other terms are of the size of the change); every proposal of
 // the chain and of the tuner then costs nb SED evaluations on the host instead of a pass over the maps and a sky-wide reduction:
 // NUMSAMPLE + 1 passes per sweep become one.  DANGX_FULLSKY_STATS=0: every evaluation a pass (A/B, and the form the reference has).

@@ -187,6 +187,12 @@ inline void idx_written(dangx_ctx* ctx, int comp) {
             for (int q = 0; q < MAXI; ++q) for (int k = 0; k < 3; ++k) ctx->idxsum_ok[l][q][k] = ctx->idxsum_dev[l][q][k] = false;
     if (comp < 0) ctx->mask_count = -1;
 }
+// index map nind of comp was swept or filled on map_n's planes: a Q+U sweep writes one value to both planes (src/dang_sample_mod.f90:465),
+// which makes them equal; a Q or U sweep writes one of them
+inline void qu_written(dangx_ctx* ctx, int comp, int nind, int map_n) {
+    if (map_n == -1) ctx->qu_equal[comp] |= 1u << nind;
+    else if (map_n == 2 || map_n == 3) ctx->qu_equal[comp] &= ~(1u << nind);
+}
 // place of the masked sum of c%indices(:, plane, nind) of component comp in chi_cache
 inline int idx_slot(int comp, int nind, int plane) { return 6 + (comp * MAXI + nind) * 3 + (plane - 1); }
 constexpr int CHI_CACHE_DOUBLES = 6 + MAXC * MAXI * 3;
