@@ -147,3 +147,12 @@ bool dx_launch_planeset(dangx_ctx* ctx, const GroupArgs& ga, const SweepList& sl
     void* args[] = {&dm, &gg, &fa, &ss, &bad, &accp, &part};
     return dx_rtc_launch(ctx, fn, nblk, ldsz, args) == 0;
 }
+
+#ifdef DX_LNL_DIAG
+// the certified likelihood's diagnostic counters (dx_chain.h: g_lnl_diag): copied to out[2], then cleared
+extern "C" int dangx_lnl_diag(unsigned long long* out) {
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_lnl_diag), 2 * sizeof(unsigned long long)) != hipSuccess) return 1;
+    const unsigned long long z[2] = {0ull, 0ull};
+    return hipMemcpyToSymbol(HIP_SYMBOL(g_lnl_diag), z, sizeof(z)) == hipSuccess ? 0 : 1;
+}
+#endif

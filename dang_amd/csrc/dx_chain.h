@@ -62,6 +62,26 @@ __device__ __forceinline__ bool mh_accept(double diff, double u3) {
 #endif
 }
 
+// The same test for a diff known only as an interval: the fp64 chain's diff d lies in [dlo, dhi].  Decided (returns true) when
+// every d in the interval takes the same decision by mh_accept's margins: dlo >= 0 or e(dlo) > u3 (1 + 2^-12) accepts
+// (exp is increasing), dhi < 0 and e(dhi) < u3 (1 - 2^-12) rejects; a NaN bound decides nothing.
+__device__ __forceinline__ bool mh_certain(double dlo, double dhi, double u3, bool& acc) {
+    const float uf = (float)u3;
+    const float elo = __builtin_amdgcn_exp2f((float)dlo * 0x1.715476p+0f);
+    const float ehi = __builtin_amdgcn_exp2f((float)dhi * 0x1.715476p+0f);
+    acc = (dlo >= 0.0) || (elo > uf * 0x1.001p+0f);
+    return acc || ((dhi < 0.0) && (ehi < uf * 0x1.ffep-1f));
+}
+
+
+#ifdef DX_LNL_DIAG
+// diagnostic (off by default): wave-steps the certified cheap likelihood evaluated [0], and of them those whose wavefront took
+// the exact branch [1]; read and cleared by dangx_lnl_diag (dangx_planeset.hip: counts the k_plane_set chains)
+__device__ unsigned long long g_lnl_diag[2];
+__device__ __forceinline__ void lnl_diag_count(int k) {
+    if (__lane_id() == __builtin_ctzll(__builtin_amdgcn_ballot_w64(true))) atomicAdd(&g_lnl_diag[k], 1ull);
+}
+#endif
 
 // ---------------------------------------------------------------------------
 // Register-resident form of the same chain (chisq likelihood, delta bandpasses, CH_POW / CH_MBB_BETA /
@@ -141,7 +161,8 @@ struct RegChain {
     //   LNL_EVAL  r = D - a' s, acc += r^2                      -- a likelihood evaluation (every proposal)
     //   LNL_ADD   r = D, D += a' s, acc += r^2                  -- the chain's FIRST evaluation, at the current index values: the
     //             member's own signal goes back into the cleaned data, and lnL of the current state is the residual's
-    //   LNL_SUB   D -= a' s                                      -- after the chain, at the values it ended on: the residual again
+    //   LNL_SUB   D -= a' s, acc += D^2                          -- after the chain, at the values it ended on: the residual again
+    //             (the same residual bits as an EVAL there, so acc0 / acc1 are that evaluation's sums)
     template <bool BATCH, int OP = 0>
     __device__ __forceinline__ double lnl(const Model& M, const Comp& c, double th, double other, double& acc0, double& acc1) {
         double s0 = 0.0, s1 = 0.0;
@@ -233,8 +254,14 @@ struct RegChain {
                         acc1 = fma(r1, r1, acc1);
                     }
                 } else if (OP == 2) {
-                    D[0][j] = fma(-is(0, j), s[t], D[0][j]);
-                    if (SP == 2) D[SP - 1][j] = fma(-is(SP - 1, j), s[t], D[SP - 1][j]);
+                    const double r0 = fma(-is(0, j), s[t], D[0][j]);
+                    D[0][j] = r0;
+                    acc0 = fma(r0, r0, acc0);
+                    if (SP == 2) {
+                        const double r1 = fma(-is(SP - 1, j), s[t], D[SP - 1][j]);
+                        D[SP - 1][j] = r1;
+                        acc1 = fma(r1, r1, acc1);
+                    }
                 } else {
                 const double r0 = fma(-is(0, j), s[t], D[0][j]);
                 acc0 = fma(r0, r0, acc0);
@@ -253,7 +280,6 @@ struct RegChain {
 #endif
             }
         }
-        if (OP == 2) return 0.0;
         if (LP > 1) {  // the other half's band sum: a + b on one lane, b + a on the other -- the same value
             acc0 += __shfl_xor(acc0, 1, 64);
             if (SP == 2) acc1 += __shfl_xor(acc1, 1, 64);
@@ -262,6 +288,80 @@ struct RegChain {
         acc0 *= -0.5; acc1 *= -0.5;
 #endif
         return acc0 + acc1;
+    }
+
+    // ---- the certified cheap evaluation (chain_finish; delta bands of CH_POW / CH_MBB_BETA / CH_MBB_T, scaled form)
+    // A~ = sum over the pixel's bands and planes of r~^2, r~ = fma(-a', s~, D) in fp64 as the EVAL form, where s~ is the SED from
+    // e = v_exp_f32(float(s0 log2e * k1)) -- the fp64 exponent s0 * k1 carried to fp32 -- and for CH_MBB_T 1/(e - 1) from
+    // v_rcp_f32 (one by one: no batched reciprocal); everything else is the fp64 factors of the exact form (F, s1).
+    __device__ __forceinline__ double lnl_cheap(const Model& M, const Comp& c, double th) {
+        double s0 = 0.0, s1 = 0.0;
+        if (MODE == CH_POW) s0 = th;
+        else if (MODE == CH_MBB_BETA) s0 = th + 1.0;
+        else { s0 = mbb_z(th); s1 = CEXP(s0 * c.nu_ref) - 1.0; }
+        const double s0l = s0 * 0x1.71547652b82fep+0;  // log2(e)
+        double acc0 = 0.0, acc1 = 0.0;
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+            const float e = __builtin_amdgcn_exp2f((float)(s0l * k1(M, c, j)));
+            double s;
+            if (MODE == CH_POW) s = (double)e;
+            else if (MODE == CH_MBB_BETA) s = F[j] * (double)e;
+            else s = (s1 * F[j]) * (double)__builtin_amdgcn_rcpf(e - 1.0f);
+            const double r0 = fma(-is(0, j), s, D[0][j]);
+            acc0 = fma(r0, r0, acc0);
+            if (SP == 2) {
+                const double r1 = fma(-is(SP - 1, j), s, D[SP - 1][j]);
+                acc1 = fma(r1, r1, acc1);
+            }
+        }
+        double a = acc0 + acc1;
+        if (LP > 1) a += __shfl_xor(a, 1, 64);
+        return a;
+    }
+
+    // The bound, once per chain, for proposals th in [lo, hi].  Let s be the exact form's fp64 SED at band j and
+    // |s - s~| <= E_j s~ (below).  With p~ = a' s~, R = D - a' s and R~ = D - p~ (real arithmetic on the fp64 operands),
+    // |R - R~| <= E_j |p~| <= E_j (|D| + |R~|), so with G = sum E_j^2 D^2, Emax = max E_j and A = sum R~^2,
+    //   |sum R^2 - sum R~^2| <= sum e (2 |R~| + e)  <=  2 sqrt(G A) + 2 Emax (1 + Emax) A + 2 G
+    //                        <=  (2 Emax (1 + Emax) + lam) A + G / lam + 2 G         (any lam > 0: 2 sqrt(GA) <= G/lam + lam A)
+    // and lam = sqrt(G / A_start) makes it tight where the chain stays near its start.  The fp64 roundings of both sums (at most
+    // 2 NB + 4 roundings of nonnegative terms, < 2^-46 relative) and of this bound's own arithmetic are covered by the factor
+    // (1 + 2^-40) and the term 2^-40 A; 2^-1000 covers squares that underflow.  lnL = -A / 2 halves it: |lnL - lnL~| <= wA A + wG.
+    // Per band, with x = s0 k1 (|x| <= xmax_j over [lo, hi]):
+    //   * the exponent carried to fp32: relative |x| (2^-24 + 2^-50) in e (s0 log2e and the product: 2^-53 each);
+    //   * v_exp_f32 modelled at 2 ulp: 2^-22;  the exact form's exp_nr <= 1 ulp and its products: < 2^-46 in all;
+    //   * CH_MBB_T: e - 1 is exact in fp32 (e >= 1); its relative error is e's amplified by 1/(1 - e^-x) <= 1 + 1/x, and
+    //     x / (1 - e^-x) <= 1 + x; v_rcp_f32 at 2 ulp: 2^-22; the exact form's batched reciprocal: <= 2 (TT - 1) roundings;
+    //   * second-order terms and the step from "relative to s" to "relative to s~": the factor 1 + 2^-8.
+    // Returns false where the fp32 exponent could leave the normal range (|x log2e| > 125: e would overflow or lose its
+    // precision) or T could reach 0: such chains take the exact evaluation for every proposal.
+    __device__ __forceinline__ bool cheap_bound(const Model& M, const Comp& c, double lo, double hi, double a_start,
+                                                double& wA, double& wG) {
+        double G = 0.0, emax = 0.0, kmax = 0.0;
+        double smax, zmin = 0.0;
+        if (MODE == CH_POW) smax = fmax(fabs(lo), fabs(hi));
+        else if (MODE == CH_MBB_BETA) smax = fmax(fabs(lo + 1.0), fabs(hi + 1.0));
+        else { smax = mbb_z(lo); zmin = mbb_z(hi); }
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+            const double k = fabs(k1(M, c, j));
+            kmax = fmax(kmax, k);
+            double e;
+            if (MODE == CH_MBB_T) e = (1.0 + smax * k) * 0x1p-24 + (2.0 + (double)__builtin_amdgcn_rcpf((float)(zmin * k))) * 0x1p-22;
+            else e = (smax * k) * 0x1p-24 + 0x1p-22;
+            e = e * (1.0 + 0x1p-8) + 0x1p-46;
+            emax = fmax(emax, e);
+#pragma unroll
+            for (int kk = 0; kk < SP; ++kk) { const double t = e * D[kk][j]; G = fma(t, t, G); }
+        }
+        if (LP > 1) { G += __shfl_xor(G, 1, 64); emax = fmax(emax, __shfl_xor(emax, 1, 64)); kmax = fmax(kmax, __shfl_xor(kmax, 1, 64)); }
+        // (any lam > 0 gives a bound: its own rounding, and 1/x from v_rcp_f32 above within the factor 1 + 2^-8, cost nothing)
+        const double lam = fmax(sqrt(G * fast_rcp(fmax(a_start, 0x1p-900))), 0x1p-400);
+        wA = 0.5 * ((2.0 * emax * (1.0 + emax) + lam) * (1.0 + 0x1p-40) + 0x1p-40);
+        wG = 0.5 * ((G * fast_rcp(lam) + 2.0 * G) * (1.0 + 0x1p-40) + 0x1p-1000);
+        const bool range = smax * kmax * 0x1.71547652b82fep+0 <= 125.0;
+        return (MODE == CH_MBB_T) ? (range && lo > 0.0 && zmin > 0.0) : range;
     }
     // after the other components are removed: d -> d/rms, 1/rms -> amp/rms
     __device__ __forceinline__ void scale() {
@@ -413,6 +513,15 @@ __device__ __forceinline__ unsigned long long chain_finish(const Model& M, const
     double cur = first ? sample0 : sample1;
     double a0, a1, c0, c1;
     const double step = c.step[q], lo = c.uni[q][0], hi = c.uni[q][1];
+    const bool ml_opt = (a.ml_mode == DANGX_ML_OPTIMIZE);
+    // the certified cheap likelihood (RegChain::lnl_cheap / cheap_bound): delta-band power law and modified
+    // blackbody chains decide a step from an interval of the fp64 chain's diff and evaluate lnL exactly only for lanes whose
+    // decision the interval cannot settle; -DDX_LNL_EXACT restores the exact evaluation of every proposal
+#if defined(DX_LNL_EXACT) || !defined(DX_CHAIN_SCALED)
+    constexpr bool kCert = false;
+#else
+    constexpr bool kCert = !RC::kBP && (MODE == CH_POW || MODE == CH_MBB_BETA || MODE == CH_MBB_T);
+#endif
     auto chain = [&](auto batch_tag) {
         constexpr bool B = decltype(batch_tag)::value;
         double lnl;
@@ -420,41 +529,99 @@ __device__ __forceinline__ unsigned long long chain_finish(const Model& M, const
         else lnl = R.template lnl<B, ADD ? 1 : 0>(M, c, cur, other, a0, a1);
         chi[0] = -2.0 * a0; chi[1] = -2.0 * a1;
         double lnl_old = lnl + prior(cur);
+        // cheap path state: lnl_old is exact (old_exact) or within wold of the exact chain's; a0 / a1 are the sums of the
+        // state at cur (sums_exact) or must be evaluated there after the loop
+        bool cert = false, old_exact = true, sums_exact = true;
+        double wA = 0.0, wG = 0.0, wold = 0.0;
+        if (kCert) {
+            const bool ok = R.cheap_bound(M, c, lo, hi, -2.0 * lnl, wA, wG) && !ml_opt;
+            cert = __builtin_amdgcn_ballot_w64(!ok) == 0ull;   // one decision per wavefront
+        }
+        // one step from the proposal and the accept uniform (:414-454)
+        auto mh_step = [&](double prop, double u3) {
+            if (prop < lo || prop > hi) return;                        // :415
+            if constexpr (!kCert) {
+                lnl = R.template lnl<B>(M, c, prop, other, c0, c1);
+                const double lnl_new = lnl + prior(prop);
+                const double diff = lnl_new - lnl_old;
+                const bool acc = ml_opt ? (diff > 0.0) : mh_accept(diff, u3);  // :443-454
+                if (acc) { cur = prop; lnl_old = lnl_new; a0 = c0; a1 = c1; ++nacc; }
+            } else {
+                const double pp = prior(prop);
+                bool acc = false, und = true;
+                double lc = 0.0, wc = 0.0;
+                if (cert) {
+                    // the fp64 chain's diff d = (lnl + pp) - lnl_old, with |lnl - lc| <= wc and |lnl_old - lold| <= wold: d is
+                    // within wc + wold of dc plus the four fp64 roundings of the two diffs (2^-49 of the operands covers them)
+                    const double A = R.lnl_cheap(M, c, prop);
+                    lc = -0.5 * A;
+                    wc = fma(wA, A, wG);
+                    const double dc = (lc + pp) - lnl_old;
+                    const double W = (wc + wold) * (1.0 + 0x1p-40) + 0x1p-49 * ((fabs(lc) + fabs(pp)) + fabs(lnl_old));
+                    und = !mh_certain(dc - W, dc + W, u3, acc);
+#ifdef DX_LNL_DIAG
+                    lnl_diag_count(0);
+                    if (__builtin_amdgcn_ballot_w64(und) != 0ull) lnl_diag_count(1);
+#endif
+                }
+                if (__builtin_amdgcn_ballot_w64(und) != 0ull) {
+                    if (und) {
+                        // the exact evaluation; after a cheap accept lnl_old is first re-evaluated at cur (the fp64 chain
+                        // evaluated that same proposal: the same bits)
+                        bool again = !old_exact;
+#pragma unroll 1
+                        for (;;) {
+                            const double l = R.template lnl<B>(M, c, again ? cur : prop, other, c0, c1);
+                            if (!again) { lnl = l; break; }
+                            lnl_old = l + prior(cur);
+                            again = false;
+                        }
+                        const double lnl_new = lnl + pp;
+                        const double diff = lnl_new - lnl_old;
+                        acc = ml_opt ? (diff > 0.0) : mh_accept(diff, u3);   // :443-454
+                        if (acc) { lnl_old = lnl_new; a0 = c0; a1 = c1; }
+                        old_exact = true;
+                        wold = 0.0;
+                    }
+                }
+                if (acc) {
+                    cur = prop;
+                    ++nacc;
+                    sums_exact = und;
+                    if (!und) { lnl_old = lc + pp; wold = wc; old_exact = false; }
+                }
+            }
+        };
         if (LP == 1 || DX_CHAIN_PAIR_RNG == 0) {
             for (int l = 1; l <= a.nsample; ++l) {
                 double u1, u2, u3;
                 uniform3(a.seed, a.stream, gpix, (uint32_t)l, u1, u2, u3);
-                const double prop = cur + rand_normal(0.0, step, u1, u2);  // :414
-                if (prop < lo || prop > hi) continue;                      // :415
-                lnl = R.template lnl<B>(M, c, prop, other, c0, c1);
-                const double lnl_new = lnl + prior(prop);
-                const double diff = lnl_new - lnl_old;
-                const bool acc = (a.ml_mode == DANGX_ML_OPTIMIZE) ? (diff > 0.0) : mh_accept(diff, u3);  // :443-454
-                if (acc) { cur = prop; lnl_old = lnl_new; a0 = c0; a1 = c1; ++nacc; }
+                mh_step(cur + rand_normal(0.0, step, u1, u2), u3);    // :414
             }
         } else {
             // Lane pairs: both lanes of a pixel would draw the SAME numbers for every step (a third of a proposal's instructions).
             // Instead lane h draws for step l + h, and the two steps take their numbers from the lane that made them: the random
             // numbers of a pixel are computed once per TWO steps -- the same draws, the same arithmetic, half the instructions.
-            auto mh_step = [&](double g, double u3) {   // one step from the proposal deviate g = rand_normal(0, step) and the accept uniform
-                const double prop = cur + g;                               // :414
-                if (prop < lo || prop > hi) return;                        // :415
-                lnl = R.template lnl<B>(M, c, prop, other, c0, c1);
-                const double lnl_new = lnl + prior(prop);
-                const double diff = lnl_new - lnl_old;
-                const bool acc = (a.ml_mode == DANGX_ML_OPTIMIZE) ? (diff > 0.0) : mh_accept(diff, u3);  // :443-454
-                if (acc) { cur = prop; lnl_old = lnl_new; a0 = c0; a1 = c1; ++nacc; }
-            };
             for (int l = 1; l <= a.nsample; l += 2) {
                 double u1, u2, u3;
                 uniform3(a.seed, a.stream, gpix, (uint32_t)(l + half), u1, u2, u3);
                 const double g = rand_normal(0.0, step, u1, u2);
                 const double go = __shfl_xor(g, 1, 64), uo = __shfl_xor(u3, 1, 64);
-                mh_step(half == 0 ? g : go, half == 0 ? u3 : uo);                          // step l: the even lane's numbers
-                if (l + 1 <= a.nsample) mh_step(half == 0 ? go : g, half == 0 ? uo : u3);  // step l + 1: the odd lane's
+                mh_step(cur + (half == 0 ? g : go), half == 0 ? u3 : uo);                          // step l: the even lane's numbers
+                if (l + 1 <= a.nsample) mh_step(cur + (half == 0 ? go : g), half == 0 ? uo : u3);  // step l + 1: the odd lane's
             }
         }
-        if (SUB) { double u0_, u1_; (void)R.template lnl<B, 2>(M, c, cur, other, u0_, u1_); }
+        // the sums of the state the chain ends on: the last accepted evaluation's (or the start's if nothing was accepted); after
+        // a cheap accept they are an exact evaluation at cur -- the SUB pass computes exactly that residual
+        if (SUB) {
+            double s0_, s1_;
+            (void)R.template lnl<B, 2>(M, c, cur, other, s0_, s1_);
+            if (!sums_exact) { a0 = s0_; a1 = s1_; }
+        } else if (kCert) {
+            if (__builtin_amdgcn_ballot_w64(!sums_exact) != 0ull) {
+                if (!sums_exact) (void)R.template lnl<B>(M, c, cur, other, a0, a1);
+            }
+        }
     };
 #ifdef DX_CHAIN_NO_BATCH_RCP
     chain(BoolTag<false>{});
