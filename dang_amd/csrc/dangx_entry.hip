@@ -93,6 +93,18 @@ static int planeset_launch(dangx_ctx* ctx, const GroupArgs& g, const SweepList& 
 static bool planeset_group(dangx_ctx* ctx, GroupArgs& g, int s1, int s2, int solve);
 static bool planeset_items(dangx_ctx* ctx, const GroupArgs& g, int map_n, int nsweeps, const int32_t* comp, const int32_t* nind, const uint64_t* stream, SweepList& sl);
 
+// Is index nind of this component a Jeffreys-prior index the register chains carry (dx_chain.h: RegChain<.., JF>)?  The power law
+// labelled 'synch' with the chisq likelihood: eval_jeffreys_prior's sum is non-trivial for that label only
+// (src/dang_lnl_mod.f90:289) -- under any other label the prior is log 0 and the chain never moves; those, and every other
+// component type, keep the run-time-typed chain.  Delta bands and the per-pixel mode are the callers' conditions.
+static bool jeffreys_fast(const dangx_comp_desc& d, int nind) {
+    return d.prior_type[nind] == DANGX_PRIOR_JEFFREYS && d.type == DANGX_POWERLAW && d.is_synch && d.lnl_type[nind] == DANGX_LNL_CHISQ;
+}
+// a prior the register chains cover: gaussian, uniform, or the Jeffreys case above
+static bool prior_fast(const dangx_comp_desc& d, int nind) {
+    return d.prior_type[nind] != DANGX_PRIOR_JEFFREYS || jeffreys_fast(d, nind);
+}
+
 // The sums of squares a sweep leaves behind are chi^2 of update_sky_model's residual -- unless a monopole has a signal on the planes:
 // the chain removes it as one more component (eval_signal, src/dang_sample_mod.f90:180-196) ON TOP of the band offset it has
 // become (src/dang_data_mod.f90:357-361), while the sky model leaves it out.  Such planes take the explicit pass.
@@ -258,7 +270,7 @@ int dangx_index_sample(dangx_ctx* ctx, int comp, int nind, int map_n, int nsampl
     const dangx_comp_desc& d = ctx->desc[comp];
     if (nind < 0 || nind >= d.nindices) return fail(ctx, "index number out of range");
     IndexArgs a;
-    a.comp = comp; a.nind = nind; a.nsample = nsample; a.ml_mode = ml_mode; a.seed = seed; a.stream = stream;
+    a.comp = comp; a.nind = nind; a.nsample = nsample; a.ml_mode = ml_mode; a.seed = seed; a.stream = stream; a.jeff = 0;
     if (map_n == -1) { a.s1 = 2; a.s2 = 3; }                       // src/dang_sample_mod.f90:157-163
     else if (map_n >= 1 && map_n <= 3) { a.s1 = a.s2 = map_n; }
     else return fail(ctx, "There is something wrong with the poltype flag (map_n must be 1,2,3 or -1)");
@@ -287,8 +299,10 @@ int dangx_index_sample(dangx_ctx* ctx, int comp, int nind, int map_n, int nsampl
     int bs = 256;
     while (bs > 64 && tabsz + per_thread * bs > 76 * 1024) bs >>= 1;
     const size_t lds = tabsz + per_thread * bs;
-    const bool reg_ok = !a.bp && d.lnl_type[nind] == DANGX_LNL_CHISQ && d.prior_type[nind] != DANGX_PRIOR_JEFFREYS &&
-                        a.mode != CH_GENERIC && dx_mh_reg_supported(ctx, a.mode, ctx->hm.nbands, Sp);
+    a.jeff = (!a.bp && jeffreys_fast(d, nind)) ? 1 : 0;
+    const bool reg_ok = !a.bp && d.lnl_type[nind] == DANGX_LNL_CHISQ && prior_fast(d, nind) &&
+                        a.mode != CH_GENERIC && dx_mh_reg_supported(ctx, a.mode, ctx->hm.nbands, Sp, a.jeff);
+    if (!reg_ok) a.jeff = 0;
     if (reg_ok) bs = BLOCK;  // register-resident form: no LDS columns
     // lanes per pixel: of the chain's register form, or of the fused launch when a solve on these planes is waiting for this
     // sweep and the model takes the one-launch form (decided now: the grid and the chi^2 buffers are sized by it)
@@ -325,9 +339,9 @@ int dangx_index_sample(dangx_ctx* ctx, int comp, int nind, int map_n, int nsampl
         ctx->pair_on = false;
         if (reg_ok && nind + 1 < d.nindices) {
             IndexArgs b = a;
-            b.nind = nind + 1; b.stream = ctx->pair_stream;
+            b.nind = nind + 1; b.stream = ctx->pair_stream; b.jeff = 0;
             b.mode = (d.type == DANGX_MBB) ? CH_MBB_T : (d.type == DANGX_LOGNORMAL && all_delta) ? CH_LOGN_W : CH_GENERIC;
-            const bool ok_b = d.lnl_type[nind + 1] == DANGX_LNL_CHISQ && d.prior_type[nind + 1] != DANGX_PRIOR_JEFFREYS;
+            const bool ok_b = !a.jeff && d.lnl_type[nind + 1] == DANGX_LNL_CHISQ && d.prior_type[nind + 1] != DANGX_PRIOR_JEFFREYS;
             unsigned long long* accp = accepted ? ctx->counters + 1 : nullptr;  // counters[1], counters[2]
             if (ok_b) {
                 Timed t(ctx, DANGX_K_INDEX_MH, Sp);
@@ -421,7 +435,7 @@ int dangx_amp_index_sample(dangx_ctx* ctx, int group, int flag, int ml_mode, int
         // (host-evaluated row against per-pixel evaluation) if it is launched after the descriptor update: first sweeps
         // on constant maps go the two-call way
         can = nind >= 0 && nind < d.nindices && !(ctx->idx_const[comp] & touched) && d.cg_group == group && d.sample_amplitude &&
-              d.lnl_type[nind] == DANGX_LNL_CHISQ && d.prior_type[nind] != DANGX_PRIOR_JEFFREYS &&
+              d.lnl_type[nind] == DANGX_LNL_CHISQ && prior_fast(d, nind) &&
               (d.type == DANGX_POWERLAW || d.type == DANGX_MBB);
     }
     if (can) {
@@ -535,7 +549,7 @@ static bool planeset_items(dangx_ctx* ctx, const GroupArgs& g, int map_n, int ns
         int gm = -1;
         for (int q = 0; q < g.ng; ++q) if (g.gc[q] == comp[s]) gm = q;
         if (!(gm >= 0 && !(ctx->idx_const[comp[s]] & touched) && d.lnl_type[nind[s]] == DANGX_LNL_CHISQ &&
-              d.prior_type[nind[s]] != DANGX_PRIOR_JEFFREYS && (d.type == DANGX_POWERLAW || d.type == DANGX_MBB || d.type == DANGX_LOGNORMAL)))
+              prior_fast(d, nind[s]) && (d.type == DANGX_POWERLAW || d.type == DANGX_MBB || d.type == DANGX_LOGNORMAL)))
             return false;
         const int mode = (d.type == DANGX_POWERLAW) ? CH_POW : (d.type == DANGX_MBB) ? (nind[s] == 0 ? CH_MBB_BETA : CH_MBB_T) : (nind[s] == 0 ? CH_LOGN_NUP : CH_LOGN_W);
         if (sl.n > 0 && sl.s[sl.n - 1].comp == comp[s] && !sl.s[sl.n - 1].pair && sl.s[sl.n - 1].nind + 1 == nind[s] &&
@@ -547,6 +561,7 @@ static bool planeset_items(dangx_ctx* ctx, const GroupArgs& g, int map_n, int ns
         if (sl.n == DX_MAX_SWEEPS) return false;
         SweepItem& it = sl.s[sl.n++];
         it.comp = comp[s]; it.nind = nind[s]; it.mode = mode; it.pair = 0; it.gmember = gm; it.stream = stream[s]; it.stream2 = 0;
+        it.jeff = jeffreys_fast(d, nind[s]) ? 1 : 0;
     }
     sl.s1 = (map_n == -1) ? 2 : map_n; sl.s2 = (map_n == -1) ? 3 : map_n;
     return true;

@@ -42,6 +42,19 @@ static void launch_fused_case(dangx_ctx* ctx, const GroupArgs& ga, const FusedAr
 bool DX_CAT(dx_launch_fused_mode, DX_REG_MODE)(dangx_ctx* ctx, const GroupArgs& ga, const FusedArgs& fa, const IndexArgs& a, int Sp,
                                               int lanes, unsigned nblk, unsigned long long* accp) {
     const int nb = ctx->hm.nbands;
+    if (a.jeff) {  // the Jeffreys sweep (power law): built in for the C3 shape
+#if DX_REG_MODE == 1
+        if (!(lanes == 1 && nb == 10 && ga.ng == 4)) return false;
+        const size_t ldsz = fused_lds(4, 10, fa.nv, 1);
+        if (Sp == 2)
+            hipLaunchKernelGGL((dxk::k_amp_index<1, 2, 10, 4, 1, true>), dim3(nblk), dim3(BLOCK), ldsz, ctx->stream, ctx->dm, ga, fa, a, ctx->counters, accp, ctx->partial);
+        else
+            hipLaunchKernelGGL((dxk::k_amp_index<1, 1, 10, 4, 1, true>), dim3(nblk), dim3(BLOCK), ldsz, ctx->stream, ctx->dm, ga, fa, a, ctx->counters, accp, ctx->partial);
+        return true;
+#else
+        return false;
+#endif
+    }
     // the instantiated (band count, group size, lanes) triples: keep fused_builtin below in step
     if (lanes == 1 && nb == 10 && ga.ng == 4) launch_fused_case<10, 4, 1>(ctx, ga, fa, a, Sp, nblk, accp);        // C3
     else if (lanes == 1 && nb == 10 && ga.ng == 3) launch_fused_case<10, 3, 1>(ctx, ga, fa, a, Sp, nblk, accp);
@@ -58,7 +71,8 @@ bool dx_launch_fused_mode1(dangx_ctx*, const GroupArgs&, const FusedArgs&, const
 bool dx_launch_fused_mode2(dangx_ctx*, const GroupArgs&, const FusedArgs&, const IndexArgs&, int, int, unsigned, unsigned long long*);
 bool dx_launch_fused_mode3(dangx_ctx*, const GroupArgs&, const FusedArgs&, const IndexArgs&, int, int, unsigned, unsigned long long*);
 
-static bool fused_builtin(int mode, int nb, int ng, int lanes) {
+static bool fused_builtin(int mode, int nb, int ng, int lanes, int jeff = 0) {
+    if (jeff) return mode == CH_POW && lanes == 1 && nb == 10 && ng == 4;
     if (lanes == 1) return (nb == 10 && (ng == 4 || ng == 3)) || (nb == 5 && ng == 3) || (nb == 3 && ng == 2);
     return mode == CH_POW && nb == 20 && ng == 6;
 }
@@ -69,9 +83,9 @@ bool dx_fused_supported(int mode, int nb, int ng) {
     return fused_builtin(mode, nb, ng, 1) || fused_builtin(mode, nb, ng, 2) || dx_rtc_enabled();
 }
 
-static std::string fused_name(int mode, int Sp, int nb, int ng, int lanes) {
+static std::string fused_name(int mode, int Sp, int nb, int ng, int lanes, int jeff) {
     return "dxk::k_amp_index<" + std::to_string(mode) + ", " + std::to_string(Sp) + ", " + std::to_string(nb) + ", " + std::to_string(ng) + ", " +
-           std::to_string(lanes) + ">";
+           std::to_string(lanes) + (jeff ? ", true>" : ">");
 }
 
 // the members' roles in the fused kernel; false: this model does not take it
@@ -108,7 +122,7 @@ static bool fused_args(dangx_ctx* ctx, const GroupArgs& ga, const IndexArgs& a, 
 // half the columns per lane: C5's 20 bands and 6 members).  A shape without a built-in instantiation is specialised HERE
 // (hiprtc or the disk cache), so that the launch that follows cannot fail: the caller sizes its grid by this answer.
 int dx_fused_lanes(dangx_ctx* ctx, const GroupArgs& ga, const IndexArgs& a, int Sp) {
-    if (!(a.mode >= CH_POW && a.mode <= CH_MBB_T) || ga.ng < 1 || ga.ng > 6) return 0;
+    if (!(a.mode >= CH_POW && a.mode <= CH_MBB_T) || ga.ng < 1 || ga.ng > 6 || (a.jeff && a.mode != CH_POW)) return 0;
     FusedArgs fa;
     if (!fused_args(ctx, ga, a, fa)) return 0;
     const int nb = ctx->hm.nbands, ng = ga.ng, cap = (Sp == 2) ? 10 : 16;
@@ -119,8 +133,8 @@ int dx_fused_lanes(dangx_ctx* ctx, const GroupArgs& ga, const IndexArgs& a, int 
     // fused one (C5, T plane: 7.4 + 12.5 ms against 21.1 ms)
     else if (nb % 2 == 0 && nb / 2 <= cap && dx_mh_reg_lanes(nb, Sp) == 2 && fused_lds(ng, nb, fa.nv, 2) <= 80u * 1024u) lanes = 2;
     if (!lanes) return 0;
-    if (fused_builtin(a.mode, nb, ng, lanes)) return lanes;
-    return dx_rtc_get(ctx, "dx_kern_fused.h", fused_name(a.mode, Sp, nb, ng, lanes)) ? lanes : 0;
+    if (fused_builtin(a.mode, nb, ng, lanes, a.jeff)) return lanes;
+    return dx_rtc_get(ctx, "dx_kern_fused.h", fused_name(a.mode, Sp, nb, ng, lanes, a.jeff)) ? lanes : 0;
 }
 
 // ga: the pending amplitude solve; a: the index sweep that follows it on the same planes; lanes: dx_fused_lanes' answer
@@ -128,6 +142,7 @@ bool dx_launch_fused(dangx_ctx* ctx, const GroupArgs& ga, const IndexArgs& a, in
     FusedArgs fa;
     if (lanes < 1 || !fused_args(ctx, ga, a, fa)) return false;
     bool done = false;
+    if (a.jeff && a.mode != CH_POW) return false;
     switch (a.mode) {
     case CH_POW: done = dx_launch_fused_mode1(ctx, ga, fa, a, Sp, lanes, nblk, accp); break;
     case CH_MBB_BETA: done = dx_launch_fused_mode2(ctx, ga, fa, a, Sp, lanes, nblk, accp); break;
@@ -136,7 +151,7 @@ bool dx_launch_fused(dangx_ctx* ctx, const GroupArgs& ga, const IndexArgs& a, in
     }
     if (done) return true;
     const int nb = ctx->hm.nbands, ng = ga.ng;
-    hipFunction_t fn = dx_rtc_get(ctx, "dx_kern_fused.h", fused_name(a.mode, Sp, nb, ng, lanes));
+    hipFunction_t fn = dx_rtc_get(ctx, "dx_kern_fused.h", fused_name(a.mode, Sp, nb, ng, lanes, a.jeff));
     if (!fn) return false;
     const Model* dm = ctx->dm;
     GroupArgs gg = ga;

@@ -34,6 +34,16 @@ bool DX_CATP(dx_launch_mh_pair_mode, DX_REG_MODE)(dangx_ctx* ctx, const IndexArg
 #define DX_CAT(a, b) DX_CAT2(a, b)
 bool DX_CAT(dx_launch_mh_reg_mode, DX_REG_MODE)(dangx_ctx* ctx, const IndexArgs& a, int Sp, unsigned nblk, unsigned long long* accp) {
     const int nb = ctx->hm.nbands;
+    if (a.jeff) {  // the Jeffreys chain (power law): built in for the C3 shape, every other shape is specialised at run time
+#if DX_REG_MODE == 1
+        if (nb != 10 || dx_mh_reg_lanes(nb, Sp) != 1) return false;
+        if (Sp == 2) hipLaunchKernelGGL((dxk::k_index_mh_reg<1, 2, 10, 1, true>), dim3(nblk), dim3(BLOCK), 0, ctx->stream, ctx->dm, a, accp, ctx->partial);
+        else hipLaunchKernelGGL((dxk::k_index_mh_reg<1, 1, 10, 1, true>), dim3(nblk), dim3(BLOCK), 0, ctx->stream, ctx->dm, a, accp, ctx->partial);
+        return true;
+#else
+        return false;
+#endif
+    }
     if (dx_mh_reg_lanes(nb, Sp) == 2) {  // nblk counts blocks of BLOCK lanes = BLOCK / 2 pixels
         if (nb != 20) return false;      // other lane-pair shapes are specialised at run time
         hipLaunchKernelGGL((dxk::k_index_mh_reg<DX_REG_MODE, 2, 20, 2>), dim3(nblk), dim3(BLOCK), 0, ctx->stream, ctx->dm, a, accp, ctx->partial);
@@ -67,9 +77,10 @@ int dx_mh_reg_lanes(int nb, int Sp) {
 bool dx_launch_mh_pair_mode2(dangx_ctx*, const IndexArgs&, const IndexArgs&, int, unsigned, unsigned long long*);
 bool dx_launch_mh_pair_mode4(dangx_ctx*, const IndexArgs&, const IndexArgs&, int, unsigned, unsigned long long*);
 
-static std::string chain_name(const char* kernel, int mode, int Sp, int nb, int lanes) {
+// (jeff: the Jeffreys instantiation; the plain ones keep the names they always had)
+static std::string chain_name(const char* kernel, int mode, int Sp, int nb, int lanes, int jeff = 0) {
     return std::string("dxk::") + kernel + "<" + std::to_string(mode) + ", " + std::to_string(Sp) + ", " + std::to_string(nb) + ", " +
-           std::to_string(lanes) + ">";
+           std::to_string(lanes) + (jeff ? ", true>" : ">");
 }
 
 // index a.nind and a.nind + 1 of one component in one launch; false: not covered (the caller makes the two launches)
@@ -94,14 +105,15 @@ bool dx_launch_mh_pair(dangx_ctx* ctx, const IndexArgs& a, const IndexArgs& b, i
 // Is the register chain available for (mode, bands, planes) on this context?  Built-in instantiations: yes; any other band
 // count: specialised NOW (hiprtc, or the disk cache), so that a later launch cannot fail -- the caller sizes its grid and its
 // chi^2 buffers for the form it is told about.
-bool dx_mh_reg_supported(dangx_ctx* ctx, int mode, int nb, int Sp) {
-    if (!(mode >= CH_POW && mode <= CH_LOGN_W)) return false;
+bool dx_mh_reg_supported(dangx_ctx* ctx, int mode, int nb, int Sp, int jeff) {
+    if (!(mode >= CH_POW && mode <= CH_LOGN_W) || (jeff && mode != CH_POW)) return false;
     const int lanes = dx_mh_reg_lanes(nb, Sp);
-    if (lanes == 2 ? nb == 20 : (nb == 3 || nb == 5 || nb == 6 || nb == 8 || nb == 10 || nb == 20)) return true;
-    return dx_rtc_get(ctx, "dx_kern_chain.h", chain_name("k_index_mh_reg", mode, Sp, nb, lanes)) != nullptr;
+    if (jeff ? (lanes == 1 && nb == 10) : lanes == 2 ? nb == 20 : (nb == 3 || nb == 5 || nb == 6 || nb == 8 || nb == 10 || nb == 20)) return true;
+    return dx_rtc_get(ctx, "dx_kern_chain.h", chain_name("k_index_mh_reg", mode, Sp, nb, lanes, jeff)) != nullptr;
 }
 bool dx_launch_mh_reg(dangx_ctx* ctx, const IndexArgs& a, int Sp, unsigned nblk, unsigned long long* accp) {
     bool done = false;
+    if (a.jeff && a.mode != CH_POW) return false;
     switch (a.mode) {
     case CH_POW: done = dx_launch_mh_reg_mode1(ctx, a, Sp, nblk, accp); break;
     case CH_MBB_BETA: done = dx_launch_mh_reg_mode2(ctx, a, Sp, nblk, accp); break;
@@ -111,7 +123,7 @@ bool dx_launch_mh_reg(dangx_ctx* ctx, const IndexArgs& a, int Sp, unsigned nblk,
     default: return false;
     }
     if (done) return true;
-    hipFunction_t fn = dx_rtc_get(ctx, "dx_kern_chain.h", chain_name("k_index_mh_reg", a.mode, Sp, ctx->hm.nbands, dx_mh_reg_lanes(ctx->hm.nbands, Sp)));
+    hipFunction_t fn = dx_rtc_get(ctx, "dx_kern_chain.h", chain_name("k_index_mh_reg", a.mode, Sp, ctx->hm.nbands, dx_mh_reg_lanes(ctx->hm.nbands, Sp), a.jeff));
     if (!fn) return false;
     const Model* dm = ctx->dm;
     IndexArgs aa = a;

@@ -7,15 +7,21 @@
 #include "dx_host.h"
 #include "dx_kern_planeset.h"
 
-// rows of the lane's column: the members' SEDs for the solve, then 1 / rms of the lane's bands on the Sp planes
-static size_t planeset_lds(int ng, int nb, int nv, int lanes, int Sp) {
-    const int rows = nv > Sp ? nv : Sp;
+// rows of the lane's column: the members' SEDs for the solve, then 1 / rms of the lane's bands on the Sp planes (and, behind
+// them, the weights of a Jeffreys item: one more row block)
+static int planeset_jeff(const SweepList& sl) {
+    for (int q = 0; q < sl.n; ++q) if (sl.s[q].jeff) return 1;
+    return 0;
+}
+static size_t planeset_lds(int ng, int nb, int nv, int lanes, int Sp, int jeff) {
+    const int rows = nv > Sp + jeff ? nv : Sp + jeff;
     return ((size_t)(TROWS * ng + 3) * nb + (size_t)rows * (nb / lanes) * BLOCK) * sizeof(double);
 }
 
-// the sweep items as template arguments: chain mode + 8 for an item that carries the component's next index too, 0 = none
+// the sweep items as template arguments: chain mode + 8 for an item that carries the component's next index too, + 16 for a chain
+// with the Jeffreys prior, 0 = none
 static void item_codes(const SweepList& sl, int code[4]) {
-    for (int q = 0; q < 4; ++q) code[q] = (q < sl.n) ? sl.s[q].mode + 8 * sl.s[q].pair : 0;
+    for (int q = 0; q < 4; ++q) code[q] = (q < sl.n) ? sl.s[q].mode + 8 * sl.s[q].pair + 16 * (sl.s[q].jeff ? 1 : 0) : 0;
 }
 static std::string planeset_name(int Sp, int nb, int ng, int lanes, int solve, const SweepList& sl, int bp) {
     int c[4];
@@ -42,6 +48,8 @@ static bool planeset_builtin(int nb, int ng, int lanes, int solve, const SweepLi
     item_codes(sl, c);
     if (nb == 20 && ng == 6 && lanes == 2) return solve && c[0] == CH_POW && c[1] == CH_MBB_BETA + 8 && c[2] == CH_LOGN_NUP && c[3] == 0;
     if (lanes == 1 && nb == 10 && ng == 4 && solve && sl.n == 0) return true;
+    if (lanes == 1 && nb == 10 && ng == 4 && c[0] == CH_POW + 16)   // C3 with the synchrotron index on the Jeffreys prior
+        return c[1] == CH_MBB_BETA + 8 && c[2] == 0 && c[3] == 0;
     if (lanes == 1 && ((nb == 10 && ng == 4) || (solve && ((nb == 5 && ng == 3) || (nb == 3 && ng == 2)))))
         return c[0] == CH_POW && c[1] == CH_MBB_BETA + 8 && c[2] == 0 && c[3] == 0;
     return false;
@@ -55,6 +63,17 @@ static void launch_builtin(dangx_ctx* ctx, const GroupArgs& ga, const FusedArgs&
     else
         hipLaunchKernelGGL((dxk::k_plane_set<1, NB, NG, LP, SOLVE, C0, C1, C2, 0>), dim3(nblk), dim3(BLOCK), ldsz, ctx->stream, ctx->dm, ga, fa, sl, ctx->counters, accp, ctx->partial);
 }
+
+// the Jeffreys instantiations of the C3 shape are a translation unit of their own (-DDX_PS_JEFF), built beside this one
+void dx_launch_planeset_jeff(dangx_ctx* ctx, const GroupArgs& ga, const FusedArgs& fa, const SweepList& sl, int Sp, int solve, unsigned nblk,
+                             size_t ldsz, unsigned long long* accp);
+#ifdef DX_PS_JEFF
+void dx_launch_planeset_jeff(dangx_ctx* ctx, const GroupArgs& ga, const FusedArgs& fa, const SweepList& sl, int Sp, int solve, unsigned nblk,
+                             size_t ldsz, unsigned long long* accp) {
+    if (solve) launch_builtin<10, 4, 1, 1, CH_POW + 16, CH_MBB_BETA + 8, 0>(ctx, ga, fa, sl, Sp, nblk, ldsz, accp);
+    else launch_builtin<10, 4, 1, 0, CH_POW + 16, CH_MBB_BETA + 8, 0>(ctx, ga, fa, sl, Sp, nblk, ldsz, accp);
+}
+#else
 
 // members' roles (as the fused kernel's), and the conditions the kernel relies on
 static bool planeset_args(dangx_ctx* ctx, const GroupArgs& ga, const SweepList& sl, FusedArgs& fa) {
@@ -101,21 +120,22 @@ int dx_planeset_lanes(dangx_ctx* ctx, const GroupArgs& ga, const SweepList& sl, 
         const int m = sl.s[q].mode;
         if (m < CH_POW || m > CH_LOGN_W) return 0;
         if (sl.s[q].pair && !(m == CH_MBB_BETA || m == CH_LOGN_NUP)) return 0;
+        if (sl.s[q].jeff && m != CH_POW) return 0;
     }
     FusedArgs fa;
     if (!planeset_args(ctx, ga, sl, fa)) return 0;
     if (solve && fa.cal && ga.nuc > 0) return 0;   // the kernel removes the templates before the solve's T / gain (no such model yet)
-    const int bp = planeset_bp(ctx);
-    if (bp) {  // sample loops exist for the power-law and mbb chains, in the one-lane form
+    const int bp = planeset_bp(ctx), jf = planeset_jeff(sl);
+    if (bp) {  // sample loops exist for the power-law and mbb chains, in the one-lane form (not with the Jeffreys prior)
         for (int q = 0; q < sl.n; ++q)
-            if (sl.s[q].mode > CH_MBB_T) return 0;
-        if (!(small_too && nb <= cap && planeset_lds(ga.ng, nb, fa.nv, 1, Sp) <= 80u * 1024u)) return 0;
+            if (sl.s[q].mode > CH_MBB_T || sl.s[q].jeff) return 0;
+        if (!(small_too && nb <= cap && planeset_lds(ga.ng, nb, fa.nv, 1, Sp, 0) <= 80u * 1024u)) return 0;
         return dx_rtc_get(ctx, "dx_kern_planeset.h", planeset_name(Sp, nb, ga.ng, 1, solve, sl, 1)) ? 1 : 0;
     }
     // one lane where registers (cap) and the members' SED columns (two blocks per CU: 80 KB each) allow it, else lane pairs
     int lanes = 0;
-    if (small_too && nb <= cap && planeset_lds(ga.ng, nb, fa.nv, 1, Sp) <= 80u * 1024u) lanes = 1;
-    else if (nb > 12 && nb % 2 == 0 && nb / 2 <= cap && planeset_lds(ga.ng, nb, fa.nv, 2, Sp) <= 80u * 1024u) lanes = 2;
+    if (small_too && nb <= cap && planeset_lds(ga.ng, nb, fa.nv, 1, Sp, jf) <= 80u * 1024u) lanes = 1;
+    else if (nb > 12 && nb % 2 == 0 && nb / 2 <= cap && planeset_lds(ga.ng, nb, fa.nv, 2, Sp, jf) <= 80u * 1024u) lanes = 2;
     if (!lanes) return 0;
     if (planeset_builtin(nb, ga.ng, lanes, solve, sl)) return lanes;
     return dx_rtc_get(ctx, "dx_kern_planeset.h", planeset_name(Sp, nb, ga.ng, lanes, solve, sl, 0)) ? lanes : 0;
@@ -126,10 +146,11 @@ bool dx_launch_planeset(dangx_ctx* ctx, const GroupArgs& ga, const SweepList& sl
     FusedArgs fa;
     if (lanes < 1 || lanes > 2 || !planeset_args(ctx, ga, sl, fa)) return false;
     const int nb = ctx->hm.nbands, ng = ga.ng, Sp = sl.s2 - sl.s1 + 1;
-    const size_t ldsz = planeset_lds(ng, nb, fa.nv, lanes, Sp);
+    const size_t ldsz = planeset_lds(ng, nb, fa.nv, lanes, Sp, planeset_jeff(sl));
     const int bp = planeset_bp(ctx);
     if (!bp && planeset_builtin(nb, ng, lanes, solve, sl)) {
-        if (nb == 20) launch_builtin<20, 6, 2, 1, CH_POW, CH_MBB_BETA + 8, CH_LOGN_NUP>(ctx, ga, fa, sl, Sp, nblk, ldsz, accp);
+        if (planeset_jeff(sl)) dx_launch_planeset_jeff(ctx, ga, fa, sl, Sp, solve, nblk, ldsz, accp);
+        else if (nb == 20) launch_builtin<20, 6, 2, 1, CH_POW, CH_MBB_BETA + 8, CH_LOGN_NUP>(ctx, ga, fa, sl, Sp, nblk, ldsz, accp);
         else if (nb == 10 && sl.n == 0) launch_builtin<10, 4, 1, 1, 0, 0, 0>(ctx, ga, fa, sl, Sp, nblk, ldsz, accp);
         else if (nb == 10 && !solve) launch_builtin<10, 4, 1, 0, CH_POW, CH_MBB_BETA + 8, 0>(ctx, ga, fa, sl, Sp, nblk, ldsz, accp);
         else if (nb == 10) launch_builtin<10, 4, 1, 1, CH_POW, CH_MBB_BETA + 8, 0>(ctx, ga, fa, sl, Sp, nblk, ldsz, accp);
@@ -148,7 +169,9 @@ bool dx_launch_planeset(dangx_ctx* ctx, const GroupArgs& ga, const SweepList& sl
     return dx_rtc_launch(ctx, fn, nblk, ldsz, args) == 0;
 }
 
-#ifdef DX_LNL_DIAG
+#endif  // DX_PS_JEFF
+
+#if defined(DX_LNL_DIAG) && !defined(DX_PS_JEFF)
 // the certified likelihood's diagnostic counters (dx_chain.h: g_lnl_diag): copied to out[2], then cleared
 extern "C" int dangx_lnl_diag(unsigned long long* out) {
     if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_lnl_diag), 2 * sizeof(unsigned long long)) != hipSuccess) return 1;

@@ -43,6 +43,7 @@ struct IndexArgs {
     int bp;           // some band is bandpass-integrated or a non-diffuse component is present: the compile-time chain
                       // modes then sum over the bandpass samples and remove the other components through comp_signal
     unsigned others;  // bit l: component l (/= comp) may have a non-zero amplitude on planes s1..s2
+    int jeff;         // host side only (it sits in what was padding): 1 = the Jeffreys instantiation of the register / fused kernel
     unsigned long long seed, stream;
 };
 
@@ -52,7 +53,7 @@ struct SweepItem {
     int mode;         // chain mode of the sweep (CH_POW ... CH_LOGN_W)
     int pair;         // 1: index nind + 1 of the same component follows in the same item (mode + 1)
     int gmember;      // the component's position among the group's members
-    int pad;
+    int jeff;         // 1: the chain carries the Jeffreys prior (CH_POW of the 'synch' component); part of the item's code
     unsigned long long stream, stream2;  // random streams of the sweep (and of the paired one)
 };
 constexpr int DX_MAX_SWEEPS = 6;

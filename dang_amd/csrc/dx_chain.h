@@ -122,14 +122,50 @@ struct BandPick {
 // the delta form.  What is chain invariant per SAMPLE (the other index's exponential of a modified blackbody) has nowhere to
 // live (85 values per pixel in bench.py --bandpass 16) and is evaluated again in every proposal: two exponentials per sample
 // instead of one for the mbb sweeps.
-template <int MODE, int SP, int NB, int LP, bool KT = false, bool BP = false>
+// JF (CH_POW, delta bands): the chain carries the Jeffreys prior of the component labelled 'synch' (eval_jeffreys_prior,
+// src/dang_lnl_mod.f90:242-304): every likelihood evaluation also leaves S = sum_j s_j^2 w_j in jS, where
+// w_j = ln(nu_j/nu_ref)^2 sum_k sigma_kj^-4 is formed once per chain (form_w) -- the reference's
+// sum_k sum_j ((1/sigma_kj)^2 (a_k s_j / a_k) ln(nu_j/nu_ref))^2 with the amplitude cancelled, so that where the reference
+// divides 0 by 0 (or inf by inf, or meets a NaN amplitude) w_j is NaN and so is S.  The weights live in registers, or (KT:
+// k_plane_set) in NB rows of the lane's LDS column behind the parked 1/rms.
+template <int MODE, int SP, int NB, int LP, bool KT = false, bool BP = false, bool JF = false>
 struct RegChain {
     static constexpr bool kBP = BP;
+    static constexpr bool kJF = JF;
+    static_assert(!JF || (MODE == CH_POW && !BP), "Jeffreys chains: power law, delta bands");
     double D[SP][NB], F[NB], ISr[SP][NB];  // cleaned data, chain-invariant SED factor, 1/rms  (scaled form: d/rms, amp/rms)
     double bpa, bpb;                       // BP: CH_MBB_BETA: z = h/(k T), exp(z nu_ref) - 1; CH_MBB_T: beta + 1
     double K1[(LP > 1 && !KT) ? NB : 1], K2[(LP > 1 && !KT) ? NB : 1];  // LP > 1: the lane's per-band constants (see k1 / k2)
     const double *kt1, *kt2;
     double amp[SP];
+    double W[(JF && !KT) ? NB : 1], jS;    // JF: the weights w_j (KT: in LDS at wcol), S of the last evaluation
+    double* wcol;
+
+    __device__ __forceinline__ double w(int j) const { return KT ? wcol[j * BLOCK] : W[j]; }
+    // the weights, from 1/rms of the lane's bands (is_of(kk, j)) and the amplitudes of the swept planes (amp[])
+    template <class ISF>
+    __device__ __forceinline__ void form_w(const Model& M, const Comp& c, ISF is_of) {
+        bool bad = false;
+#pragma unroll
+        for (int kk = 0; kk < SP; ++kk) bad = bad || !(fabs(amp[kk]) > 0.0 && fabs(amp[kk]) < INFINITY);
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+            const double t0 = is_of(0, j) * is_of(0, j);
+            double q = t0 * t0;
+            if (SP == 2) { const double t1 = is_of(SP - 1, j) * is_of(SP - 1, j); q = fma(t1, t1, q); }
+            const double l = k1(M, c, j);
+            const double wj = bad ? __longlong_as_double(0x7ff8000000000000ll) : (l * l) * q;
+            if (KT) wcol[j * BLOCK] = wj; else W[j] = wj;
+        }
+    }
+    // S alone at index value th (a chain that starts from likelihood sums it was handed evaluates no likelihood first)
+    __device__ __forceinline__ void jeff_eval(const Model& M, const Comp& c, double th) {
+        double S = 0.0;
+#pragma unroll
+        for (int j = 0; j < NB; ++j) { const double e = CEXP(th * k1(M, c, j)); S = fma(e * e, w(j), S); }
+        if (LP > 1) S += __shfl_xor(S, 1, 64);
+        jS = S;
+    }
 
     __device__ __forceinline__ double is(int kk, int j) const { return ISr[kk][j]; }
     __device__ __forceinline__ void set_is(int kk, int j, double v) { ISr[kk][j] = v; }
@@ -172,6 +208,7 @@ struct RegChain {
         else if (MODE == CH_LOGN_NUP) { s0 = log_pos(th); s1 = other; }  // log(nu/(nu_p*1e9)) = lnu9 - log(nu_p)
         else s1 = th;  // CH_LOGN_W
         acc0 = 0.0; acc1 = 0.0;
+        double S = 0.0;  // JF: the prior's sum, beside chi^2 (not in the SUB pass: no prior is evaluated there)
         // log-normal: ln(nu/nu_p)/w as a product with 1/w (v_rcp_f64 + two Newton steps, once per evaluation) instead of one
         // IEEE division per band -- the expression the amplitude kernels use for the same SED (sed_tile), <= 1 ulp from it
 #ifdef DX_CHAIN_IEEEDIV
@@ -270,6 +307,7 @@ struct RegChain {
                     acc1 = fma(r1, r1, acc1);
                 }
                 }
+                if (JF && OP != 2) S = fma(s[t] * s[t], w(j), S);
 #else
                 const double r0 = (D[0][j] - amp[0] * s[t]) * is(0, j);
                 acc0 = acc0 - 0.5 * (r0 * r0);
@@ -283,7 +321,9 @@ struct RegChain {
         if (LP > 1) {  // the other half's band sum: a + b on one lane, b + a on the other -- the same value
             acc0 += __shfl_xor(acc0, 1, 64);
             if (SP == 2) acc1 += __shfl_xor(acc1, 1, 64);
+            if (JF && OP != 2) S += __shfl_xor(S, 1, 64);
         }
+        if (JF && OP != 2) jS = S;
 #ifdef DX_CHAIN_SCALED
         acc0 *= -0.5; acc1 *= -0.5;
 #endif
@@ -472,6 +512,11 @@ __device__ __forceinline__ unsigned long long chain_finish(const Model& M, const
     const int npix = M.npix;
     double* out = c.idx + ((long long)a.nind * M.nmaps) * npix + i;
     const bool first = (a.nind == 0);
+    constexpr bool JEFF = RC::kJF;
+#if !defined(DX_CHAIN_SCALED)
+    static_assert(!JEFF, "the Jeffreys chain exists in the scaled form");
+#endif
+    if (JEFF && SCALE) R.form_w(M, c, [&](int kk, int j) { return R.is(kk, j); });  // ISr is still 1/rms here
     if (SCALE) R.scale();
     // --- chain-invariant SED factor
     if (MODE == CH_MBB_BETA) {
@@ -492,7 +537,8 @@ __device__ __forceinline__ unsigned long long chain_finish(const Model& M, const
         }
     }
     const double other = first ? sample1 : sample0;  // the index that is not sampled
-    // --- chain (gaussian / uniform prior inline; jeffreys falls back to the LDS form on the host side)
+    // --- chain (gaussian / uniform prior inline; JEFF: the prior of an evaluation is jprior of the sum it left in R.jS; every
+    // other Jeffreys configuration keeps the LDS form, decided on the host side)
     const unsigned long long gpix = (unsigned long long)(M.pix0 + i);
     const int q = a.nind;
     const bool gauss = c.prior_type[q] == DANGX_PRIOR_GAUSSIAN;
@@ -509,6 +555,13 @@ __device__ __forceinline__ unsigned long long chain_finish(const Model& M, const
 #endif
         return (arg > 745.0) ? -INFINITY : -arg - lgden;
     };
+    // log(sqrt(S)): S is positive and normal unless the weights are NaN (an amplitude the reference divides by is 0 or not
+    // finite) or the SEDs leave the range -- log_pos reads only the bits, those lanes take the library's routine
+    auto jprior = [&](double S) -> double {
+        double p = log_pos(sqrt(S));
+        if (!(S >= 0x1p-1022 && S < INFINITY)) p = log(sqrt(S));
+        return p;
+    };
     unsigned long long nacc = 0;
     double cur = first ? sample0 : sample1;
     double a0, a1, c0, c1;
@@ -520,15 +573,16 @@ __device__ __forceinline__ unsigned long long chain_finish(const Model& M, const
 #if defined(DX_LNL_EXACT) || !defined(DX_CHAIN_SCALED)
     constexpr bool kCert = false;
 #else
-    constexpr bool kCert = !RC::kBP && (MODE == CH_POW || MODE == CH_MBB_BETA || MODE == CH_MBB_T);
+    // (not for JEFF: the interval bounds the likelihood only, the prior moves with the SED too)
+    constexpr bool kCert = !RC::kBP && !JEFF && (MODE == CH_POW || MODE == CH_MBB_BETA || MODE == CH_MBB_T);
 #endif
     auto chain = [&](auto batch_tag) {
         constexpr bool B = decltype(batch_tag)::value;
         double lnl;
-        if (acc_in) { a0 = acc_in[0]; a1 = acc_in[1]; lnl = a0 + a1; }
+        if (acc_in) { a0 = acc_in[0]; a1 = acc_in[1]; lnl = a0 + a1; if (JEFF) R.jeff_eval(M, c, cur); }
         else lnl = R.template lnl<B, ADD ? 1 : 0>(M, c, cur, other, a0, a1);
         chi[0] = -2.0 * a0; chi[1] = -2.0 * a1;
-        double lnl_old = lnl + prior(cur);
+        double lnl_old = lnl + (JEFF ? jprior(R.jS) : prior(cur));
         // cheap path state: lnl_old is exact (old_exact) or within wold of the exact chain's; a0 / a1 are the sums of the
         // state at cur (sums_exact) or must be evaluated there after the loop
         bool cert = false, old_exact = true, sums_exact = true;
@@ -542,7 +596,7 @@ __device__ __forceinline__ unsigned long long chain_finish(const Model& M, const
             if (prop < lo || prop > hi) return;                        // :415
             if constexpr (!kCert) {
                 lnl = R.template lnl<B>(M, c, prop, other, c0, c1);
-                const double lnl_new = lnl + prior(prop);
+                const double lnl_new = lnl + (JEFF ? jprior(R.jS) : prior(prop));
                 const double diff = lnl_new - lnl_old;
                 const bool acc = ml_opt ? (diff > 0.0) : mh_accept(diff, u3);  // :443-454
                 if (acc) { cur = prop; lnl_old = lnl_new; a0 = c0; a1 = c1; ++nacc; }
@@ -662,8 +716,8 @@ __device__ __forceinline__ unsigned long long chain_finish(const Model& M, const
 
 // Staging of a register chain: the component's index values, data_raw (:173-177) and 1/rms of the lane's bands, every
 // other component removed (:180-196).  The caller has dealt with masked pixels.
-template <int MODE, int SP, int NB, int LP>
-__device__ __forceinline__ void index_chain_stage(const Model& M, const IndexArgs& a, const Comp& c, RegChain<MODE, SP, NB, LP>& R,
+template <int MODE, int SP, int NB, int LP, class RC>
+__device__ __forceinline__ void index_chain_stage(const Model& M, const IndexArgs& a, const Comp& c, RC& R,
                                                   const BandPick<LP>& pick, int i, double& sample0, double& sample1) {
     const int npix = M.npix;
     const int jb = pick.half * NB;  // first band of this lane
@@ -725,7 +779,7 @@ __device__ __forceinline__ void index_chain_stage(const Model& M, const IndexArg
 }
 
 // NB = bands per lane (all of them for LP == 1, half for LP == 2); half = which half this lane owns
-template <int MODE, int SP, int NB, int LP>
+template <int MODE, int SP, int NB, int LP, bool JF = false>
 __device__ __forceinline__ unsigned long long index_chain_reg(const Model& M, const IndexArgs& a, int i, int half, double chi[4]) {
     const int npix = M.npix;
     const Comp& c = M.comp[a.comp];
@@ -738,7 +792,7 @@ __device__ __forceinline__ unsigned long long index_chain_reg(const Model& M, co
         return 0ull;
     }
     const BandPick<LP> pick = {half};
-    RegChain<MODE, SP, NB, LP> R;
+    RegChain<MODE, SP, NB, LP, false, false, JF> R;
     double sample0, sample1;
     index_chain_stage<MODE, SP, NB, LP>(M, a, c, R, pick, i, sample0, sample1);
     return chain_finish<MODE, SP, NB, LP>(M, a, c, R, pick, sample0, sample1, i, half, chi);

@@ -307,7 +307,7 @@ int dx_launch_sv_mixed(dangx_ctx* ctx, const GroupArgs& a, long long SN, const d
 // LDS-form Metropolis kernel (fast = chisq likelihood with CH_POW / CH_MBB_*; otherwise the generic chain)
 void dx_launch_mh_lds(dangx_ctx* ctx, const IndexArgs& a, bool fast, int Sp, unsigned nblk, int bs, size_t lds, unsigned long long* accp);
 // register-resident Metropolis kernels; return false when (mode, nb) is not instantiated
-bool dx_mh_reg_supported(dangx_ctx* ctx, int mode, int nb, int Sp);
+bool dx_mh_reg_supported(dangx_ctx* ctx, int mode, int nb, int Sp, int jeff = 0);  // jeff: the Jeffreys chain (CH_POW)
 bool dx_mh_pair_supported(int mode_a, int mode_b, int nb, int Sp);
 bool dx_launch_mh_pair(dangx_ctx* ctx, const IndexArgs& a, const IndexArgs& b, int Sp, unsigned nblk, unsigned long long* accp);
 bool dx_fused_supported(int mode, int nb, int ng);

@@ -21,7 +21,8 @@ namespace dxk {
 #ifndef DX_CHAIN_WAVES
 #define DX_CHAIN_WAVES(SP, NB, LP) (((SP) == 1 && (NB) <= 10) ? 3 : ((SP) == 2 && (NB) / (LP) > DX_CHAIN_ONE_WAVE_FROM) ? 1 : 2)
 #endif
-template <int MODE, int SP, int NB, int LP>
+// JF: the chain carries the Jeffreys prior of the 'synch' component (dx_chain.h: RegChain<.., JF>; CH_POW only)
+template <int MODE, int SP, int NB, int LP, bool JF = false>
 __global__ __launch_bounds__(BLOCK, DX_CHAIN_WAVES(SP, NB, LP)) void k_index_mh_reg(const Model* __restrict__ Mp, IndexArgs a,
                                                         unsigned long long* __restrict__ accepted,
                                                         double* __restrict__ chi_partial) {
@@ -30,7 +31,7 @@ __global__ __launch_bounds__(BLOCK, DX_CHAIN_WAVES(SP, NB, LP)) void k_index_mh_
     const long long t = (long long)blockIdx.x * BLOCK + tid;
     const int i = (int)(t / LP), half = (int)(t % LP);
     double chi[4] = {0.0, 0.0, 0.0, 0.0};
-    unsigned long long nacc = (i < M.npix) ? index_chain_reg<MODE, SP, NB / LP, LP>(M, a, i, half, chi) : 0ull;
+    unsigned long long nacc = (i < M.npix) ? index_chain_reg<MODE, SP, NB / LP, LP, JF>(M, a, i, half, chi) : 0ull;
     if (accepted) {
         for (int o = 32; o > 0; o >>= 1) nacc += __shfl_down(nacc, o, 64);
         if ((tid & 63) == 0 && nacc) atomicAdd(accepted, nacc);

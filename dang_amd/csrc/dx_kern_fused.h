@@ -84,7 +84,8 @@ __device__ __forceinline__ void sed_column_bp(const Model& M, const Comp& c2, co
 // lane needs, which is what lets a 20-band, 6-member group (C5) keep two waves per SIMD.  The band sums are then associated
 // as (first half) + (second half) -- the stand-alone amplitude kernel adds band by band: the last bits of the amplitudes
 // differ from the two-launch form (LP = 1 instantiations are bit for bit the two launches).
-template <int MODE, int SP, int NB, int NG, int LP>
+// JF: the sweep carries the Jeffreys prior of the 'synch' component (dx_chain.h: RegChain<.., JF>; CH_POW only)
+template <int MODE, int SP, int NB, int NG, int LP, bool JF = false>
 __global__ __launch_bounds__(BLOCK, DX_FUSED_WAVES(SP, NB)) void k_amp_index(const Model* __restrict__ Mp, GroupArgs ga, FusedArgs fa, IndexArgs a,
                                                                                   unsigned long long* __restrict__ not_spd,
                                                                                   unsigned long long* __restrict__ accepted,
@@ -114,7 +115,7 @@ __global__ __launch_bounds__(BLOCK, DX_FUSED_WAVES(SP, NB)) void k_amp_index(con
     }
     if (live) {
         const BandPick<LP> pick = {half};
-        RegChain<MODE, SP, NBL, LP> R;
+        RegChain<MODE, SP, NBL, LP, false, false, JF> R;
         R.set_k(M, c, pick);
         const long long bstride = (long long)M.nmaps * npix;
         const unsigned long long gpix = (unsigned long long)(M.pix0 + i);

@@ -42,26 +42,32 @@ template <bool V> struct ItemFlag { static constexpr bool value = V; };
 // one item of the sweep list for member it.gmember: chain (and the paired chain of index nind + 1, as index_chain_pair does);
 // R0.D holds the full residual / rms of the lane's bands, rows 0 .. SP*NBL-1 of the lane's LDS column hold 1 / rms.  Leaves the
 // member's two index values in sample0 / sample1.  LAST: nothing follows, the residual need not be restored.
-template <int MODE, int PAIR, int SP, int NBL, int LP, int NG, bool FIRST, bool LAST, bool BP, typename RFirst>
+// JF: the item's chain carries the Jeffreys prior; its weights go to rows SP*NBL .. of the lane's column (RegChain::form_w)
+template <int MODE, int PAIR, int SP, int NBL, int LP, int NG, bool FIRST, bool LAST, bool BP, bool JF, typename RFirst>
 __device__ __forceinline__ void ps_item(const Model& M, const SweepList& sl, const SweepItem& it, RFirst& R0, int i, int half,
                                         int jb, int NB, const double* __restrict__ tab, const double* __restrict__ col,
                                         double& sample0, double& sample1, double chi_first[4],
-                                        double chi_last[4], unsigned int* __restrict__ accepted, int slot, const double* first_acc) {
+                                        double chi_last[4], unsigned int* __restrict__ accepted, int slot, const double* first_acc,
+                                        double* wrow) {
     const Comp& c = M.comp[it.comp];
     const BandPick<LP> pick = {half};
     const int npix = M.npix;
     IndexArgs a;
     a.comp = it.comp; a.nind = it.nind; a.s1 = sl.s1; a.s2 = sl.s2; a.nsample = sl.nsample; a.ml_mode = sl.ml_mode; a.mode = MODE;
-    a.bp = 0; a.others = 0u; a.seed = sl.seed; a.stream = it.stream;
+    a.bp = 0; a.others = 0u; a.jeff = 0; a.seed = sl.seed; a.stream = it.stream;
     // per-band constants from the block's table in LDS, in the one-lane form too (as scalar operands from the model instead: 86.4
     // against 87.1 it/s at C3 on one device -- the scalar registers are what the kernel is short of)
-    RegChain<MODE, SP, NBL, LP, true, BP> R;
+    RegChain<MODE, SP, NBL, LP, true, BP, JF> R;
     R.set_kt(tab, NB, NG, it.gmember, jb);
 #pragma unroll
     for (int kk = 0; kk < SP; ++kk) {
         R.amp[kk] = c.amp[(long long)(sl.s1 + kk - 1) * npix + i];   // the lane's own store after the solve, or the map in memory
 #pragma unroll
         for (int j = 0; j < NBL; ++j) { R.D[kk][j] = R0.D[kk][j]; R.ISr[kk][j] = col[(kk * NBL + j) * BLOCK] * R.amp[kk]; }
+    }
+    if (JF) {
+        R.wcol = wrow;   // rows SP*NBL .. (SP+1)*NBL-1 of the lane's column: disjoint from the 1/rms rows read through col
+        R.form_w(M, c, [&](int kk, int j) { return col[(kk * NBL + j) * BLOCK]; });
     }
     double chia[4] = {0.0, 0.0, 0.0, 0.0}, va, acc[2];
     // FIRST: the kernel has put this member's signal back already, from its SED column of the solve (R0.D is the cleaned data and
@@ -114,7 +120,8 @@ __device__ __forceinline__ void ps_item(const Model& M, const SweepList& sl, con
 }
 
 // C0 .. C3: the sweep items of the launch, compile-time: chain mode (CH_POW, CH_MBB_BETA, CH_LOGN_NUP ...) + 8 when index nind + 1 of
-// the same component follows in the same item (mbb: beta then T; log-normal: nu_p then w), 0 = no item.  A run-time switch over
+// the same component follows in the same item (mbb: beta then T; log-normal: nu_p then w), + 16 when the chain carries the Jeffreys
+// prior (CH_POW of the 'synch' component), 0 = no item.  A run-time switch over
 // the modes inside one kernel costs the register allocator ~200 spills (three inlined chains share one frame); a model's
 // sweep sequence is fixed for a run, so it is part of the specialisation: C5 = <POW, MBB_BETA + 8, LOGN_NUP> is built in, any
 // other sequence is compiled on first use (dangx_rtc.hip).
@@ -143,7 +150,7 @@ __global__ __launch_bounds__(BLOCK, DX_PS_WAVES(SP, NB, LP, SOLVE, C0)) void k_p
     double chi[4] = {0.0, 0.0, 0.0, 0.0};
     // masked sums of the index maps the launch sweeps (mask_avg's numerator, src/dang_util_mod.f90:186-206: what write_stats_to_term
     // prints after the phase): the value each chain ends on, by-products like chi^2 -- rows 4 .. of chi_partial
-    constexpr int NS0 = C0 ? 1 + (C0 >> 3) : 0, NS1 = C1 ? 1 + (C1 >> 3) : 0, NS2 = C2 ? 1 + (C2 >> 3) : 0, NS3 = C3 ? 1 + (C3 >> 3) : 0;
+    constexpr int NS0 = C0 ? 1 + ((C0 >> 3) & 1) : 0, NS1 = C1 ? 1 + ((C1 >> 3) & 1) : 0, NS2 = C2 ? 1 + ((C2 >> 3) & 1) : 0, NS3 = C3 ? 1 + ((C3 >> 3) & 1) : 0;
     constexpr int NS = NS0 + NS1 + NS2 + NS3;
     const bool live = in_range && !is_masked(mk);
     if (in_range && !live && half == 0) {  // masked: x stays (:695); every swept index map gets a zero (:223, :480-483)
@@ -368,9 +375,10 @@ __global__ __launch_bounds__(BLOCK, DX_PS_WAVES(SP, NB, LP, SOLVE, C0)) void k_p
                 double sample0, sample1, unused[4];
                 // a component's sweeps are consecutive and travel in ONE item: no lane reads here what its partner wrote
                 load_theta(M, c, i, sl.s1, sample0, sample1);
-                ps_item<(CODE & 7), (CODE >> 3), SP, NBL, LP, NG, FIRST, LAST, (BP != 0)>(M, sl, it, R0, i, half, jb, NB, tab, col, sample0, sample1,
-                                                                              FIRST ? chi : unused, chi, accepted ? acc_blk : nullptr, slot, first_acc);
-                slot += 1 + (CODE >> 3);
+                ps_item<(CODE & 7), ((CODE >> 3) & 1), SP, NBL, LP, NG, FIRST, LAST, (BP != 0), ((CODE >> 4) != 0)>(M, sl, it, R0, i, half, jb, NB, tab, col, sample0, sample1,
+                                                                              FIRST ? chi : unused, chi, accepted ? acc_blk : nullptr, slot, first_acc,
+                                                                              col + (SP * NBL) * BLOCK);
+                slot += 1 + ((CODE >> 3) & 1);
             }
         };
         run(ItemCode<C0>{}, ItemFlag<true>{}, ItemFlag<C1 == 0>{}, 0);
@@ -400,7 +408,7 @@ __global__ __launch_bounds__(BLOCK, DX_PS_WAVES(SP, NB, LP, SOLVE, C0)) void k_p
                 if (code[q] != 0) {
                     const double* at = M.comp[sl.s[q].comp].idx + ((long long)sl.s[q].nind * M.nmaps + (sl.s1 - 1)) * npix + i;
                     isum[first[q]] = at[0];
-                    if ((code[q] >> 3) != 0) isum[first[q] + 1] = at[(long long)M.nmaps * npix];
+                    if (((code[q] >> 3) & 1) != 0) isum[first[q] + 1] = at[(long long)M.nmaps * npix];
                 }
         }
         __shared__ double sh[4 + NS][BLOCK / 64];

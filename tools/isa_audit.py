@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """ISA audit of the hot kernels: per kernel the register / spill footprint and, per loop, what the loop body issues.
 
-usage: tools/isa_audit.py [--unit dangx_planeset.hip] [--defs "-DX ..."] [--match k_plane_set] [-o profiles/rNN_isa_audit.md]
+usage: tools/isa_audit.py [--unit dangx_planeset.hip] [--defs="-DX ..."] [--match k_plane_set] [-o profiles/rNN_isa_audit.md]
+(the Jeffreys instantiations of k_plane_set are a unit of their own: --defs=-DDX_PS_JEFF; those of k_index_mh_reg / k_amp_index are in
+the --defs=-DDX_REG_MODE=1 units of dangx_mhreg.hip / dangx_fused.hip)
 
 Compiles one translation unit of dang_amd/csrc with --save-temps (gfx950), walks the device assembly and reports for every
 kernel whose mangled name contains --match:
