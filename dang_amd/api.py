@@ -620,6 +620,7 @@ class Engine:
     # -- posterior moments (dangx_moments_*: the chain's running mean / second moment, accumulated in HBM)
     def moments_begin(self, sel=None):
         """Start (or restart) accumulating: sel[l] = selection word of component l (include/dangx.h; None = every plane)."""
+        self._moment_pairs, self._moment_lag1 = [], False   # dangx_moments_begin drops what moments_pairs registered
         if sel is None:
             self._chk(self.lib.dangx_moments_begin(self.h, None))
             full = (1 << self.nmaps) - 1
@@ -642,7 +643,8 @@ class Engine:
 
     def moments_get(self, l, what, stat, ddof=0, device=False, out=None):
         """Mean (stat 'mean' / 0) or standard deviation ('std' / 1, sqrt(m2 / (n - ddof))) of component l's amplitude (what 0)
-        or index j (what 1 + j) as [nmaps][npix].  Planes that are not selected keep what `out` holds (default zeros).
+        or index j (what 1 + j) as [nmaps][npix]; after moments_pairs(..., lag1=True) also the lag-1 autocorrelation ('rho1' / 2)
+        and the AR(1) effective sample size ('ess' / 3).  Planes that are not selected keep what `out` holds (default zeros).
         device=True: a torch cuda tensor filled on the device (no host round trip)."""
         st = L.STAT_CODES[stat] if isinstance(stat, str) else int(stat)
         if device:
@@ -667,6 +669,34 @@ class Engine:
             out = np.zeros((self.nmaps, self.nbands))
         assert out.dtype == np.float64 and out.flags.c_contiguous and out.shape == (self.nmaps, self.nbands)
         self._chk(self.lib.dangx_moments_get_template(self.h, l, st, int(ddof), out.ctypes.data))
+        return out
+
+    def moments_pairs(self, pairs, lag1=True):
+        """Register second-order statistics after moments_begin and before the first moments_accumulate: the cross terms of
+        pairs = [((l_a, what_a, plane_a), (l_b, what_b, plane_b)), ...] (what / plane as in moments_get, plane 0-based) and, with
+        lag1, the lag-1 autocorrelation of every selected plane.  A second call replaces the first."""
+        p = np.ascontiguousarray(np.asarray(list(pairs), dtype=np.int32).reshape(-1, 6))
+        self._chk(self.lib.dangx_moments_pairs(self.h, 1 if lag1 else 0, p.shape[0], p.ctypes.data if p.size else None))
+        self._moment_pairs = [(tuple(int(v) for v in r[:3]), tuple(int(v) for v in r[3:])) for r in p]
+        self._moment_lag1 = bool(lag1)
+
+    def moments_get_pair(self, p, stat, ddof=0, device=False, out=None):
+        """Covariance ('cov' / 0: C / (n - ddof)) or correlation ('corr' / 1) of registered pair p as [npix]; NaN where a variance
+        is zero.  device=True: a torch cuda tensor filled on the device."""
+        st = L.PAIR_STAT_CODES[stat] if isinstance(stat, str) else int(stat)
+        if device:
+            import torch
+            if out is None:
+                dev = self._device if self._device is not None and self._device >= 0 else torch.cuda.current_device()
+                out = torch.zeros((self.npix,), dtype=torch.float64, device=torch.device("cuda", dev))
+            assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float64 and tuple(out.shape) == (self.npix,)
+            self._chk(self.lib.dangx_moments_get_pair_dev(self.h, int(p), st, int(ddof), out.data_ptr()))
+            self.synchronize()
+            return out
+        if out is None:
+            out = np.zeros(self.npix)
+        assert isinstance(out, np.ndarray) and out.dtype == np.float64 and out.flags.c_contiguous and out.shape == (self.npix,)
+        self._chk(self.lib.dangx_moments_get_pair(self.h, int(p), st, int(ddof), out.ctypes.data))
         return out
 
     def moments_end(self):
@@ -1117,7 +1147,7 @@ def posterior_maps(ddata, ddof=0, masked_value=None, engines=None):
                 continue
             key = (c.label, "amplitude" if what == 0 else (c.ind_label[what - 1] if what - 1 < len(c.ind_label) else "index%d" % what))
             entry = {"n": n}
-            for stat in ("mean", "std"):
+            for stat in ("mean", "std") + (("rho1", "ess") if getattr(engs[0], "_moment_lag1", False) else ()):
                 if what == 0 and c.type in GLOBAL_TYPES:
                     entry[stat] = engs[0].moments_get_template(l, stat, ddof)
                     continue
@@ -1127,6 +1157,63 @@ def posterior_maps(ddata, ddof=0, masked_value=None, engines=None):
                     parts.append(_mask_fill(m, e.ddata.masks, masked_value) if masked_value is not None else m)
                 entry[stat] = np.concatenate(parts, axis=-1) if len(parts) > 1 else parts[0]
             out[key] = entry
+    return out
+
+
+def _plane_name(c, what):
+    return "amplitude" if what == 0 else (c.ind_label[what - 1] if what - 1 < len(c.ind_label) else "index%d" % what)
+
+
+def default_moment_pairs(dpar, component_list, sel):
+    """The degeneracies of a pixel's own parameters, as [((l, what, plane), (l, what, plane)), ...] for moments_pairs: per component
+    and plane k, (amplitude, index j) for every sampled index j whose plane k and the amplitude's plane k are both in `sel`, then
+    (index 0, index 1) when both are sampled on plane k.  Component order, then plane, then that pair order.  Pure Python."""
+    pairs = []
+    for l, c in enumerate(component_list):
+        if c.type in GLOBAL_TYPES:
+            continue
+        w = int(sel[l])
+        for k in range(3):
+            ind = [j for j in range(c.nindices) if (w >> (3 + 3 * j + k)) & 1]
+            if (w >> k) & 1:
+                pairs += [((l, 0, k), (l, 1 + j, k)) for j in ind]
+            if 0 in ind and 1 in ind:
+                pairs.append(((l, 1, k), (l, 2, k)))
+    return pairs
+
+
+def moments_pairs(dpar, ddata, pairs=None, lag1=True, engines=None):
+    """dangx_moments_pairs on every context of this process, after moments_begin and before the first moments_accumulate;
+    pairs=None: default_moment_pairs of the selection moments_begin made.  Returns the pair list."""
+    engs = _engines_of(ddata, engines)
+    if pairs is None:
+        sel = getattr(engs[0], "_moment_sel", None)
+        if sel is None:
+            raise DangxError("moments_pairs: moments_begin was not called")
+        pairs = default_moment_pairs(dpar, engs[0].component_list, sel)
+    pairs = [(tuple(a), tuple(b)) for a, b in pairs]
+    for e in engs:
+        e.moments_pairs(pairs, lag1=lag1)
+    return pairs
+
+
+def posterior_pair_maps(ddata, stat="corr", ddof=0, masked_value=None, engines=None):
+    """{((label_a, name_a, plane_a), (label_b, name_b, plane_b)): [npix]} of the pairs moments_pairs registered: their correlation
+    ('corr') or covariance ('cov', with ddof) maps; names as posterior_maps' keys, planes 0-based.  Several contexts of this
+    process: their shards side by side.  masked_value: as in posterior_maps."""
+    engs = _engines_of(ddata, engines)
+    pairs = getattr(engs[0], "_moment_pairs", None)
+    if pairs is None:
+        raise DangxError("posterior_pair_maps: moments_pairs was not called")
+    comps = engs[0].component_list
+    out = {}
+    for p, (a, b) in enumerate(pairs):
+        parts = []
+        for e in engs:
+            m = e.moments_get_pair(p, stat, ddof)
+            parts.append(_mask_fill(m, e.ddata.masks, masked_value) if masked_value is not None else m)
+        key = tuple((comps[l].label, _plane_name(comps[l], what), k) for l, what, k in (a, b))
+        out[key] = np.concatenate(parts, axis=-1) if len(parts) > 1 else parts[0]
     return out
 
 

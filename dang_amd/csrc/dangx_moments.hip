@@ -13,14 +13,45 @@
 //
 // Template amplitudes of global-amplitude members (<= 3 x nbands values) live on the host (ctx->tamp, current after every call
 // that samples them) and get the same update there: accumulation adds no device-to-host synchronisation.
+//
+// dangx_moments_pairs adds two second-order statistics, streams of the same shape (expressions in dx_moments_host.h):
+//   lag-1 autocorrelation of every selected plane: k_moments_accum_lag replaces k_moments_accum and keeps, beside mean and m2, the
+//     first sample r, the previous sample and P = sum (x_t - r)(x_{t-1} - r) -- one read of x, at most 10 x 8 B per element (read
+//     x, mean, m2, prev, r, P; write mean, m2, prev, P).  The previous sample is written by the thread that read it.
+//   cross terms of pairs of planes: k_moments_pairs, C += (a - mean_a_old)(b - mean_b_new) with mean_b_new formed in registers,
+//     6 x 8 B per element (read a, b, both old means, C; write C).  It is a launch of its own BEFORE the launch that updates the
+//     means (stream order), so no block reads a mean another block is writing.
+// Without dangx_moments_pairs an accumulation is the one k_moments_accum launch, as before.
 #include "dx_host.h"
+#include "dx_moments_host.h"
 
 #include <cstdint>
+
+static_assert(DX_MOM_MAX_PAIRS == DANGX_MAX_PAIRS, "dx_moments_host.h and include/dangx.h disagree");
 
 struct MomSeg {           // one selected plane: the chain's plane (resolved at accumulate time) and its two accumulators
     const double* x;
     double* mean;
     double* m2;
+    long long n;
+};
+
+struct LagSeg {           // a selected plane with lag-1 tracking: MomSeg + previous sample, first sample, P
+    const double* x;
+    double* mean;
+    double* m2;
+    double* prev;
+    double* first;
+    double* P;
+    long long n;
+};
+
+struct PairSeg {          // a pair of selected planes and its cross-term accumulator
+    const double* xa;
+    const double* xb;
+    const double* ma;
+    const double* mb;
+    double* C;
     long long n;
 };
 
@@ -37,6 +68,15 @@ struct DxMoments {
     double tm_mean[MAXC][3][MAXB] = {}, tm_m2[MAXC][3][MAXB] = {};
     double* scratch = nullptr;       // [nmaps][npix]: what the host getter copies from
     unsigned grid_target = 0;        // blocks of a full-machine launch
+    // dangx_moments_pairs
+    bool lag1 = false;
+    double* lag = nullptr;           // [prev | first | P], acc_half doubles each, planes at the offsets of acc
+    LagSeg* d_lag = nullptr;
+    struct Pair { int a, b; long long off; };   // indices into segs; off: the pair's plane in pc (at the phase of a's mean)
+    std::vector<Pair> pairs;
+    double* pc = nullptr;
+    PairSeg* d_pairs = nullptr;
+    double tm_prev[MAXC][3][MAXB] = {}, tm_first[MAXC][3][MAXB] = {}, tm_P[MAXC][3][MAXB] = {};
 };
 
 namespace {
@@ -89,6 +129,122 @@ __global__ __launch_bounds__(BLOCK) void k_moments_accum(const MomSeg* __restric
     }
 }
 
+// Welford's update and the lag-1 state from one read of x.  FIRST (sample 1): r = prev = x, P stays the 0 it was allocated with.
+template <bool FIRST>
+__device__ __forceinline__ void lag_step(double x, double& mean, double& m2, double& prev, double r, double& P, double inv_n) {
+    if (FIRST) prev = x;
+    else dx_lag_update(x, prev, r, P);
+    welford(x, mean, m2, inv_n);
+}
+
+template <bool FIRST>
+__device__ __forceinline__ void lag_one(const LagSeg& s, long long i, double inv_n) {
+    const double x = s.x[i];
+    double m = s.mean[i], q = s.m2[i], pv = 0.0, P = 0.0;
+    if (!FIRST) { pv = s.prev[i]; P = s.P[i]; }
+    lag_step<FIRST>(x, m, q, pv, FIRST ? x : s.first[i], P, inv_n);
+    s.mean[i] = m; s.m2[i] = q; s.prev[i] = pv;
+    if (FIRST) s.first[i] = x;
+    else s.P[i] = P;
+}
+
+// k_moments_accum with the lag-1 state; the accumulators of a plane share their 16-byte phase by construction (dangx_moments_begin
+// / _pairs), so as there only the chain's plane can be off phase
+template <bool FIRST>
+__global__ __launch_bounds__(BLOCK) void k_moments_accum_lag(const LagSeg* __restrict__ segs, double inv_n) {
+    const LagSeg s = segs[blockIdx.y];
+    const long long n = s.n;
+    const long long gid = (long long)blockIdx.x * BLOCK + threadIdx.x, stride = (long long)gridDim.x * BLOCK;
+    const uintptr_t ax = reinterpret_cast<uintptr_t>(s.x), am = reinterpret_cast<uintptr_t>(s.mean);
+    const uintptr_t others = (am ^ reinterpret_cast<uintptr_t>(s.m2)) | (am ^ reinterpret_cast<uintptr_t>(s.prev)) |
+                             (am ^ reinterpret_cast<uintptr_t>(s.first)) | (am ^ reinterpret_cast<uintptr_t>(s.P));
+    if ((((ax ^ am) | others) & 15) != 0) {   // no common 16-byte phase: element by element
+        for (long long i = gid; i < n; i += stride) lag_one<FIRST>(s, i, inv_n);
+        return;
+    }
+    const long long head = ((ax & 15) != 0 && n > 0) ? 1 : 0;
+    const long long npair = (n - head) / 2, tail = head + 2 * npair;
+    if (gid == 0 && head) lag_one<FIRST>(s, 0, inv_n);
+    if (gid == 1 && tail < n) lag_one<FIRST>(s, tail, inv_n);
+    const GD2* __restrict__ x2 = (const GD2*)(s.x + head);
+    GD2* __restrict__ m2v = (GD2*)(s.mean + head);
+    GD2* __restrict__ q2v = (GD2*)(s.m2 + head);
+    GD2* __restrict__ pv2 = (GD2*)(s.prev + head);
+    GD2* __restrict__ r2 = (GD2*)(s.first + head);
+    GD2* __restrict__ P2 = (GD2*)(s.P + head);
+    for (long long p = gid; p < npair; p += stride) {
+        const dbl2 x = x2[p], m = m2v[p], q = q2v[p];
+        double m0 = m.x, m1 = m.y, q0 = q.x, q1 = q.y;
+        if (FIRST) {
+            welford(x.x, m0, q0, inv_n);
+            welford(x.y, m1, q1, inv_n);
+            pv2[p] = x; r2[p] = x;
+        } else {
+            const dbl2 pv = pv2[p], r = r2[p], P = P2[p];
+            double pv0 = pv.x, pv1 = pv.y, P0 = P.x, P1 = P.y;
+            lag_step<false>(x.x, m0, q0, pv0, r.x, P0, inv_n);
+            lag_step<false>(x.y, m1, q1, pv1, r.y, P1, inv_n);
+            pv2[p] = dbl2{pv0, pv1}; P2[p] = dbl2{P0, P1};
+        }
+        m2v[p] = dbl2{m0, m1}; q2v[p] = dbl2{q0, q1};
+    }
+}
+
+// blockIdx.y = pair.  Reads the means as the PREVIOUS accumulation left them: launched before the kernel that updates them.
+__global__ __launch_bounds__(BLOCK) void k_moments_pairs(const PairSeg* __restrict__ segs, double inv_n) {
+    const PairSeg s = segs[blockIdx.y];
+    const long long n = s.n;
+    const long long gid = (long long)blockIdx.x * BLOCK + threadIdx.x, stride = (long long)gridDim.x * BLOCK;
+    const uintptr_t ac = reinterpret_cast<uintptr_t>(s.C);
+    const uintptr_t diff = (ac ^ reinterpret_cast<uintptr_t>(s.xa)) | (ac ^ reinterpret_cast<uintptr_t>(s.xb)) |
+                           (ac ^ reinterpret_cast<uintptr_t>(s.ma)) | (ac ^ reinterpret_cast<uintptr_t>(s.mb));
+    if ((diff & 15) != 0) {   // the two planes (or an adopted buffer) are at different 16-byte phases: element by element
+        for (long long i = gid; i < n; i += stride) s.C[i] = dx_pair_update(s.xa[i], s.xb[i], s.ma[i], s.mb[i], s.C[i], inv_n);
+        return;
+    }
+    const long long head = ((ac & 15) != 0 && n > 0) ? 1 : 0;
+    const long long npair = (n - head) / 2, tail = head + 2 * npair;
+    if (gid == 0 && head) s.C[0] = dx_pair_update(s.xa[0], s.xb[0], s.ma[0], s.mb[0], s.C[0], inv_n);
+    if (gid == 1 && tail < n) s.C[tail] = dx_pair_update(s.xa[tail], s.xb[tail], s.ma[tail], s.mb[tail], s.C[tail], inv_n);
+    const GD2* __restrict__ a2 = (const GD2*)(s.xa + head);
+    const GD2* __restrict__ b2 = (const GD2*)(s.xb + head);
+    const GD2* __restrict__ ma2 = (const GD2*)(s.ma + head);
+    const GD2* __restrict__ mb2 = (const GD2*)(s.mb + head);
+    GD2* __restrict__ C2 = (GD2*)(s.C + head);
+    for (long long p = gid; p < npair; p += stride) {
+        const dbl2 a = a2[p], b = b2[p], ma = ma2[p], mb = mb2[p], c = C2[p];
+        C2[p] = dbl2{dx_pair_update(a.x, b.x, ma.x, mb.x, c.x, inv_n), dx_pair_update(a.y, b.y, ma.y, mb.y, c.y, inv_n)};
+    }
+}
+
+struct FinishLagArgs {
+    const double* mean[3];
+    const double* m2[3];
+    const double* prev[3];
+    const double* first[3];
+    const double* P[3];
+    double* out[3];
+    long long n;
+    int stat;    // 2 = rho1, 3 = ESS
+    double cnt;  // samples
+};
+
+__global__ __launch_bounds__(BLOCK) void k_moments_finish_lag(FinishLagArgs a) {
+    const int p = blockIdx.y;
+    for (long long i = (long long)blockIdx.x * BLOCK + threadIdx.x; i < a.n; i += (long long)gridDim.x * BLOCK) {
+        const double rho = dx_lag_rho1(a.mean[p][i], a.m2[p][i], a.prev[p][i], a.first[p][i], a.P[p][i], a.cnt);
+        a.out[p][i] = a.stat == 2 ? rho : dx_lag_ess(rho, a.cnt);
+    }
+}
+
+// out = C / (n - ddof), or C / sqrt(m2_a m2_b)
+__global__ __launch_bounds__(BLOCK) void k_moments_finish_pair(const double* __restrict__ C, const double* __restrict__ m2a,
+                                                               const double* __restrict__ m2b, double* __restrict__ out, long long n,
+                                                               int stat, double dn) {
+    for (long long i = (long long)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * BLOCK)
+        out[i] = dx_pair_stat(C[i], m2a[i], m2b[i], stat, dn);
+}
+
 struct FinishArgs {
     const double* mean[3];
     const double* m2[3];
@@ -131,6 +287,10 @@ void release(DxMoments* m) {
     if (m->d_table) (void)hipFree(m->d_table);
     if (m->acc) (void)hipFree(m->acc);
     if (m->scratch) (void)hipFree(m->scratch);
+    if (m->lag) (void)hipFree(m->lag);
+    if (m->d_lag) (void)hipFree(m->d_lag);
+    if (m->pc) (void)hipFree(m->pc);
+    if (m->d_pairs) (void)hipFree(m->d_pairs);
     delete m;
 }
 
@@ -147,7 +307,10 @@ int get_planes(dangx_ctx* ctx, int comp, int what, int stat, int ddof, unsigned&
     DxMoments* m = ctx->mom;
     if (comp < 0 || comp >= ctx->dims.ncomp) return fail(ctx, "posterior moments: component index out of range");
     if (what < 0 || what > DANGX_MAX_IND) return fail(ctx, "posterior moments: what must be 0 (amplitude) or 1 + index number");
-    if (stat != 0 && stat != 1) return fail(ctx, "posterior moments: stat must be 0 (mean) or 1 (standard deviation)");
+    if (stat < 0 || stat > 3)
+        return fail(ctx, "posterior moments: stat must be 0 (mean), 1 (standard deviation), 2 (lag-1 autocorrelation) or 3 (effective sample size)");
+    if (stat >= 2 && !m->lag1)
+        return fail(ctx, "posterior moments: the lag-1 autocorrelation is not tracked (dangx_moments_pairs with lag1 != 0 was not called)");
     if (m->count == 0) return fail(ctx, "posterior moments: no sample accumulated");
     if (stat == 1 && (ddof < 0 || m->count - ddof <= 0)) return fail(ctx, "posterior moments: standard deviation needs 0 <= ddof < n");
     planes = (unsigned)(m->sel[comp] >> (what == 0 ? 0 : 3 + 3 * (what - 1))) & 7u;
@@ -158,6 +321,27 @@ int get_planes(dangx_ctx* ctx, int comp, int what, int stat, int ddof, unsigned&
 // k_moments_finish of the selected planes of (comp, what) into dst ([nmaps][npix], device)
 int finish(dangx_ctx* ctx, int comp, int what, int stat, int ddof, unsigned planes, double* dst) {
     DxMoments* m = ctx->mom;
+    if (stat >= 2) {   // rho1 / ESS from the lag-1 state
+        FinishLagArgs a{};
+        int np = 0;
+        for (const auto& s : m->segs) {
+            if (s.comp != comp || s.what != what || !((planes >> s.plane) & 1u)) continue;
+            a.mean[np] = m->acc + s.off;
+            a.m2[np] = m->acc + m->acc_half + s.off;
+            a.prev[np] = m->lag + s.off;
+            a.first[np] = m->lag + m->acc_half + s.off;
+            a.P[np] = m->lag + 2 * m->acc_half + s.off;
+            a.out[np] = dst + (long long)s.plane * ctx->dims.npix;
+            ++np;
+        }
+        a.n = ctx->dims.npix;
+        a.stat = stat;
+        a.cnt = (double)m->count;
+        const unsigned gx = std::max(1u, std::min(nblocks(a.n), 1024u));
+        hipLaunchKernelGGL(k_moments_finish_lag, dim3(gx, np), dim3(BLOCK), 0, ctx->stream, a);
+        HIPCHK(ctx, hipGetLastError());
+        return 0;
+    }
     FinishArgs a{};
     int np = 0;
     for (const auto& s : m->segs) {
@@ -242,6 +426,74 @@ int dangx_moments_begin(dangx_ctx* ctx, const int32_t* sel) {
     return 0;
 }
 
+int dangx_moments_pairs(dangx_ctx* ctx, int lag1, int npairs, const int32_t* pairs) {
+    if (!ctx || need(ctx)) return 1;
+    DxMoments* m = ctx->mom;
+    if (m->count != 0)
+        return fail(ctx, "posterior moments: dangx_moments_pairs is legal only before the first dangx_moments_accumulate after dangx_moments_begin");
+    const int ncomp = ctx->dims.ncomp;
+    int nind[MAXC] = {}, global[MAXC] = {};
+    for (int l = 0; l < ncomp; ++l) {
+        nind[l] = m->nind[l];
+        global[l] = is_global_type(m->type[l]) ? 1 : 0;
+    }
+    const std::string why = dx_pairs_check(npairs, pairs, ncomp, ctx->dims.nmaps, m->sel, nind, global);
+    if (!why.empty()) return fail(ctx, "posterior moments: dangx_moments_pairs: " + why);
+    auto seg_of = [&](const int32_t* q) {
+        for (size_t i = 0; i < m->segs.size(); ++i)
+            if (m->segs[i].comp == q[0] && m->segs[i].what == q[1] && m->segs[i].plane == q[2]) return (int)i;
+        return -1;
+    };
+    std::vector<DxMoments::Pair> np;
+    long long off = 0;
+    for (int p = 0; p < npairs; ++p) {
+        DxMoments::Pair pr{seg_of(pairs + 6 * p), seg_of(pairs + 6 * p + 3), 0};
+        if (pr.a < 0 || pr.b < 0) return fail(ctx, "posterior moments: dangx_moments_pairs: pair " + std::to_string(p) + ": a plane that is not selected");
+        if ((off & 1) != (m->segs[pr.a].off & 1)) ++off;
+        pr.off = off;
+        off += ctx->dims.npix;
+        np.push_back(pr);
+    }
+    (void)hipSetDevice(ctx->device);
+    // everything new is allocated before anything old is dropped: a failure leaves the registration as it was
+    double *lag = nullptr, *pc = nullptr;
+    LagSeg* d_lag = nullptr;
+    PairSeg* d_pairs = nullptr;
+    auto bail = [&](hipError_t e, const char* what) {
+        ctx->err = std::string("posterior moments: dangx_moments_pairs: ") + what + ": " + hipGetErrorString(e);
+        if (lag) (void)hipFree(lag);
+        if (pc) (void)hipFree(pc);
+        if (d_lag) (void)hipFree(d_lag);
+        if (d_pairs) (void)hipFree(d_pairs);
+        return 1;
+    };
+    hipError_t e;
+    if (lag1 && !m->segs.empty()) {
+        const size_t bytes = sizeof(double) * 3 * (size_t)m->acc_half;
+        if ((e = hipMalloc(&lag, bytes)) != hipSuccess) return bail(e, "hipMalloc");
+        if ((e = hipMemsetAsync(lag, 0, bytes, ctx->stream)) != hipSuccess) return bail(e, "hipMemsetAsync");
+        if ((e = hipMalloc(&d_lag, sizeof(LagSeg) * m->segs.size())) != hipSuccess) return bail(e, "hipMalloc");
+    }
+    if (!np.empty()) {
+        if ((e = hipMalloc(&pc, sizeof(double) * (size_t)off)) != hipSuccess) return bail(e, "hipMalloc");
+        if ((e = hipMemsetAsync(pc, 0, sizeof(double) * (size_t)off, ctx->stream)) != hipSuccess) return bail(e, "hipMemsetAsync");
+        if ((e = hipMalloc(&d_pairs, sizeof(PairSeg) * np.size())) != hipSuccess) return bail(e, "hipMalloc");
+    }
+    if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return bail(e, "hipStreamSynchronize");
+    if (m->lag) (void)hipFree(m->lag);
+    if (m->d_lag) (void)hipFree(m->d_lag);
+    if (m->pc) (void)hipFree(m->pc);
+    if (m->d_pairs) (void)hipFree(m->d_pairs);
+    m->lag = lag; m->d_lag = d_lag; m->pc = pc; m->d_pairs = d_pairs;
+    m->lag1 = lag1 != 0;
+    m->pairs = np;
+    m->table.clear();   // the next accumulation uploads the tables
+    std::memset(m->tm_prev, 0, sizeof m->tm_prev);
+    std::memset(m->tm_first, 0, sizeof m->tm_first);
+    std::memset(m->tm_P, 0, sizeof m->tm_P);
+    return 0;
+}
+
 int dangx_moments_accumulate(dangx_ctx* ctx) {
     if (!ctx || need(ctx)) return 1;
     DxMoments* m = ctx->mom;
@@ -261,21 +513,54 @@ int dangx_moments_accumulate(dangx_ctx* ctx) {
         for (size_t i = 0; same && i < t.size(); ++i) same = t[i].x == m->table[i].x;
         if (!same) {   // first accumulation, or a component's buffers were adopted again: one upload (and a host wait) here only
             HIPCHK(ctx, hipMemcpyAsync(m->d_table, t.data(), sizeof(MomSeg) * t.size(), hipMemcpyHostToDevice, ctx->stream));
+            std::vector<LagSeg> tl;
+            std::vector<PairSeg> tp;
+            if (m->d_lag) {
+                for (size_t i = 0; i < t.size(); ++i) {
+                    double* g = m->lag + m->segs[i].off;
+                    tl.push_back(LagSeg{t[i].x, t[i].mean, t[i].m2, g, g + m->acc_half, g + 2 * m->acc_half, t[i].n});
+                }
+                HIPCHK(ctx, hipMemcpyAsync(m->d_lag, tl.data(), sizeof(LagSeg) * tl.size(), hipMemcpyHostToDevice, ctx->stream));
+            }
+            if (m->d_pairs) {
+                for (const auto& p : m->pairs)
+                    tp.push_back(PairSeg{t[p.a].x, t[p.b].x, t[p.a].mean, t[p.b].mean, m->pc + p.off, (long long)ctx->dims.npix});
+                HIPCHK(ctx, hipMemcpyAsync(m->d_pairs, tp.data(), sizeof(PairSeg) * tp.size(), hipMemcpyHostToDevice, ctx->stream));
+            }
             HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
             m->table = t;
         }
-        const unsigned nseg = (unsigned)t.size();
         const long long pairs = (ctx->dims.npix + 1) / 2;
+        if (!m->pairs.empty()) {   // the cross terms read the means of the previous accumulation: a launch of its own, first
+            const unsigned npr = (unsigned)m->pairs.size();
+            const unsigned gx = std::max(1u, std::min(nblocks(pairs), (m->grid_target + npr - 1) / npr));
+            Timed tm(ctx, DANGX_K_MOMENTS, 2);   // the profile tells them apart by their plane count: two planes per element
+            hipLaunchKernelGGL(k_moments_pairs, dim3(gx, npr), dim3(BLOCK), 0, ctx->stream, (const PairSeg*)m->d_pairs, inv_n);
+            HIPCHK(ctx, hipGetLastError());
+        }
+        const unsigned nseg = (unsigned)t.size();
         const unsigned gx = std::max(1u, std::min(nblocks(pairs), (m->grid_target + nseg - 1) / nseg));
         Timed tm(ctx, DANGX_K_MOMENTS);
-        hipLaunchKernelGGL(k_moments_accum, dim3(gx, nseg), dim3(BLOCK), 0, ctx->stream, (const MomSeg*)m->d_table, inv_n);
+        if (!m->lag1)
+            hipLaunchKernelGGL(k_moments_accum, dim3(gx, nseg), dim3(BLOCK), 0, ctx->stream, (const MomSeg*)m->d_table, inv_n);
+        else if (m->count == 0)
+            hipLaunchKernelGGL(k_moments_accum_lag<true>, dim3(gx, nseg), dim3(BLOCK), 0, ctx->stream, (const LagSeg*)m->d_lag, inv_n);
+        else
+            hipLaunchKernelGGL(k_moments_accum_lag<false>, dim3(gx, nseg), dim3(BLOCK), 0, ctx->stream, (const LagSeg*)m->d_lag, inv_n);
         HIPCHK(ctx, hipGetLastError());
     }
     for (int l = 0; l < ctx->dims.ncomp; ++l) {
         if (!m->sel[l] || !is_global_type(ctx->desc[l].type)) continue;
         for (int k = 0; k < ctx->dims.nmaps; ++k)
             if ((m->sel[l] >> k) & 1)
-                for (int j = 0; j < ctx->dims.nbands; ++j) host_welford(ctx->tamp[l][k][j], m->tm_mean[l][k][j], m->tm_m2[l][k][j], inv_n);
+                for (int j = 0; j < ctx->dims.nbands; ++j) {
+                    const double x = ctx->tamp[l][k][j];
+                    if (m->lag1) {
+                        if (m->count == 0) m->tm_prev[l][k][j] = m->tm_first[l][k][j] = x;
+                        else dx_lag_update(x, m->tm_prev[l][k][j], m->tm_first[l][k][j], m->tm_P[l][k][j]);
+                    }
+                    host_welford(x, m->tm_mean[l][k][j], m->tm_m2[l][k][j], inv_n);
+                }
     }
     ++m->count;
     return 0;
@@ -326,8 +611,48 @@ int dangx_moments_get_template(dangx_ctx* ctx, int comp, int stat, int ddof, dou
     const double dn = (double)(m->count - ddof);
     for (int k = 0; k < ctx->dims.nmaps; ++k)
         if ((planes >> k) & 1u)
-            for (int j = 0; j < ctx->dims.nbands; ++j)
-                ta[k * ctx->dims.nbands + j] = stat == 0 ? m->tm_mean[comp][k][j] : std::sqrt(m->tm_m2[comp][k][j] / dn);
+            for (int j = 0; j < ctx->dims.nbands; ++j) {
+                double v;
+                if (stat >= 2) {
+                    v = dx_lag_rho1(m->tm_mean[comp][k][j], m->tm_m2[comp][k][j], m->tm_prev[comp][k][j], m->tm_first[comp][k][j],
+                                    m->tm_P[comp][k][j], (double)m->count);
+                    if (stat == 3) v = dx_lag_ess(v, (double)m->count);
+                } else {
+                    v = stat == 0 ? m->tm_mean[comp][k][j] : std::sqrt(m->tm_m2[comp][k][j] / dn);
+                }
+                ta[k * ctx->dims.nbands + j] = v;
+            }
+    return 0;
+}
+
+int dangx_moments_get_pair_dev(dangx_ctx* ctx, int pair, int stat, int ddof, double* out_dev) {
+    if (!ctx || !out_dev || need(ctx)) return 1;
+    DxMoments* m = ctx->mom;
+    if (pair < 0 || pair >= (int)m->pairs.size())
+        return fail(ctx, "posterior moments: pair index out of range (" + std::to_string(m->pairs.size()) + " pairs registered)");
+    if (stat != 0 && stat != 1) return fail(ctx, "posterior moments: the stat of a pair must be 0 (covariance) or 1 (correlation)");
+    if (m->count == 0) return fail(ctx, "posterior moments: no sample accumulated");
+    if (stat == 0 && (ddof < 0 || m->count - ddof <= 0)) return fail(ctx, "posterior moments: covariance needs 0 <= ddof < n");
+    (void)hipSetDevice(ctx->device);
+    const auto& p = m->pairs[pair];
+    const long long n = ctx->dims.npix;
+    const unsigned gx = std::max(1u, std::min(nblocks(n), 1024u));
+    hipLaunchKernelGGL(k_moments_finish_pair, dim3(gx), dim3(BLOCK), 0, ctx->stream, (const double*)(m->pc + p.off),
+                       (const double*)(m->acc + m->acc_half + m->segs[p.a].off), (const double*)(m->acc + m->acc_half + m->segs[p.b].off),
+                       out_dev, n, stat, (double)(m->count - ddof));
+    HIPCHK(ctx, hipGetLastError());
+    return 0;
+}
+
+int dangx_moments_get_pair(dangx_ctx* ctx, int pair, int stat, int ddof, double* out) {
+    if (!ctx || !out || need(ctx)) return 1;
+    DxMoments* m = ctx->mom;
+    (void)hipSetDevice(ctx->device);
+    const long long np = ctx->dims.npix;
+    if (!m->scratch) HIPCHK(ctx, hipMalloc(&m->scratch, sizeof(double) * (size_t)np * ctx->dims.nmaps));
+    if (dangx_moments_get_pair_dev(ctx, pair, stat, ddof, m->scratch)) return 1;
+    HIPCHK(ctx, hipMemcpyAsync(out, m->scratch, sizeof(double) * (size_t)np, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return 0;
 }
 

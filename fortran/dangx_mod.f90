@@ -545,6 +545,25 @@ module dangx_mod
        type(c_ptr), value :: ctx, ta                ! real(c_double)(nbands, nmaps) == C [map][band]
        integer(c_int), value :: comp, stat, ddof
      end function
+     ! lag-1 autocorrelation / effective sample size of every selected plane (lag1 /= 0) and cross terms of npairs pairs of
+     ! selected pixel planes: pairs(6, npairs) = (comp_a, what_a, plane_a, comp_b, what_b, plane_b), everything 0-based as in C.
+     ! Only between dangx_moments_begin and the first dangx_moments_accumulate.  stat 2 (rho1) and 3 (ESS) of dangx_moments_get need it.
+     integer(c_int) function dangx_moments_pairs(ctx, lag1, npairs, pairs) bind(C, name='dangx_moments_pairs')
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx, pairs             ! pairs: integer(c_int32_t)(6, npairs) or c_null_ptr
+       integer(c_int), value :: lag1, npairs
+     end function
+     ! pair: 0-based; stat: 0 = covariance with ddof, 1 = correlation; out: (0:npix-1) of this shard
+     integer(c_int) function dangx_moments_get_pair(ctx, pair, stat, ddof, out) bind(C, name='dangx_moments_get_pair')
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx, out
+       integer(c_int), value :: pair, stat, ddof
+     end function
+     integer(c_int) function dangx_moments_get_pair_dev(ctx, pair, stat, ddof, out_dev) bind(C, name='dangx_moments_get_pair_dev')
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx, out_dev
+       integer(c_int), value :: pair, stat, ddof
+     end function
      integer(c_int) function dangx_moments_end(ctx) bind(C, name='dangx_moments_end')
        import :: c_int, c_ptr
        type(c_ptr), value :: ctx

@@ -249,6 +249,35 @@ contains
     call dangx_check(sky%ctx(1), dangx_moments_get_template(sky%ctx(1), comp, stat, ddof, ta), 'dangx_moments_get_template')
   end subroutine dangx_sky_moments_get_template
 
+  ! lag-1 autocorrelation of every selected plane (lag1) and the cross terms of pairs(6, npairs) = (comp_a, what_a, plane_a,
+  ! comp_b, what_b, plane_b), 0-based as in include/dangx.h, on every context: after dangx_sky_moments_begin, before the first
+  ! accumulate.  dangx_sky_moments_get then takes stat 2 (rho1) and 3 (ESS) as well.
+  subroutine dangx_sky_moments_pairs(sky, lag1, npairs, pairs)
+    type(dangx_sky), intent(in) :: sky
+    logical, intent(in) :: lag1
+    integer, intent(in) :: npairs
+    integer(c_int32_t), intent(in), target :: pairs(:,:)
+    type(c_ptr) :: p
+    integer :: r
+    p = c_null_ptr
+    if (npairs > 0) p = c_loc(pairs)
+    do r = 1, sky%nctx
+       call dangx_check(sky%ctx(r), dangx_moments_pairs(sky%ctx(r), merge(1, 0, lag1), npairs, p), 'dangx_moments_pairs')
+    end do
+  end subroutine dangx_sky_moments_pairs
+
+  ! pair: 0-based; stat 0 = covariance with ddof, 1 = correlation; out: c_loc of a full-sky (0:npix-1) array, every context fills
+  ! its pixel range
+  subroutine dangx_sky_moments_get_pair(sky, pair, stat, ddof, out)
+    type(dangx_sky), intent(in) :: sky
+    integer, intent(in) :: pair, stat, ddof
+    type(c_ptr), intent(in) :: out
+    integer :: r
+    do r = 1, sky%nctx
+       call dangx_check(sky%ctx(r), dangx_moments_get_pair(sky%ctx(r), pair, stat, ddof, at_pix(out, sky%pix0(r))), 'dangx_moments_get_pair')
+    end do
+  end subroutine dangx_sky_moments_get_pair
+
   function dangx_sky_moments_count(sky) result(n)
     type(dangx_sky), intent(in) :: sky
     integer(c_int64_t) :: n, m

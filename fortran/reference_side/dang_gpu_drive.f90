@@ -18,6 +18,9 @@
 ! posterior summaries as INTEGRATION.md shows them -- posterior_begin_gpu before the loop, posterior_accumulate_gpu after
 ! write_data_gpu -- and, after the state, the result file gets the sample count and, for the mean and then the standard
 ! deviation (ddof 0), every component's c%amplitude, c%indices and c%template_amplitudes as posterior_to_host_gpu leaves them.
+! DANG_POSTERIOR_PAIRS=1 beside it: posterior_pairs_gpu(dpar, .true.) after posterior_begin_gpu, and behind the above the same
+! dump for the lag-1 autocorrelation (stat 2) and the effective sample size (stat 3), the number of pairs and every pair's
+! correlation map.  Without it the result file is what DANG_POSTERIOR alone gives.
 subroutine mpi_allreduce(sendbuf, recvbuf, count, datatype, op, comm, ierror)
   ! the wrapper's MPI branch is never taken here (numprocs = 1); the symbol only has to exist
   integer :: sendbuf, recvbuf(*), count, datatype, op, comm, ierror
@@ -51,7 +54,8 @@ program dang_gpu_drive
   character(len=512) :: fin, fout, arg, mode
   integer :: u, i, j, l, k, npix0, niter, ngroups, nctx, tile, t, it_first
   integer :: post_burn, post_thin, post_len, post_stat
-  logical :: post
+  logical :: post, post_pairs
+  real(c_double), allocatable :: pair_map(:)
   integer(i8b) :: c0, c1, crate
   real(dp) :: secs
 
@@ -154,6 +158,9 @@ program dang_gpu_drive
      read(arg(1:post_len), *) post_burn, post_thin
      call posterior_begin_gpu(dpar)
   end if
+  call get_environment_variable('DANG_POSTERIOR_PAIRS', arg, post_len)
+  post_pairs = post .and. post_len > 0
+  if (post_pairs) call posterior_pairs_gpu(dpar, .true.)
   secs = 0.d0; it_first = 3
   do iter = 1, niter
      if (iter == it_first + 1) then                       ! time iterations it_first+1 .. niter: the first two full ones warm up (index maps that start spatially constant take the generic launches once, kernels specialised at run time are compiled on first use)
@@ -202,7 +209,7 @@ program dang_gpu_drive
   end if
   if (post) then
      write(u) real(dangx_sky_moments_count(gpu_sky), c_double)
-     do post_stat = 0, 1
+     do post_stat = 0, merge(3, 1, post_pairs)
         call posterior_to_host_gpu(ddata, post_stat, 0)
         do l = 1, ncomp
            cc => component_list(l)%p
@@ -211,6 +218,14 @@ program dang_gpu_drive
            if (allocated(cc%template_amplitudes)) write(u) cc%template_amplitudes
         end do
      end do
+     if (post_pairs) then
+        write(u) real(gpu_post_npairs, c_double)
+        allocate(pair_map(0:npix-1))
+        do i = 1, gpu_post_npairs
+           call posterior_pair_to_host_gpu(i, 1, 0, pair_map)
+           write(u) pair_map
+        end do
+     end if
   end if
   close(u)
   write(*,'(a,a,a,i0,a,i0,a,es24.16)') 'dang_gpu_drive ok: mode = ', trim(mode), '  contexts = ', nctx, '  npix = ', npix, &

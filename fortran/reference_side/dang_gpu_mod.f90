@@ -38,6 +38,8 @@ module dang_gpu_mod
   integer(c_int64_t)    :: gpu_seed = 1234_c_int64_t   ! the reference calls RANDOM_SEED() unseeded (src/dang.f90:67)
   integer(i4b)          :: gpu_pix0 = 0                ! first pixel of this PROCESS (0 unless the driver is run under MPI)
   integer(c_int32_t), allocatable, target :: gpu_post_sel(:)   ! posterior_begin_gpu's selection words, one per component
+  integer(c_int32_t), allocatable, target :: gpu_post_pairs(:,:)   ! posterior_pairs_gpu's pairs (6, gpu_post_npairs), 0-based as in C
+  integer(i4b) :: gpu_post_npairs = 0
 
 contains
 
@@ -721,7 +723,72 @@ contains
        end do
     end do
     call dangx_sky_moments_begin(gpu_sky, gpu_post_sel)
+    gpu_post_npairs = 0
   end subroutine posterior_begin_gpu
+
+  ! after posterior_begin_gpu, before the first posterior_accumulate_gpu that takes a sample: the second-order summaries.  lag1:
+  ! the lag-1 autocorrelation and AR(1) effective sample size of every selected plane (stat 2 and 3 of posterior_to_host_gpu).
+  ! Pairs, as dang_amd.api.default_moment_pairs: per component and plane k, (amplitude, index j) for every sampled index j whose
+  ! plane k and the amplitude's plane k are selected, then (index 1, index 2) when both are sampled on plane k -- component
+  ! order, then plane, then that order; read with posterior_pair_to_host_gpu (pair = 1 .. gpu_post_npairs).
+  subroutine posterior_pairs_gpu(dpar, lag1)
+    type(dang_params) :: dpar
+    logical, intent(in) :: lag1
+    type(dang_comps), pointer :: cc
+    integer(i4b) :: i, j, k, n, pass
+    logical :: amp, ind(2)
+    if (.not. allocated(gpu_post_sel)) then
+       write(*,*) 'posterior_pairs_gpu: posterior_begin_gpu was not called'
+       stop 1
+    end if
+    do pass = 1, 2                                    ! count, then fill
+       n = 0
+       do i = 1, ncomp
+          cc => component_list(i)%p
+          if (trim(cc%type) == 'template' .or. trim(cc%type) == 'monopole' .or. trim(cc%type) == 'hi_fit') cycle
+          do k = 0, nmaps - 1
+             amp = btest(gpu_post_sel(i), k)
+             ind = .false.
+             do j = 1, min(cc%nindices, 2)
+                ind(j) = btest(gpu_post_sel(i), 3 + 3*(j-1) + k)
+             end do
+             do j = 1, 2
+                if (amp .and. ind(j)) call add(i-1, 0, j, k)
+             end do
+             if (ind(1) .and. ind(2)) call add(i-1, 1, 2, k)
+          end do
+       end do
+       if (pass == 1) then
+          if (allocated(gpu_post_pairs)) deallocate(gpu_post_pairs)
+          allocate(gpu_post_pairs(6, max(n, 1))); gpu_post_pairs = 0
+       end if
+    end do
+    gpu_post_npairs = n
+    call dangx_sky_moments_pairs(gpu_sky, lag1, n, gpu_post_pairs)
+  contains
+    subroutine add(comp, wa, wb, plane)
+      integer(i4b), intent(in) :: comp, wa, wb, plane
+      n = n + 1
+      if (pass == 2) gpu_post_pairs(:, n) = int([comp, wa, plane, comp, wb, plane], c_int32_t)
+    end subroutine add
+  end subroutine posterior_pairs_gpu
+
+  ! covariance (stat = 0, with ddof) or correlation (stat = 1) map of pair `pair` (1-based, posterior_pairs_gpu's order) into
+  ! out(0:npix-1); under MPI every rank fills its pixel range and the ranges are merged as rank_window merges a plane
+  subroutine posterior_pair_to_host_gpu(pair, stat, ddof, out)
+    integer(i4b), intent(in) :: pair, stat, ddof
+    real(dp), intent(inout), target :: out(0:)
+    real(dp), allocatable, target :: w(:,:)
+    if (pair < 1 .or. pair > gpu_post_npairs) then
+       write(*,*) 'posterior_pair_to_host_gpu: pair out of range', pair, gpu_post_npairs
+       stop 1
+    end if
+    allocate(w(0:npix-1, 1))
+    call rank_window(w, 1, .true.)
+    call dangx_sky_moments_get_pair(gpu_sky, pair - 1, stat, ddof, c_loc(w))
+    call rank_window(w, 1, .false.)
+    out(0:npix-1) = w(:, 1)
+  end subroutine posterior_pair_to_host_gpu
 
   ! after write_data_gpu in the loop: one sample of the current state, every thin-th iteration after burn_in.  Enqueued on every
   ! context's stream behind the iteration's launches: the host does not wait
@@ -730,8 +797,9 @@ contains
     if (it > burn_in .and. mod(it - burn_in, max(thin, 1)) == 0) call dangx_sky_moments_accumulate(gpu_sky)
   end subroutine posterior_accumulate_gpu
 
-  ! after the loop: c%amplitude, c%indices and c%template_amplitudes become the mean (stat = 0) or the standard deviation (stat = 1,
-  ! sqrt(m2 / (n - ddof))) on the selected planes -- the other planes keep what they hold -- so that the reference's own
+  ! after the loop: c%amplitude, c%indices and c%template_amplitudes become the mean (stat = 0), the standard deviation (stat = 1,
+  ! sqrt(m2 / (n - ddof))) or, after posterior_pairs_gpu with lag1, the lag-1 autocorrelation (stat = 2) or the effective
+  ! sample size (stat = 3) on the selected planes -- the other planes keep what they hold -- so that the reference's own
   ! ddata%write_maps(dpar, 'mean') / (dpar, 'std') writes them.  This replaces the host copy of the chain state: the next
   ! dangx_refresh_host_state restores it.  No routine of this wrapper uploads the host c%amplitude / c%indices /
   ! c%template_amplitudes to the device except dangx_init (through dangx_push_state and dangx_sky_set_template), so the chain

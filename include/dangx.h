@@ -508,6 +508,26 @@ int dangx_moments_get(dangx_ctx *ctx, int comp, int what, int stat, int ddof, do
 int dangx_moments_get_dev(dangx_ctx *ctx, int comp, int what, int stat, int ddof, double *out_dev);
 /* template / monopole / hi_fit members: the moments of c%template_amplitudes, [map][band] as dangx_get_template_amplitudes */
 int dangx_moments_get_template(dangx_ctx *ctx, int comp, int stat, int ddof, double *ta);
+/* Second-order summaries of the same samples x_1..x_n (mean and m2 = sum (x_t - mean)^2 as above), streamed like the moments:
+ *   lag-1 autocorrelation rho1 = [sum_{t=2..n} (x_t - mean)(x_{t-1} - mean)] / m2 (the biased acf estimator) and the AR(1)
+ *   effective sample size ESS = n (1 - rho)/(1 + rho), rho = max(rho1, 0), of every selected plane when lag1 != 0 (rows of
+ *   c%template_amplitudes included);
+ *   cross terms C = sum (a_t - mean_a)(b_t - mean_b) of npairs pairs of selected pixel planes at the same pixel:
+ *   pairs[p] = {comp_a, what_a, plane_a, comp_b, what_b, plane_b}, what as in dangx_moments_get, plane 0-based.
+ * Legal after dangx_moments_begin and before the first dangx_moments_accumulate (count 0); a second call replaces the first,
+ * dangx_moments_begin drops everything.  Errors (nothing changes, an earlier registration stays): count > 0, a plane that is not
+ * selected, a template / monopole / hi_fit amplitude in a pair, a == b, npairs > DANGX_MAX_PAIRS, a failed allocation (one f64
+ * plane per pair, three per plane when lag1 != 0).  With pairs an accumulation is two launches (the cross terms read the means
+ * of the previous accumulation, so they go first), otherwise one. */
+#define DANGX_MAX_PAIRS 64
+int dangx_moments_pairs(dangx_ctx *ctx, int lag1, int npairs, const int32_t *pairs);
+/* dangx_moments_get / _get_dev / _get_template additionally take stat 2 = rho1 and 3 = ESS (ddof ignored; an error when lag-1
+ * is not tracked).  A sample that never moved (a masked pixel) and n = 1 give NaN: 0/0, as np.corrcoef does.
+ * stat: 0 = covariance C / (n - ddof), 1 = correlation C / sqrt(m2_a m2_b) (NaN where either variance is 0); out: [npix] of this
+ * shard.  Errors: pair out of range, n = 0, covariance with n - ddof <= 0. */
+int dangx_moments_get_pair(dangx_ctx *ctx, int pair, int stat, int ddof, double *out);
+/* the same into a device array, asynchronously on the context's stream */
+int dangx_moments_get_pair_dev(dangx_ctx *ctx, int pair, int stat, int ddof, double *out_dev);
 /* frees the accumulators */
 int dangx_moments_end(dangx_ctx *ctx);
 

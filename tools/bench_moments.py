@@ -3,7 +3,11 @@
 iterations of the C3 model: blocks of iterations without and with accumulation after every iteration, alternating in one process;
 then the k_moments kernel time from the profile and its bandwidth in algorithmic bytes (5 x 8 B per selected element) against the
 6.29 TB/s measured copy ceiling of the MI355X.
-    python3 tools/bench_moments.py [nside=1024] [steps per block=10] [rounds=5]"""
+    python3 tools/bench_moments.py [nside=1024] [steps per block=10] [rounds=5] [--lag1] [--pairs default]
+--lag1 / --pairs default: after the above, `rounds` alternating rounds of `steps` accumulations each of (a) the plain accumulate,
+(b) with lag-1 tracking (k_moments_accum_lag: 10 x 8 B per selected element) and (c) with the default pairs (k_moments_pairs: 6 x 8 B
+per pair element, timed apart from the mean launch that follows it); per launch the algorithmic bytes, the achieved bytes/s and
+their ratio to (a) in the same round."""
 import os
 import sys
 import time
@@ -17,9 +21,14 @@ from dang_amd import synth  # noqa: E402
 
 COPY_CEILING_TBS = 6.29
 
-nside = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
-steps = int(sys.argv[2]) if len(sys.argv) > 2 else 10
-rounds = int(sys.argv[3]) if len(sys.argv) > 3 else 5
+args = [a for a in sys.argv[1:] if not a.startswith("--") and a != "default"]
+want_lag1 = "--lag1" in sys.argv
+want_pairs = "--pairs" in sys.argv
+if want_pairs and sys.argv[sys.argv.index("--pairs") + 1:][:1] != ["default"]:
+    sys.exit("--pairs takes 'default'")
+nside = int(args[0]) if len(args) > 0 else 1024
+steps = int(args[1]) if len(args) > 1 else 10
+rounds = int(args[2]) if len(args) > 2 else 5
 dev = torch.device("cuda", 0)
 dpar, ddata, bands, comps, meta = synth.make_sky("C3", nside=nside, device=dev, as_numpy=False)
 eng = da.initialize(bands, comps, ddata, npix_global=meta["npix_global"], device=0)
@@ -66,3 +75,48 @@ print("k_moments: %.3f ms per launch (%d launches, profiled alone); %.2f GB algo
       "%.2f of the %.2f TB/s copy ceiling" % (k_ms, prof["launches"], nbytes * 1e-9, planes, meta["npix"], nbytes / k_ms * 1e-9,
                                               nbytes / k_ms * 1e-9 / COPY_CEILING_TBS, COPY_CEILING_TBS))
 print("accumulation overhead beyond the kernel: %.3f ms per iteration" % (a - p - k_ms))
+
+
+def launches(mode):
+    """ms per launch of `steps` accumulations after a fresh begin: mode 'plain' | 'lag1' | 'pairs' -> (mean launch, pair launch or None)"""
+    da.moments_begin(dpar, ddata, sel=sel)
+    npairs = 0
+    if mode == "lag1":
+        da.moments_pairs(dpar, ddata, pairs=[], lag1=True)
+    elif mode == "pairs":
+        npairs = len(da.moments_pairs(dpar, ddata, lag1=False))
+    da.moments_accumulate(ddata)   # table upload; with lag-1 the first-sample form of the kernel
+    eng.profile(True)
+    for _ in range(steps):
+        da.moments_accumulate(ddata)
+    tot = eng.profile_get()["k_moments"]
+    pr = eng.profile_get(by_planes=True).get(("k_moments", 2))
+    eng.profile(False)
+    if pr is None:
+        return tot["total_ms"] / tot["launches"], None, npairs
+    return (tot["total_ms"] - pr["total_ms"]) / (tot["launches"] - pr["launches"]), pr["total_ms"] / pr["launches"], npairs
+
+
+if want_lag1 or want_pairs:
+    npx = meta["npix"]
+    res = {"plain": [], "lag1": [], "pairs": []}
+    for r in range(rounds):
+        a_ms = launches("plain")[0]
+        a_bw = 5 * 8 * planes * npx / a_ms * 1e-9
+        res["plain"].append(a_bw)
+        line = "round %d: (a) plain %.3f ms, %.2f GB -> %.2f TB/s" % (r + 1, a_ms, 5 * 8 * planes * npx * 1e-9, a_bw)
+        if want_lag1:
+            b_ms = launches("lag1")[0]
+            b_bw = 10 * 8 * planes * npx / b_ms * 1e-9
+            res["lag1"].append(b_bw / a_bw)
+            line += "; (b) lag-1 %.3f ms, %.2f GB -> %.2f TB/s = %.3f of (a)" % (b_ms, 10 * 8 * planes * npx * 1e-9, b_bw, b_bw / a_bw)
+        if want_pairs:
+            _, c_ms, npairs = launches("pairs")
+            c_bw = 6 * 8 * npairs * npx / c_ms * 1e-9
+            res["pairs"].append(c_bw / a_bw)
+            line += "; (c) %d pairs %.3f ms, %.2f GB -> %.2f TB/s = %.3f of (a)" % (npairs, c_ms, 6 * 8 * npairs * npx * 1e-9, c_bw, c_bw / a_bw)
+        print(line)
+    print("(a) over the rounds: %.2f .. %.2f TB/s" % (min(res["plain"]), max(res["plain"])))
+    for key, name in (("lag1", "(b) lag-1"), ("pairs", "(c) pairs")):
+        if res[key]:
+            print("%s / (a): median %.3f (spread %.3f .. %.3f); target >= 0.9" % (name, float(np.median(res[key])), min(res[key]), max(res[key])))
