@@ -9,6 +9,7 @@ from .api import (BandInfo, DangCGGroup, DangComps, DangData, DangParams, DangxE
                   compute_chisq, convert_maps, fit_band_gain, gibbs_iteration, index_sample_coarse_multi, normalize_bandpass, refresh_host_state, index_means, initialize, return_poltype_flag, sample_calibrators, sample_cg_groups,
                   sample_index_mh_fullsky, sample_spectral_parameters, stream_id, tune_perpixel, fusable_first_sweeps, plan_plane_sets, sky_amp_sample, sky_plane_set_sample,
                   default_moment_selection, moments_begin, moments_accumulate, posterior_maps,
-                  default_moment_pairs, moments_pairs, posterior_pair_maps)
+                  default_moment_pairs, moments_pairs, posterior_pair_maps,
+                  default_hist_planes, moments_hist, posterior_quantile_maps)
 
 __version__ = "0.1.0"

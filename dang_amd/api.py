@@ -621,6 +621,7 @@ class Engine:
     def moments_begin(self, sel=None):
         """Start (or restart) accumulating: sel[l] = selection word of component l (include/dangx.h; None = every plane)."""
         self._moment_pairs, self._moment_lag1 = [], False   # dangx_moments_begin drops what moments_pairs registered
+        self._moment_hist = None                            # ... and what moments_hist registered
         if sel is None:
             self._chk(self.lib.dangx_moments_begin(self.h, None))
             full = (1 << self.nmaps) - 1
@@ -697,6 +698,74 @@ class Engine:
             out = np.zeros(self.npix)
         assert isinstance(out, np.ndarray) and out.dtype == np.float64 and out.flags.c_contiguous and out.shape == (self.npix,)
         self._chk(self.lib.dangx_moments_get_pair(self.h, int(p), st, int(ddof), out.ctypes.data))
+        return out
+
+    def moments_hist(self, planes, ranges=None, nbins=64, bits=16):
+        """Register per-pixel histograms after moments_begin and before the first moments_accumulate: planes = [(l, what, plane), ...]
+        (what / plane as in moments_pairs), ranges = [(lo, hi) or None, ...] or None (None = the default: an index plane's
+        uni_prior; an amplitude plane has none), nbins in {8, 16, 32, 64} counters of bits in {16, 32} per pixel, nbins * bits / 8
+        <= 128.  A second call replaces the first.  Definitions: include/dangx.h.
+        The range this object reports for a default (`_moment_hist["ranges"]`, posterior_quantile_maps' "range") is the
+        component's uni_prior as comp_desc() writes it into the descriptor -- what the library takes when the descriptor has not
+        been replaced through dangx_set_component with other bounds since this Engine was built; pass explicit ranges otherwise."""
+        p = np.ascontiguousarray(np.asarray(list(planes), dtype=np.int32).reshape(-1, 3))
+        rp = None
+        if ranges is not None:
+            ranges = list(ranges)
+            assert len(ranges) == p.shape[0]
+            rg = np.array([(np.nan, np.nan) if r is None else (float(r[0]), float(r[1])) for r in ranges], dtype=np.float64).reshape(-1, 2)
+            rp = np.ascontiguousarray(rg)
+        self._chk(self.lib.dangx_moments_hist(self.h, p.shape[0], p.ctypes.data if p.size else None,
+                                              rp.ctypes.data if rp is not None and rp.size else None, int(nbins), int(bits)))
+        eff = []
+        for r, (l, what, k) in enumerate(p):
+            if rp is not None and not np.isnan(rp[r, 0]):
+                eff.append((float(rp[r, 0]), float(rp[r, 1])))
+            else:
+                up = comp_desc(self.component_list[l]).uni_prior[what - 1]      # the descriptor's own words
+                eff.append((float(up[0]), float(up[1])))
+        self._moment_hist = {"planes": [tuple(int(v) for v in r) for r in p], "ranges": eff, "nbins": int(nbins), "bits": int(bits)}
+
+    def _hist_shape(self):
+        h = getattr(self, "_moment_hist", None)
+        if not h:
+            raise DangxError("moments_hist was not called")
+        return h["nbins"], (np.uint16 if h["bits"] == 16 else np.uint32)
+
+    def moments_hist_get(self, reg, device=False):
+        """The raw counters [npix][nbins] of registration reg of this shard (uint16 / uint32); device=True: a torch cuda tensor
+        (int16 / int32 holding the same bits: torch has no wider unsigned types everywhere)."""
+        nbins, dt = self._hist_shape()
+        if device:
+            import torch
+            dev = self._device if self._device is not None and self._device >= 0 else torch.cuda.current_device()
+            out = torch.zeros((self.npix, nbins), dtype=torch.int16 if dt is np.uint16 else torch.int32, device=torch.device("cuda", dev))
+            self._chk(self.lib.dangx_moments_hist_get_dev(self.h, int(reg), out.data_ptr()))
+            self.synchronize()
+            return out
+        out = np.zeros((self.npix, nbins), dtype=dt)
+        self._chk(self.lib.dangx_moments_hist_get(self.h, int(reg), out.ctypes.data))
+        return out
+
+    def moments_hist_stat(self, reg, stat, q=None, device=False):
+        """Read-out of registration reg: stat 'quantile' / 0 = the quantiles q (each strictly inside (0, 1), at most 16) as
+        [nq][npix]; 'mode' / 1 = the centre of the fullest bin; 'n' / 2 = the counted samples, as [npix] float64.  NaN where no
+        sample was counted (quantile, mode).  device=True: a torch cuda tensor filled on the device."""
+        st = L.HIST_STAT_CODES[stat] if isinstance(stat, str) else int(stat)
+        qa = np.ascontiguousarray(np.atleast_1d(np.asarray(q if q is not None else [], dtype=np.float64)))
+        if st == 0 and not 1 <= qa.size <= L.MAX_HIST_Q:
+            raise DangxError("moments_hist_stat: a read-out takes 1 to %d quantiles" % L.MAX_HIST_Q)
+        shape = (qa.size, self.npix) if st == 0 else (self.npix,)
+        qp = qa.ctypes.data if qa.size else None
+        if device:
+            import torch
+            dev = self._device if self._device is not None and self._device >= 0 else torch.cuda.current_device()
+            out = torch.zeros(shape, dtype=torch.float64, device=torch.device("cuda", dev))
+            self._chk(self.lib.dangx_moments_hist_stat_dev(self.h, int(reg), st, qa.size, qp, out.data_ptr()))
+            self.synchronize()
+            return out
+        out = np.zeros(shape)
+        self._chk(self.lib.dangx_moments_hist_stat(self.h, int(reg), st, qa.size, qp, out.ctypes.data))
         return out
 
     def moments_end(self):
@@ -1214,6 +1283,62 @@ def posterior_pair_maps(ddata, stat="corr", ddof=0, masked_value=None, engines=N
             parts.append(_mask_fill(m, e.ddata.masks, masked_value) if masked_value is not None else m)
         key = tuple((comps[l].label, _plane_name(comps[l], what), k) for l, what, k in (a, b))
         out[key] = np.concatenate(parts, axis=-1) if len(parts) > 1 else parts[0]
+    return out
+
+
+def default_hist_planes(dpar, component_list, sel):
+    """[(l, what, plane), ...] for moments_hist: every plane in `sel` of every index the run samples (c.sample_index[j], the flag
+    default_moment_selection follows), in component / index / plane order.  Their default range is the index's uni_prior, which
+    the chain never leaves.  Pure Python."""
+    planes = []
+    for l, c in enumerate(component_list):
+        if c.type in GLOBAL_TYPES:
+            continue
+        for j in range(c.nindices):
+            if j < len(c.sample_index) and c.sample_index[j]:
+                planes += [(l, 1 + j, k) for k in range(3) if (int(sel[l]) >> (3 + 3 * j + k)) & 1]
+    return planes
+
+
+def moments_hist(dpar, ddata, planes=None, ranges=None, nbins=64, bits=16, engines=None):
+    """dangx_moments_hist on every context of this process, after moments_begin and before the first moments_accumulate;
+    planes=None: default_hist_planes of the selection moments_begin made.  Returns the plane list."""
+    engs = _engines_of(ddata, engines)
+    if planes is None:
+        sel = getattr(engs[0], "_moment_sel", None)
+        if sel is None:
+            raise DangxError("moments_hist: moments_begin was not called")
+        planes = default_hist_planes(dpar, engs[0].component_list, sel)
+    planes = [tuple(int(v) for v in p) for p in planes]
+    for e in engs:
+        e.moments_hist(planes, ranges=ranges, nbins=nbins, bits=bits)
+    return planes
+
+
+def posterior_quantile_maps(ddata, q=(0.16, 0.5, 0.84), masked_value=None, engines=None):
+    """{(label, name, plane): {'q': [nq][npix], 'mode': [npix], 'n': [npix], 'range': (lo, hi), 'nbins'}} of the histograms
+    moments_hist registered; names as posterior_maps' keys, planes 0-based.  Several contexts of this process: their shards side by
+    side.  masked_value: as in posterior_maps.  Raises when the contexts differ in sample count or registration."""
+    engs = _engines_of(ddata, engines)
+    regs = [getattr(e, "_moment_hist", None) for e in engs]
+    if not regs[0]:
+        raise DangxError("posterior_quantile_maps: moments_hist was not called")
+    if any(r != regs[0] for r in regs[1:]):
+        raise DangxError("posterior_quantile_maps: the contexts hold different histogram registrations")
+    counts = {e.moments_count() for e in engs}
+    if len(counts) != 1:
+        raise DangxError("posterior_quantile_maps: the contexts hold different sample counts %s" % sorted(counts))
+    comps = engs[0].component_list
+    out = {}
+    for r, (l, what, k) in enumerate(regs[0]["planes"]):
+        entry = {"range": regs[0]["ranges"][r], "nbins": regs[0]["nbins"]}
+        for name, stat in (("q", "quantile"), ("mode", "mode"), ("n", "n")):
+            parts = []
+            for e in engs:
+                m = e.moments_hist_stat(r, stat, q=q if stat == "quantile" else None)
+                parts.append(_mask_fill(m, e.ddata.masks, masked_value) if masked_value is not None else m)
+            entry[name] = np.concatenate(parts, axis=-1) if len(parts) > 1 else parts[0]
+        out[(comps[l].label, _plane_name(comps[l], what), k)] = entry
     return out
 
 

@@ -22,12 +22,21 @@
 //     6 x 8 B per element (read a, b, both old means, C; write C).  It is a launch of its own BEFORE the launch that updates the
 //     means (stream order), so no block reads a mean another block is writing.
 // Without dangx_moments_pairs an accumulation is the one k_moments_accum launch, as before.
+//
+// dangx_moments_hist adds fixed-range per-pixel histograms of registered pixel planes (definitions in dx_hist_host.h): a record of
+// nbins counters (<= 128 bytes, a power of two: never across a 128-byte request) per pixel and registration, in an allocation of
+// the library's own.  k_moments_hist takes one sample of every registered plane in ONE launch of its own (blockIdx.y =
+// registration) behind the moments': the thread that read a pixel's x loads, increments and stores the ONE 32-bit word holding the
+// bin -- no atomics, a pixel's record belongs to one thread -- and a sample outside the range touches no record.  k_hist_stat
+// reads a record as 16-byte pieces and leaves quantiles, the mode or the count of counted samples.  Nothing registered: no launch.
 #include "dx_host.h"
 #include "dx_moments_host.h"
+#include "dx_hist_host.h"
 
 #include <cstdint>
 
 static_assert(DX_MOM_MAX_PAIRS == DANGX_MAX_PAIRS, "dx_moments_host.h and include/dangx.h disagree");
+static_assert(DX_HIST_MAX == DANGX_MAX_HIST, "dx_hist_host.h and include/dangx.h disagree");
 
 struct MomSeg {           // one selected plane: the chain's plane (resolved at accumulate time) and its two accumulators
     const double* x;
@@ -55,6 +64,14 @@ struct PairSeg {          // a pair of selected planes and its cross-term accumu
     long long n;
 };
 
+struct HistSeg {          // one registered histogram: the chain's plane (resolved at accumulate time) and its records
+    const double* x;
+    uint32_t* rec;        // [n][words] 32-bit words, 256-byte aligned
+    double lo, hi, scale;
+    long long n;
+    int nbins, bits;
+};
+
 struct DxMoments {
     int32_t sel[MAXC] = {};          // effective selection (bits as in include/dangx.h)
     int type[MAXC] = {}, nind[MAXC] = {};  // shape key recorded at begin
@@ -77,6 +94,14 @@ struct DxMoments {
     double* pc = nullptr;
     PairSeg* d_pairs = nullptr;
     double tm_prev[MAXC][3][MAXB] = {}, tm_first[MAXC][3][MAXB] = {}, tm_P[MAXC][3][MAXB] = {};
+    // dangx_moments_hist
+    struct Hist { int seg; double lo, hi; long long off; };   // seg: index into segs; off: the records' first word in hrec
+    std::vector<Hist> hists;
+    int hbins = 0, hbits = 0;
+    uint32_t* hrec = nullptr;        // every registration's records, each block at a multiple of 256 bytes
+    HistSeg* d_hist = nullptr;
+    double* hscratch = nullptr;      // what the host form of the read-out copies from
+    size_t hscratch_bytes = 0;
 };
 
 namespace {
@@ -217,6 +242,97 @@ __global__ __launch_bounds__(BLOCK) void k_moments_pairs(const PairSeg* __restri
     }
 }
 
+typedef __attribute__((address_space(1))) uint32_t GU32;   // a 32-bit word in global memory
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(1))) u32x4 GU4;      // a 16-byte piece of a record in global memory
+
+// one sample into pixel i's record: the one word holding the bin is loaded, incremented and stored; outside the range, nothing.
+// The 16-bit halves of a word belong to the same pixel and the host bounds the count by 2^bits - 1: no carry into the other half.
+__device__ __forceinline__ void hist_one(const HistSeg& s, int words, long long i, double x) {
+    if (!dx_hist_counted(x, s.lo, s.hi)) return;
+    const int b = dx_hist_bin(x, s.lo, s.scale, s.nbins);
+    GU32* w = (GU32*)s.rec + i * words + dx_hist_word_of(b, s.bits);
+    *w = *w + dx_hist_one(b, s.bits);
+}
+
+// blockIdx.y = registration; x is read as the moments read it (pairs of doubles, the odd first / last element alone; a plane off
+// the 16-byte grid shifts by its head element), the records are the library's own
+__global__ __launch_bounds__(BLOCK) void k_moments_hist(const HistSeg* __restrict__ segs) {
+    const HistSeg s = segs[blockIdx.y];
+    const long long n = s.n;
+    const int words = dx_hist_words(s.nbins, s.bits);
+    const long long gid = (long long)blockIdx.x * BLOCK + threadIdx.x, stride = (long long)gridDim.x * BLOCK;
+    const uintptr_t ax = reinterpret_cast<uintptr_t>(s.x);
+    if ((ax & 7) != 0) {   // not even a double's alignment: element by element
+        for (long long i = gid; i < n; i += stride) hist_one(s, words, i, s.x[i]);
+        return;
+    }
+    const long long head = ((ax & 15) != 0 && n > 0) ? 1 : 0;
+    const long long npair = (n - head) / 2, tail = head + 2 * npair;   // tail < n: one element after the last pair
+    if (gid == 0 && head) hist_one(s, words, 0, s.x[0]);
+    if (gid == 1 && tail < n) hist_one(s, words, tail, s.x[tail]);
+    const GD2* __restrict__ x2 = (const GD2*)(s.x + head);
+    for (long long p = gid; p < npair; p += stride) {
+        const dbl2 x = x2[p];
+        hist_one(s, words, head + 2 * p, x.x);
+        hist_one(s, words, head + 2 * p + 1, x.y);
+    }
+}
+
+struct HistStatArgs {
+    const uint32_t* rec;
+    double q[DX_HIST_MAX_Q];   // the quantile levels (stat 0), by value: nothing of the caller's is read after the call returns
+    double* out;          // [nq][n] (stat 0) or [n]
+    double lo, hi;
+    long long n;
+    int nbins, bits, stat, nq;
+};
+
+// every 16-byte piece of pixel i's record in order, f(count, bin) per bin until f says stop
+template <class F>
+__device__ __forceinline__ void hist_walk(const GU4* __restrict__ rec, long long i, int pieces, int bits, F f) {
+    int b = 0;
+    for (int p = 0; p < pieces; ++p) {
+        const u32x4 v = rec[i * pieces + p];
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (bits == 16) {
+                if (f(w[k] & 0xffffu, b)) return;
+                if (f(w[k] >> 16, b + 1)) return;
+                b += 2;
+            } else {
+                if (f(w[k], b)) return;
+                ++b;
+            }
+        }
+    }
+}
+
+// a lane walks its own record: once for N and the mode, once more per quantile (those passes hit the cache)
+__global__ __launch_bounds__(BLOCK) void k_hist_stat(HistStatArgs a) {
+    const GU4* __restrict__ rec = (const GU4*)a.rec;
+    const int pieces = dx_hist_words(a.nbins, a.bits) / 4;
+    const double width = (a.hi - a.lo) / (double)a.nbins;
+    for (long long i = (long long)blockIdx.x * BLOCK + threadIdx.x; i < a.n; i += (long long)gridDim.x * BLOCK) {
+        unsigned long long N = 0;
+        uint32_t best_c = 0;
+        int best_b = -1;
+        hist_walk(rec, i, pieces, a.bits, [&](uint32_t c, int b) { N += c; dx_hist_mstep(c, b, best_c, best_b); return false; });
+        if (a.stat == 1) { a.out[i] = dx_hist_mode_value(best_b, a.lo, width); continue; }
+        if (a.stat == 2) { a.out[i] = (double)N; continue; }
+        for (int j = 0; j < a.nq; ++j) {
+            double val = (double)NAN;
+            if (N > 0) {
+                const double target = a.q[j] * (double)N;
+                unsigned long long cum = 0;
+                hist_walk(rec, i, pieces, a.bits, [&](uint32_t c, int b) { return dx_hist_qstep(c, b, target, cum, a.lo, width, val); });
+            }
+            a.out[(long long)j * a.n + i] = val;
+        }
+    }
+}
+
 struct FinishLagArgs {
     const double* mean[3];
     const double* m2[3];
@@ -291,6 +407,9 @@ void release(DxMoments* m) {
     if (m->d_lag) (void)hipFree(m->d_lag);
     if (m->pc) (void)hipFree(m->pc);
     if (m->d_pairs) (void)hipFree(m->d_pairs);
+    if (m->hrec) (void)hipFree(m->hrec);
+    if (m->d_hist) (void)hipFree(m->d_hist);
+    if (m->hscratch) (void)hipFree(m->hscratch);
     delete m;
 }
 
@@ -501,6 +620,10 @@ int dangx_moments_accumulate(dangx_ctx* ctx) {
         if (m->sel[l] && (!ctx->comp_set[l] || ctx->desc[l].type != m->type[l] || ctx->desc[l].nindices != m->nind[l]))
             return fail(ctx, "posterior moments: component " + std::to_string(l) + " changed type or nindices since dangx_moments_begin");
     if (ctx->have_pending) return fail(ctx, "posterior moments: an amplitude solve is still pending");   // not at a call boundary
+    if (!m->hists.empty()) {   // no counter ever wraps: refused before anything is touched
+        const std::string why = dx_hist_limit_check(m->count + 1, m->hbits);
+        if (!why.empty()) return fail(ctx, "posterior moments: dangx_moments_accumulate: " + why);
+    }
     (void)hipSetDevice(ctx->device);
     const double inv_n = 1.0 / (double)(m->count + 1);
     if (!m->segs.empty()) {
@@ -527,6 +650,13 @@ int dangx_moments_accumulate(dangx_ctx* ctx) {
                     tp.push_back(PairSeg{t[p.a].x, t[p.b].x, t[p.a].mean, t[p.b].mean, m->pc + p.off, (long long)ctx->dims.npix});
                 HIPCHK(ctx, hipMemcpyAsync(m->d_pairs, tp.data(), sizeof(PairSeg) * tp.size(), hipMemcpyHostToDevice, ctx->stream));
             }
+            std::vector<HistSeg> th;
+            if (m->d_hist) {
+                for (const auto& h : m->hists)
+                    th.push_back(HistSeg{t[h.seg].x, m->hrec + h.off, h.lo, h.hi, dx_hist_scale(h.lo, h.hi, m->hbins), (long long)ctx->dims.npix,
+                                         m->hbins, m->hbits});
+                HIPCHK(ctx, hipMemcpyAsync(m->d_hist, th.data(), sizeof(HistSeg) * th.size(), hipMemcpyHostToDevice, ctx->stream));
+            }
             HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
             m->table = t;
         }
@@ -547,6 +677,14 @@ int dangx_moments_accumulate(dangx_ctx* ctx) {
             hipLaunchKernelGGL(k_moments_accum_lag<true>, dim3(gx, nseg), dim3(BLOCK), 0, ctx->stream, (const LagSeg*)m->d_lag, inv_n);
         else
             hipLaunchKernelGGL(k_moments_accum_lag<false>, dim3(gx, nseg), dim3(BLOCK), 0, ctx->stream, (const LagSeg*)m->d_lag, inv_n);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    if (!m->hists.empty()) {   // the histograms: a launch of their own, independent of the accumulators above
+        const long long pairs = (ctx->dims.npix + 1) / 2;
+        const unsigned nreg = (unsigned)m->hists.size();
+        const unsigned gx = std::max(1u, std::min(nblocks(pairs), (m->grid_target + nreg - 1) / nreg));
+        Timed tm(ctx, DANGX_K_HIST);
+        hipLaunchKernelGGL(k_moments_hist, dim3(gx, nreg), dim3(BLOCK), 0, ctx->stream, (const HistSeg*)m->d_hist);
         HIPCHK(ctx, hipGetLastError());
     }
     for (int l = 0; l < ctx->dims.ncomp; ++l) {
@@ -652,6 +790,150 @@ int dangx_moments_get_pair(dangx_ctx* ctx, int pair, int stat, int ddof, double*
     if (!m->scratch) HIPCHK(ctx, hipMalloc(&m->scratch, sizeof(double) * (size_t)np * ctx->dims.nmaps));
     if (dangx_moments_get_pair_dev(ctx, pair, stat, ddof, m->scratch)) return 1;
     HIPCHK(ctx, hipMemcpyAsync(out, m->scratch, sizeof(double) * (size_t)np, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+int dangx_moments_hist(dangx_ctx* ctx, int nreg, const int32_t* planes, const double* range, int nbins, int bits) {
+    if (!ctx || need(ctx)) return 1;
+    DxMoments* m = ctx->mom;
+    if (m->count != 0)
+        return fail(ctx, "posterior moments: dangx_moments_hist is legal only before the first dangx_moments_accumulate after dangx_moments_begin");
+    const int ncomp = ctx->dims.ncomp;
+    int nind[MAXC] = {}, global[MAXC] = {};
+    for (int l = 0; l < ncomp; ++l) {
+        nind[l] = m->nind[l];
+        global[l] = is_global_type(m->type[l]) ? 1 : 0;
+    }
+    // the ranges with the defaults filled in: an index plane's is that index's uni_prior as the descriptor holds it now
+    const int nr = std::max(0, std::min(nreg, DX_HIST_MAX));
+    std::vector<double> rg(2 * (size_t)nr, 0.0);
+    std::vector<int> has(nr, 0);
+    for (int r = 0; planes && r < nr; ++r) {
+        const int l = planes[3 * r], w = planes[3 * r + 1];
+        if (range && !std::isnan(range[2 * r])) {
+            rg[2 * r] = range[2 * r]; rg[2 * r + 1] = range[2 * r + 1];
+            has[r] = 1;
+        } else if (l >= 0 && l < ncomp && w >= 1 && w <= nind[l] && w <= DANGX_MAX_IND) {
+            rg[2 * r] = ctx->desc[l].uni_prior[w - 1][0]; rg[2 * r + 1] = ctx->desc[l].uni_prior[w - 1][1];
+            has[r] = 1;
+        } else if (w != 0) {
+            has[r] = 1;   // out of range: dx_hist_check names it
+        }
+    }
+    const std::string why = dx_hist_check(nreg, planes, rg.data(), has.data(), nbins, bits, ncomp, ctx->dims.nmaps, m->sel, nind, global);
+    if (!why.empty()) return fail(ctx, "posterior moments: dangx_moments_hist: " + why);
+    const long long np = ctx->dims.npix, words = dx_hist_words(nbins, bits);
+    std::vector<DxMoments::Hist> nh;
+    long long off = 0;   // in 32-bit words; every registration's block starts at a multiple of 256 bytes
+    for (int r = 0; r < nreg; ++r) {
+        int seg = -1;
+        for (size_t i = 0; i < m->segs.size(); ++i)
+            if (m->segs[i].comp == planes[3 * r] && m->segs[i].what == planes[3 * r + 1] && m->segs[i].plane == planes[3 * r + 2]) seg = (int)i;
+        if (seg < 0) return fail(ctx, "posterior moments: dangx_moments_hist: registration " + std::to_string(r) + ": a plane that is not selected");
+        nh.push_back(DxMoments::Hist{seg, rg[2 * r], rg[2 * r + 1], off});
+        off += (np * words + 63) / 64 * 64;
+    }
+    (void)hipSetDevice(ctx->device);
+    // everything new is allocated before anything old is dropped: a failure leaves the registration as it was
+    uint32_t* hrec = nullptr;
+    HistSeg* d_hist = nullptr;
+    auto bail = [&](hipError_t e, const char* what) {
+        ctx->err = std::string("posterior moments: dangx_moments_hist: ") + what + ": " + hipGetErrorString(e);
+        if (hrec) (void)hipFree(hrec);
+        if (d_hist) (void)hipFree(d_hist);
+        return 1;
+    };
+    hipError_t e;
+    if (!nh.empty()) {
+        if ((e = hipMalloc(&hrec, sizeof(uint32_t) * (size_t)off)) != hipSuccess) return bail(e, "hipMalloc");
+        if ((e = hipMemsetAsync(hrec, 0, sizeof(uint32_t) * (size_t)off, ctx->stream)) != hipSuccess) return bail(e, "hipMemsetAsync");
+        if ((e = hipMalloc(&d_hist, sizeof(HistSeg) * nh.size())) != hipSuccess) return bail(e, "hipMalloc");
+        if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return bail(e, "hipStreamSynchronize");
+    }
+    if (m->hrec) (void)hipFree(m->hrec);
+    if (m->d_hist) (void)hipFree(m->d_hist);
+    m->hrec = hrec; m->d_hist = d_hist;
+    m->hists = nh;
+    m->hbins = nbins; m->hbits = bits;
+    m->table.clear();   // the next accumulation uploads the tables
+    return 0;
+}
+
+namespace {
+
+int hist_reg(dangx_ctx* ctx, int reg) {
+    if (need(ctx)) return 1;
+    const DxMoments* m = ctx->mom;
+    if (reg < 0 || reg >= (int)m->hists.size())
+        return fail(ctx, "posterior moments: histogram registration out of range (" + std::to_string(m->hists.size()) + " registered)");
+    if (m->count == 0) return fail(ctx, "posterior moments: no sample accumulated");
+    return 0;
+}
+
+}  // namespace
+
+int dangx_moments_hist_get_dev(dangx_ctx* ctx, int reg, void* counts_dev) {
+    if (!ctx || !counts_dev || hist_reg(ctx, reg)) return 1;
+    DxMoments* m = ctx->mom;
+    (void)hipSetDevice(ctx->device);
+    const size_t bytes = sizeof(uint32_t) * (size_t)ctx->dims.npix * dx_hist_words(m->hbins, m->hbits);
+    HIPCHK(ctx, hipMemcpyAsync(counts_dev, m->hrec + m->hists[reg].off, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    return 0;
+}
+
+int dangx_moments_hist_get(dangx_ctx* ctx, int reg, void* counts) {
+    if (!ctx || !counts || hist_reg(ctx, reg)) return 1;
+    DxMoments* m = ctx->mom;
+    (void)hipSetDevice(ctx->device);
+    const size_t bytes = sizeof(uint32_t) * (size_t)ctx->dims.npix * dx_hist_words(m->hbins, m->hbits);
+    HIPCHK(ctx, hipMemcpyAsync(counts, m->hrec + m->hists[reg].off, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+static int hist_stat_check(dangx_ctx* ctx, int reg, int stat, int nq, const double* q) {
+    if (hist_reg(ctx, reg)) return 1;
+    if (stat < 0 || stat > 2) return fail(ctx, "posterior moments: the stat of a histogram must be 0 (quantiles), 1 (mode) or 2 (counted samples)");
+    if (stat == 0) {
+        if (nq < 1 || nq > DX_HIST_MAX_Q || !q)
+            return fail(ctx, "posterior moments: a histogram read-out takes 1 to " + std::to_string(DX_HIST_MAX_Q) + " quantiles");
+        for (int j = 0; j < nq; ++j)
+            if (!(q[j] > 0.0 && q[j] < 1.0)) return fail(ctx, "posterior moments: every quantile must lie strictly inside (0, 1)");
+    }
+    return 0;
+}
+
+int dangx_moments_hist_stat_dev(dangx_ctx* ctx, int reg, int stat, int nq, const double* q, double* out_dev) {
+    if (!ctx || !out_dev || hist_stat_check(ctx, reg, stat, nq, q)) return 1;
+    DxMoments* m = ctx->mom;
+    (void)hipSetDevice(ctx->device);
+    const auto& h = m->hists[reg];
+    HistStatArgs a{};
+    a.rec = m->hrec + h.off; a.out = out_dev; a.lo = h.lo; a.hi = h.hi; a.n = ctx->dims.npix;
+    a.nbins = m->hbins; a.bits = m->hbits; a.stat = stat; a.nq = stat == 0 ? nq : 0;
+    for (int j = 0; j < a.nq; ++j) a.q[j] = q[j];
+    const unsigned gx = std::max(1u, std::min(nblocks(a.n), 2048u));
+    hipLaunchKernelGGL(k_hist_stat, dim3(gx), dim3(BLOCK), 0, ctx->stream, a);
+    HIPCHK(ctx, hipGetLastError());
+    return 0;
+}
+
+int dangx_moments_hist_stat(dangx_ctx* ctx, int reg, int stat, int nq, const double* q, double* out) {
+    if (!ctx || !out || hist_stat_check(ctx, reg, stat, nq, q)) return 1;   // before anything is allocated
+    DxMoments* m = ctx->mom;
+    (void)hipSetDevice(ctx->device);
+    const int rows = stat == 0 ? nq : 1;
+    const size_t bytes = sizeof(double) * (size_t)ctx->dims.npix * rows;
+    if (bytes > m->hscratch_bytes) {
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        if (m->hscratch) (void)hipFree(m->hscratch);
+        m->hscratch = nullptr; m->hscratch_bytes = 0;
+        HIPCHK(ctx, hipMalloc(&m->hscratch, bytes));
+        m->hscratch_bytes = bytes;
+    }
+    if (dangx_moments_hist_stat_dev(ctx, reg, stat, nq, q, m->hscratch)) return 1;
+    HIPCHK(ctx, hipMemcpyAsync(out, m->hscratch, bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return 0;
 }

@@ -564,6 +564,36 @@ module dangx_mod
        type(c_ptr), value :: ctx, out_dev
        integer(c_int), value :: pair, stat, ddof
      end function
+     ! per-pixel histograms of nreg pixel planes: planes(3, nreg) = (comp, what, plane), 0-based as in C; range(2, nreg) = (lo, hi),
+     ! c_null_ptr or a NaN lo = the default (an index plane's uni_prior; an amplitude plane has none); nbins in 8/16/32/64 counters
+     ! of bits 16/32, nbins*bits/8 <= 128.  Only between dangx_moments_begin and the first dangx_moments_accumulate.
+     integer(c_int) function dangx_moments_hist(ctx, nreg, planes, range, nbins, bits) bind(C, name='dangx_moments_hist')
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx, planes, range     ! integer(c_int32_t)(3, nreg), real(c_double)(2, nreg) or c_null_ptr
+       integer(c_int), value :: nreg, nbins, bits
+     end function
+     ! reg: 0-based; counts: (nbins, 0:npix-1) of this shard, integer(c_int16_t) or integer(c_int32_t) holding the unsigned counters
+     integer(c_int) function dangx_moments_hist_get(ctx, reg, counts) bind(C, name='dangx_moments_hist_get')
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx, counts
+       integer(c_int), value :: reg
+     end function
+     integer(c_int) function dangx_moments_hist_get_dev(ctx, reg, counts_dev) bind(C, name='dangx_moments_hist_get_dev')
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx, counts_dev
+       integer(c_int), value :: reg
+     end function
+     ! stat 0: the nq quantiles q(nq) (each inside (0, 1), nq <= 16) as out(0:npix-1, nq); 1: the mode; 2: the counted samples (out(0:npix-1))
+     integer(c_int) function dangx_moments_hist_stat(ctx, reg, stat, nq, q, out) bind(C, name='dangx_moments_hist_stat')
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx, q, out
+       integer(c_int), value :: reg, stat, nq
+     end function
+     integer(c_int) function dangx_moments_hist_stat_dev(ctx, reg, stat, nq, q, out_dev) bind(C, name='dangx_moments_hist_stat_dev')
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx, q, out_dev
+       integer(c_int), value :: reg, stat, nq
+     end function
      integer(c_int) function dangx_moments_end(ctx) bind(C, name='dangx_moments_end')
        import :: c_int, c_ptr
        type(c_ptr), value :: ctx

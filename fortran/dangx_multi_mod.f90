@@ -278,6 +278,59 @@ contains
     end do
   end subroutine dangx_sky_moments_get_pair
 
+  ! per-pixel histograms of planes(3, nreg) = (comp, what, plane), 0-based as in include/dangx.h, on every context: after
+  ! dangx_sky_moments_begin, before the first accumulate.  range: c_loc of real(c_double)(2, nreg) or c_null_ptr (the defaults)
+  subroutine dangx_sky_moments_hist(sky, nreg, planes, range, nbins, bits)
+    type(dangx_sky), intent(in) :: sky
+    integer, intent(in) :: nreg, nbins, bits
+    integer(c_int32_t), intent(in), target :: planes(:,:)
+    type(c_ptr), intent(in) :: range
+    type(c_ptr) :: p
+    integer :: r
+    p = c_null_ptr
+    if (nreg > 0) p = c_loc(planes)
+    do r = 1, sky%nctx
+       call dangx_check(sky%ctx(r), dangx_moments_hist(sky%ctx(r), nreg, p, range, nbins, bits), 'dangx_moments_hist')
+    end do
+  end subroutine dangx_sky_moments_hist
+
+  ! reg: 0-based.  stat 0: the nq quantiles q into out = c_loc of a full-sky (0:npix-1, nq) array; 1: the mode, 2: the counted
+  ! samples into a full-sky (0:npix-1) array.  A context writes its quantile rows packed, so with several contexts each row goes
+  ! through a call of its own into that context's pixel range
+  subroutine dangx_sky_moments_hist_stat(sky, reg, stat, nq, q, out, npix)
+    type(dangx_sky), intent(in) :: sky
+    integer, intent(in) :: reg, stat, nq
+    real(c_double), intent(in), target :: q(:)
+    type(c_ptr), intent(in) :: out
+    integer(c_int64_t), intent(in) :: npix                ! pixels of the full-sky array: the stride between quantile rows
+    integer :: r, j
+    do r = 1, sky%nctx
+       if (stat /= 0 .or. (sky%nctx == 1 .and. int(sky%npix(1), c_int64_t) == npix)) then
+          call dangx_check(sky%ctx(r), dangx_moments_hist_stat(sky%ctx(r), reg, stat, nq, c_loc(q), at_pix(out, sky%pix0(r))), &
+               'dangx_moments_hist_stat')
+       else
+          do j = 1, nq
+             call dangx_check(sky%ctx(r), dangx_moments_hist_stat(sky%ctx(r), reg, stat, 1, c_loc(q(j)), &
+                  at_pix(out, sky%pix0(r) + (j-1)*npix)), 'dangx_moments_hist_stat')
+          end do
+       end if
+    end do
+  end subroutine dangx_sky_moments_hist_stat
+
+  ! reg: 0-based; counts: c_loc of a full-sky (nbins, 0:npix-1) array of integer(c_int16_t) (bits = 16) or integer(c_int32_t)
+  ! (bits = 32) holding the unsigned counters; every context fills the records of its pixel range
+  subroutine dangx_sky_moments_hist_get(sky, reg, counts, nbins, bits)
+    type(dangx_sky), intent(in) :: sky
+    integer, intent(in) :: reg, nbins, bits
+    type(c_ptr), intent(in) :: counts
+    type(c_ptr) :: p
+    integer :: r
+    do r = 1, sky%nctx
+       p = transfer(transfer(counts, 0_c_intptr_t) + int(nbins*bits/8, c_intptr_t)*sky%pix0(r), p)
+       call dangx_check(sky%ctx(r), dangx_moments_hist_get(sky%ctx(r), reg, p), 'dangx_moments_hist_get')
+    end do
+  end subroutine dangx_sky_moments_hist_get
+
   function dangx_sky_moments_count(sky) result(n)
     type(dangx_sky), intent(in) :: sky
     integer(c_int64_t) :: n, m

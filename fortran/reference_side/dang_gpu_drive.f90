@@ -21,6 +21,9 @@
 ! DANG_POSTERIOR_PAIRS=1 beside it: posterior_pairs_gpu(dpar, .true.) after posterior_begin_gpu, and behind the above the same
 ! dump for the lag-1 autocorrelation (stat 2) and the effective sample size (stat 3), the number of pairs and every pair's
 ! correlation map.  Without it the result file is what DANG_POSTERIOR alone gives.
+! DANG_POSTERIOR_HIST=<nbins> beside DANG_POSTERIOR: posterior_hist_gpu(dpar, nbins, 16) after posterior_begin_gpu, and behind
+! everything above the number of registrations and, per registration, the 0.16 / 0.5 / 0.84 quantile maps and the counted
+! samples N.  Without it the result file keeps its length to the byte.
 subroutine mpi_allreduce(sendbuf, recvbuf, count, datatype, op, comm, ierror)
   ! the wrapper's MPI branch is never taken here (numprocs = 1); the symbol only has to exist
   integer :: sendbuf, recvbuf(*), count, datatype, op, comm, ierror
@@ -54,8 +57,9 @@ program dang_gpu_drive
   character(len=512) :: fin, fout, arg, mode
   integer :: u, i, j, l, k, npix0, niter, ngroups, nctx, tile, t, it_first
   integer :: post_burn, post_thin, post_len, post_stat
-  logical :: post, post_pairs
-  real(c_double), allocatable :: pair_map(:)
+  logical :: post, post_pairs, post_hist
+  integer :: hist_bins
+  real(c_double), allocatable :: pair_map(:), q_map(:,:), n_map(:)
   integer(i8b) :: c0, c1, crate
   real(dp) :: secs
 
@@ -161,6 +165,12 @@ program dang_gpu_drive
   call get_environment_variable('DANG_POSTERIOR_PAIRS', arg, post_len)
   post_pairs = post .and. post_len > 0
   if (post_pairs) call posterior_pairs_gpu(dpar, .true.)
+  call get_environment_variable('DANG_POSTERIOR_HIST', arg, post_len)
+  post_hist = post .and. post_len > 0
+  if (post_hist) then
+     read(arg(1:post_len), *) hist_bins
+     call posterior_hist_gpu(dpar, hist_bins, 16)
+  end if
   secs = 0.d0; it_first = 3
   do iter = 1, niter
      if (iter == it_first + 1) then                       ! time iterations it_first+1 .. niter: the first two full ones warm up (index maps that start spatially constant take the generic launches once, kernels specialised at run time are compiled on first use)
@@ -224,6 +234,15 @@ program dang_gpu_drive
         do i = 1, gpu_post_npairs
            call posterior_pair_to_host_gpu(i, 1, 0, pair_map)
            write(u) pair_map
+        end do
+     end if
+     if (post_hist) then
+        write(u) real(gpu_post_nhist, c_double)
+        allocate(q_map(0:npix-1, 3), n_map(0:npix-1))
+        do i = 1, gpu_post_nhist
+           call posterior_quantile_to_host_gpu(i, [0.16d0, 0.5d0, 0.84d0], q_map)
+           call posterior_hist_n_to_host_gpu(i, n_map)
+           write(u) q_map, n_map
         end do
      end if
   end if

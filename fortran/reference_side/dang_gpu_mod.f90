@@ -40,6 +40,8 @@ module dang_gpu_mod
   integer(c_int32_t), allocatable, target :: gpu_post_sel(:)   ! posterior_begin_gpu's selection words, one per component
   integer(c_int32_t), allocatable, target :: gpu_post_pairs(:,:)   ! posterior_pairs_gpu's pairs (6, gpu_post_npairs), 0-based as in C
   integer(i4b) :: gpu_post_npairs = 0
+  integer(c_int32_t), allocatable, target :: gpu_post_hist(:,:)    ! posterior_hist_gpu's planes (3, gpu_post_nhist), 0-based as in C
+  integer(i4b) :: gpu_post_nhist = 0
 
 contains
 
@@ -724,6 +726,7 @@ contains
     end do
     call dangx_sky_moments_begin(gpu_sky, gpu_post_sel)
     gpu_post_npairs = 0
+    gpu_post_nhist = 0
   end subroutine posterior_begin_gpu
 
   ! after posterior_begin_gpu, before the first posterior_accumulate_gpu that takes a sample: the second-order summaries.  lag1:
@@ -789,6 +792,84 @@ contains
     call rank_window(w, 1, .false.)
     out(0:npix-1) = w(:, 1)
   end subroutine posterior_pair_to_host_gpu
+
+  ! after posterior_begin_gpu, before the first posterior_accumulate_gpu that takes a sample: per-pixel histograms (nbins counters
+  ! of `bits` bits, include/dangx.h) of every selected plane of every index the run samples (c%sample_index(j)), over that index's
+  ! uni_prior -- as dang_amd.api.default_hist_planes: component order, then index, then plane.  Read with
+  ! posterior_quantile_to_host_gpu / posterior_hist_n_to_host_gpu (reg = 1 .. gpu_post_nhist).
+  subroutine posterior_hist_gpu(dpar, nbins, bits)
+    type(dang_params) :: dpar
+    integer(i4b), intent(in) :: nbins, bits
+    type(dang_comps), pointer :: cc
+    integer(i4b) :: i, j, k, n, pass
+    if (.not. allocated(gpu_post_sel)) then
+       write(*,*) 'posterior_hist_gpu: posterior_begin_gpu was not called'
+       stop 1
+    end if
+    do pass = 1, 2                                    ! count, then fill
+       n = 0
+       do i = 1, ncomp
+          cc => component_list(i)%p
+          if (trim(cc%type) == 'template' .or. trim(cc%type) == 'monopole' .or. trim(cc%type) == 'hi_fit') cycle
+          do j = 1, cc%nindices
+             if (.not. cc%sample_index(j)) cycle
+             do k = 0, nmaps - 1
+                if (.not. btest(gpu_post_sel(i), 3 + 3*(j-1) + k)) cycle
+                n = n + 1
+                if (pass == 2) gpu_post_hist(:, n) = int([i-1, j, k], c_int32_t)
+             end do
+          end do
+       end do
+       if (pass == 1) then
+          if (allocated(gpu_post_hist)) deallocate(gpu_post_hist)
+          allocate(gpu_post_hist(3, max(n, 1))); gpu_post_hist = 0
+       end if
+    end do
+    gpu_post_nhist = n
+    call dangx_sky_moments_hist(gpu_sky, n, gpu_post_hist, c_null_ptr, nbins, bits)
+  end subroutine posterior_hist_gpu
+
+  ! the quantiles q(:) (each inside (0, 1), at most 16) of histogram `reg` (1-based, posterior_hist_gpu's order) into
+  ! out(0:npix-1, size(q)); under MPI every rank fills its pixel range and the ranges are merged as rank_window merges a plane.
+  ! NaN where no sample of the pixel was counted
+  subroutine posterior_quantile_to_host_gpu(reg, q, out)
+    integer(i4b), intent(in) :: reg
+    real(dp), intent(in) :: q(:)
+    real(dp), intent(inout), target :: out(0:, :)
+    real(dp), allocatable, target :: w(:,:)
+    real(c_double), allocatable, target :: qq(:)
+    integer(i4b) :: nq
+    if (reg < 1 .or. reg > gpu_post_nhist) then
+       write(*,*) 'posterior_quantile_to_host_gpu: registration out of range', reg, gpu_post_nhist
+       stop 1
+    end if
+    nq = size(q)
+    allocate(w(0:npix-1, nq), qq(nq))
+    qq = q
+    call rank_window(w, 2**nq - 1, .true.)
+    call dangx_sky_moments_hist_stat(gpu_sky, reg - 1, 0, nq, qq, c_loc(w), int(npix, c_int64_t))
+    call rank_window(w, 2**nq - 1, .false.)
+    out(0:npix-1, 1:nq) = w
+  end subroutine posterior_quantile_to_host_gpu
+
+  ! the number of counted samples of every pixel of histogram `reg` into out(0:npix-1); the samples outside the range are the
+  ! accumulation count minus this
+  subroutine posterior_hist_n_to_host_gpu(reg, out)
+    integer(i4b), intent(in) :: reg
+    real(dp), intent(inout), target :: out(0:)
+    real(dp), allocatable, target :: w(:,:)
+    real(c_double), target :: qq(1)
+    if (reg < 1 .or. reg > gpu_post_nhist) then
+       write(*,*) 'posterior_hist_n_to_host_gpu: registration out of range', reg, gpu_post_nhist
+       stop 1
+    end if
+    allocate(w(0:npix-1, 1))
+    qq = 0.5d0
+    call rank_window(w, 1, .true.)
+    call dangx_sky_moments_hist_stat(gpu_sky, reg - 1, 2, 0, qq, c_loc(w), int(npix, c_int64_t))
+    call rank_window(w, 1, .false.)
+    out(0:npix-1) = w(:, 1)
+  end subroutine posterior_hist_n_to_host_gpu
 
   ! after write_data_gpu in the loop: one sample of the current state, every thin-th iteration after burn_in.  Enqueued on every
   ! context's stream behind the iteration's launches: the host does not wait

@@ -74,7 +74,7 @@ enum { DANGX_COARSE_REFERENCE = 0, DANGX_COARSE_DEGRADED = 1 };
 /* kernel ids for dangx_profile_get / dangx_profile_get_planes */
 enum {
     DANGX_K_AMP_DIRECT = 0, DANGX_K_INDEX_MH = 1, DANGX_K_SKY_CHISQ = 2, DANGX_K_REDUCE = 3,
-    DANGX_K_CG_AX = 4, DANGX_K_CG_VEC = 5, DANGX_K_AMP_INDEX = 6, DANGX_K_MOMENTS = 7, DANGX_K_COUNT = 8
+    DANGX_K_CG_AX = 4, DANGX_K_CG_VEC = 5, DANGX_K_AMP_INDEX = 6, DANGX_K_MOMENTS = 7, DANGX_K_HIST = 8, DANGX_K_COUNT = 9
 };
 
 typedef struct dangx_ctx dangx_ctx;
@@ -528,6 +528,39 @@ int dangx_moments_pairs(dangx_ctx *ctx, int lag1, int npairs, const int32_t *pai
 int dangx_moments_get_pair(dangx_ctx *ctx, int pair, int stat, int ddof, double *out);
 /* the same into a device array, asynchronously on the context's stream */
 int dangx_moments_get_pair_dev(dangx_ctx *ctx, int pair, int stat, int ddof, double *out_dev);
+/* Per-pixel histograms of selected pixel planes, accumulated on the same samples as the moments (k_moments_hist, a launch of its own
+ * per accumulation, only when something is registered), and their read-out as quantile / mode / count maps (k_hist_stat): what
+ * scripts/parameter_plotter.py takes from a pixel's trace (np.percentile, corner's histograms) without a sample leaving the device.
+ * Definitions (dang_amd/csrc/dx_hist_host.h; the kernels and the host evaluate the same inline functions):
+ *   registration r = a pixel plane planes[r] = {comp, what, plane} (what as in dangx_moments_get, plane 0-based) with a range
+ *     lo < hi (both finite), nbins in {8, 16, 32, 64} and counters of bits in {16, 32}, nbins * bits / 8 <= 128: a pixel's record is
+ *     a power-of-two number of bytes <= 128 and never crosses a 128-byte memory request.
+ *   bin of a sample x: counted iff x >= lo && x <= hi (NaN, +-inf are not); scale = nbins / (hi - lo) formed once in f64;
+ *     b = min((int)((x - lo) * scale), nbins - 1) -- np.histogram(x, nbins, (lo, hi)) on generic data; on interior edges THIS is
+ *     the definition.  N = sum of a pixel's counters; samples outside the range = dangx_moments_count - N.
+ *   quantile q in (0, 1): target = q * (double)N; walking the bins in order with cum = the sum before bin b, the first bin with
+ *     c_b > 0 && cum + c_b >= target gives lo + ((hi - lo) / nbins) * (b + (target - cum) / c_b); N = 0 gives NaN.  The value lies
+ *     in the closed bin that holds the ceil(q N)-th smallest counted sample.
+ *   mode: the centre of the fullest bin, the lowest on ties; N = 0 gives NaN.
+ * dangx_moments_hist: range[r] = {lo, hi}; range == NULL or a NaN lo = the default, which an index plane has (that index's uni_prior
+ *   in the descriptor at registration time: the chain never leaves it, src/dang_sample_mod.f90:415) and an amplitude plane has not.
+ *   Legal after dangx_moments_begin and before the first dangx_moments_accumulate, independent of dangx_moments_pairs (either order,
+ *   neither drops the other); a second call replaces the first (nreg = 0: none), dangx_moments_begin drops it.  Errors (nothing
+ *   changes, an earlier registration stays): count > 0, a plane that is not selected, a template / monopole / hi_fit amplitude
+ *   (not a pixel plane), a bad nbins or bits or a record over 128 bytes, hi <= lo or a non-finite bound, an amplitude plane
+ *   without a range, nreg > DANGX_MAX_HIST, the same plane twice, a failed allocation (nbins * bits / 8 bytes per pixel and
+ *   registration).  With histograms registered dangx_moments_accumulate fails before touching anything, naming the limit, when the
+ *   new count would exceed 2^bits - 1: no counter ever wraps or saturates.
+ * dangx_moments_hist_get: the raw records [npix][nbins] of this shard as uint16_t (bits 16) or uint32_t (bits 32).
+ * dangx_moments_hist_stat: stat 0 = the nq quantiles q[0..nq) as out[nq][npix] (1 <= nq <= 16, every q strictly inside (0, 1));
+ *   stat 1 = the mode, stat 2 = N as f64 (out[npix]; nq and q ignored).  Errors: reg out of range, no sample accumulated, a bad stat.
+ * The _dev forms write a device array of this shard, asynchronously on the context's stream. */
+#define DANGX_MAX_HIST 32
+int dangx_moments_hist(dangx_ctx *ctx, int nreg, const int32_t *planes, const double *range, int nbins, int bits);
+int dangx_moments_hist_get(dangx_ctx *ctx, int reg, void *counts);
+int dangx_moments_hist_get_dev(dangx_ctx *ctx, int reg, void *counts_dev);
+int dangx_moments_hist_stat(dangx_ctx *ctx, int reg, int stat, int nq, const double *q, double *out);
+int dangx_moments_hist_stat_dev(dangx_ctx *ctx, int reg, int stat, int nq, const double *q, double *out_dev);
 /* frees the accumulators */
 int dangx_moments_end(dangx_ctx *ctx);
 

@@ -3,11 +3,15 @@
 iterations of the C3 model: blocks of iterations without and with accumulation after every iteration, alternating in one process;
 then the k_moments kernel time from the profile and its bandwidth in algorithmic bytes (5 x 8 B per selected element) against the
 6.29 TB/s measured copy ceiling of the MI355X.
-    python3 tools/bench_moments.py [nside=1024] [steps per block=10] [rounds=5] [--lag1] [--pairs default]
+    python3 tools/bench_moments.py [nside=1024] [steps per block=10] [rounds=5] [--lag1] [--pairs default] [--hist [nbins=64]]
 --lag1 / --pairs default: after the above, `rounds` alternating rounds of `steps` accumulations each of (a) the plain accumulate,
 (b) with lag-1 tracking (k_moments_accum_lag: 10 x 8 B per selected element) and (c) with the default pairs (k_moments_pairs: 6 x 8 B
 per pair element, timed apart from the mean launch that follows it); per launch the algorithmic bytes, the achieved bytes/s and
-their ratio to (a) in the same round."""
+their ratio to (a) in the same round.
+--hist [nbins]: alternating rounds of (a) the plain accumulate and (h) the histogram launch (k_moments_hist, 16-bit counters) on the
+default index planes, at nbins and at 16 bins; per launch the line-granular traffic -- 8 B of x plus the record's 128-byte request
+read and written once per counted pixel -- its bytes/s and the ratio to
+(a)'s algorithmic bytes/s in the same round; then the read-out of three quantiles of one plane and the records' memory."""
 import os
 import sys
 import time
@@ -21,7 +25,14 @@ from dang_amd import synth  # noqa: E402
 
 COPY_CEILING_TBS = 6.29
 
-args = [a for a in sys.argv[1:] if not a.startswith("--") and a != "default"]
+argv = list(sys.argv[1:])
+hist_bins = 0
+if "--hist" in argv:
+    i = argv.index("--hist")
+    hist_bins = 64
+    if i + 1 < len(argv) and argv[i + 1].isdigit():
+        hist_bins = int(argv.pop(i + 1))
+args = [a for a in argv if not a.startswith("--") and a != "default"]
 want_lag1 = "--lag1" in sys.argv
 want_pairs = "--pairs" in sys.argv
 if want_pairs and sys.argv[sys.argv.index("--pairs") + 1:][:1] != ["default"]:
@@ -120,3 +131,47 @@ if want_lag1 or want_pairs:
     for key, name in (("lag1", "(b) lag-1"), ("pairs", "(c) pairs")):
         if res[key]:
             print("%s / (a): median %.3f (spread %.3f .. %.3f); target >= 0.9" % (name, float(np.median(res[key])), min(res[key]), max(res[key])))
+
+
+def hist_launches(nbins, bits=16):
+    """(ms per k_moments_hist launch, ms per plain k_moments launch beside it, registrations, counted pixels per launch, read-out ms)"""
+    da.moments_begin(dpar, ddata, sel=sel)
+    hp = da.moments_hist(dpar, ddata, nbins=nbins, bits=bits)
+    da.moments_accumulate(ddata)   # table upload
+    eng.profile(True)
+    for _ in range(steps):
+        da.moments_accumulate(ddata)
+    prof = eng.profile_get()
+    eng.profile(False)
+    counted = sum(float(eng.moments_hist_stat(r, "n", device=True).sum()) for r in range(len(hp))) / (steps + 1)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    eng.moments_hist_stat(0, "quantile", q=(0.16, 0.5, 0.84), device=True)
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    return (prof["k_hist"]["total_ms"] / prof["k_hist"]["launches"], prof["k_moments"]["total_ms"] / prof["k_moments"]["launches"],
+            len(hp), counted, (t1 - t0) * 1e3)
+
+
+if hist_bins:
+    npx = meta["npix"]
+    forms = [hist_bins] + ([16] if hist_bins != 16 else [])
+    ratios = {nb: [] for nb in forms}
+    for r in range(rounds):
+        a_ms = launches("plain")[0]
+        a_bw = 5 * 8 * planes * npx / a_ms * 1e-9
+        line = "round %d: (a) plain %.3f ms -> %.2f TB/s" % (r + 1, a_ms, a_bw)
+        for nb in forms:
+            h_ms, m_ms, nreg, counted, q_ms = hist_launches(nb)
+            traffic = 8.0 * nreg * npx + 2 * 128.0 * counted
+            h_bw = traffic / h_ms * 1e-9
+            ratios[nb].append(h_bw / a_bw)
+            line += "; (h) %d bins x 16 bit on %d planes %.3f ms, %.2f GB line-granular (%.0f counted pixels) -> %.2f TB/s = %.3f of (a)" \
+                    "; k_moments beside it %.3f ms; 3 quantiles of one plane %.3f ms" % (nb, nreg, h_ms, traffic * 1e-9, counted, h_bw,
+                                                                                       h_bw / a_bw, m_ms, q_ms)
+        print(line)
+    for nb in forms:
+        print("(h) %d bins / (a): median %.3f (spread %.3f .. %.3f)" % (nb, float(np.median(ratios[nb])), min(ratios[nb]), max(ratios[nb])))
+    nreg = len(da.default_hist_planes(dpar, comps, sel))
+    print("records: %d B x %d pixels x %d planes = %.2f GB at %d bins x 16 bit" % (hist_bins * 2, npx, nreg, hist_bins * 2.0 * npx * nreg * 1e-9, hist_bins))
+    da.moments_begin(dpar, ddata, sel=sel)   # drops the records
