@@ -13,9 +13,31 @@ static int planeset_jeff(const SweepList& sl) {
     for (int q = 0; q < sl.n; ++q) if (sl.s[q].jeff) return 1;
     return 0;
 }
-static size_t planeset_lds(int ng, int nb, int nv, int lanes, int Sp, int jeff) {
-    const int rows = nv > Sp + jeff ? nv : Sp + jeff;
+// keep: one more row block behind all of these, for the Planck factors of the launch's modified-blackbody item (planeset_keep)
+static size_t planeset_lds(int ng, int nb, int nv, int lanes, int Sp, int jeff, int keep = 0) {
+    const int rows = (nv > Sp + jeff ? nv : Sp + jeff) + (keep ? 1 : 0);
     return ((size_t)(TROWS * ng + 3) * nb + (size_t)rows * (nb / lanes) * BLOCK) * sizeof(double);
+}
+
+// What the launch keeps of the solve's SED evaluation for the chains of its first modified-blackbody item (SweepList::keep,
+// dx_kern_planeset.h: ps_item): 1 = the member's Planck factors, in a row block of their own; 2 = its SED column too, which costs
+// nothing where the column's slot lies behind the rows that 1 / rms is parked in (and the item is not the first one, whose chain
+// evaluates nothing before its first proposal).  One lane per pixel, delta bands, no Jeffreys item (its weights take the rows
+// behind 1 / rms), and only where the block stays within 80 KB: the reuse is never paid for with a resident block.
+static int planeset_keep(const SweepList& sl, const FusedArgs& fa, int ng, int nb, int lanes, int Sp, int bp) {
+#ifdef DX_BOUNDARY_REEVAL
+    return 0;
+#else
+    if (lanes != 1 || bp || planeset_jeff(sl)) return 0;
+    const int n = sl.n < 4 ? sl.n : 4;
+    for (int q = 0; q < n; ++q) {
+        if (sl.s[q].mode != CH_MBB_BETA) continue;
+        const int v = fa.vslot[sl.s[q].gmember];
+        if (v < 0 || planeset_lds(ng, nb, fa.nv, lanes, Sp, 0, 1) > 80u * 1024u) return 0;
+        return (q > 0 && v >= Sp) ? 2 : 1;
+    }
+    return 0;
+#endif
 }
 
 // the sweep items as template arguments: chain mode + 8 for an item that carries the component's next index too, + 16 for a chain
@@ -142,12 +164,14 @@ int dx_planeset_lanes(dangx_ctx* ctx, const GroupArgs& ga, const SweepList& sl, 
 }
 
 // accp: per-sweep counters (sum over items of 1 + pair entries) or null
-bool dx_launch_planeset(dangx_ctx* ctx, const GroupArgs& ga, const SweepList& sl, int lanes, int solve, unsigned nblk, unsigned long long* accp) {
+bool dx_launch_planeset(dangx_ctx* ctx, const GroupArgs& ga, const SweepList& sl_in, int lanes, int solve, unsigned nblk, unsigned long long* accp) {
     FusedArgs fa;
-    if (lanes < 1 || lanes > 2 || !planeset_args(ctx, ga, sl, fa)) return false;
+    if (lanes < 1 || lanes > 2 || !planeset_args(ctx, ga, sl_in, fa)) return false;
+    SweepList sl = sl_in;
     const int nb = ctx->hm.nbands, ng = ga.ng, Sp = sl.s2 - sl.s1 + 1;
-    const size_t ldsz = planeset_lds(ng, nb, fa.nv, lanes, Sp, planeset_jeff(sl));
     const int bp = planeset_bp(ctx);
+    sl.keep = planeset_keep(sl, fa, ng, nb, lanes, Sp, bp);
+    const size_t ldsz = planeset_lds(ng, nb, fa.nv, lanes, Sp, planeset_jeff(sl), sl.keep);
     if (!bp && planeset_builtin(nb, ng, lanes, solve, sl)) {
         if (planeset_jeff(sl)) dx_launch_planeset_jeff(ctx, ga, fa, sl, Sp, solve, nblk, ldsz, accp);
         else if (nb == 20) launch_builtin<20, 6, 2, 1, CH_POW, CH_MBB_BETA + 8, CH_LOGN_NUP>(ctx, ga, fa, sl, Sp, nblk, ldsz, accp);

@@ -59,7 +59,11 @@ struct SweepItem {
 constexpr int DX_MAX_SWEEPS = 6;
 constexpr int DX_MAX_IDXSUM = 8;   // index maps one plane-set launch can sweep (4 items, each with its component's next index)
 struct SweepList {
-    int n, nsample, ml_mode, s1, s2, pad;
+    int n, nsample, ml_mode, s1, s2;
+    // what the launch keeps of its modified-blackbody item's solve for that item's chains (k_plane_set, set by the launcher that
+    // sizes the LDS; 0 from every other caller): 1 = the Planck factors, in the row block behind the columns and the parked
+    // 1 / rms; 2 = the member's SED column as well (its slot lies behind the parked 1 / rms)
+    int keep;
     unsigned long long seed;
     SweepItem s[DX_MAX_SWEEPS];
 };

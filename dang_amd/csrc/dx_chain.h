@@ -128,10 +128,16 @@ struct BandPick {
 // sum_k sum_j ((1/sigma_kj)^2 (a_k s_j / a_k) ln(nu_j/nu_ref))^2 with the amplitude cancelled, so that where the reference
 // divides 0 by 0 (or inf by inf, or meets a NaN amplitude) w_j is NaN and so is S.  The weights live in registers, or (KT:
 // k_plane_set) in NB rows of the lane's LDS column behind the parked 1/rms.
-template <int MODE, int SP, int NB, int LP, bool KT = false, bool BP = false, bool JF = false>
+// KEPT (k_plane_set; LP == 1, delta bands, no Jeffreys prior): chain_finish takes the chain-invariant factor from where it was
+// formed before -- a beta chain's Planck factors from the column fcol (stride BLOCK) where the solve's sed_column left them
+// (fcol null: evaluated as ever), a T chain's power-law factors set in F[] by the caller as the beta chain's closing
+// evaluation left them (chain_finish, HAND).  Same operands, same operations: the same bits.
+template <int MODE, int SP, int NB, int LP, bool KT = false, bool BP = false, bool JF = false, bool KEPT = false>
 struct RegChain {
     static constexpr bool kBP = BP;
     static constexpr bool kJF = JF;
+    static constexpr bool kKept = KEPT;
+    static_assert(!KEPT || (LP == 1 && !BP && !JF && (MODE == CH_MBB_BETA || MODE == CH_MBB_T)), "kept factors: one-lane delta-band mbb chains");
     static_assert(!JF || (MODE == CH_POW && !BP), "Jeffreys chains: power law, delta bands");
     double D[SP][NB], F[NB], ISr[SP][NB];  // cleaned data, chain-invariant SED factor, 1/rms  (scaled form: d/rms, amp/rms)
     double bpa, bpb;                       // BP: CH_MBB_BETA: z = h/(k T), exp(z nu_ref) - 1; CH_MBB_T: beta + 1
@@ -140,6 +146,7 @@ struct RegChain {
     double amp[SP];
     double W[(JF && !KT) ? NB : 1], jS;    // JF: the weights w_j (KT: in LDS at wcol), S of the last evaluation
     double* wcol;
+    const double* fcol;                    // KEPT, CH_MBB_BETA
 
     __device__ __forceinline__ double w(int j) const { return KT ? wcol[j * BLOCK] : W[j]; }
     // the weights, from 1/rms of the lane's bands (is_of(kk, j)) and the amplitudes of the swept planes (amp[])
@@ -199,8 +206,11 @@ struct RegChain {
     //             member's own signal goes back into the cleaned data, and lnL of the current state is the residual's
     //   LNL_SUB   D -= a' s, acc += D^2                          -- after the chain, at the values it ended on: the residual again
     //             (the same residual bits as an EVAL there, so acc0 / acc1 are that evaluation's sums)
-    template <bool BATCH, int OP = 0>
-    __device__ __forceinline__ double lnl(const Model& M, const Comp& c, double th, double other, double& acc0, double& acc1) {
+    // EOUT (CH_MBB_BETA, delta bands): the band's power-law factor e_j = exp((beta + 1) ln(nu_j / nu_ref)) also goes to eout[j]
+    template <bool BATCH, int OP = 0, bool EOUT = false>
+    __device__ __forceinline__ double lnl(const Model& M, const Comp& c, double th, double other, double& acc0, double& acc1,
+                                          double* eout = nullptr) {
+        static_assert(!EOUT || (MODE == CH_MBB_BETA && !BP), "the exported factor is the beta chain's");
         double s0 = 0.0, s1 = 0.0;
         if (MODE == CH_POW) s0 = th;
         else if (MODE == CH_MBB_BETA) s0 = th + 1.0;
@@ -272,6 +282,7 @@ struct RegChain {
                     s[t] = CEXPS(-0.5 * (l * l)) * k2(c, j);
                 } else {
                     const double e = CEXP(s0 * k1(M, c, j));
+                    if (EOUT) eout[j] = e;
                     if (MODE == CH_POW) s[t] = e;
                     else if (MODE == CH_MBB_BETA) s[t] = F[j] * e;
                     else s[t] = CDIV(s1, e - 1.0) * F[j];
@@ -327,6 +338,29 @@ struct RegChain {
 #ifdef DX_CHAIN_SCALED
         acc0 *= -0.5; acc1 *= -0.5;
 #endif
+        return acc0 + acc1;
+    }
+
+    // The LNL_ADD evaluation of a chain whose SED column at the current index values is still in the lane's LDS column
+    // (k_plane_set keeps the member's column of the solve where its slot lies behind the parked 1/rms; scol: stride BLOCK): the
+    // band loop of lnl<.., 1> with s_j read instead of evaluated.  The stored s_j = f_j * exp_nr(p0 lnr_j) of sed_column is the
+    // product F[j] * e of lnl: f_j is F[j] (RegChain, KEPT), p0 = beta + 1 = s0, lnr_j = k1(j), all from the same table rows.
+    __device__ __forceinline__ double lnl_add_kept(const double* scol, double& acc0, double& acc1) {
+        static_assert(LP == 1 && !JF && !BP, "one lane, delta bands, no prior sum");
+        acc0 = 0.0; acc1 = 0.0;
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+            const double s = scol[j * BLOCK];
+            const double r0 = D[0][j];
+            D[0][j] = fma(is(0, j), s, r0);
+            acc0 = fma(r0, r0, acc0);
+            if (SP == 2) {
+                const double r1 = D[SP - 1][j];
+                D[SP - 1][j] = fma(is(SP - 1, j), s, r1);
+                acc1 = fma(r1, r1, acc1);
+            }
+        }
+        acc0 *= -0.5; acc1 *= -0.5;
         return acc0 + acc1;
     }
 
@@ -501,11 +535,18 @@ __device__ __forceinline__ void subtract_other_pair(const Model& M, const Comp& 
 // k_index_mh_pair); final_value (nullable) receives the value the chain ends at.
 // ADD / SUB (k_plane_set's resident-residual form, see RegChain::lnl): R.D arrives as the full residual and the first evaluation
 // puts the component's own signal back (ADD); after the chain the signal at the values it ended on is taken out again (SUB).
-template <int MODE, int SP, int NB, int LP, bool SCALE = true, bool ADD = false, bool SUB = false, class RC>
+// HAND (k_plane_set, the beta chain of a modified blackbody's pair; not with SUB): the chain hands e_j = exp((beta + 1) lnr_j) at
+// the value it ended on to hand[j] -- the chain-invariant factor of the T chain that follows (RegChain, KEPT).  ONE exact
+// evaluation at cur after the loop, by every lane, yields them and the closing sums of the lanes whose last accept was cheap;
+// the other lanes keep their sums (the evaluation would return the same bits: it repeats the one that was accepted).
+// scol (ADD, the chain's R is KEPT): the member's SED column at the current values, kept from the solve, or null.
+template <int MODE, int SP, int NB, int LP, bool SCALE = true, bool ADD = false, bool SUB = false, bool HAND = false, class RC>
 __device__ __forceinline__ unsigned long long chain_finish(const Model& M, const IndexArgs& a, const Comp& c, RC& R,
                                                            const BandPick<LP>& pick, double sample0, double sample1, int i, int half,
                                                            double chi[4], double* final_value = nullptr,
-                                                           const double* acc_in = nullptr, double* acc_out = nullptr) {
+                                                           const double* acc_in = nullptr, double* acc_out = nullptr,
+                                                           double* hand = nullptr, const double* scol = nullptr) {
+    static_assert(!HAND || (MODE == CH_MBB_BETA && !SUB && !RC::kBP && LP == 1), "the hand-over is the one-lane delta-band beta chain's");
     // acc_in (k_plane_set, second chain of a component's pair): the likelihood sums of the state this chain starts from, as the
     // chain before it left them -- the same state, the same SED (another factorisation of it): no first evaluation.
     // acc_out: the sums of the state the chain ends on.
@@ -519,7 +560,12 @@ __device__ __forceinline__ unsigned long long chain_finish(const Model& M, const
     if (JEFF && SCALE) R.form_w(M, c, [&](int kk, int j) { return R.is(kk, j); });  // ISr is still 1/rms here
     if (SCALE) R.scale();
     // --- chain-invariant SED factor
-    if (MODE == CH_MBB_BETA) {
+    if (MODE == CH_MBB_BETA && RC::kKept && R.fcol) {
+#pragma unroll
+        for (int j = 0; j < NB; ++j) R.F[j] = R.fcol[j * BLOCK];
+    } else if (MODE == CH_MBB_T && RC::kKept) {
+        // F is the beta chain's hand-over
+    } else if (MODE == CH_MBB_BETA) {
         const double z = mbb_z(sample1);
         const double A = CEXP(z * c.nu_ref) - 1.0;
 #pragma unroll
@@ -580,6 +626,10 @@ __device__ __forceinline__ unsigned long long chain_finish(const Model& M, const
         constexpr bool B = decltype(batch_tag)::value;
         double lnl;
         if (acc_in) { a0 = acc_in[0]; a1 = acc_in[1]; lnl = a0 + a1; if (JEFF) R.jeff_eval(M, c, cur); }
+        else if constexpr (ADD && RC::kKept) {
+            if (scol) lnl = R.lnl_add_kept(scol, a0, a1);
+            else lnl = R.template lnl<B, 1>(M, c, cur, other, a0, a1);
+        }
         else lnl = R.template lnl<B, ADD ? 1 : 0>(M, c, cur, other, a0, a1);
         chi[0] = -2.0 * a0; chi[1] = -2.0 * a1;
         double lnl_old = lnl + (JEFF ? jprior(R.jS) : prior(cur));
@@ -667,9 +717,13 @@ __device__ __forceinline__ unsigned long long chain_finish(const Model& M, const
         }
         // the sums of the state the chain ends on: the last accepted evaluation's (or the start's if nothing was accepted); after
         // a cheap accept they are an exact evaluation at cur -- the SUB pass computes exactly that residual
-        if (SUB) {
+        if constexpr (SUB) {
             double s0_, s1_;
             (void)R.template lnl<B, 2>(M, c, cur, other, s0_, s1_);
+            if (!sums_exact) { a0 = s0_; a1 = s1_; }
+        } else if constexpr (HAND) {
+            double s0_, s1_;
+            (void)R.template lnl<B, 0, true>(M, c, cur, other, s0_, s1_, hand);
             if (!sums_exact) { a0 = s0_; a1 = s1_; }
         } else if (kCert) {
             if (__builtin_amdgcn_ballot_w64(!sums_exact) != 0ull) {

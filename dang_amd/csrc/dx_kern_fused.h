@@ -24,9 +24,12 @@ namespace dxk {
 
 // SEDs of one varying member for the lane's NBL bands (bands jb .. jb + NBL - 1 of the model's NB) -> its LDS column; the
 // expressions of k_amp_reg's sed_tile (dangx_ampreg.hip), band by band
+// fcol (k_plane_set, a modified blackbody whose beta chain follows in the launch): the member's Planck factors
+// A / (exp(z nu_j) - 1) go to that column too -- they are the chain-invariant factor F[j] of its beta chain (chain_finish forms
+// A * fast_rcp(exp_nr(z nu_j) - 1) from the same z = mbb_z(T), A = exp_nr(z nu_ref) - 1 and nu_j: the same bits)
 template <int NBL>
 __device__ __forceinline__ void sed_column(int type, const double* __restrict__ tab, int NB, int NG, int g, int jb, const Prep& p,
-                                           double* __restrict__ colg) {
+                                           double* __restrict__ colg, double* __restrict__ fcol = nullptr) {
     const double* lnr = tab + (TROWS * g) * NB + jb;
     const double* cst = lnr + NB;
     const double* lnu9 = cst + NB;
@@ -44,6 +47,10 @@ __device__ __forceinline__ void sed_column(int type, const double* __restrict__ 
             double f[TT];
 #pragma unroll
             for (int t = 0; t < TT; ++t) f[t] = p.p2 * fast_rcp(exp_nr(p.p1 * nuc[j0 + t]) - 1.0);
+            if (fcol) {
+#pragma unroll
+                for (int t = 0; t < TT; ++t) fcol[(j0 + t) * BLOCK] = f[t];
+            }
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int t = 0; t < TT; ++t) colg[(j0 + t) * BLOCK] = f[t] * exp_nr(p.p0 * lnr[j0 + t]);

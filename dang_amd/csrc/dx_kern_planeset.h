@@ -43,12 +43,29 @@ template <bool V> struct ItemFlag { static constexpr bool value = V; };
 // R0.D holds the full residual / rms of the lane's bands, rows 0 .. SP*NBL-1 of the lane's LDS column hold 1 / rms.  Leaves the
 // member's two index values in sample0 / sample1.  LAST: nothing follows, the residual need not be restored.
 // JF: the item's chain carries the Jeffreys prior; its weights go to rows SP*NBL .. of the lane's column (RegChain::form_w)
+//
+// What the item does not evaluate again at its chain boundaries (one lane per pixel, delta bands; -DDX_BOUNDARY_REEVAL restores
+// the evaluations for A/B timing).  Each value is formed by the same operations on the same operands as the evaluation it
+// replaces, so every map, sum and count keeps its bits (tests/test_gpu_planeset_boundary.py):
+//   fkeep   a modified blackbody's beta chain takes its chain-invariant Planck factors from the column where the solve's
+//           sed_column left them (the member's indices have not moved since: a component's sweeps travel in one item) instead of
+//           NBL exponentials and reciprocals;
+//   skeep   where the member's SED column of the solve also survived the parking of 1 / rms, the chain's first evaluation
+//           (LNL_ADD) reads s_j from it instead of NBL more exponentials;
+//   pair    the T chain's factors exp((beta + 1) lnr_j) at the value the beta chain ended on come out of that chain's closing
+//           evaluation (chain_finish, HAND) instead of NBL exponentials in the T chain's setup.
+// fkeep / skeep are null where the launcher found no room for them (SweepList::keep).
+#ifdef DX_BOUNDARY_REEVAL
+#define DX_PS_SHARE(MODE, LP, BP, JF) false
+#else
+#define DX_PS_SHARE(MODE, LP, BP, JF) ((MODE) == CH_MBB_BETA && (LP) == 1 && !(BP) && !(JF))
+#endif
 template <int MODE, int PAIR, int SP, int NBL, int LP, int NG, bool FIRST, bool LAST, bool BP, bool JF, typename RFirst>
 __device__ __forceinline__ void ps_item(const Model& M, const SweepList& sl, const SweepItem& it, RFirst& R0, int i, int half,
                                         int jb, int NB, const double* __restrict__ tab, const double* __restrict__ col,
                                         double& sample0, double& sample1, double chi_first[4],
                                         double chi_last[4], unsigned int* __restrict__ accepted, int slot, const double* first_acc,
-                                        double* wrow) {
+                                        double* wrow, const double* fkeep, const double* skeep) {
     const Comp& c = M.comp[it.comp];
     const BandPick<LP> pick = {half};
     const int npix = M.npix;
@@ -57,8 +74,10 @@ __device__ __forceinline__ void ps_item(const Model& M, const SweepList& sl, con
     a.bp = 0; a.others = 0u; a.jeff = 0; a.seed = sl.seed; a.stream = it.stream;
     // per-band constants from the block's table in LDS, in the one-lane form too (as scalar operands from the model instead: 86.4
     // against 87.1 it/s at C3 on one device -- the scalar registers are what the kernel is short of)
-    RegChain<MODE, SP, NBL, LP, true, BP, JF> R;
+    constexpr bool SHARE = DX_PS_SHARE(MODE, LP, BP, JF);
+    RegChain<MODE, SP, NBL, LP, true, BP, JF, SHARE> R;
     R.set_kt(tab, NB, NG, it.gmember, jb);
+    R.fcol = fkeep;
 #pragma unroll
     for (int kk = 0; kk < SP; ++kk) {
         R.amp[kk] = c.amp[(long long)(sl.s1 + kk - 1) * npix + i];   // the lane's own store after the solve, or the map in memory
@@ -73,16 +92,22 @@ __device__ __forceinline__ void ps_item(const Model& M, const SweepList& sl, con
     // FIRST: the kernel has put this member's signal back already, from its SED column of the solve (R0.D is the cleaned data and
     // first_acc the likelihood sums of the state the solve left): no evaluation before the first proposal.  Later items: the
     // chain's first evaluation adds the signal back (LNL_ADD)
-    unsigned long long na = chain_finish<MODE, SP, NBL, LP, false, !FIRST, (!PAIR && !LAST)>(M, a, c, R, pick, sample0, sample1, i, half, chia, &va,
-                                                                                            FIRST ? first_acc : nullptr, acc);
+    constexpr bool HAND = SHARE && PAIR != 0;
+    double ej[HAND ? NBL : 1];
+    unsigned long long na = chain_finish<MODE, SP, NBL, LP, false, !FIRST, (!PAIR && !LAST), HAND>(M, a, c, R, pick, sample0, sample1, i, half, chia, &va,
+                                                                                                  FIRST ? first_acc : nullptr, acc, ej, skeep);
     if (it.nind == 0) sample0 = va; else sample1 = va;
     if (FIRST) { chi_first[0] = chia[0]; chi_first[1] = chia[1]; }
     chi_last[2] = chia[2]; chi_last[3] = chia[3];
     unsigned long long nb_ = 0ull;
     if (PAIR) {
         constexpr int MODEB = (MODE == CH_MBB_BETA || MODE == CH_LOGN_NUP) ? MODE + 1 : MODE;  // only those two modes have a pair
-        RegChain<MODEB, SP, NBL, LP, true, BP> RB;
+        RegChain<MODEB, SP, NBL, LP, true, BP, false, HAND> RB;
         RB.set_kt(tab, NB, NG, it.gmember, jb);
+        if (HAND) {
+#pragma unroll
+            for (int j = 0; j < NBL; ++j) RB.F[j] = ej[j];
+        }
 #pragma unroll
         for (int kk = 0; kk < SP; ++kk) {
             RB.amp[kk] = R.amp[kk];
@@ -132,7 +157,8 @@ __global__ __launch_bounds__(BLOCK, DX_PS_WAVES(SP, NB, LP, SOLVE, C0)) void k_p
                                                         unsigned long long* __restrict__ not_spd, unsigned long long* __restrict__ accepted,
                                                         double* __restrict__ chi_partial) {
     constexpr int NBL = NB / LP;
-    extern __shared__ double lds[];  // [constant table | per-lane column: max(nv, SP) * NBL rows -- the SEDs, then 1 / rms]
+    // [constant table | per-lane column: max(nv, SP) * NBL rows -- the SEDs, then 1 / rms | sl.keep: NBL rows of Planck factors]
+    extern __shared__ double lds[];
     const Model& M = *Mp;
     const int npix = M.npix, tid = threadIdx.x;
     double* tab = lds;
@@ -167,6 +193,14 @@ __global__ __launch_bounds__(BLOCK, DX_PS_WAVES(SP, NB, LP, SOLVE, C0)) void k_p
         const long long bstride = (long long)M.nmaps * npix;
         const unsigned long long gpix = (unsigned long long)(M.pix0 + i);
         const bool sample = (ga.ml_mode == DANGX_ML_SAMPLE);
+        // what the launch's modified-blackbody item keeps of the solve (ps_item; the launcher sized the LDS for it): item KQ's
+        // member, its Planck factors in the row block behind everything else, its SED column where that is not parked over
+        constexpr int KQ = ((C0 & 7) == CH_MBB_BETA) ? 0 : ((C1 & 7) == CH_MBB_BETA) ? 1 : ((C2 & 7) == CH_MBB_BETA) ? 2 : 3;
+        constexpr bool KEEPC = DX_PS_SHARE(CH_MBB_BETA, LP, BP, false) &&
+                               ((C0 & 7) == CH_MBB_BETA || (C1 & 7) == CH_MBB_BETA || (C2 & 7) == CH_MBB_BETA || (C3 & 7) == CH_MBB_BETA);
+        const int kv = (KEEPC && sl.keep > 0) ? fa.vslot[sl.s[KQ].gmember] : -1;
+        double* const fkeep = (kv >= 0) ? col + ((fa.nv > SP ? fa.nv : SP) * NBL) * BLOCK : nullptr;
+        const double* const skeep = (kv >= 0 && sl.keep == 2) ? col + (kv * NBL) * BLOCK : nullptr;
         // ---- SED columns of the varying members, once: their indices are equal on the planes of the launch (launcher)
 #pragma unroll 1
         for (int v = 0; v < fa.nv; ++v) {
@@ -174,7 +208,8 @@ __global__ __launch_bounds__(BLOCK, DX_PS_WAVES(SP, NB, LP, SOLVE, C0)) void k_p
             double t0v, t1v;
             load_theta(M, c2, i, sl.s1, t0v, t1v);
             if (BP) sed_column_bp<NBL>(M, c2, tab, NB, NG, fa.vcomp[v], sed_prep(c2, t0v, t1v), col + (v * NBL) * BLOCK);
-            else sed_column<NBL>(fa.vtype[v], tab, NB, NG, fa.vcomp[v], jb, sed_prep(c2, t0v, t1v), col + (v * NBL) * BLOCK);
+            else sed_column<NBL>(fa.vtype[v], tab, NB, NG, fa.vcomp[v], jb, sed_prep(c2, t0v, t1v), col + (v * NBL) * BLOCK,
+                                 (KEEPC && v == kv) ? fkeep : nullptr);
         }
         RegChain<CH_POW, SP, NBL, LP> R0;  // storage for the maps of the plane set: d and 1/sigma, then the residual
 #pragma unroll
@@ -377,7 +412,8 @@ __global__ __launch_bounds__(BLOCK, DX_PS_WAVES(SP, NB, LP, SOLVE, C0)) void k_p
                 load_theta(M, c, i, sl.s1, sample0, sample1);
                 ps_item<(CODE & 7), ((CODE >> 3) & 1), SP, NBL, LP, NG, FIRST, LAST, (BP != 0), ((CODE >> 4) != 0)>(M, sl, it, R0, i, half, jb, NB, tab, col, sample0, sample1,
                                                                               FIRST ? chi : unused, chi, accepted ? acc_blk : nullptr, slot, first_acc,
-                                                                              col + (SP * NBL) * BLOCK);
+                                                                              col + (SP * NBL) * BLOCK, (KEEPC && q == KQ) ? fkeep : nullptr,
+                                                                              (KEEPC && q == KQ) ? skeep : nullptr);
                 slot += 1 + ((CODE >> 3) & 1);
             }
         };
