@@ -10,6 +10,7 @@ from .api import (BandInfo, DangCGGroup, DangComps, DangData, DangParams, DangxE
                   sample_index_mh_fullsky, sample_spectral_parameters, stream_id, tune_perpixel, fusable_first_sweeps, plan_plane_sets, sky_amp_sample, sky_plane_set_sample,
                   default_moment_selection, moments_begin, moments_accumulate, posterior_maps,
                   default_moment_pairs, moments_pairs, posterior_pair_maps,
-                  default_hist_planes, moments_hist, posterior_quantile_maps)
+                  default_hist_planes, moments_hist, posterior_quantile_maps,
+                  default_signal_specs, moments_signals, posterior_signal_maps)
 
 __version__ = "0.1.0"

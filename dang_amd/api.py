@@ -622,6 +622,7 @@ class Engine:
         """Start (or restart) accumulating: sel[l] = selection word of component l (include/dangx.h; None = every plane)."""
         self._moment_pairs, self._moment_lag1 = [], False   # dangx_moments_begin drops what moments_pairs registered
         self._moment_hist = None                            # ... and what moments_hist registered
+        self._moment_signals = None                         # ... and what moments_signals registered
         if sel is None:
             self._chk(self.lib.dangx_moments_begin(self.h, None))
             full = (1 << self.nmaps) - 1
@@ -768,7 +769,37 @@ class Engine:
         self._chk(self.lib.dangx_moments_hist_stat(self.h, int(reg), st, qa.size, qp, out.ctypes.data))
         return out
 
+    def moments_signals(self, specs):
+        """Register component signals after moments_begin and before the first moments_accumulate: specs = [(l, band, kind), ...],
+        kind 0, 1, 2 = plane T, Q, U of eval_signal(band, pix, plane) = amplitude * sed of component l ('T' / 'Q' / 'U' accepted),
+        kind 3 / 'P' = its polarised intensity sqrt(Q^2 + U^2).  Independent of the selection, of moments_pairs and of
+        moments_hist; a second call replaces the first.  Definitions: include/dangx.h."""
+        sp = [(int(l), int(j), L.SIGNAL_KINDS.index(k) if isinstance(k, str) else int(k)) for l, j, k in specs]
+        p = np.ascontiguousarray(np.asarray(sp, dtype=np.int32).reshape(-1, 3))
+        self._chk(self.lib.dangx_moments_signals(self.h, p.shape[0], p.ctypes.data if p.size else None))
+        self._moment_signals = sp
+
+    def moments_get_signal(self, s, stat, ddof=0, device=False, out=None):
+        """Mean ('mean' / 0) or standard deviation ('std' / 1, sqrt(m2 / (n - ddof))) of registered signal s as [npix].
+        device=True: a torch cuda tensor filled on the device."""
+        st = L.STAT_CODES[stat] if isinstance(stat, str) else int(stat)
+        if device:
+            import torch
+            if out is None:
+                dev = self._device if self._device is not None and self._device >= 0 else torch.cuda.current_device()
+                out = torch.zeros((self.npix,), dtype=torch.float64, device=torch.device("cuda", dev))
+            assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float64 and tuple(out.shape) == (self.npix,)
+            self._chk(self.lib.dangx_moments_get_signal_dev(self.h, int(s), st, int(ddof), out.data_ptr()))
+            self.synchronize()
+            return out
+        if out is None:
+            out = np.zeros(self.npix)
+        assert isinstance(out, np.ndarray) and out.dtype == np.float64 and out.flags.c_contiguous and out.shape == (self.npix,)
+        self._chk(self.lib.dangx_moments_get_signal(self.h, int(s), st, int(ddof), out.ctypes.data))
+        return out
+
     def moments_end(self):
+        self._moment_signals = None
         self._chk(self.lib.dangx_moments_end(self.h))
 
     # -- profiling
@@ -1339,6 +1370,70 @@ def posterior_quantile_maps(ddata, q=(0.16, 0.5, 0.84), masked_value=None, engin
                 parts.append(_mask_fill(m, e.ddata.masks, masked_value) if masked_value is not None else m)
             entry[name] = np.concatenate(parts, axis=-1) if len(parts) > 1 else parts[0]
         out[(comps[l].label, _plane_name(comps[l], what), k)] = entry
+    return out
+
+
+def default_signal_specs(dpar, component_list, bands):
+    """[(l, band, kind), ...] for moments_signals: for every non-global component whose amplitude is sampled and that has at least
+    one sampled index (without one its signal is a constant multiple of its amplitude), the signal at the band whose nu_c is
+    nearest the component's nu_ref (the lowest band on ties) on every plane default_moment_selection selects for its amplitude,
+    plus P (kind 3) when both Q and U are.  Component order, then kind.  Pure Python."""
+    sel = default_moment_selection(dpar, component_list)
+    specs = []
+    for l, c in enumerate(component_list):
+        if c.type in GLOBAL_TYPES or not c.sample_amplitude:
+            continue
+        if not any(j < len(c.sample_index) and c.sample_index[j] for j in range(c.nindices)):
+            continue
+        w = int(sel[l]) & 7
+        if not w:
+            continue
+        ref = float(c.nu_ref) * (1e9 if float(c.nu_ref) < 1e7 else 1.0)       # Hz, the library's own rules (dangx_set_band / _set_component)
+        dist = [abs(float(b.nu_c) * (1e9 if float(b.nu_c) < 1e9 else 1.0) - ref) for b in bands]
+        band = dist.index(min(dist))
+        kinds = [k for k in range(3) if (w >> k) & 1]
+        if (w & 6) == 6:
+            kinds.append(3)
+        specs += [(l, band, k) for k in kinds]
+    return specs
+
+
+def moments_signals(dpar, ddata, specs=None, engines=None):
+    """dangx_moments_signals on every context of this process, after moments_begin and before the first moments_accumulate;
+    specs=None: default_signal_specs of the run.  Returns the spec list [(l, band, kind), ...]."""
+    engs = _engines_of(ddata, engines)
+    if specs is None:
+        specs = default_signal_specs(dpar, engs[0].component_list, engs[0].bands)
+    specs = [(int(l), int(j), L.SIGNAL_KINDS.index(k) if isinstance(k, str) else int(k)) for l, j, k in specs]
+    for e in engs:
+        e.moments_signals(specs)
+    return specs
+
+
+def posterior_signal_maps(ddata, ddof=0, masked_value=None, engines=None):
+    """{(component label, band label, 'T' | 'Q' | 'U' | 'P'): {'mean', 'std', 'n'}} of the signals moments_signals registered, as
+    host arrays [npix].  Several contexts of this process: their shards side by side.  masked_value: as in posterior_maps."""
+    engs = _engines_of(ddata, engines)
+    regs = [getattr(e, "_moment_signals", None) for e in engs]
+    if regs[0] is None:
+        raise DangxError("posterior_signal_maps: moments_signals was not called")
+    if any(r != regs[0] for r in regs[1:]):
+        raise DangxError("posterior_signal_maps: the contexts hold different signal registrations")
+    counts = {e.moments_count() for e in engs}
+    if len(counts) != 1:
+        raise DangxError("posterior_signal_maps: the contexts hold different sample counts %s" % sorted(counts))
+    n = counts.pop()
+    comps, bands = engs[0].component_list, engs[0].bands
+    out = {}
+    for s, (l, j, kind) in enumerate(regs[0]):
+        entry = {"n": n}
+        for stat in ("mean", "std"):
+            parts = []
+            for e in engs:
+                m = e.moments_get_signal(s, stat, ddof)
+                parts.append(_mask_fill(m, e.ddata.masks, masked_value) if masked_value is not None else m)
+            entry[stat] = np.concatenate(parts, axis=-1) if len(parts) > 1 else parts[0]
+        out[(comps[l].label, bands[j].label, L.SIGNAL_KINDS[kind])] = entry
     return out
 
 

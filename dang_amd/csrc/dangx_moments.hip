@@ -29,14 +29,24 @@
 // registration) behind the moments': the thread that read a pixel's x loads, increments and stores the ONE 32-bit word holding the
 // bin -- no atomics, a pixel's record belongs to one thread -- and a sample outside the range touches no record.  k_hist_stat
 // reads a record as 16-byte pieces and leaves quantiles, the mode or the count of counted samples.  Nothing registered: no launch.
+//
+// dangx_moments_signals adds the moments of component signals at a band (definitions in dx_signal_host.h): the sample
+// comp_signal(band, pix, plane) = amplitude * sed(indices) of a diffuse component -- what write_maps' output_fg maps hold
+// (src/dang_data_mod.f90:596-617) -- and its polarised intensity P = sqrt(Q^2 + U^2), nonlinear in the sampled parameters and so not
+// derivable from their moments.  k_moments_signal is a launch of its own behind the others (blockIdx.y = segment: a component
+// and plane class with up to 8 bands): a thread reads a pixel's amplitude and index values once, prepares the SED once per plane
+// and updates the f64 mean / m2 planes of every registered output of every band of the segment.  Segments with an integrated
+// band go to a second launch of the kernel's BP form (the streaming form carries no bandpass code).  Nothing registered: no launch.
 #include "dx_host.h"
 #include "dx_moments_host.h"
 #include "dx_hist_host.h"
+#include "dx_signal_host.h"
 
 #include <cstdint>
 
 static_assert(DX_MOM_MAX_PAIRS == DANGX_MAX_PAIRS, "dx_moments_host.h and include/dangx.h disagree");
 static_assert(DX_HIST_MAX == DANGX_MAX_HIST, "dx_hist_host.h and include/dangx.h disagree");
+static_assert(DX_SIG_MAX == DANGX_MAX_SIGNALS, "dx_signal_host.h and include/dangx.h disagree");
 
 struct MomSeg {           // one selected plane: the chain's plane (resolved at accumulate time) and its two accumulators
     const double* x;
@@ -72,6 +82,25 @@ struct HistSeg {          // one registered histogram: the chain's plane (resolv
     int nbins, bits;
 };
 
+struct SigBand {          // one band of a signal segment: the accumulators of its outputs (slot 0..2: T, or Q, U, P), null = not wanted
+    double* mean[3];
+    double* m2[3];
+    int band;
+    unsigned want;        // bit o: output slot o is registered
+};
+
+struct SigSeg {           // a (component, plane class) with up to DX_SIG_SEG_BANDS bands; the chain's planes resolved at accumulate time
+    const double* amp;    // the component's [nmaps][npix]: what the table is compared by
+    const double* idx;    // the component's [nind][nmaps][npix]
+    // src[k][0..2]: the amplitude and the two index planes of plane k of the class.  A plane the component does not have (an index
+    // beyond nindices) or no output needs points at a plane that IS read: the load hits the cache and its value is never used
+    const double* src[2][3];
+    long long n;
+    int comp, k0, np, nb; // k0: first plane (1-based) of the class, np: planes of the class (1: T, 2: Q+U)
+    int vec, nind;        // nind: indices of the component (load_theta: an index beyond it is 0.0).  vec 0: element by element; 1 / 2: pairs of pixels, every plane read and every accumulator at 16-byte phase 0 / 8
+    SigBand b[DX_SIG_SEG_BANDS];
+};
+
 struct DxMoments {
     int32_t sel[MAXC] = {};          // effective selection (bits as in include/dangx.h)
     int type[MAXC] = {}, nind[MAXC] = {};  // shape key recorded at begin
@@ -102,6 +131,16 @@ struct DxMoments {
     HistSeg* d_hist = nullptr;
     double* hscratch = nullptr;      // what the host form of the read-out copies from
     size_t hscratch_bytes = 0;
+    // dangx_moments_signals
+    struct Sig { int comp, band, kind; long long off; };   // off: the signal's mean plane in sacc (its m2 plane: + sacc_half)
+    std::vector<Sig> sigs;
+    std::vector<DxSigSeg> sig_plan;
+    int sig_type[MAXC] = {}, sig_nind[MAXC] = {};   // shape key of the registered components at registration
+    bool sig_used[MAXC] = {};
+    std::vector<SigSeg> sig_table;   // the table as last uploaded
+    SigSeg* d_sig = nullptr;
+    double* sacc = nullptr;          // [mean: sacc_half doubles | m2: sacc_half doubles]
+    long long sacc_half = 0;
 };
 
 namespace {
@@ -279,6 +318,118 @@ __global__ __launch_bounds__(BLOCK) void k_moments_hist(const HistSeg* __restric
     }
 }
 
+typedef const SigSeg __attribute__((address_space(4))) * sig_kptr;   // the segment table through the scalar cache (dx_sed.h: kptr)
+
+// comp_sed for a registered signal.  Registration refuses the global-amplitude types, and the host puts a segment into the
+// launch of k_moments_signal<false> only when every band of it is a delta bandpass: told so, the compiler drops the template
+// and bandpass-integrated forms from the streaming kernel.  The expressions evaluated are comp_sed's in both kernels.
+template <bool BP>
+__device__ __forceinline__ double sig_sed(const Model& M, const Comp& c, int i, int k, int j, const Prep& p) {
+    __builtin_assume(c.type >= DANGX_POWERLAW && c.type <= DANGX_TCMB);
+    if (!BP) __builtin_assume(M.band[j].n == 0);
+    return comp_sed(M, c, i, k, j, p);
+}
+
+// v[e] of four values for a wave-uniform e: explicit selects, so that the register arrays below are never indexed dynamically
+__device__ __forceinline__ double sel4(int e, double v0, double v1, double v2, double v3) {
+    return e == 0 ? v0 : e == 1 ? v1 : e == 2 ? v2 : v3;
+}
+__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }   // a wave-uniform value kept in a VGPR
+__device__ __forceinline__ void put4(int e, double (&v)[4], double x) {
+    v[0] = e == 0 ? x : v[0]; v[1] = e == 1 ? x : v[1]; v[2] = e == 2 ? x : v[2]; v[3] = e == 3 ? x : v[3];
+}
+
+// blockIdx.y = segment.  One sample of every registered signal: Welford's update of k_moments_accum on x = eval_signal.
+// The blocks of a segment stride over its items: pairs of pixels (16-byte accesses) where every plane read and every accumulator
+// share their 16-byte phase (vec), the odd first / last element alone; element by element otherwise.  An item holds up to four
+// evaluation slots e = 2 * (plane of the class) + (half of the pair); every slot goes through the SAME code (the loops over e:
+// one copy of sed_prep and comp_sed in the kernel), so a result does not depend on which kind of item held its pixel.
+template <bool BP>
+__global__ __launch_bounds__(BLOCK) void k_moments_signal(const Model* __restrict__ Mp, const SigSeg* __restrict__ segs, double inv_n) {
+    const Model& M = *Mp;
+    const sig_kptr s = reinterpret_cast<sig_kptr>(reinterpret_cast<uintptr_t>(segs + blockIdx.y));
+    const Comp& c = M.comp[s->comp];
+    const long long n = s->n;
+    const long long gid = (long long)blockIdx.x * BLOCK + threadIdx.x, stride = (long long)gridDim.x * BLOCK;
+    const int vec = BP ? 0 : s->vec;   // segments with an integrated band: issue bound, element by element
+    const long long head = (vec == 2 && n > 0) ? 1 : 0;
+    const long long npair = vec ? (n - head) / 2 : 0, tail = head + 2 * npair;   // tail < n: one element after the last pair
+    const long long nitems = vec ? npair + head + (tail < n ? 1 : 0) : n;
+    // The scalar register file belongs to the SED's band constants (comp_sed alone takes ~95 SGPRs): everything wave-uniform of this
+    // kernel's own is parked in vector registers -- the segment's pointers, counts and the band records are read with vector loads
+    // through sv -- and comes back through uni() for the few uses that need a scalar (loop bounds, the band index).
+    int k0 = s->k0, np2 = 2 * s->np, nb = s->nb, nind = s->nind, estep = vec ? 1 : 2;   // estep: the odd slots of an element-by-element item are not evaluated
+    long long item_stride = stride, item_end = nitems, pair_end = npair, i_head = head, i_tail = tail;
+    const double *pa0 = s->src[0][0], *pt00 = s->src[0][1], *pt01 = s->src[0][2];
+    const double *pa1 = s->src[1][0], *pt10 = s->src[1][1], *pt11 = s->src[1][2];
+    const SigBand* sv = segs[blockIdx.y].b;
+    asm volatile("" : "+v"(item_stride), "+v"(item_end), "+v"(pair_end), "+v"(i_head), "+v"(i_tail), "+v"(inv_n));
+    asm volatile("" : "+v"(pa0), "+v"(pt00), "+v"(pt01), "+v"(pa1), "+v"(pt10), "+v"(pt11), "+v"(sv));
+    asm volatile("" : "+v"(k0), "+v"(np2), "+v"(nb), "+v"(nind), "+v"(estep));
+    for (long long t = gid; t < item_end; t += item_stride) {
+        const bool single = t >= pair_end;
+        const long long i = !single ? i_head + 2 * t : !vec ? t : (t == pair_end && i_head) ? 0 : i_tail;   // the item's first pixel
+        double a[4] = {0.0, 0.0, 0.0, 0.0}, t0[4] = {0.0, 0.0, 0.0, 0.0}, t1[4] = {0.0, 0.0, 0.0, 0.0};
+        if (single) {
+            a[0] = pa0[i]; t0[0] = pt00[i]; t1[0] = pt01[i];
+            if (np2 == 4) { a[2] = pa1[i]; t0[2] = pt10[i]; t1[2] = pt11[i]; }
+        } else {
+            dbl2 v = *(const GD2*)(pa0 + i); a[0] = v.x; a[1] = v.y;
+            v = *(const GD2*)(pt00 + i); t0[0] = v.x; t0[1] = v.y;
+            v = *(const GD2*)(pt01 + i); t1[0] = v.x; t1[1] = v.y;
+            if (np2 == 4) {
+                v = *(const GD2*)(pa1 + i); a[2] = v.x; a[3] = v.y;
+                v = *(const GD2*)(pt10 + i); t0[2] = v.x; t0[3] = v.y;
+                v = *(const GD2*)(pt11 + i); t1[2] = v.x; t1[3] = v.y;
+            }
+        }
+        double q0[4] = {0.0, 0.0, 0.0, 0.0}, q1[4] = {0.0, 0.0, 0.0, 0.0}, q2[4] = {0.0, 0.0, 0.0, 0.0};   // the slots' Prep
+#pragma nounroll
+        for (int e = 0; e < uni(np2); e += uni(estep)) {
+            // load_theta's values: an index the component does not have is 0.0 (its slot was loaded from a plane that is read anyway)
+            const Prep pr = sed_prep(c, nind > 0 ? sel4(e, t0[0], t0[1], t0[2], t0[3]) : 0.0, nind > 1 ? sel4(e, t1[0], t1[1], t1[2], t1[3]) : 0.0);
+            put4(e, q0, pr.p0); put4(e, q1, pr.p1); put4(e, q2, pr.p2);
+        }
+        for (int b = 0; b < uni(nb); ++b) {
+            const unsigned want = sv[b].want;
+            const int band = uni(sv[b].band);
+            const unsigned planes = (want & 4u) ? 3u : want & 3u;   // P needs both
+            double x[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma nounroll
+            for (int e = 0; e < uni(np2); e += uni(estep)) {
+                if (!uni((int)((planes >> (e >> 1)) & 1u))) continue;
+                const Prep pr = {sel4(e, q0[0], q0[1], q0[2], q0[3]), sel4(e, q1[0], q1[1], q1[2], q1[3]), sel4(e, q2[0], q2[1], q2[2], q2[3])};
+                const double sed = sig_sed<BP>(M, c, (int)i + (single ? 0 : (e & 1)), uni(k0) + (e >> 1), band, pr);   // never a pixel past the item
+                // eval_signal: the bare SED for T_cmb, else the ROUNDED product amplitude * sed
+                put4(e, x, (c.type == DANGX_TCMB) ? sed : dx_signal_product(sel4(e, a[0], a[1], a[2], a[3]), sed));
+            }
+            double pol[2] = {0.0, 0.0};
+            if (want & 4u) {
+                pol[0] = dx_signal_pol(x[0], x[2]);
+                pol[1] = dx_signal_pol(x[1], x[3]);
+            }
+#pragma unroll
+            for (int o = 0; o < 3; ++o) {
+                if (!((want >> o) & 1u)) continue;
+                const double y0 = o == 0 ? x[0] : o == 1 ? x[2] : pol[0], y1 = o == 0 ? x[1] : o == 1 ? x[3] : pol[1];
+                double* mp = sv[b].mean[o] + i;
+                double* qp = sv[b].m2[o] + i;
+                if (single) {
+                    double m = *mp, q = *qp;
+                    welford(y0, m, q, inv_n);
+                    *mp = m; *qp = q;
+                } else {
+                    const dbl2 m = *(GD2*)mp, q = *(GD2*)qp;
+                    double m0 = m.x, m1 = m.y, r0 = q.x, r1 = q.y;
+                    welford(y0, m0, r0, inv_n);
+                    welford(y1, m1, r1, inv_n);
+                    *(GD2*)mp = dbl2{m0, m1}; *(GD2*)qp = dbl2{r0, r1};
+                }
+            }
+        }
+    }
+}
+
 struct HistStatArgs {
     const uint32_t* rec;
     double q[DX_HIST_MAX_Q];   // the quantile levels (stat 0), by value: nothing of the caller's is read after the call returns
@@ -410,6 +561,8 @@ void release(DxMoments* m) {
     if (m->hrec) (void)hipFree(m->hrec);
     if (m->d_hist) (void)hipFree(m->d_hist);
     if (m->hscratch) (void)hipFree(m->hscratch);
+    if (m->d_sig) (void)hipFree(m->d_sig);
+    if (m->sacc) (void)hipFree(m->sacc);
     delete m;
 }
 
@@ -476,6 +629,89 @@ int finish(dangx_ctx* ctx, int comp, int what, int stat, int ddof, unsigned plan
     const unsigned gx = std::max(1u, std::min(nblocks(a.n), 1024u));
     hipLaunchKernelGGL(k_moments_finish, dim3(gx, np), dim3(BLOCK), 0, ctx->stream, a);
     HIPCHK(ctx, hipGetLastError());
+    return 0;
+}
+
+// first plane (1-based) and plane count of a class
+inline int sig_k0(int cls) { return cls == 0 ? 1 : 2; }
+
+// the device table of the registered signals for the chain's planes as they are now
+size_t sig_table(const dangx_ctx* ctx, const DxMoments* m, std::vector<SigSeg>& t) {
+    const long long np = ctx->dims.npix;
+    const int nmaps = ctx->dims.nmaps;
+    t.clear();
+    size_t ndelta = 0;   // delta-band segments first (k_moments_signal<false>), then those with an integrated band
+    for (int pass = 0; pass < 2; ++pass)
+    for (const DxSigSeg& ps : m->sig_plan) {
+        bool bp = false;
+        for (int b = 0; b < ps.nb; ++b) bp = bp || ctx->hm.band[ps.b[b].band].n != 0;
+        if (bp != (pass == 1)) continue;
+        if (!bp) ++ndelta;
+        SigSeg s;
+        std::memset(&s, 0, sizeof s);   // the tables are compared as bytes
+        s.amp = ctx->amp[ps.comp];
+        s.idx = ctx->idx[ps.comp];
+        s.n = np;
+        s.comp = ps.comp; s.k0 = sig_k0(ps.cls); s.np = ps.cls == 0 ? 1 : 2; s.nb = ps.nb;
+        s.nind = ctx->desc[ps.comp].nindices;
+        uintptr_t phase = 0, diff = 0;   // diff: bit 3 set when two addresses differ in their 16-byte phase
+        bool first = true;
+        auto see = [&](const double* q) {
+            const uintptr_t a = reinterpret_cast<uintptr_t>(q);
+            if (first) { phase = a; first = false; }
+            diff |= (a ^ phase) & 15;
+        };
+        unsigned needp = 0;              // bit k: an output of some band needs plane k0 + k
+        for (int b = 0; b < ps.nb; ++b) {
+            SigBand& sb = s.b[b];
+            sb.band = ps.b[b].band;
+            for (int o = 0; o < 3; ++o) {
+                const int sg = ps.b[b].sig[o];
+                if (sg < 0) continue;
+                sb.want |= 1u << o;
+                sb.mean[o] = m->sacc + m->sigs[sg].off;
+                sb.m2[o] = m->sacc + m->sacc_half + m->sigs[sg].off;
+                see(sb.mean[o]); see(sb.m2[o]);
+                needp |= (o == 2) ? 3u : 1u << o;
+            }
+        }
+        const double* fallback = s.amp + (long long)(s.k0 - 1 + ((needp & 1u) ? 0 : 1)) * np;   // an amplitude plane that is read
+        for (int k = 0; k < 2; ++k) {
+            const long long plane = s.k0 - 1 + k;
+            const bool read = k < s.np && ((needp >> k) & 1u);
+            for (int q = 0; q < 3; ++q) {
+                const bool has = read && (q == 0 || q - 1 < ctx->desc[ps.comp].nindices);
+                s.src[k][q] = !has ? fallback : q == 0 ? s.amp + plane * np : s.idx + ((long long)(q - 1) * nmaps + plane) * np;
+                see(s.src[k][q]);
+            }
+        }
+        s.vec = diff ? 0 : ((phase & 15) ? 2 : 1);
+        t.push_back(s);
+    }
+    return ndelta;
+}
+
+// finish of one plane pair (mean, m2) into dst [npix]
+int finish_plane(dangx_ctx* ctx, const double* mean, const double* m2, int stat, double dn, double* dst) {
+    FinishArgs a{};
+    a.mean[0] = mean; a.m2[0] = m2; a.out[0] = dst;
+    a.n = ctx->dims.npix;
+    a.stat = stat;
+    a.dn = dn;
+    const unsigned gx = std::max(1u, std::min(nblocks(a.n), 1024u));
+    hipLaunchKernelGGL(k_moments_finish, dim3(gx, 1), dim3(BLOCK), 0, ctx->stream, a);
+    HIPCHK(ctx, hipGetLastError());
+    return 0;
+}
+
+int signal_get_check(dangx_ctx* ctx, int sig, int stat, int ddof) {
+    if (need(ctx)) return 1;
+    const DxMoments* m = ctx->mom;
+    if (sig < 0 || sig >= (int)m->sigs.size())
+        return fail(ctx, "posterior moments: signal index out of range (" + std::to_string(m->sigs.size()) + " signals registered)");
+    if (stat != 0 && stat != 1) return fail(ctx, "posterior moments: the stat of a signal must be 0 (mean) or 1 (standard deviation)");
+    if (m->count == 0) return fail(ctx, "posterior moments: no sample accumulated");
+    if (stat == 1 && (ddof < 0 || m->count - ddof <= 0)) return fail(ctx, "posterior moments: standard deviation needs 0 <= ddof < n");
     return 0;
 }
 
@@ -619,12 +855,16 @@ int dangx_moments_accumulate(dangx_ctx* ctx) {
     for (int l = 0; l < ctx->dims.ncomp; ++l)
         if (m->sel[l] && (!ctx->comp_set[l] || ctx->desc[l].type != m->type[l] || ctx->desc[l].nindices != m->nind[l]))
             return fail(ctx, "posterior moments: component " + std::to_string(l) + " changed type or nindices since dangx_moments_begin");
+    for (int l = 0; l < ctx->dims.ncomp; ++l)
+        if (m->sig_used[l] && (!ctx->comp_set[l] || ctx->desc[l].type != m->sig_type[l] || ctx->desc[l].nindices != m->sig_nind[l]))
+            return fail(ctx, "posterior moments: component " + std::to_string(l) + " changed type or nindices since dangx_moments_signals");
     if (ctx->have_pending) return fail(ctx, "posterior moments: an amplitude solve is still pending");   // not at a call boundary
     if (!m->hists.empty()) {   // no counter ever wraps: refused before anything is touched
         const std::string why = dx_hist_limit_check(m->count + 1, m->hbits);
         if (!why.empty()) return fail(ctx, "posterior moments: dangx_moments_accumulate: " + why);
     }
     (void)hipSetDevice(ctx->device);
+    if (!m->sigs.empty() && sync_model(ctx)) return 1;   // the SEDs read the device model: current before anything is launched
     const double inv_n = 1.0 / (double)(m->count + 1);
     if (!m->segs.empty()) {
         std::vector<MomSeg> t(m->segs.size());
@@ -686,6 +926,33 @@ int dangx_moments_accumulate(dangx_ctx* ctx) {
         Timed tm(ctx, DANGX_K_HIST);
         hipLaunchKernelGGL(k_moments_hist, dim3(gx, nreg), dim3(BLOCK), 0, ctx->stream, (const HistSeg*)m->d_hist);
         HIPCHK(ctx, hipGetLastError());
+    }
+    if (!m->sigs.empty()) {   // the component signals: a launch of their own, independent of everything above
+        std::vector<SigSeg> t;
+        const size_t ndelta = sig_table(ctx, m, t);
+        const bool same = t.size() == m->sig_table.size() && std::memcmp(t.data(), m->sig_table.data(), sizeof(SigSeg) * t.size()) == 0;
+        if (!same) {   // first accumulation, a component's buffers adopted again or a band's bandpass replaced: one upload (and a host wait)
+            HIPCHK(ctx, hipMemcpyAsync(m->d_sig, t.data(), sizeof(SigSeg) * t.size(), hipMemcpyHostToDevice, ctx->stream));
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+            m->sig_table = t;
+        }
+        const long long pairs = (ctx->dims.npix + 1) / 2;
+        if (ndelta) {
+            const unsigned nseg = (unsigned)ndelta;
+            const unsigned gx = std::max(1u, std::min(nblocks(pairs), (m->grid_target + nseg - 1) / nseg));
+            Timed tm(ctx, DANGX_K_SIGNAL);
+            hipLaunchKernelGGL(k_moments_signal<false>, dim3(gx, nseg), dim3(BLOCK), 0, ctx->stream, (const Model*)ctx->dm,
+                               (const SigSeg*)m->d_sig, inv_n);
+            HIPCHK(ctx, hipGetLastError());
+        }
+        if (t.size() > ndelta) {   // segments with an integrated band: element by element
+            const unsigned nseg = (unsigned)(t.size() - ndelta);
+            const unsigned gx = std::max(1u, std::min(nblocks(ctx->dims.npix), (m->grid_target + nseg - 1) / nseg));
+            Timed tm(ctx, DANGX_K_SIGNAL, 2);   // the profile tells the two forms apart by this mark
+            hipLaunchKernelGGL(k_moments_signal<true>, dim3(gx, nseg), dim3(BLOCK), 0, ctx->stream, (const Model*)ctx->dm,
+                               (const SigSeg*)(m->d_sig + ndelta), inv_n);
+            HIPCHK(ctx, hipGetLastError());
+        }
     }
     for (int l = 0; l < ctx->dims.ncomp; ++l) {
         if (!m->sel[l] || !is_global_type(ctx->desc[l].type)) continue;
@@ -934,6 +1201,88 @@ int dangx_moments_hist_stat(dangx_ctx* ctx, int reg, int stat, int nq, const dou
     }
     if (dangx_moments_hist_stat_dev(ctx, reg, stat, nq, q, m->hscratch)) return 1;
     HIPCHK(ctx, hipMemcpyAsync(out, m->hscratch, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+int dangx_moments_signals(dangx_ctx* ctx, int nsig, const int32_t* spec) {
+    if (!ctx || need(ctx)) return 1;
+    DxMoments* m = ctx->mom;
+    if (m->count != 0)
+        return fail(ctx, "posterior moments: dangx_moments_signals is legal only before the first dangx_moments_accumulate after dangx_moments_begin");
+    const int ncomp = ctx->dims.ncomp, nmaps = ctx->dims.nmaps;
+    int set[MAXC] = {}, global[MAXC] = {};
+    for (int l = 0; l < ncomp; ++l) {
+        set[l] = ctx->comp_set[l] ? 1 : 0;
+        global[l] = is_global_type(ctx->desc[l].type) ? 1 : 0;
+    }
+    const std::string why = dx_signal_check(nsig, spec, ncomp, ctx->dims.nbands, nmaps, set, global);
+    if (!why.empty()) return fail(ctx, "posterior moments: dangx_moments_signals: " + why);
+    (void)hipSetDevice(ctx->device);
+    bool used[MAXC] = {};
+    for (int s = 0; s < nsig; ++s) used[spec[3 * s]] = true;
+    for (int l = 0; l < ncomp; ++l)   // the chain's maps exist from here on (what dangx_get_amplitude does on first use)
+        if (used[l] && ensure_state(ctx, l)) return 1;
+    const std::vector<DxSigSeg> plan = dx_signal_plan(nsig, spec, ncomp, ctx->dims.nbands);
+    // accumulators: every signal's planes at the 16-byte phase of the first plane of its class, so that the streams line up
+    std::vector<DxMoments::Sig> ns;
+    long long off = 0;
+    for (int s = 0; s < nsig; ++s) {
+        DxMoments::Sig sg{spec[3 * s], spec[3 * s + 1], spec[3 * s + 2], 0};
+        const double* plane = ctx->amp[sg.comp] + (long long)(sig_k0(dx_signal_class(sg.kind)) - 1) * ctx->dims.npix;
+        const long long phase = (long long)((reinterpret_cast<uintptr_t>(plane) >> 3) & 1);
+        if ((off & 1) != phase) ++off;
+        sg.off = off;
+        off += ctx->dims.npix;
+        ns.push_back(sg);
+    }
+    const long long half = off + (off & 1);   // even: the m2 half has the phases of the mean half
+    // everything new is allocated before anything old is dropped: a failure leaves the registration as it was
+    double* sacc = nullptr;
+    SigSeg* d_sig = nullptr;
+    auto bail = [&](hipError_t e, const char* what) {
+        ctx->err = std::string("posterior moments: dangx_moments_signals: ") + what + ": " + hipGetErrorString(e);
+        if (sacc) (void)hipFree(sacc);
+        if (d_sig) (void)hipFree(d_sig);
+        return 1;
+    };
+    hipError_t e;
+    if (!ns.empty()) {
+        if ((e = hipMalloc(&sacc, sizeof(double) * 2 * (size_t)half)) != hipSuccess) return bail(e, "hipMalloc");
+        if ((e = hipMemsetAsync(sacc, 0, sizeof(double) * 2 * (size_t)half, ctx->stream)) != hipSuccess) return bail(e, "hipMemsetAsync");
+        if ((e = hipMalloc(&d_sig, sizeof(SigSeg) * plan.size())) != hipSuccess) return bail(e, "hipMalloc");
+        if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return bail(e, "hipStreamSynchronize");
+    }
+    if (m->sacc) (void)hipFree(m->sacc);
+    if (m->d_sig) (void)hipFree(m->d_sig);
+    m->sacc = sacc; m->d_sig = d_sig; m->sacc_half = half;
+    m->sigs = ns;
+    m->sig_plan = plan;
+    m->sig_table.clear();   // the next accumulation uploads the table
+    for (int l = 0; l < MAXC; ++l) {
+        m->sig_used[l] = l < ncomp && used[l];
+        m->sig_type[l] = m->sig_used[l] ? ctx->desc[l].type : 0;
+        m->sig_nind[l] = m->sig_used[l] ? ctx->desc[l].nindices : 0;
+    }
+    return 0;
+}
+
+int dangx_moments_get_signal_dev(dangx_ctx* ctx, int sig, int stat, int ddof, double* out_dev) {
+    if (!ctx || !out_dev || signal_get_check(ctx, sig, stat, ddof)) return 1;
+    DxMoments* m = ctx->mom;
+    (void)hipSetDevice(ctx->device);
+    const long long off = m->sigs[sig].off;
+    return finish_plane(ctx, m->sacc + off, m->sacc + m->sacc_half + off, stat, (double)(m->count - ddof), out_dev);
+}
+
+int dangx_moments_get_signal(dangx_ctx* ctx, int sig, int stat, int ddof, double* out) {
+    if (!ctx || !out || signal_get_check(ctx, sig, stat, ddof)) return 1;   // before anything is allocated
+    DxMoments* m = ctx->mom;
+    (void)hipSetDevice(ctx->device);
+    const long long np = ctx->dims.npix;
+    if (!m->scratch) HIPCHK(ctx, hipMalloc(&m->scratch, sizeof(double) * (size_t)np * ctx->dims.nmaps));
+    if (dangx_moments_get_signal_dev(ctx, sig, stat, ddof, m->scratch)) return 1;
+    HIPCHK(ctx, hipMemcpyAsync(out, m->scratch, sizeof(double) * (size_t)np, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return 0;
 }

@@ -594,6 +594,25 @@ module dangx_mod
        type(c_ptr), value :: ctx, q, out_dev
        integer(c_int), value :: reg, stat, nq
      end function
+     ! moments of component signals at a band (eval_signal(band, pix, map) = amplitude * sed, what write_maps' output_fg maps hold):
+     ! spec(3, nsig) = (comp, band, kind), 0-based as in C; kind 0, 1, 2 = plane T, Q, U, 3 = P = sqrt(Q**2 + U**2) (nmaps == 3).
+     ! Only between dangx_moments_begin and the first dangx_moments_accumulate; template / monopole / hi_fit members are refused.
+     integer(c_int) function dangx_moments_signals(ctx, nsig, spec) bind(C, name='dangx_moments_signals')
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx, spec              ! spec: integer(c_int32_t)(3, nsig) or c_null_ptr
+       integer(c_int), value :: nsig
+     end function
+     ! sig: 0-based; stat: 0 = mean, 1 = std with ddof; out: (0:npix-1) of this shard
+     integer(c_int) function dangx_moments_get_signal(ctx, sig, stat, ddof, out) bind(C, name='dangx_moments_get_signal')
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx, out
+       integer(c_int), value :: sig, stat, ddof
+     end function
+     integer(c_int) function dangx_moments_get_signal_dev(ctx, sig, stat, ddof, out_dev) bind(C, name='dangx_moments_get_signal_dev')
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx, out_dev
+       integer(c_int), value :: sig, stat, ddof
+     end function
      integer(c_int) function dangx_moments_end(ctx) bind(C, name='dangx_moments_end')
        import :: c_int, c_ptr
        type(c_ptr), value :: ctx

@@ -331,6 +331,33 @@ contains
     end do
   end subroutine dangx_sky_moments_hist_get
 
+  ! moments of component signals spec(3, nsig) = (comp, band, kind), 0-based as in include/dangx.h, on every context: after
+  ! dangx_sky_moments_begin, before the first accumulate
+  subroutine dangx_sky_moments_signals(sky, nsig, spec)
+    type(dangx_sky), intent(in) :: sky
+    integer, intent(in) :: nsig
+    integer(c_int32_t), intent(in), target :: spec(:,:)
+    type(c_ptr) :: p
+    integer :: r
+    p = c_null_ptr
+    if (nsig > 0) p = c_loc(spec)
+    do r = 1, sky%nctx
+       call dangx_check(sky%ctx(r), dangx_moments_signals(sky%ctx(r), nsig, p), 'dangx_moments_signals')
+    end do
+  end subroutine dangx_sky_moments_signals
+
+  ! sig: 0-based; stat 0 = mean, 1 = standard deviation with ddof; out: c_loc of a full-sky (0:npix-1) array, every context fills
+  ! its pixel range
+  subroutine dangx_sky_moments_get_signal(sky, sig, stat, ddof, out)
+    type(dangx_sky), intent(in) :: sky
+    integer, intent(in) :: sig, stat, ddof
+    type(c_ptr), intent(in) :: out
+    integer :: r
+    do r = 1, sky%nctx
+       call dangx_check(sky%ctx(r), dangx_moments_get_signal(sky%ctx(r), sig, stat, ddof, at_pix(out, sky%pix0(r))), 'dangx_moments_get_signal')
+    end do
+  end subroutine dangx_sky_moments_get_signal
+
   function dangx_sky_moments_count(sky) result(n)
     type(dangx_sky), intent(in) :: sky
     integer(c_int64_t) :: n, m

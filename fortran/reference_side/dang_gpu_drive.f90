@@ -24,6 +24,9 @@
 ! DANG_POSTERIOR_HIST=<nbins> beside DANG_POSTERIOR: posterior_hist_gpu(dpar, nbins, 16) after posterior_begin_gpu, and behind
 ! everything above the number of registrations and, per registration, the 0.16 / 0.5 / 0.84 quantile maps and the counted
 ! samples N.  Without it the result file keeps its length to the byte.
+! DANG_POSTERIOR_SIGNAL=1 beside DANG_POSTERIOR: posterior_signal_gpu(dpar) after posterior_begin_gpu, and behind everything else the
+! number of signals and per signal its (comp, band, kind), its mean and its standard deviation (ddof 0).  Without it the result
+! file is what the other switches give.
 subroutine mpi_allreduce(sendbuf, recvbuf, count, datatype, op, comm, ierror)
   ! the wrapper's MPI branch is never taken here (numprocs = 1); the symbol only has to exist
   integer :: sendbuf, recvbuf(*), count, datatype, op, comm, ierror
@@ -57,9 +60,9 @@ program dang_gpu_drive
   character(len=512) :: fin, fout, arg, mode
   integer :: u, i, j, l, k, npix0, niter, ngroups, nctx, tile, t, it_first
   integer :: post_burn, post_thin, post_len, post_stat
-  logical :: post, post_pairs, post_hist
+  logical :: post, post_pairs, post_hist, post_sig
   integer :: hist_bins
-  real(c_double), allocatable :: pair_map(:), q_map(:,:), n_map(:)
+  real(c_double), allocatable :: pair_map(:), q_map(:,:), n_map(:), sig_map(:)
   integer(i8b) :: c0, c1, crate
   real(dp) :: secs
 
@@ -171,6 +174,9 @@ program dang_gpu_drive
      read(arg(1:post_len), *) hist_bins
      call posterior_hist_gpu(dpar, hist_bins, 16)
   end if
+  call get_environment_variable('DANG_POSTERIOR_SIGNAL', arg, post_len)
+  post_sig = post .and. post_len > 0
+  if (post_sig) call posterior_signal_gpu(dpar)
   secs = 0.d0; it_first = 3
   do iter = 1, niter
      if (iter == it_first + 1) then                       ! time iterations it_first+1 .. niter: the first two full ones warm up (index maps that start spatially constant take the generic launches once, kernels specialised at run time are compiled on first use)
@@ -243,6 +249,17 @@ program dang_gpu_drive
            call posterior_quantile_to_host_gpu(i, [0.16d0, 0.5d0, 0.84d0], q_map)
            call posterior_hist_n_to_host_gpu(i, n_map)
            write(u) q_map, n_map
+        end do
+     end if
+     if (post_sig) then
+        write(u) real(gpu_post_nsig, c_double)
+        allocate(sig_map(0:npix-1))
+        do i = 1, gpu_post_nsig
+           write(u) real(gpu_post_sig(:, i), c_double)
+           call posterior_signal_to_host_gpu(i, 0, 0, sig_map)
+           write(u) sig_map
+           call posterior_signal_to_host_gpu(i, 1, 0, sig_map)
+           write(u) sig_map
         end do
      end if
   end if

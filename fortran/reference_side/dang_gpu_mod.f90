@@ -42,6 +42,8 @@ module dang_gpu_mod
   integer(i4b) :: gpu_post_npairs = 0
   integer(c_int32_t), allocatable, target :: gpu_post_hist(:,:)    ! posterior_hist_gpu's planes (3, gpu_post_nhist), 0-based as in C
   integer(i4b) :: gpu_post_nhist = 0
+  integer(c_int32_t), allocatable, target :: gpu_post_sig(:,:)     ! posterior_signal_gpu's signals (3, gpu_post_nsig) = (comp, band, kind), 0-based as in C
+  integer(i4b) :: gpu_post_nsig = 0
 
 contains
 
@@ -727,6 +729,7 @@ contains
     call dangx_sky_moments_begin(gpu_sky, gpu_post_sel)
     gpu_post_npairs = 0
     gpu_post_nhist = 0
+    gpu_post_nsig = 0
   end subroutine posterior_begin_gpu
 
   ! after posterior_begin_gpu, before the first posterior_accumulate_gpu that takes a sample: the second-order summaries.  lag1:
@@ -870,6 +873,78 @@ contains
     call rank_window(w, 1, .false.)
     out(0:npix-1) = w(:, 1)
   end subroutine posterior_hist_n_to_host_gpu
+
+  ! after posterior_begin_gpu, before the first posterior_accumulate_gpu that takes a sample: mean and standard deviation of the
+  ! component signals c%eval_signal(band, pix, map) (what write_maps' output_fg maps hold) -- as dang_amd.api.default_signal_specs:
+  ! every component that is no template / monopole / hi_fit, whose amplitude is sampled and that has at least one sampled index,
+  ! at the band whose nu_c is nearest its nu_ref (the lowest band on ties), on every plane posterior_begin_gpu selected for its
+  ! amplitude, plus P = sqrt(Q**2 + U**2) (kind 3) when both Q and U are.  Component order, then kind.  Read with
+  ! posterior_signal_to_host_gpu (sig = 1 .. gpu_post_nsig).
+  subroutine posterior_signal_gpu(dpar)
+    type(dang_params) :: dpar
+    type(dang_comps), pointer :: cc
+    integer(i4b) :: i, j, k, n, pass, band, w
+    real(dp) :: ref, nu, d, dbest
+    if (.not. allocated(gpu_post_sel)) then
+       write(*,*) 'posterior_signal_gpu: posterior_begin_gpu was not called'
+       stop 1
+    end if
+    do pass = 1, 2                                    ! count, then fill
+       n = 0
+       do i = 1, ncomp
+          cc => component_list(i)%p
+          if (trim(cc%type) == 'template' .or. trim(cc%type) == 'monopole' .or. trim(cc%type) == 'hi_fit') cycle
+          if (.not. cc%sample_amplitude) cycle
+          if (cc%nindices < 1) cycle
+          if (.not. any(cc%sample_index(1:cc%nindices))) cycle
+          w = iand(gpu_post_sel(i), 7)
+          if (w == 0) cycle
+          ref = cc%nu_ref
+          if (ref < 1.d7) ref = ref*1.d9             ! Hz, src/dang_param_mod.f90:571-573
+          band = 1; dbest = huge(1.d0)
+          do j = 1, nbands
+             nu = bp(j)%nu_c
+             if (nu < 1.d9) nu = nu*1.d9             ! Hz, src/dang_bp_mod.f90:35-37
+             d = abs(nu - ref)
+             if (d < dbest) then
+                dbest = d; band = j
+             end if
+          end do
+          do k = 0, 3
+             if (k < 3) then
+                if (.not. btest(w, k)) cycle
+             else
+                if (iand(w, 6) /= 6) cycle
+             end if
+             n = n + 1
+             if (pass == 2) gpu_post_sig(:, n) = int([i-1, band-1, k], c_int32_t)
+          end do
+       end do
+       if (pass == 1) then
+          if (allocated(gpu_post_sig)) deallocate(gpu_post_sig)
+          allocate(gpu_post_sig(3, max(n, 1))); gpu_post_sig = 0
+       end if
+    end do
+    gpu_post_nsig = n
+    call dangx_sky_moments_signals(gpu_sky, n, gpu_post_sig)
+  end subroutine posterior_signal_gpu
+
+  ! mean (stat = 0) or standard deviation (stat = 1, with ddof) map of signal `sig` (1-based, posterior_signal_gpu's order) into
+  ! out(0:npix-1); under MPI every rank fills its pixel range and the ranges are merged as rank_window merges a plane
+  subroutine posterior_signal_to_host_gpu(sig, stat, ddof, out)
+    integer(i4b), intent(in) :: sig, stat, ddof
+    real(dp), intent(inout), target :: out(0:)
+    real(dp), allocatable, target :: w(:,:)
+    if (sig < 1 .or. sig > gpu_post_nsig) then
+       write(*,*) 'posterior_signal_to_host_gpu: signal out of range', sig, gpu_post_nsig
+       stop 1
+    end if
+    allocate(w(0:npix-1, 1))
+    call rank_window(w, 1, .true.)
+    call dangx_sky_moments_get_signal(gpu_sky, sig - 1, stat, ddof, c_loc(w))
+    call rank_window(w, 1, .false.)
+    out(0:npix-1) = w(:, 1)
+  end subroutine posterior_signal_to_host_gpu
 
   ! after write_data_gpu in the loop: one sample of the current state, every thin-th iteration after burn_in.  Enqueued on every
   ! context's stream behind the iteration's launches: the host does not wait

@@ -74,7 +74,8 @@ enum { DANGX_COARSE_REFERENCE = 0, DANGX_COARSE_DEGRADED = 1 };
 /* kernel ids for dangx_profile_get / dangx_profile_get_planes */
 enum {
     DANGX_K_AMP_DIRECT = 0, DANGX_K_INDEX_MH = 1, DANGX_K_SKY_CHISQ = 2, DANGX_K_REDUCE = 3,
-    DANGX_K_CG_AX = 4, DANGX_K_CG_VEC = 5, DANGX_K_AMP_INDEX = 6, DANGX_K_MOMENTS = 7, DANGX_K_HIST = 8, DANGX_K_COUNT = 9
+    DANGX_K_CG_AX = 4, DANGX_K_CG_VEC = 5, DANGX_K_AMP_INDEX = 6, DANGX_K_MOMENTS = 7, DANGX_K_HIST = 8, DANGX_K_SIGNAL = 9,
+    DANGX_K_COUNT = 10
 };
 
 typedef struct dangx_ctx dangx_ctx;
@@ -561,6 +562,32 @@ int dangx_moments_hist_get(dangx_ctx *ctx, int reg, void *counts);
 int dangx_moments_hist_get_dev(dangx_ctx *ctx, int reg, void *counts_dev);
 int dangx_moments_hist_stat(dangx_ctx *ctx, int reg, int stat, int nq, const double *q, double *out);
 int dangx_moments_hist_stat_dev(dangx_ctx *ctx, int reg, int stat, int nq, const double *q, double *out_dev);
+/* Moments of component signals at a band, accumulated on the same samples (k_moments_signal: a launch of its own per accumulation, and a second one for the signals at bandpass-integrated bands,
+ * only when something is registered): what write_maps' output_fg maps hold (c%eval_signal(band, pix, map),
+ * src/dang_data_mod.f90:596-617) and scripts/make_mean_maps.py averages -- nonlinear in the sampled amplitude and indices, so
+ * not derivable from their moments.  Definitions (dang_amd/csrc/dx_signal_host.h):
+ *   spec[s] = {comp, band, kind}; kind 0, 1, 2 = plane T, Q, U, kind 3 = the polarised intensity P (nmaps == 3).
+ *   one sample of kinds 0-2 at a pixel: amplitude * sed, ROUNDED as a product, sed as dangx_eval_sed(comp, band, kind + 1) returns
+ *     it (delta and integrated bandpasses, spatially constant index planes, band units); the bare sed for T_cmb.  A NaN sample
+ *     stays NaN; nothing is skipped (an all-zero amplitude plane gives 0 * sed).
+ *   kind 3: sqrt(sQ * sQ + sU * sU) of those two rounded samples (two rounded products, a rounded sum).
+ *   The update is k_moments_accum's on accumulators of the library's own (two f64 planes per signal).
+ * dangx_moments_signals: legal after dangx_moments_begin and before the first dangx_moments_accumulate, independent of
+ *   dangx_moments_pairs / _hist (either order, none drops another) and of the selection words (a signal's planes need not be
+ *   selected; an empty selection plus signals is a valid run); a second call replaces the first (nsig = 0: none),
+ *   dangx_moments_begin / _end drop it.  Errors (nothing changes, an earlier registration stays): count > 0, comp / band / kind
+ *   out of range, a kind the model's nmaps does not have, a template / monopole / hi_fit member (its signal is a host-side
+ *   amplitude, read by dangx_moments_get_template, times a fixed map), the same signal twice, nsig > DANGX_MAX_SIGNALS, a failed
+ *   allocation.  dangx_moments_accumulate fails when a registered component changed type or nindices since.
+ * dangx_moments_get_signal: stat 0 = mean, 1 = standard deviation sqrt(m2 / (n - ddof)); out: [npix] of this shard.  Errors: sig
+ *   out of range, n = 0, a bad stat, stat = 1 with n - ddof <= 0.  The _dev form writes a device array, asynchronously on the
+ *   context's stream.
+ * Not covered: the polarisation angle (a circular statistic), lag-1 / pairs / histograms of signals, frequencies that are not
+ * bands of the model. */
+#define DANGX_MAX_SIGNALS 64
+int dangx_moments_signals(dangx_ctx *ctx, int nsig, const int32_t *spec);
+int dangx_moments_get_signal(dangx_ctx *ctx, int sig, int stat, int ddof, double *out);
+int dangx_moments_get_signal_dev(dangx_ctx *ctx, int sig, int stat, int ddof, double *out_dev);
 /* frees the accumulators */
 int dangx_moments_end(dangx_ctx *ctx);
 

@@ -3,7 +3,7 @@
 iterations of the C3 model: blocks of iterations without and with accumulation after every iteration, alternating in one process;
 then the k_moments kernel time from the profile and its bandwidth in algorithmic bytes (5 x 8 B per selected element) against the
 6.29 TB/s measured copy ceiling of the MI355X.
-    python3 tools/bench_moments.py [nside=1024] [steps per block=10] [rounds=5] [--lag1] [--pairs default] [--hist [nbins=64]]
+    python3 tools/bench_moments.py [nside=1024] [steps per block=10] [rounds=5] [--lag1] [--pairs default] [--hist [nbins=64]] [--signals [--bandpass]]
 --lag1 / --pairs default: after the above, `rounds` alternating rounds of `steps` accumulations each of (a) the plain accumulate,
 (b) with lag-1 tracking (k_moments_accum_lag: 10 x 8 B per selected element) and (c) with the default pairs (k_moments_pairs: 6 x 8 B
 per pair element, timed apart from the mean launch that follows it); per launch the algorithmic bytes, the achieved bytes/s and
@@ -11,7 +11,13 @@ their ratio to (a) in the same round.
 --hist [nbins]: alternating rounds of (a) the plain accumulate and (h) the histogram launch (k_moments_hist, 16-bit counters) on the
 default index planes, at nbins and at 16 bins; per launch the line-granular traffic -- 8 B of x plus the record's 128-byte request
 read and written once per counted pixel -- its bytes/s and the ratio to
-(a)'s algorithmic bytes/s in the same round; then the read-out of three quantiles of one plane and the records' memory."""
+(a)'s algorithmic bytes/s in the same round; then the read-out of three quantiles of one plane and the records' memory.
+--signals: alternating rounds of (a) the plain accumulate and (s) the signal launch (k_moments_signal) on the default signals; per
+launch the algorithmic bytes -- per segment (amplitude planes + index planes read + 4 x outputs) x 8 B x pixels -- its bytes/s and
+the ratio to (a)'s in the same round.
+--signals --bandpass: every second band of the model becomes an integrated bandpass of nine samples (the bands of the default
+signals among them), and only the signal launch is timed -- the bandpass form of k_moments_signal, a launch of its own; no Gibbs
+iteration is run."""
 import os
 import sys
 import time
@@ -41,8 +47,29 @@ nside = int(args[0]) if len(args) > 0 else 1024
 steps = int(args[1]) if len(args) > 1 else 10
 rounds = int(args[2]) if len(args) > 2 else 5
 dev = torch.device("cuda", 0)
-dpar, ddata, bands, comps, meta = synth.make_sky("C3", nside=nside, device=dev, as_numpy=False)
+want_bandpass = "--bandpass" in sys.argv
+dpar, ddata, bands, comps, meta = synth.make_sky("C3", nside=nside, device=dev, as_numpy=False, start="truth" if want_bandpass else "prior")
+if want_bandpass:
+    rng = np.random.default_rng(4)
+    for b in bands[1::2]:
+        nu = b.nu_c * 1e9 * np.linspace(0.9, 1.1, 9)
+        tau = rng.uniform(0.2, 1.0, nu.size)
+        b.id, b.nu0, b.tau0 = "bp", nu, tau / tau.sum()
 eng = da.initialize(bands, comps, ddata, npix_global=meta["npix_global"], device=0)
+if want_bandpass:
+    da.moments_begin(dpar, ddata, sel=np.zeros(len(comps), dtype=np.int32))
+    specs = da.moments_signals(dpar, ddata)
+    assert all(bands[j].id != "delta" for l, j, k in specs)
+    da.moments_accumulate(ddata)   # table upload
+    for r in range(rounds):
+        eng.profile(True)
+        for _ in range(steps):
+            da.moments_accumulate(ddata)
+        prof = eng.profile_get()["k_signal"]
+        eng.profile(False)
+        print("round %d: bandpass form, %d signals at integrated bands of 9 samples: %.3f ms per launch (%d launches)"
+              % (r + 1, len(specs), prof["total_ms"] / prof["launches"], prof["launches"]))
+    sys.exit(0)
 it = 1
 for _ in range(2):
     da.gibbs_iteration(dpar, ddata, it, want_counts=False)
@@ -175,3 +202,43 @@ if hist_bins:
     nreg = len(da.default_hist_planes(dpar, comps, sel))
     print("records: %d B x %d pixels x %d planes = %.2f GB at %d bins x 16 bit" % (hist_bins * 2, npx, nreg, hist_bins * 2.0 * npx * nreg * 1e-9, hist_bins))
     da.moments_begin(dpar, ddata, sel=sel)   # drops the records
+
+
+def signal_planes(specs):
+    """planes of 8 B per pixel one launch moves: per (component, plane class) the amplitude and index planes read once, and per
+    output its mean and m2 read and written"""
+    total = 0
+    for l, cls in sorted({(l, 0 if k == 0 else 1) for l, j, k in specs}):
+        kinds = {k for ll, j, k in specs if ll == l and (0 if k == 0 else 1) == cls}
+        read = 1 if cls == 0 else (2 if (3 in kinds or {1, 2} <= kinds) else 1)
+        total += read * (1 + comps[l].nindices) + 4 * sum(1 for ll, j, k in specs if ll == l and (0 if k == 0 else 1) == cls)
+    return total
+
+
+def signal_launches():
+    da.moments_begin(dpar, ddata, sel=sel)
+    specs = da.moments_signals(dpar, ddata)
+    da.moments_accumulate(ddata)   # table upload
+    eng.profile(True)
+    for _ in range(steps):
+        da.moments_accumulate(ddata)
+    prof = eng.profile_get()
+    eng.profile(False)
+    return prof["k_signal"]["total_ms"] / prof["k_signal"]["launches"], prof["k_moments"]["total_ms"] / prof["k_moments"]["launches"], specs
+
+
+if "--signals" in sys.argv:
+    npx = meta["npix"]
+    ratios = []
+    for r in range(rounds):
+        a_ms = launches("plain")[0]
+        a_bw = 5 * 8 * planes * npx / a_ms * 1e-9
+        s_ms, m_ms, specs = signal_launches()
+        traffic = 8.0 * signal_planes(specs) * npx
+        s_bw = traffic / s_ms * 1e-9
+        ratios.append(s_bw / a_bw)
+        print("round %d: (a) plain %.3f ms -> %.2f TB/s; (s) %d signals %.3f ms, %.2f GB algorithmic -> %.2f TB/s = %.3f of (a); k_moments "
+              "beside it %.3f ms" % (r + 1, a_ms, a_bw, len(specs), s_ms, traffic * 1e-9, s_bw, s_bw / a_bw, m_ms))
+    print("(s) / (a): median %.3f (spread %.3f .. %.3f); target >= 0.9" % (float(np.median(ratios)), min(ratios), max(ratios)))
+    print("accumulators: 16 B x %d pixels x %d signals = %.2f GB" % (npx, len(specs), 16.0 * npx * len(specs) * 1e-9))
+    da.moments_begin(dpar, ddata, sel=sel)   # drops the accumulators
