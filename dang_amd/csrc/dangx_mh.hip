@@ -58,8 +58,8 @@ __device__ __forceinline__ double chain_lnl(const ChainCtx& C, double th, int ln
         case CH_POW: s = exp_nr(s0 * c.lnr[j]); break;
         case CH_MBB_BETA: s = C.F(j) * exp_nr(s0 * c.lnr[j]); break;
         case CH_MBB_T: s = s1 / (exp_nr(s0 * M.band[j].nu_c) - 1.0) * C.F(j); break;
-        case CH_LOGN_NUP: { const double l = (c.lnu9[j] - s0) / s1; s = exp_sat(-0.5 * (l * l)) * c.cst[j]; break; }
-        case CH_LOGN_W: { const double l = C.F(j) / s1; s = exp_sat(-0.5 * (l * l)) * c.cst[j]; break; }
+        case CH_LOGN_NUP: { const double l = (c.lnu9[j] - s0) / s1; s = exp_any(-0.5 * (l * l)) * c.cst[j]; break; }
+        case CH_LOGN_W: { const double l = C.F(j) / s1; s = exp_any(-0.5 * (l * l)) * c.cst[j]; break; }
         default: s = (c.type == DANGX_HIFIT) ? 0.0 : sed_eval(M, c, j, pr); break;
         }
         // eval_signal (src/dang_component_mod.f90:754-776): amplitude(pix,map) * sed; T_cmb: the sed itself;
@@ -344,8 +344,8 @@ __device__ __forceinline__ unsigned long long index_chain(const Model& M, const 
             if (a.ml_mode == DANGX_ML_OPTIMIZE) {
                 acc = diff > 0.0;  // :443-447
             } else {
-                // :448-454  diff > log(u)  <=>  diff >= 0 or exp(diff) > u   (u in (0,1)); diff has no bound: exp_sat
-                acc = (diff >= 0.0) || (exp_sat(diff) > u3);
+                // :448-454  diff > log(u)  <=>  diff >= 0 or exp(diff) > u   (u in (0,1)); diff has no bound: exp_any
+                acc = (diff >= 0.0) || (exp_any(diff) > u3);
             }
             if (acc) {
                 cur = prop;

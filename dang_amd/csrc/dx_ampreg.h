@@ -53,24 +53,24 @@ __device__ __forceinline__ void sed_tile(int type, const double* __restrict__ ta
     case DANGX_MBB: {  // :947-948, in two passes of TB chains each (bounds the registers the scheduler may spend)
         double f[TB];
 #pragma unroll
-        for (int t = 0; t < TB; ++t) { f[t] = p.p2 * fast_rcp(exp_nr(p.p1 * nuc[t]) - 1.0); }
+        for (int t = 0; t < TB; ++t) { f[t] = p.p2 * fast_rcp_ends(exp_nr(p.p1 * nuc[t]) - 1.0); }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int t = 0; t < TB; ++t) { colg[t * BLOCK] = f[t] * exp_nr(p.p0 * lnr[t]); }
         break;
     }
     case DANGX_FREEFREE: {  // :1026-1027
-        const double rp1 = fast_rcp(p.p1);
+        const double rp1 = fast_rcp_ends(p.p1);
 #pragma unroll
         for (int t = 0; t < TB; ++t) { colg[t * BLOCK] = (ff_gaunt(lnu9[t], p.p0) * rp1) * cst[t]; }
         break;
     }
     case DANGX_LOGNORMAL: {  // :988
-        const double rp1 = fast_rcp(p.p1);
+        const double rp1 = fast_rcp_ends(p.p1);
 #pragma unroll
         for (int t = 0; t < TB; ++t) {
             const double l = (lnu9[t] - p.p2) * rp1;
-            colg[t * BLOCK] = exp_sat(-0.5 * (l * l)) * cst[t];
+            colg[t * BLOCK] = exp_any(-0.5 * (l * l)) * cst[t];
            
         }
         break;

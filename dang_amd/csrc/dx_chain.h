@@ -10,18 +10,26 @@ template <bool V> struct BoolTag { static constexpr bool value = V; };
 #ifdef DX_CHAIN_LIBEXP
 #define CEXP(x) exp(x)
 #define CEXPS(x) exp(x)
+#define CEXPA(x) exp(x)
 #define CEXP1(x) exp(x)
 #else
 #define CEXP(x) exp_nr(x)      // |x| < 1e9: power law, Planck factor (mbb_z)
-#define CEXPS(x) exp_sat(x)    // any x: the log-normal SED, -(ln(nu/nu_p)/w)^2/2 has no bound for a narrow width
+#define CEXPS(x) exp_sat(x)    // |x| <= 1e16: the log-normal SED -(ln(nu/nu_p)/w)^2/2 of a chain whose width stays above 2^-16
+#define CEXPA(x) exp_any(x)    // any x: the same SED for a narrow width (no bound), outside the proposal loops
 #define CEXP1(x) exp_nr_v(x)   // a call site that runs once per proposal (dx_math.h: fma_vc); any x
 #endif
 // reciprocals of the rms and inside the modified-blackbody SED: v_rcp_f64 + two Newton steps (<= 1 ulp, 6 vector
 // instructions) instead of the IEEE division sequence (11); -DDX_CHAIN_IEEEDIV restores a / b
 #ifdef DX_CHAIN_IEEEDIV
 #define CDIV(a, b) ((a) / (b))
+#define CDIVE(a, b) ((a) / (b))
+#define CRCPE(b) (1.0 / (b))
 #else
 #define CDIV(a, b) ((a) * fast_rcp(b))
+// the same where b can be +inf or 0 (a Planck denominator exp(h nu / k T) - 1 at a temperature near 0: 1/inf = 0 in the
+// reference's arithmetic, NaN from fast_rcp): outside the proposal loops, and in the chains that can get there (chain_finish)
+#define CDIVE(a, b) ((a) * fast_rcp_ends(b))
+#define CRCPE(b) fast_rcp_ends(b)
 #endif
 
 // the chain's residual: with DX_CHAIN_SCALED (default) the staged planes hold d/sigma and a/sigma (the amplitude is fixed
@@ -198,7 +206,9 @@ struct RegChain {
         }
     }
 
-    // BATCH (CH_MBB_T only): the tile's Planck denominators share one reciprocal -- chain_finish decides once per chain
+    // BATCH (CH_MBB_T, CH_LOGN_*): chain_finish has decided, once per chain, that no proposal can leave the domains of the fast
+    // helpers (a Planck denominator that overflows, a width below 2^-16).  CH_MBB_T: the tile's Planck denominators then share
+    // one reciprocal.  Without it the band loop takes fast_rcp_ends / exp_any (dx_math.h), which hold for every argument.
     // OP: what the band loop does with the component's signal a/rms * s (the resident-residual form of k_plane_set, LNL_ADD /
     // LNL_SUB: D holds the FULL residual (d - sum of all members) / rms between the sweeps of a launch):
     //   LNL_EVAL  r = D - a' s, acc += r^2                      -- a likelihood evaluation (every proposal)
@@ -224,7 +234,7 @@ struct RegChain {
 #ifdef DX_CHAIN_IEEEDIV
         const double rs1 = 1.0 / s1;
 #else
-        const double rs1 = (MODE == CH_LOGN_NUP || MODE == CH_LOGN_W) ? fast_rcp(s1) : 0.0;
+        const double rs1 = (MODE == CH_LOGN_NUP || MODE == CH_LOGN_W) ? (BATCH ? fast_rcp(s1) : fast_rcp_ends(s1)) : 0.0;
 #endif
         // bands in tiles of TT: TT independent exp chains interleave, then accumulate in band order
         // (BP: one band at a time -- a bandpass-integrated band interleaves its own samples)
@@ -245,10 +255,10 @@ struct RegChain {
                     for (int q = 0; q < n; ++q) sj = sj + tau[q] * CEXP(s0 * lnr[q]);
                 } else if (MODE == CH_MBB_BETA) {   // :949-954, T fixed: tau * A / (e^{z nu} - 1) * (nu/nu_ref)^(beta+1)
 #pragma unroll 4
-                    for (int q = 0; q < n; ++q) sj = sj + (tau[q] * bpb) * fast_rcp(CEXP(bpa * nu[q]) - 1.0) * CEXP(s0 * lnr[q]);
+                    for (int q = 0; q < n; ++q) sj = sj + (tau[q] * bpb) * CRCPE(CEXP(bpa * nu[q]) - 1.0) * CEXP(s0 * lnr[q]);
                 } else {                            // CH_MBB_T, beta fixed
 #pragma unroll 4
-                    for (int q = 0; q < n; ++q) sj = sj + (tau[q] * s1) * fast_rcp(CEXP(s0 * nu[q]) - 1.0) * CEXP(bpa * lnr[q]);
+                    for (int q = 0; q < n; ++q) sj = sj + (tau[q] * s1) * CRCPE(CEXP(s0 * nu[q]) - 1.0) * CEXP(bpa * lnr[q]);
                 }
                 s[0] = sj;
             } else
@@ -276,16 +286,16 @@ struct RegChain {
                 const int j = j0 + t;
                 if (MODE == CH_LOGN_NUP) {
                     const double l = (k1(M, c, j) - s0) * rs1;
-                    s[t] = CEXPS(-0.5 * (l * l)) * k2(c, j);
+                    s[t] = (BATCH ? CEXPS(-0.5 * (l * l)) : CEXPA(-0.5 * (l * l))) * k2(c, j);
                 } else if (MODE == CH_LOGN_W) {
                     const double l = F[j] * rs1;
-                    s[t] = CEXPS(-0.5 * (l * l)) * k2(c, j);
+                    s[t] = (BATCH ? CEXPS(-0.5 * (l * l)) : CEXPA(-0.5 * (l * l))) * k2(c, j);
                 } else {
                     const double e = CEXP(s0 * k1(M, c, j));
                     if (EOUT) eout[j] = e;
                     if (MODE == CH_POW) s[t] = e;
                     else if (MODE == CH_MBB_BETA) s[t] = F[j] * e;
-                    else s[t] = CDIV(s1, e - 1.0) * F[j];
+                    else s[t] = (BATCH ? CDIV(s1, e - 1.0) : CDIVE(s1, e - 1.0)) * F[j];
                 }
             }
 #pragma unroll
@@ -465,18 +475,18 @@ __device__ __forceinline__ void subtract_other(const Model& M, const Comp& c2, i
         break;
     case DANGX_MBB:
 #pragma unroll
-        for (int j = 0; j < NB; ++j) Dk[j] -= amp2 * (CDIV(pr.p2, CEXP(pr.p1 * pick.nu_c(M, j, NB)) - 1.0) * CEXP(pr.p0 * pick(c2.lnr, j, NB)));
+        for (int j = 0; j < NB; ++j) Dk[j] -= amp2 * (CDIVE(pr.p2, CEXP(pr.p1 * pick.nu_c(M, j, NB)) - 1.0) * CEXP(pr.p0 * pick(c2.lnr, j, NB)));
         break;
     case DANGX_FREEFREE:
 #pragma unroll
         for (int j = 0; j < NB; ++j) Dk[j] -= amp2 * (ff_gaunt(pick(c2.lnu9, j, NB), pr.p0) / pr.p1 * pick(c2.cst, j, NB));
         break;
     case DANGX_LOGNORMAL: {
-        const double rp1 = fast_rcp(pr.p1);  // as sed_tile (dangx_ampreg.hip) forms it
+        const double rp1 = fast_rcp_ends(pr.p1);  // as sed_tile (dangx_ampreg.hip) forms it
 #pragma unroll
         for (int j = 0; j < NB; ++j) {
             const double l2 = (pick(c2.lnu9, j, NB) - pr.p2) * rp1;
-            Dk[j] -= amp2 * (CEXPS(-0.5 * (l2 * l2)) * pick(c2.cst, j, NB));
+            Dk[j] -= amp2 * (CEXPA(-0.5 * (l2 * l2)) * pick(c2.cst, j, NB));
         }
         break;
     }
@@ -501,7 +511,7 @@ __device__ __forceinline__ void subtract_other_pair(const Model& M, const Comp& 
     case DANGX_MBB:
 #pragma unroll
         for (int j = 0; j < NB; ++j) {
-            const double s = CDIV(pr.p2, CEXP(pr.p1 * pick.nu_c(M, j, NB)) - 1.0) * CEXP(pr.p0 * pick(c2.lnr, j, NB));
+            const double s = CDIVE(pr.p2, CEXP(pr.p1 * pick.nu_c(M, j, NB)) - 1.0) * CEXP(pr.p0 * pick(c2.lnr, j, NB));
             Da[j] -= ampa * s; Db[j] -= ampb * s;
         }
         break;
@@ -513,11 +523,11 @@ __device__ __forceinline__ void subtract_other_pair(const Model& M, const Comp& 
         }
         break;
     case DANGX_LOGNORMAL: {
-        const double rp1 = fast_rcp(pr.p1);
+        const double rp1 = fast_rcp_ends(pr.p1);
 #pragma unroll
         for (int j = 0; j < NB; ++j) {
             const double l2 = (pick(c2.lnu9, j, NB) - pr.p2) * rp1;
-            const double s = CEXPS(-0.5 * (l2 * l2)) * pick(c2.cst, j, NB);
+            const double s = CEXPA(-0.5 * (l2 * l2)) * pick(c2.cst, j, NB);
             Da[j] -= ampa * s; Db[j] -= ampb * s;
         }
         break;
@@ -569,7 +579,7 @@ __device__ __forceinline__ unsigned long long chain_finish(const Model& M, const
         const double z = mbb_z(sample1);
         const double A = CEXP(z * c.nu_ref) - 1.0;
 #pragma unroll
-        for (int j = 0; j < NB; ++j) R.F[j] = CDIV(A, CEXP(z * pick.nu_c(M, j, NB)) - 1.0);
+        for (int j = 0; j < NB; ++j) R.F[j] = CDIVE(A, CEXP(z * pick.nu_c(M, j, NB)) - 1.0);
         if (RC::kBP) { R.bpa = z; R.bpb = A; }   // bandpass-integrated bands: the same two numbers per SAMPLE (RegChain::lnl)
     } else if (MODE == CH_MBB_T) {
 #pragma unroll
@@ -752,6 +762,15 @@ __device__ __forceinline__ unsigned long long chain_finish(const Model& M, const
         if (__builtin_amdgcn_ballot_w64(unsafe) == 0ull) chain(BoolTag<true>{});
         else chain(BoolTag<false>{});
 #endif
+    } else if (MODE == CH_LOGN_NUP || MODE == CH_LOGN_W) {
+        // The log-normal SED exp(-(ln(nu / nu_p) / w)^2 / 2): |ln(nu / nu_p)| < 2^11 for normal frequencies, so a width that stays
+        // above 2^-16 keeps the argument inside exp_sat's range (2^53) and 1/w inside fast_rcp's; a chain whose width (the
+        // fixed one, or the lowest it can propose) is narrower, 0 or NaN takes the forms that hold for every argument -- decided
+        // once per chain and wavefront, as above.
+        const double wmin = (MODE == CH_LOGN_W) ? fmin(lo, cur) : other;
+        const bool unsafe = !(wmin >= 0x1p-16 && wmin < INFINITY);
+        if (__builtin_amdgcn_ballot_w64(unsafe) == 0ull) chain(BoolTag<true>{});
+        else chain(BoolTag<false>{});
     } else {
         chain(BoolTag<false>{});
     }

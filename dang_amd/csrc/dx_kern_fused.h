@@ -26,7 +26,7 @@ namespace dxk {
 // expressions of k_amp_reg's sed_tile (dangx_ampreg.hip), band by band
 // fcol (k_plane_set, a modified blackbody whose beta chain follows in the launch): the member's Planck factors
 // A / (exp(z nu_j) - 1) go to that column too -- they are the chain-invariant factor F[j] of its beta chain (chain_finish forms
-// A * fast_rcp(exp_nr(z nu_j) - 1) from the same z = mbb_z(T), A = exp_nr(z nu_ref) - 1 and nu_j: the same bits)
+// A * fast_rcp_ends(exp_nr(z nu_j) - 1) from the same z = mbb_z(T), A = exp_nr(z nu_ref) - 1 and nu_j: the same bits)
 template <int NBL>
 __device__ __forceinline__ void sed_column(int type, const double* __restrict__ tab, int NB, int NG, int g, int jb, const Prep& p,
                                            double* __restrict__ colg, double* __restrict__ fcol = nullptr) {
@@ -46,7 +46,7 @@ __device__ __forceinline__ void sed_column(int type, const double* __restrict__ 
         for (int j0 = 0; j0 < NBL; j0 += TT) {
             double f[TT];
 #pragma unroll
-            for (int t = 0; t < TT; ++t) f[t] = p.p2 * fast_rcp(exp_nr(p.p1 * nuc[j0 + t]) - 1.0);
+            for (int t = 0; t < TT; ++t) f[t] = p.p2 * fast_rcp_ends(exp_nr(p.p1 * nuc[j0 + t]) - 1.0);
             if (fcol) {
 #pragma unroll
                 for (int t = 0; t < TT; ++t) fcol[(j0 + t) * BLOCK] = f[t];
@@ -56,20 +56,20 @@ __device__ __forceinline__ void sed_column(int type, const double* __restrict__ 
             for (int t = 0; t < TT; ++t) colg[(j0 + t) * BLOCK] = f[t] * exp_nr(p.p0 * lnr[j0 + t]);
         }
     } else if (type == DANGX_FREEFREE) {
-        const double rp1 = fast_rcp(p.p1);
+        const double rp1 = fast_rcp_ends(p.p1);
 #pragma unroll 1
         for (int j0 = 0; j0 < NBL; j0 += TT) {
 #pragma unroll
             for (int t = 0; t < TT; ++t) colg[(j0 + t) * BLOCK] = (ff_gaunt(lnu9[j0 + t], p.p0) * rp1) * cst[j0 + t];
         }
     } else {  // DANGX_LOGNORMAL
-        const double rp1 = fast_rcp(p.p1);
+        const double rp1 = fast_rcp_ends(p.p1);
 #pragma unroll 1
         for (int j0 = 0; j0 < NBL; j0 += TT) {
 #pragma unroll
             for (int t = 0; t < TT; ++t) {
                 const double l = (lnu9[j0 + t] - p.p2) * rp1;
-                colg[(j0 + t) * BLOCK] = exp_sat(-0.5 * (l * l)) * cst[j0 + t];
+                colg[(j0 + t) * BLOCK] = exp_any(-0.5 * (l * l)) * cst[j0 + t];
             }
         }
     }

@@ -3,7 +3,9 @@
 // The Gibbs path is bound by fp64 transcendentals, and the device library's general-purpose
 // log/sin/pow carry argument-range and special-case handling the path never needs
 // (measured in ISA instructions on gfx950: exp 19 f64 ops, log 76, sin 108, pow 148).
-// The helpers below are valid on the ranges the kernels use and keep <= 1-2 ulp accuracy.
+// The helpers below are valid on the ranges the kernels use and keep <= 1-3 ulp accuracy; each states its domain, and
+// tests/test_gpu_mathlib.py and tests/test_gpu_mathlib_helpers.py run every one of them on the device over that domain and at
+// its ends ("Device math helpers", has the measured maxima).
 #pragma once
 #include "dx_rtc_compat.h"
 
@@ -25,7 +27,9 @@ __device__ __forceinline__ double fma_vc(double r, double p, double c) {
 #endif
 }
 
-// 1/x for finite normal x, <= 1 ulp (v_rcp_f64 is good to 2^-23; each Newton step squares the error)
+// 1/x for finite normal x, <= 1 ulp (measured 0.5; v_rcp_f64 is good to 2^-23; each Newton step squares the error).  Denormal
+// results (|x| >= 2^1022) come out within one denormal spacing.  NOT for x = +-0, +-inf or denormal x: v_rcp_f64 gives the IEEE
+// +-inf / +-0 there and the Newton steps make NaN of it (fma(-inf, 0, 1)) -- see fast_rcp_ends.
 __device__ __forceinline__ double fast_rcp(double x) {
     double r = __builtin_amdgcn_rcp(x);
     double e = fma(-x, r, 1.0);
@@ -33,7 +37,25 @@ __device__ __forceinline__ double fast_rcp(double x) {
     e = fma(-x, r, 1.0);
     return fma(r, e, r);
 }
-// 1/sqrt(x) for finite normal x > 0: Goldschmidt iteration on g ~ sqrt(x), h ~ 1/(2 sqrt(x))
+// 1/x for EVERY x, with the IEEE values at the ends fast_rcp leaves out: +-inf -> +-0, and +-0 and the denormals whose
+// reciprocal overflows -> +-inf, are v_rcp_f64's own results, which the Newton steps turn into NaN (fma(-inf, 0, 1)): where the
+// seed is 0 or inf it is the result.  (Denormals within 2^-23 of 2^-1024 may give inf where 1/x is just below the largest
+// double: the seed's own error.)  Every other argument: fast_rcp's operations, the same bits.  One v_cmp_class_f64 and two
+// selects more: for call sites outside the proposal loops, and for the chains whose Planck denominator exp(h nu / k T) - 1
+// can overflow (dx_chain.h)
+__device__ __forceinline__ double fast_rcp_ends(double x) {
+    const double r0 = __builtin_amdgcn_rcp(x);
+    double e = fma(-x, r0, 1.0);
+    double r = fma(r0, e, r0);
+    e = fma(-x, r, 1.0);
+    r = fma(r, e, r);
+    return __builtin_amdgcn_class(r0, 0x264) ? r0 : r;   // the seed is -inf, -0, +0 or +inf
+}
+// 1/sqrt(x) for finite normal x > 0: Goldschmidt iteration on g ~ sqrt(x), h ~ 1/(2 sqrt(x)).  The second step's result carries
+// the roundings of g0 = x y and of g1, h1 (half each: (eta0 + eta1 - eta2) / 2) and its own: relative error <= 2.5 * 2^-53, i.e.
+// 1.25 to 2.5 ulp depending on where the result lies in its binade (measured 1.63 ulp; DESIGN.md has the recurrence).  NaN at
+// x = 0 and x = +inf (the seed is inf / 0), garbage for x < 0 and denormal x: the call sites keep away (a sum of squares of
+// finite nonzero 1/rms-scaled SEDs; rand_normal selects around its -0).
 __device__ __forceinline__ double fast_rsqrt(double x) {
     const double y = __builtin_amdgcn_rsq(x);
     double g = x * y, h = 0.5 * y;
@@ -44,8 +66,8 @@ __device__ __forceinline__ double fast_rsqrt(double x) {
     return h + h;
 }
 
-// sqrt(x) for finite normal x > 0 by the same Goldschmidt iteration (<= 1 ulp; 8 vector instructions, the IEEE sqrt
-// sequence is 15)
+// sqrt(x) for finite normal x > 0 by the same Goldschmidt iteration (relative error <= 2.5 * 2^-53 as above, measured 1.43 ulp;
+// 8 vector instructions, the IEEE sqrt sequence is 15)
 __device__ __forceinline__ double fast_sqrt(double x) {
     const double y = __builtin_amdgcn_rsq(x);
     double g = x * y, h = 0.5 * y;
@@ -189,7 +211,11 @@ __device__ __forceinline__ double log_pos(double x) {
 // of inf / 0), and the kernels never compare such a value with an outcome that depends on it (an accept test
 // `exp(diff) > u` is false either way; `diff >= 0` is tested first).  Six of the library routine's 22 vector
 // instructions are those selects: the Metropolis chains are vector-issue bound, so this is 1/8 of their proposal loop.
-// exp_sat: for arguments of any size (log-normal SED with a narrow width, Planck function at low temperature).
+// exp_sat: for |x| <= 1e16 (tested out there: +inf, the denormals, +0).  Beyond 2^53 / log2e the product x log2e no longer
+// resolves the integer part, the reduced argument is garbage and so is the polynomial's sign: on the device
+// exp_sat(1e300) = -inf, exp_sat(-1e100) = -inf, exp_sat(-1e300) = +inf, exp_sat(-1e20) = -0 and exp_sat(+-inf) = NaN.  A call
+// site whose argument has no bound (log-normal SED with a narrow width, Planck function at low temperature, an accept test
+// on a difference of overflowing likelihoods) takes exp_any.
 __device__ __forceinline__ double exp_sat(double x) {
     const double dn = rint(x * 0x1.71547652b82fep+0);
     const double r = fma(dn, -0x1.abc9e3b39803fp-56, fma(dn, -0x1.62e42fefa39efp-1, x));
@@ -205,6 +231,16 @@ __device__ __forceinline__ double exp_sat(double x) {
     p = fma(r, p, 1.0);
     p = fma(r, p, 1.0);
     return ldexp(p, (int)dn);
+}
+
+// exp(x) for EVERY x: the argument is held at +-2^20, where ldexp has long saturated, by two compares and selects that let a
+// NaN through -- exp_sat's own bits wherever exp_sat is right, +inf / +0 beyond and at +-inf (IEEE arithmetic on the function),
+// NaN for NaN.  Six vector instructions more than exp_sat: for call sites outside the proposal loops, and the log-normal chains
+// whose width can be that narrow (dx_chain.h)
+__device__ __forceinline__ double exp_any(double x) {
+    x = (x > 0x1p+20) ? 0x1p+20 : x;
+    x = (x < -0x1p+20) ? -0x1p+20 : x;
+    return exp_sat(x);
 }
 
 // 2^(j/128), j = 0..127, as hi + lo (lo = the rounding error of hi, |lo| < 2^-53 hi): the table of exp_nr's table form.  One
@@ -325,7 +361,8 @@ __device__ __forceinline__ double exp_nr(double x) {
 #endif
 }
 
-// the same routine for a call site that runs once per loop iteration (the accept test): coefficients by fma_vc
+// the same routine for a call site that runs once per loop iteration (the accept test): coefficients by fma_vc.  Bit for bit
+// exp_sat, and its domain: |x| <= 1e16 (mh_accept calls it only where v_exp_f32 put exp(diff) next to a uniform: |diff| < 24)
 __device__ __forceinline__ double exp_nr_v(double x) {
     const double dn = rint(x * 0x1.71547652b82fep+0);
     const double r = fma(dn, -0x1.abc9e3b39803fp-56, fma(dn, -0x1.62e42fefa39efp-1, x));

@@ -59,6 +59,7 @@ def lib():
         l.dgo_eval_normal_prior.restype = C.c_double
         l.dgo_eval_normal_prior.argtypes = [C.c_double] * 3
         l.dgo_uniform2.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, _D]
+        l.dgo_uniform3.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, _D]
         l.dgo_B_nu.restype = C.c_double
         l.dgo_B_nu.argtypes = [C.c_double, C.c_double]
         l.dgo_bnu_prime_RJ.restype = C.c_double
@@ -348,3 +349,9 @@ def uniform2(seed, stream, pix, draw):
     u = (C.c_double * 2)()
     lib().dgo_uniform2(seed, stream, pix, draw, u)
     return u[0], u[1]
+
+
+def uniform3(seed, stream, pix, draw):
+    u = (C.c_double * 3)()
+    lib().dgo_uniform3(seed, stream, pix, draw, u)
+    return u[0], u[1], u[2]

@@ -217,3 +217,70 @@ def test_convert_maps_scales_adopted_device_buffers_in_place(built):
     for j in range(meta["nbands"]):
         assert torch.equal(ddata.sig_map[j], sig0[j] * conv[j]) and torch.equal(ddata.rms_map[j], rms0[j] * conv[j])
     assert conv[0] == 1.0 and conv[1] == 1.0 / eng.unit_conversion(1, "a2t") and conv[2] == 1.0 / eng.unit_conversion(2, "a2f")
+
+
+def _two_band(comps_spec, freqs, seed=9):
+    """Nside 1 (12 pixels), two delta bands, T only: components from (label, type, nu_ref, cg_group, amplitude sigma,
+    [(index label, start value, step, sampled, [low, high])])"""
+    npix, nb, nmaps = 12, len(freqs), 1
+    rng = np.random.default_rng(seed)
+    bands = [BandInfo("b%d" % j, freqs[j]) for j in range(nb)]
+    comps = []
+    for label, ctype, nu_ref, group, asig, idx in comps_spec:
+        nind = len(idx)
+        comps.append(DangComps(label=label, type=ctype, nu_ref=nu_ref, cg_group=group, nindices=nind,
+                               ind_label=[i[0] for i in idx], sample_index=[i[3] for i in idx], index_mode=[2] * nind,
+                               lnl_type=["chisq"] * nind, prior_type=["uniform"] * nind, gauss_prior=[[i[1], 1.0] for i in idx],
+                               uni_prior=[list(i[4]) for i in idx], step_size=[i[2] for i in idx], pol_flag=[[L.FLAG_T]] * nind,
+                               amplitude=asig * (1.0 + rng.uniform(size=(nmaps, npix))),
+                               indices=np.stack([np.full((nmaps, npix), i[1]) for i in idx])))
+    o = O.Oracle(bands, comps, DangData(sig_map=np.zeros((nb, nmaps, npix)), rms_map=np.ones((nb, nmaps, npix)), masks=np.ones((nmaps, npix))))
+    sky, _ = o.sky_model()
+    assert np.isfinite(sky).all()
+    rms = 0.5 + rng.uniform(size=sky.shape)
+    dd = DangData(sig_map=sky + rms * rng.standard_normal(sky.shape), rms_map=rms, masks=np.ones((nmaps, npix)), pol_type=[1], nump=float(npix))
+    groups = sorted({c[3] for c in comps_spec})
+    dpar = DangParams(cg_groups=[DangCGGroup(g, pol_flag=[L.FLAG_T]) for g in groups])
+    return dpar, dd, bands, comps, dict(npix=npix, npix_global=npix, pix0=0, nbands=nb, nmaps=nmaps)
+
+
+def _sweep_and_compare(case, solve_groups, sweeps):
+    dpar, ddata, bands, comps, meta = case
+    eng, orc = pair(case)
+    for it in (1, 2):
+        for g in solve_groups:
+            s = da.stream_id(it, 0, g, 0, L.FLAG_T)
+            _, bad = eng.amp_sample(g, L.FLAG_T, "sample", dpar.seed, s)
+            assert bad == orc.amp_sample_direct(g, L.FLAG_T, "sample", dpar.seed, s, "reference") == 0
+        for l, j in sweeps:
+            s = da.stream_id(it, 1, l, j, L.FLAG_T)
+            ag = eng.index_sample(l, j, 1, 20, "sample", dpar.seed, s)
+            assert ag == orc.sample_index_mh(l, j, 1, 20, "sample", dpar.seed, s)
+    for l in range(len(comps)):
+        assert np.isfinite(eng.get_indices(l)).all()
+    assert_amps_close(eng, orc, len(comps), 1e-9)
+    assert_indices_close(eng, orc, comps, 1e-12)
+    sky, _ = orc.sky_model()
+    a, b = eng.sky_model_chisq(1, 1), orc.chisq(1, 1, 1.0, sky)[0] * meta["nbands"]
+    assert np.isfinite(a) and abs(a - b) <= 1e-10 * max(abs(b), 1e-300)
+    return eng, orc
+
+
+def test_cold_dust_planck_denominator_overflows(built):
+    """A modified blackbody whose temperature prior reaches 0.01 K: at 857 GHz h nu / (k T) passes 709.8 below 0.06 K, the Planck
+    denominator exp(h nu / k T) - 1 is +inf and the band's SED is 1/inf = 0 in the reference's arithmetic -- not the NaN that
+    v_rcp_f64 followed by Newton steps makes of it (dx_math.h: fast_rcp_ends)."""
+    spec = [("dust", "mbb", 100.0, 1, 100.0, [("beta", 1.6, 0.05, True, [0.5, 3.0]), ("T", 0.04, 0.01, True, [0.01, 0.5])])]
+    eng, orc = _sweep_and_compare(_two_band(spec, [100.0, 857.0]), [1], [(0, 0), (0, 1)])
+    T = eng.get_indices(0)[1, 0]
+    print("temperatures after two sweeps:", T.tolist())
+    assert T.min() < 0.057     # the chains did stay where the 857 GHz denominator overflows
+
+
+def test_lognormal_of_vanishing_width(built):
+    """A log-normal component so narrow that -(ln(nu/nu_p)/w)^2/2 leaves the range where exp_sat's reduction works (|x| <= 1e16:
+    beyond it the sign is arbitrary and the result can be -inf): exp(-big) = +0 in the reference's arithmetic, the component
+    vanishes from both bands, and a power law beside it is fitted as if it were alone (dx_math.h: exp_any)."""
+    spec = [("synch", "power-law", 30.0, 1, 20.0, [("beta", -3.1, 0.05, True, [-4.5, -1.5])]),
+            ("ame", "lognormal", 22.0, 2, 15.0, [("nu_p", 21.0, 0.5, True, [5.0, 60.0]), ("w", 1e-60, 0.0, False, [1e-70, 1.0])])]
+    _sweep_and_compare(_two_band(spec, [23.0, 41.0]), [1], [(0, 0), (1, 0)])
