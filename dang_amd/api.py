@@ -1437,6 +1437,219 @@ def posterior_signal_maps(ddata, ddof=0, masked_value=None, engines=None):
     return out
 
 
+# --------------------------------------------------------------------------- several chains: R-hat and pooled summaries
+# dangx_chains_* (include/dangx.h): the accumulators of K chains of one device are combined on the device and only the map asked
+# for is written.  `engines` below is one Engine per chain (the same shard of each); a "chain" of the map functions is a ddata
+# or the list of that chain's shard engines in shard order.
+
+def _chains_call(engines, fn, *args):
+    engines = list(engines)
+    arr, n = _ctx_array(engines)
+    if getattr(engines[0].lib, fn)(arr, n, *args) != 0:
+        raise DangxError(engines[0].lib.dangx_last_error(engines[0].h).decode())
+
+
+def _chains_out(e, shape, device, out):
+    """(array, pointer) of a read-out's destination: a float64 torch cuda tensor (device=True) or a numpy array, zeros by default."""
+    if device:
+        import torch
+        if out is None:
+            dev = e._device if e._device is not None and e._device >= 0 else torch.cuda.current_device()
+            out = torch.zeros(shape, dtype=torch.float64, device=torch.device("cuda", dev))
+            torch.cuda.current_stream(dev).synchronize()   # the fill runs on torch's stream, the read-out on the first chain's
+        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float64 and tuple(out.shape) == tuple(shape)
+        return out, out.data_ptr()
+    if out is None:
+        out = np.zeros(shape)
+    assert isinstance(out, np.ndarray) and out.dtype == np.float64 and out.flags.c_contiguous and out.shape == tuple(shape)
+    return out, out.ctypes.data
+
+
+def chains_get(engines, l, what, stat, ddof=0, device=False, out=None):
+    """Over the chains `engines`: 'mean' / 0 = pooled mean, 'std' / 1 = pooled standard deviation sqrt(M / (N - ddof)), 'rhat' / 2 =
+    Gelman-Rubin R-hat, 'W' / 3 = within-chain variance, 'B' / 4 = B/n, the variance of the chain means, 'ess' / 5 = the sum of the
+    chains' AR(1) effective sample sizes, of component l's amplitude (what 0) or index j (what 1 + j) as [nmaps][npix].  R-hat, W
+    and B need equal sample counts >= 2; NaN R-hat where no chain ever moved (a masked pixel).  device=True: a torch cuda tensor,
+    written asynchronously on the first chain's stream (synchronize that engine, or use that stream, before reading it)."""
+    e = engines[0]
+    st = L.CHAINS_STAT_CODES[stat] if isinstance(stat, str) else int(stat)
+    out, ptr = _chains_out(e, (e.nmaps, e.npix), device, out)
+    _chains_call(engines, "dangx_chains_get_dev" if device else "dangx_chains_get", int(l), int(what), st, int(ddof), ptr)
+    return out
+
+
+def chains_get_template(engines, l, stat, ddof=0, out=None):
+    """chains_get's statistics of the rows of c%template_amplitudes of a template / monopole / hi_fit member, [nmaps][nbands]."""
+    e = engines[0]
+    st = L.CHAINS_STAT_CODES[stat] if isinstance(stat, str) else int(stat)
+    out, ptr = _chains_out(e, (e.nmaps, e.nbands), False, out)
+    _chains_call(engines, "dangx_chains_get_template", int(l), st, int(ddof), ptr)
+    return out
+
+
+def chains_get_signal(engines, s, stat, ddof=0, device=False, out=None):
+    """chains_get's statistics 'mean', 'std', 'rhat', 'W', 'B' of registered signal s (the same registration in every chain), [npix]."""
+    e = engines[0]
+    st = L.CHAINS_STAT_CODES[stat] if isinstance(stat, str) else int(stat)
+    out, ptr = _chains_out(e, (e.npix,), device, out)
+    _chains_call(engines, "dangx_chains_get_signal_dev" if device else "dangx_chains_get_signal", int(s), st, int(ddof), ptr)
+    return out
+
+
+def chains_get_pair(engines, p, stat, ddof=0, device=False, out=None):
+    """Pooled covariance ('cov' / 0: C / (N - ddof)) or correlation ('corr' / 1) of registered pair p over the chains, [npix]."""
+    e = engines[0]
+    st = L.PAIR_STAT_CODES[stat] if isinstance(stat, str) else int(stat)
+    out, ptr = _chains_out(e, (e.npix,), device, out)
+    _chains_call(engines, "dangx_chains_get_pair_dev" if device else "dangx_chains_get_pair", int(p), st, int(ddof), ptr)
+    return out
+
+
+def chains_hist_stat(engines, reg, stat, q=None, device=False, out=None):
+    """Engine.moments_hist_stat on the bins of all chains summed: 'quantile' / 0 -> [nq][npix], 'mode' / 1, 'n' / 2 -> [npix]."""
+    e = engines[0]
+    st = L.HIST_STAT_CODES[stat] if isinstance(stat, str) else int(stat)
+    qa = np.ascontiguousarray(np.atleast_1d(np.asarray(q if q is not None else [], dtype=np.float64)))
+    if st == 0 and not 1 <= qa.size <= L.MAX_HIST_Q:
+        raise DangxError("chains_hist_stat: a read-out takes 1 to %d quantiles" % L.MAX_HIST_Q)
+    out, ptr = _chains_out(e, (qa.size, e.npix) if st == 0 else (e.npix,), device, out)
+    _chains_call(engines, "dangx_chains_hist_stat_dev" if device else "dangx_chains_hist_stat", int(reg), st, qa.size,
+                 qa.ctypes.data if qa.size else None, ptr)
+    return out
+
+
+def open_chain(dpar, ddata, seed, stream=None, tcmb=None):
+    """A further chain over the same data: (dpar_k, ddata_k).  dpar_k is a copy of dpar with its own seed.  ddata_k shares ddata's
+    sig_map / rms_map / masks objects -- for device tensors its Engine adopts the same HBM, host arrays are uploaded once more --
+    and carries a new Engine (ddata_k.engine) on the same pix0 / npix_global / device that owns deep copies of the component state
+    as ddata.engine's component_list holds it.  Starting values are the caller's: put them into ddata_k.engine afterwards
+    (put_amplitude / put_indices), dispersed for R-hat to mean something."""
+    import copy
+    import dataclasses
+    src = ddata.engine
+    if src is None:
+        raise DangxError("open_chain: ddata has no engine (call initialize first)")
+    dpar_k = copy.copy(dpar)
+    dpar_k.seed = int(seed)
+    ddata_k = dataclasses.replace(ddata, engine=None, sky_model=None, res_map=None, chi_map=None,
+                                  gain=None if ddata.gain is None else np.array(ddata.gain, dtype=np.float64),
+                                  offset=None if ddata.offset is None else np.array(ddata.offset, dtype=np.float64))
+    comps = copy.deepcopy(src.component_list)
+    ddata_k.engine = Engine(src.bands, comps, ddata_k, npix_global=src.npix_global, pix0=src.pix0, device=src._device, stream=stream,
+                            tcmb=tcmb)
+    return dpar_k, ddata_k
+
+
+def _chain_engines(chain):
+    return [chain.engine] if hasattr(chain, "engine") else list(chain)
+
+
+def _chains_shards(chains, who):
+    """[[chain 0's engine of shard s, chain 1's, ...] for every shard s] and the per-chain sample counts."""
+    chs = [_chain_engines(c) for c in chains]
+    if not 2 <= len(chs) <= L.MAX_CHAINS:
+        raise DangxError("%s: takes 2 to %d chains, not %d" % (who, L.MAX_CHAINS, len(chs)))
+    if len({len(c) for c in chs}) != 1:
+        raise DangxError("%s: the chains hold different numbers of shards %s" % (who, [len(c) for c in chs]))
+    counts = []
+    for k, c in enumerate(chs):
+        ns = {e.moments_count() for e in c}
+        if len(ns) != 1:
+            raise DangxError("%s: the contexts of chain %d hold different sample counts %s" % (who, k, sorted(ns)))
+        counts.append(ns.pop())
+    return [list(col) for col in zip(*chs)], counts
+
+
+def _chains_map(shards, get, masked_value):
+    parts = []
+    for col in shards:
+        m = get(col)
+        parts.append(_mask_fill(m, col[0].ddata.masks, masked_value) if masked_value is not None else m)
+    return np.concatenate(parts, axis=-1) if len(parts) > 1 else parts[0]
+
+
+def _chains_stats(counts, lag1):
+    """The statistics a set of chains with these counts carries: R-hat, W and B only for equal counts >= 2."""
+    equal = len(set(counts)) == 1 and counts[0] >= 2
+    return ("mean", "std") + (("rhat", "W", "B") if equal else ()) + (("ess",) if lag1 else ())
+
+
+def chains_posterior_maps(chains, ddof=0, masked_value=None):
+    """posterior_maps over several chains (each a ddata, or the list of that chain's shard engines in shard order): the same keys,
+    every entry {'n', 'nchains', 'mean', 'std', 'rhat', 'W', 'B'} (+ 'ess' when every chain tracks lag-1) with the pooled mean and
+    standard deviation, R-hat, the within-chain variance and B/n of chains_get.  'n' is the samples per chain -- a list, and no
+    'rhat' / 'W' / 'B', when the chains hold different counts.  Shards side by side; masked_value as in posterior_maps."""
+    shards, counts = _chains_shards(chains, "chains_posterior_maps")
+    first = shards[0]
+    sel = getattr(first[0], "_moment_sel", None)
+    if sel is None:
+        raise DangxError("chains_posterior_maps: moments_begin was not called")
+    lag1 = all(getattr(e, "_moment_lag1", False) for col in shards for e in col)
+    out = {}
+    for l, c in enumerate(first[0].component_list):
+        for what in range(1 + c.nindices):
+            if not (int(sel[l]) >> (0 if what == 0 else 3 + 3 * (what - 1))) & 7:
+                continue
+            entry = {"n": counts[0] if len(set(counts)) == 1 else list(counts), "nchains": len(counts)}
+            for stat in _chains_stats(counts, lag1):
+                if what == 0 and c.type in GLOBAL_TYPES:
+                    entry[stat] = chains_get_template(first, l, stat, ddof)
+                else:
+                    entry[stat] = _chains_map(shards, lambda col: chains_get(col, l, what, stat, ddof), masked_value)
+            out[(c.label, _plane_name(c, what))] = entry
+    return out
+
+
+def chains_pair_maps(chains, stat="corr", ddof=0, masked_value=None):
+    """posterior_pair_maps over several chains: the pooled correlation ('corr') or covariance ('cov', with ddof) of every pair."""
+    shards, _ = _chains_shards(chains, "chains_pair_maps")
+    pairs = getattr(shards[0][0], "_moment_pairs", None)
+    if pairs is None:
+        raise DangxError("chains_pair_maps: moments_pairs was not called")
+    comps = shards[0][0].component_list
+    out = {}
+    for p, (a, b) in enumerate(pairs):
+        key = tuple((comps[l].label, _plane_name(comps[l], what), k) for l, what, k in (a, b))
+        out[key] = _chains_map(shards, lambda col: chains_get_pair(col, p, stat, ddof), masked_value)
+    return out
+
+
+def chains_quantile_maps(chains, q=(0.16, 0.5, 0.84), masked_value=None):
+    """posterior_quantile_maps over several chains: 'q', 'mode' and 'n' of the bins of all chains summed (+ 'range', 'nbins')."""
+    shards, _ = _chains_shards(chains, "chains_quantile_maps")
+    reg0 = getattr(shards[0][0], "_moment_hist", None)
+    if not reg0:
+        raise DangxError("chains_quantile_maps: moments_hist was not called")
+    if any(getattr(e, "_moment_hist", None) != reg0 for col in shards for e in col):
+        raise DangxError("chains_quantile_maps: the contexts hold different histogram registrations")
+    comps = shards[0][0].component_list
+    out = {}
+    for r, (l, what, k) in enumerate(reg0["planes"]):
+        entry = {"range": reg0["ranges"][r], "nbins": reg0["nbins"]}
+        for name, stat in (("q", "quantile"), ("mode", "mode"), ("n", "n")):
+            entry[name] = _chains_map(shards, lambda col: chains_hist_stat(col, r, stat, q=q if stat == "quantile" else None), masked_value)
+        out[(comps[l].label, _plane_name(comps[l], what), k)] = entry
+    return out
+
+
+def chains_signal_maps(chains, ddof=0, masked_value=None):
+    """posterior_signal_maps over several chains: {'n', 'nchains', 'mean', 'std', 'rhat', 'W', 'B'} per registered signal."""
+    shards, counts = _chains_shards(chains, "chains_signal_maps")
+    reg0 = getattr(shards[0][0], "_moment_signals", None)
+    if reg0 is None:
+        raise DangxError("chains_signal_maps: moments_signals was not called")
+    if any(getattr(e, "_moment_signals", None) != reg0 for col in shards for e in col):
+        raise DangxError("chains_signal_maps: the contexts hold different signal registrations")
+    comps, bands = shards[0][0].component_list, shards[0][0].bands
+    out = {}
+    for s, (l, j, kind) in enumerate(reg0):
+        entry = {"n": counts[0] if len(set(counts)) == 1 else list(counts), "nchains": len(counts)}
+        for stat in _chains_stats(counts, False):
+            entry[stat] = _chains_map(shards, lambda col: chains_get_signal(col, s, stat, ddof), masked_value)
+        out[(comps[l].label, bands[j].label, L.SIGNAL_KINDS[kind])] = entry
+    return out
+
+
 # --------------------------------------------------------------------------- full-sky mode, tuner, calibrators
 # The chains themselves live behind the C ABI (dang_amd/csrc/dangx_sky.hip: dangx_fullsky_sample, dangx_tune_perpixel,
 # dangx_fit_band_gain, dangx_update_tcmb) -- one implementation for this mirror, the Fortran layers and any other host.

@@ -57,8 +57,10 @@ DX_HD double dx_hist_value(double lo, double width, double t) {
 }
 
 // one bin of the quantile walk: c = the bin's count, cum = the sum before it (updated).  True when bin b is the first with
-// c > 0 && cum + c >= target; out is then the quantile
-DX_HD bool dx_hist_qstep(uint32_t c, int b, double target, unsigned long long& cum, double lo, double width, double& out) {
+// c > 0 && cum + c >= target; out is then the quantile.  CT: uint32_t for one record, a 64-bit count for the bins of several
+// chains summed (dangx_chains_hist_stat): the same expression for both
+template <class CT>
+DX_HD bool dx_hist_qstep(CT c, int b, double target, unsigned long long& cum, double lo, double width, double& out) {
     if (c > 0 && (double)(cum + c) >= target) {
         out = dx_hist_value(lo, width, (double)b + (target - (double)cum) / (double)c);
         return true;
@@ -68,7 +70,8 @@ DX_HD bool dx_hist_qstep(uint32_t c, int b, double target, unsigned long long& c
 }
 
 // one bin of the mode search: the fullest bin, the lowest on ties (best_c starts at 0, best_b at -1)
-DX_HD void dx_hist_mstep(uint32_t c, int b, uint32_t& best_c, int& best_b) {
+template <class CT>
+DX_HD void dx_hist_mstep(CT c, int b, CT& best_c, int& best_b) {
     if (c > best_c) { best_c = c; best_b = b; }
 }
 

@@ -617,6 +617,69 @@ module dangx_mod
        import :: c_int, c_ptr
        type(c_ptr), value :: ctx
      end function
+     ! read-outs over several chains: ctxs(nchains) = one context per chain (2..8, one device, the same shard), each with its own
+     ! dangx_moments_* accumulators.  stat: 0 = pooled mean, 1 = pooled std (ddof), 2 = R-hat, 3 = W, 4 = B/n, 5 = pooled ESS
+     ! (signals: 0..4); comp, what, sig, pair, reg 0-based as in C; outputs laid out as the single-chain getters lay them out.
+     ! Errors are reported on ctxs(1): call dangx_check(ctxs(1), status, ...).
+     integer(c_int) function dangx_chains_get(ctxs, nchains, comp, what, stat, ddof, out) bind(C, name='dangx_chains_get')
+       import :: c_int, c_ptr
+       type(c_ptr), intent(in) :: ctxs(*)
+       integer(c_int), value :: nchains, comp, what, stat, ddof
+       type(c_ptr), value :: out
+     end function
+     integer(c_int) function dangx_chains_get_dev(ctxs, nchains, comp, what, stat, ddof, out_dev) bind(C, name='dangx_chains_get_dev')
+       import :: c_int, c_ptr
+       type(c_ptr), intent(in) :: ctxs(*)
+       integer(c_int), value :: nchains, comp, what, stat, ddof
+       type(c_ptr), value :: out_dev
+     end function
+     ! ta: (nbands, nmaps) rows of c%template_amplitudes of a template / monopole / hi_fit member
+     integer(c_int) function dangx_chains_get_template(ctxs, nchains, comp, stat, ddof, ta) bind(C, name='dangx_chains_get_template')
+       import :: c_int, c_ptr
+       type(c_ptr), intent(in) :: ctxs(*)
+       integer(c_int), value :: nchains, comp, stat, ddof
+       type(c_ptr), value :: ta
+     end function
+     integer(c_int) function dangx_chains_get_signal(ctxs, nchains, sig, stat, ddof, out) bind(C, name='dangx_chains_get_signal')
+       import :: c_int, c_ptr
+       type(c_ptr), intent(in) :: ctxs(*)
+       integer(c_int), value :: nchains, sig, stat, ddof
+       type(c_ptr), value :: out
+     end function
+     integer(c_int) function dangx_chains_get_signal_dev(ctxs, nchains, sig, stat, ddof, out_dev) &
+          bind(C, name='dangx_chains_get_signal_dev')
+       import :: c_int, c_ptr
+       type(c_ptr), intent(in) :: ctxs(*)
+       integer(c_int), value :: nchains, sig, stat, ddof
+       type(c_ptr), value :: out_dev
+     end function
+     ! stat: 0 = covariance (ddof), 1 = correlation
+     integer(c_int) function dangx_chains_get_pair(ctxs, nchains, pair, stat, ddof, out) bind(C, name='dangx_chains_get_pair')
+       import :: c_int, c_ptr
+       type(c_ptr), intent(in) :: ctxs(*)
+       integer(c_int), value :: nchains, pair, stat, ddof
+       type(c_ptr), value :: out
+     end function
+     integer(c_int) function dangx_chains_get_pair_dev(ctxs, nchains, pair, stat, ddof, out_dev) bind(C, name='dangx_chains_get_pair_dev')
+       import :: c_int, c_ptr
+       type(c_ptr), intent(in) :: ctxs(*)
+       integer(c_int), value :: nchains, pair, stat, ddof
+       type(c_ptr), value :: out_dev
+     end function
+     ! stat, nq, q, out as in dangx_moments_hist_stat, on the bins of all chains summed
+     integer(c_int) function dangx_chains_hist_stat(ctxs, nchains, reg, stat, nq, q, out) bind(C, name='dangx_chains_hist_stat')
+       import :: c_int, c_ptr
+       type(c_ptr), intent(in) :: ctxs(*)
+       integer(c_int), value :: nchains, reg, stat, nq
+       type(c_ptr), value :: q, out
+     end function
+     integer(c_int) function dangx_chains_hist_stat_dev(ctxs, nchains, reg, stat, nq, q, out_dev) &
+          bind(C, name='dangx_chains_hist_stat_dev')
+       import :: c_int, c_ptr
+       type(c_ptr), intent(in) :: ctxs(*)
+       integer(c_int), value :: nchains, reg, stat, nq
+       type(c_ptr), value :: q, out_dev
+     end function
      integer(c_int) function dangx_profile_enable(ctx, on) bind(C, name='dangx_profile_enable')
        import :: c_int, c_ptr
        type(c_ptr), value :: ctx

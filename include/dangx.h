@@ -75,7 +75,8 @@ enum { DANGX_COARSE_REFERENCE = 0, DANGX_COARSE_DEGRADED = 1 };
 enum {
     DANGX_K_AMP_DIRECT = 0, DANGX_K_INDEX_MH = 1, DANGX_K_SKY_CHISQ = 2, DANGX_K_REDUCE = 3,
     DANGX_K_CG_AX = 4, DANGX_K_CG_VEC = 5, DANGX_K_AMP_INDEX = 6, DANGX_K_MOMENTS = 7, DANGX_K_HIST = 8, DANGX_K_SIGNAL = 9,
-    DANGX_K_COUNT = 10
+    DANGX_K_CHAINS = 10,   /* the read-outs over several chains (dangx_chains_*): nothing else is ever counted here */
+    DANGX_K_COUNT = 11
 };
 
 typedef struct dangx_ctx dangx_ctx;
@@ -590,6 +591,42 @@ int dangx_moments_get_signal(dangx_ctx *ctx, int sig, int stat, int ddof, double
 int dangx_moments_get_signal_dev(dangx_ctx *ctx, int sig, int stat, int ddof, double *out_dev);
 /* frees the accumulators */
 int dangx_moments_end(dangx_ctx *ctx);
+
+/* ---- read-outs over SEVERAL chains: Gelman-Rubin R-hat and pooled posterior summaries ---------------------------------------
+ * ctxs[0..nchains) are contexts of ONE device holding the same shard, each with its own chain and its own dangx_moments_*
+ * accumulators (the data planes can be shared: dangx_adopt_device_data).  The read-outs combine the per-chain accumulators on the
+ * device and write only the map asked for; they touch no accumulator, chain or cache, and a run that never calls them launches
+ * what it launched before.  Definitions (dang_amd/csrc/dx_chains_host.h), per element, chain k with n_k samples, mean_k and
+ * m2_k = sum_t (x_t - mean_k)^2, N = sum n_k:
+ *   pooled mean / M2: the chains folded in list order from chain 0's own values, d = mean_k - mu, n' = n + n_k,
+ *     mu += d (n_k / n'), M += m2_k + d^2 (n n_k / n') -- every added term >= 0.  Pooled std = sqrt(M / (N - ddof)).
+ *   W = (sum_k m2_k) / (K (n - 1));  B/n = sum_k (d_k - dbar)^2 / (K - 1) with d_k = mean_k - mean_0, dbar = (sum d_k) / K;
+ *   R-hat = sqrt(((n - 1)/n W + B/n) / W) (Gelman et al., BDA3 eq. 11.4): NaN where no chain ever moved (a masked pixel), +inf
+ *     where only the means differ.  These three need equal n_k = n >= 2.
+ *   pooled ESS = sum_k ESS_k of dangx_moments_get's stat 3 (every chain must track lag-1; NaN propagates).
+ *   pooled pair term C += C_k + d_a d_b (n n_k / n'); covariance = C / (N - ddof), correlation = C / sqrt(M_a M_b).
+ *   pooled histogram: bin b = sum_k c_{k,b} in 64-bit integers; N, quantiles and mode by dangx_moments_hist_stat's rules on them.
+ * stat of dangx_chains_get / _get_template: 0 = pooled mean, 1 = pooled std, 2 = R-hat, 3 = W, 4 = B/n, 5 = pooled ESS;
+ *   of _get_signal: 0-4; of _get_pair: 0 = covariance, 1 = correlation; of _hist_stat: as dangx_moments_hist_stat.
+ * Host forms write host arrays laid out as the single-chain getters lay them out and return after the copy; _dev forms write a
+ * packed device array asynchronously.  The kernel runs on ctxs[0]'s stream: before it every other chain's stream records an
+ * event that stream waits on, after it that stream records an event the other streams wait on, so a following
+ * dangx_moments_accumulate on any chain cannot overwrite what the kernel reads.
+ * Errors (message on ctxs[0], naming the chain; nothing is written): nchains outside 2..DANGX_MAX_CHAINS, a context listed twice,
+ * contexts on different devices (peer access is not supported), differing npix / pix0 / nmaps, a chain without
+ * dangx_moments_begin or without a sample, a (comp, what) plane not selected in some chain, a pair / signal / histogram
+ * registration (for a histogram including lo, hi, nbins and bits) that is not the same in every chain, unequal n or n < 2 for
+ * stats 2-4, lag-1 missing in some chain for stat 5, a bad ddof. */
+#define DANGX_MAX_CHAINS 8
+int dangx_chains_get(dangx_ctx *const *ctxs, int nchains, int comp, int what, int stat, int ddof, double *out);
+int dangx_chains_get_dev(dangx_ctx *const *ctxs, int nchains, int comp, int what, int stat, int ddof, double *out_dev);
+int dangx_chains_get_template(dangx_ctx *const *ctxs, int nchains, int comp, int stat, int ddof, double *ta);
+int dangx_chains_get_signal(dangx_ctx *const *ctxs, int nchains, int sig, int stat, int ddof, double *out);
+int dangx_chains_get_signal_dev(dangx_ctx *const *ctxs, int nchains, int sig, int stat, int ddof, double *out_dev);
+int dangx_chains_get_pair(dangx_ctx *const *ctxs, int nchains, int pair, int stat, int ddof, double *out);
+int dangx_chains_get_pair_dev(dangx_ctx *const *ctxs, int nchains, int pair, int stat, int ddof, double *out_dev);
+int dangx_chains_hist_stat(dangx_ctx *const *ctxs, int nchains, int reg, int stat, int nq, const double *q, double *out);
+int dangx_chains_hist_stat_dev(dangx_ctx *const *ctxs, int nchains, int reg, int stat, int nq, const double *q, double *out_dev);
 
 /* ---- per-kernel timing with HIP events on the context's stream ----------------- */
 int dangx_profile_enable(dangx_ctx *ctx, int on);

@@ -3,7 +3,7 @@
 iterations of the C3 model: blocks of iterations without and with accumulation after every iteration, alternating in one process;
 then the k_moments kernel time from the profile and its bandwidth in algorithmic bytes (5 x 8 B per selected element) against the
 6.29 TB/s measured copy ceiling of the MI355X.
-    python3 tools/bench_moments.py [nside=1024] [steps per block=10] [rounds=5] [--lag1] [--pairs default] [--hist [nbins=64]] [--signals [--bandpass]]
+    python3 tools/bench_moments.py [nside=1024] [steps per block=10] [rounds=5] [--lag1] [--pairs default] [--hist [nbins=64]] [--signals [--bandpass]] [--chains K]
 --lag1 / --pairs default: after the above, `rounds` alternating rounds of `steps` accumulations each of (a) the plain accumulate,
 (b) with lag-1 tracking (k_moments_accum_lag: 10 x 8 B per selected element) and (c) with the default pairs (k_moments_pairs: 6 x 8 B
 per pair element, timed apart from the mean launch that follows it); per launch the algorithmic bytes, the achieved bytes/s and
@@ -17,7 +17,12 @@ launch the algorithmic bytes -- per segment (amplitude planes + index planes rea
 the ratio to (a)'s in the same round.
 --signals --bandpass: every second band of the model becomes an integrated bandpass of nine samples (the bands of the default
 signals among them), and only the signal launch is timed -- the bandpass form of k_moments_signal, a launch of its own; no Gibbs
-iteration is run."""
+iteration is run.
+--chains K: K chains over the same data (open_chain), three samples each with lag-1 and one histogram plane (64 bins x 16 bit);
+`rounds` alternating rounds of `steps` read-outs each, timed with events on the stream: (y) the single-chain std read-out
+(k_moments_finish: 2 x 8 B per element), (r) R-hat over the chains ((2 K + 1) x 8 B), (e) the pooled ESS ((5 K + 1) x 8 B) and (q)
+three pooled quantiles (K x 128 B + 3 x 8 B per pixel); per read-out its bytes/s and the ratio to (y) in the same round.  Nothing
+else of the above is run."""
 import os
 import sys
 import time
@@ -38,6 +43,10 @@ if "--hist" in argv:
     hist_bins = 64
     if i + 1 < len(argv) and argv[i + 1].isdigit():
         hist_bins = int(argv.pop(i + 1))
+nchains = 0
+if "--chains" in argv:
+    i = argv.index("--chains")
+    nchains = int(argv.pop(i + 1))
 args = [a for a in argv if not a.startswith("--") and a != "default"]
 want_lag1 = "--lag1" in sys.argv
 want_pairs = "--pairs" in sys.argv
@@ -69,6 +78,57 @@ if want_bandpass:
         eng.profile(False)
         print("round %d: bandpass form, %d signals at integrated bands of 9 samples: %.3f ms per launch (%d launches)"
               % (r + 1, len(specs), prof["total_ms"] / prof["launches"], prof["launches"]))
+    sys.exit(0)
+if nchains:
+    runs = [(dpar, ddata)] + [da.open_chain(dpar, ddata, dpar.seed + k) for k in range(1, nchains)]
+    engs = [d.engine for _, d in runs]
+    for p, d in runs:
+        sel = da.moments_begin(p, d)
+        da.moments_pairs(p, d, pairs=[], lag1=True)
+        hp = da.moments_hist(p, d, planes=da.default_hist_planes(p, comps, sel)[:1], nbins=64, bits=16)
+    for it in (1, 2, 3):
+        for p, d in runs:
+            da.gibbs_iteration(p, d, it, want_counts=False)
+            da.moments_accumulate(d)
+    l, what, _ = hp[0]
+    nplanes = bin((int(sel[l]) >> (3 + 3 * (what - 1))) & 7).count("1")
+    npx = meta["npix"]
+    out = torch.zeros((meta["nmaps"], npx), dtype=torch.float64, device=dev)
+    outq = torch.zeros((3, npx), dtype=torch.float64, device=dev)
+    q3 = (0.16, 0.5, 0.84)
+
+    def timed(fn):
+        fn()   # first use: scratch, events
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(steps):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / steps
+
+    forms = [("y", "single-chain std", 2 * 8 * nplanes, lambda: eng._chk(eng.lib.dangx_moments_get_dev(eng.h, l, what, 1, 0, out.data_ptr()))),
+             ("r", "R-hat", (2 * nchains + 1) * 8 * nplanes, lambda: da.chains_get(engs, l, what, "rhat", device=True, out=out)),
+             ("e", "pooled ESS", (5 * nchains + 1) * 8 * nplanes, lambda: da.chains_get(engs, l, what, "ess", device=True, out=out)),
+             ("q", "3 pooled quantiles", nchains * 128 + 3 * 8, lambda: da.chains_hist_stat(engs, 0, "quantile", q=q3, device=True, out=outq))]
+    ratios = {k: [] for k, _, _, _ in forms[1:]}
+    print("C3 at Nside %d, %d chains of %d samples, %s index %d: %d planes of %d pixels" % (nside, nchains, engs[0].moments_count(),
+                                                                                          comps[l].label, what, nplanes, npx))
+    for r in range(rounds):
+        line, y_bw = "round %d:" % (r + 1), None
+        for key, name, per_pix, fn in forms:
+            ms = timed(fn)
+            bw = per_pix * npx / ms * 1e-9
+            if key == "y":
+                y_bw = bw
+            else:
+                ratios[key].append(bw / y_bw)
+            line += " (%s) %s %.3f ms, %.3f GB -> %.2f TB/s%s;" % (key, name, ms, per_pix * npx * 1e-9, bw, "" if key == "y" else " = %.3f of (y)" % (bw / y_bw))
+        print(line)
+    for key, name, _, _ in forms[1:]:
+        print("(%s) %s / (y): median %.3f (spread %.3f .. %.3f)%s" % (key, name, float(np.median(ratios[key])), min(ratios[key]), max(ratios[key]),
+                                                                     "" if key == "q" else "; expected >= 0.8"))
     sys.exit(0)
 it = 1
 for _ in range(2):
