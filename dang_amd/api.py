@@ -146,6 +146,28 @@ class DangxError(RuntimeError):
     pass
 
 
+def _readout_dest(e, shape, device, out=None, dtype=np.float64):
+    """(array, pointer) of the destination of a read-out of Engine e (Engine.moments_* and chains_*): a torch cuda tensor
+    (device=True) or a numpy array of `dtype` -- as a tensor, torch's type of the same width -- zeros unless `out` is given.
+    After it allocates a zero-filled tensor it waits for torch's current stream: the fill runs there, the library's write on the
+    engine's stream (of several chains: the first chain's), and the wait orders the fill before that write where the two
+    streams differ.  This holds for the single-chain device read-outs as it does for the multi-chain ones."""
+    shape = tuple(shape)
+    if device:
+        import torch
+        tdt = {np.float64: torch.float64, np.uint16: torch.int16, np.uint32: torch.int32}[dtype]
+        if out is None:
+            dev = e._device if e._device is not None and e._device >= 0 else torch.cuda.current_device()
+            out = torch.zeros(shape, dtype=tdt, device=torch.device("cuda", dev))
+            torch.cuda.current_stream(dev).synchronize()
+        assert out.is_cuda and out.is_contiguous() and out.dtype == tdt and tuple(out.shape) == shape
+        return out, out.data_ptr()
+    if out is None:
+        out = np.zeros(shape, dtype=dtype)
+    assert isinstance(out, np.ndarray) and out.dtype == dtype and out.flags.c_contiguous and out.shape == shape
+    return out, out.ctypes.data
+
+
 class Engine:
     """Owns one dangx context = one pixel shard on one MI355X."""
 
@@ -649,19 +671,10 @@ class Engine:
         and the AR(1) effective sample size ('ess' / 3).  Planes that are not selected keep what `out` holds (default zeros).
         device=True: a torch cuda tensor filled on the device (no host round trip)."""
         st = L.STAT_CODES[stat] if isinstance(stat, str) else int(stat)
+        out, ptr = _readout_dest(self, (self.nmaps, self.npix), device, out)
+        self._chk((self.lib.dangx_moments_get_dev if device else self.lib.dangx_moments_get)(self.h, l, int(what), st, int(ddof), ptr))
         if device:
-            import torch
-            if out is None:
-                dev = self._device if self._device is not None and self._device >= 0 else torch.cuda.current_device()
-                out = torch.zeros((self.nmaps, self.npix), dtype=torch.float64, device=torch.device("cuda", dev))
-            assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float64 and tuple(out.shape) == (self.nmaps, self.npix)
-            self._chk(self.lib.dangx_moments_get_dev(self.h, l, int(what), st, int(ddof), out.data_ptr()))
             self.synchronize()
-            return out
-        if out is None:
-            out = np.zeros((self.nmaps, self.npix))
-        assert isinstance(out, np.ndarray) and out.dtype == np.float64 and out.flags.c_contiguous and out.shape == (self.nmaps, self.npix)
-        self._chk(self.lib.dangx_moments_get(self.h, l, int(what), st, int(ddof), out.ctypes.data))
         return out
 
     def moments_get_template(self, l, stat, ddof=0, out=None):
@@ -686,19 +699,10 @@ class Engine:
         """Covariance ('cov' / 0: C / (n - ddof)) or correlation ('corr' / 1) of registered pair p as [npix]; NaN where a variance
         is zero.  device=True: a torch cuda tensor filled on the device."""
         st = L.PAIR_STAT_CODES[stat] if isinstance(stat, str) else int(stat)
+        out, ptr = _readout_dest(self, (self.npix,), device, out)
+        self._chk((self.lib.dangx_moments_get_pair_dev if device else self.lib.dangx_moments_get_pair)(self.h, int(p), st, int(ddof), ptr))
         if device:
-            import torch
-            if out is None:
-                dev = self._device if self._device is not None and self._device >= 0 else torch.cuda.current_device()
-                out = torch.zeros((self.npix,), dtype=torch.float64, device=torch.device("cuda", dev))
-            assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float64 and tuple(out.shape) == (self.npix,)
-            self._chk(self.lib.dangx_moments_get_pair_dev(self.h, int(p), st, int(ddof), out.data_ptr()))
             self.synchronize()
-            return out
-        if out is None:
-            out = np.zeros(self.npix)
-        assert isinstance(out, np.ndarray) and out.dtype == np.float64 and out.flags.c_contiguous and out.shape == (self.npix,)
-        self._chk(self.lib.dangx_moments_get_pair(self.h, int(p), st, int(ddof), out.ctypes.data))
         return out
 
     def moments_hist(self, planes, ranges=None, nbins=64, bits=16):
@@ -737,15 +741,10 @@ class Engine:
         """The raw counters [npix][nbins] of registration reg of this shard (uint16 / uint32); device=True: a torch cuda tensor
         (int16 / int32 holding the same bits: torch has no wider unsigned types everywhere)."""
         nbins, dt = self._hist_shape()
+        out, ptr = _readout_dest(self, (self.npix, nbins), device, dtype=dt)
+        self._chk((self.lib.dangx_moments_hist_get_dev if device else self.lib.dangx_moments_hist_get)(self.h, int(reg), ptr))
         if device:
-            import torch
-            dev = self._device if self._device is not None and self._device >= 0 else torch.cuda.current_device()
-            out = torch.zeros((self.npix, nbins), dtype=torch.int16 if dt is np.uint16 else torch.int32, device=torch.device("cuda", dev))
-            self._chk(self.lib.dangx_moments_hist_get_dev(self.h, int(reg), out.data_ptr()))
             self.synchronize()
-            return out
-        out = np.zeros((self.npix, nbins), dtype=dt)
-        self._chk(self.lib.dangx_moments_hist_get(self.h, int(reg), out.ctypes.data))
         return out
 
     def moments_hist_stat(self, reg, stat, q=None, device=False):
@@ -758,15 +757,10 @@ class Engine:
             raise DangxError("moments_hist_stat: a read-out takes 1 to %d quantiles" % L.MAX_HIST_Q)
         shape = (qa.size, self.npix) if st == 0 else (self.npix,)
         qp = qa.ctypes.data if qa.size else None
+        out, ptr = _readout_dest(self, shape, device)
+        self._chk((self.lib.dangx_moments_hist_stat_dev if device else self.lib.dangx_moments_hist_stat)(self.h, int(reg), st, qa.size, qp, ptr))
         if device:
-            import torch
-            dev = self._device if self._device is not None and self._device >= 0 else torch.cuda.current_device()
-            out = torch.zeros(shape, dtype=torch.float64, device=torch.device("cuda", dev))
-            self._chk(self.lib.dangx_moments_hist_stat_dev(self.h, int(reg), st, qa.size, qp, out.data_ptr()))
             self.synchronize()
-            return out
-        out = np.zeros(shape)
-        self._chk(self.lib.dangx_moments_hist_stat(self.h, int(reg), st, qa.size, qp, out.ctypes.data))
         return out
 
     def moments_signals(self, specs):
@@ -783,19 +777,10 @@ class Engine:
         """Mean ('mean' / 0) or standard deviation ('std' / 1, sqrt(m2 / (n - ddof))) of registered signal s as [npix].
         device=True: a torch cuda tensor filled on the device."""
         st = L.STAT_CODES[stat] if isinstance(stat, str) else int(stat)
+        out, ptr = _readout_dest(self, (self.npix,), device, out)
+        self._chk((self.lib.dangx_moments_get_signal_dev if device else self.lib.dangx_moments_get_signal)(self.h, int(s), st, int(ddof), ptr))
         if device:
-            import torch
-            if out is None:
-                dev = self._device if self._device is not None and self._device >= 0 else torch.cuda.current_device()
-                out = torch.zeros((self.npix,), dtype=torch.float64, device=torch.device("cuda", dev))
-            assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float64 and tuple(out.shape) == (self.npix,)
-            self._chk(self.lib.dangx_moments_get_signal_dev(self.h, int(s), st, int(ddof), out.data_ptr()))
             self.synchronize()
-            return out
-        if out is None:
-            out = np.zeros(self.npix)
-        assert isinstance(out, np.ndarray) and out.dtype == np.float64 and out.flags.c_contiguous and out.shape == (self.npix,)
-        self._chk(self.lib.dangx_moments_get_signal(self.h, int(s), st, int(ddof), out.ctypes.data))
         return out
 
     def moments_end(self):
@@ -1449,22 +1434,6 @@ def _chains_call(engines, fn, *args):
         raise DangxError(engines[0].lib.dangx_last_error(engines[0].h).decode())
 
 
-def _chains_out(e, shape, device, out):
-    """(array, pointer) of a read-out's destination: a float64 torch cuda tensor (device=True) or a numpy array, zeros by default."""
-    if device:
-        import torch
-        if out is None:
-            dev = e._device if e._device is not None and e._device >= 0 else torch.cuda.current_device()
-            out = torch.zeros(shape, dtype=torch.float64, device=torch.device("cuda", dev))
-            torch.cuda.current_stream(dev).synchronize()   # the fill runs on torch's stream, the read-out on the first chain's
-        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float64 and tuple(out.shape) == tuple(shape)
-        return out, out.data_ptr()
-    if out is None:
-        out = np.zeros(shape)
-    assert isinstance(out, np.ndarray) and out.dtype == np.float64 and out.flags.c_contiguous and out.shape == tuple(shape)
-    return out, out.ctypes.data
-
-
 def chains_get(engines, l, what, stat, ddof=0, device=False, out=None):
     """Over the chains `engines`: 'mean' / 0 = pooled mean, 'std' / 1 = pooled standard deviation sqrt(M / (N - ddof)), 'rhat' / 2 =
     Gelman-Rubin R-hat, 'W' / 3 = within-chain variance, 'B' / 4 = B/n, the variance of the chain means, 'ess' / 5 = the sum of the
@@ -1473,7 +1442,7 @@ def chains_get(engines, l, what, stat, ddof=0, device=False, out=None):
     written asynchronously on the first chain's stream (synchronize that engine, or use that stream, before reading it)."""
     e = engines[0]
     st = L.CHAINS_STAT_CODES[stat] if isinstance(stat, str) else int(stat)
-    out, ptr = _chains_out(e, (e.nmaps, e.npix), device, out)
+    out, ptr = _readout_dest(e, (e.nmaps, e.npix), device, out)
     _chains_call(engines, "dangx_chains_get_dev" if device else "dangx_chains_get", int(l), int(what), st, int(ddof), ptr)
     return out
 
@@ -1482,7 +1451,7 @@ def chains_get_template(engines, l, stat, ddof=0, out=None):
     """chains_get's statistics of the rows of c%template_amplitudes of a template / monopole / hi_fit member, [nmaps][nbands]."""
     e = engines[0]
     st = L.CHAINS_STAT_CODES[stat] if isinstance(stat, str) else int(stat)
-    out, ptr = _chains_out(e, (e.nmaps, e.nbands), False, out)
+    out, ptr = _readout_dest(e, (e.nmaps, e.nbands), False, out)
     _chains_call(engines, "dangx_chains_get_template", int(l), st, int(ddof), ptr)
     return out
 
@@ -1491,7 +1460,7 @@ def chains_get_signal(engines, s, stat, ddof=0, device=False, out=None):
     """chains_get's statistics 'mean', 'std', 'rhat', 'W', 'B' of registered signal s (the same registration in every chain), [npix]."""
     e = engines[0]
     st = L.CHAINS_STAT_CODES[stat] if isinstance(stat, str) else int(stat)
-    out, ptr = _chains_out(e, (e.npix,), device, out)
+    out, ptr = _readout_dest(e, (e.npix,), device, out)
     _chains_call(engines, "dangx_chains_get_signal_dev" if device else "dangx_chains_get_signal", int(s), st, int(ddof), ptr)
     return out
 
@@ -1500,7 +1469,7 @@ def chains_get_pair(engines, p, stat, ddof=0, device=False, out=None):
     """Pooled covariance ('cov' / 0: C / (N - ddof)) or correlation ('corr' / 1) of registered pair p over the chains, [npix]."""
     e = engines[0]
     st = L.PAIR_STAT_CODES[stat] if isinstance(stat, str) else int(stat)
-    out, ptr = _chains_out(e, (e.npix,), device, out)
+    out, ptr = _readout_dest(e, (e.npix,), device, out)
     _chains_call(engines, "dangx_chains_get_pair_dev" if device else "dangx_chains_get_pair", int(p), st, int(ddof), ptr)
     return out
 
@@ -1512,7 +1481,7 @@ def chains_hist_stat(engines, reg, stat, q=None, device=False, out=None):
     qa = np.ascontiguousarray(np.atleast_1d(np.asarray(q if q is not None else [], dtype=np.float64)))
     if st == 0 and not 1 <= qa.size <= L.MAX_HIST_Q:
         raise DangxError("chains_hist_stat: a read-out takes 1 to %d quantiles" % L.MAX_HIST_Q)
-    out, ptr = _chains_out(e, (qa.size, e.npix) if st == 0 else (e.npix,), device, out)
+    out, ptr = _readout_dest(e, (qa.size, e.npix) if st == 0 else (e.npix,), device, out)
     _chains_call(engines, "dangx_chains_hist_stat_dev" if device else "dangx_chains_hist_stat", int(reg), st, qa.size,
                  qa.ctypes.data if qa.size else None, ptr)
     return out

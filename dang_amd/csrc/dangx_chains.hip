@@ -1,0 +1,496 @@
+// dangx_chains.hip -- dangx_chains_*: read-outs over the accumulators of SEVERAL chains of one device (definitions in dx_chains_host.h).  Nothing here
+// touches an accumulator, a chain or a cache: three read-only kernels combine the per-chain planes and write only the map asked for.
+//   k_chains_stat  planes and signals (blockIdx.y = plane, up to three): pooled mean / std, R-hat, W, B/n read K x (mean, m2) --
+//                  a stat that does not use one of the two does not load it -- and write one f64: at most (2 K + 1) x 8 B per
+//                  element; the pooled ESS reads K x (mean, m2, prev, first, P), (5 K + 1) x 8 B.
+//   k_chains_pair  one pair: K x (mean_a, mean_b, C) for the covariance, + K x (m2_a, m2_b) for the correlation.
+//   k_chains_hist  a lane sums its pixel's K records piece by piece in 64-bit integers and takes k_hist_stat's steps on the sums.
+// The pointers of all chains travel by value (ChainsArgs + DxChainsPar: 1.3 KB of the 4 KB kernel-argument segment).  Pairs of elements are read
+// as 16 bytes where every pointer of a plane shares out's 16-byte phase, element by element otherwise (chains whose buffers were
+// adopted at different alignments; dx_stream.h); both forms evaluate the same header functions.  No LDS, no atomics, no scratch.
+// The chains' state is read through DxMoments' accessors (dx_moments_state.h); dangx_moments.hip accumulates it.
+#include "dx_moments_state.h"
+#include "dx_hist_host.h"
+#include "dx_chains_host.h"
+#include "dx_stream.h"
+
+static_assert(DX_CHAINS_MAX == DANGX_MAX_CHAINS, "dx_chains_host.h and include/dangx.h disagree");
+
+namespace {
+
+struct ChainsArgs {       // the pointer table of a plane / signal read-out; read through the kernel-argument segment (chains_kptr)
+    const double* mean[3][DX_CHAINS_MAX];
+    const double* m2[3][DX_CHAINS_MAX];
+    const double* prev[3][DX_CHAINS_MAX];    // DX_CH_ESS only
+    const double* first[3][DX_CHAINS_MAX];
+    const double* P[3][DX_CHAINS_MAX];
+    double* out[3];
+};
+static_assert(sizeof(ChainsArgs) + sizeof(DxChainsPar) <= 2048, "the arguments must stay well inside the 4 KB kernel-argument segment");
+// The table is indexed by blockIdx.y: read where the kernel arguments lie (scalar loads at a computed offset), never copied.
+// It is the kernels' FIRST argument, i.e. offset 0 of the segment.
+typedef const ChainsArgs __attribute__((address_space(4))) * chains_kptr;
+
+// V consecutive elements of plane p from element i on
+template <int V>
+__device__ __forceinline__ void chains_item(chains_kptr a, const DxChainsPar& par, int stat, int p, long long i) {
+    double r[V];
+    if (stat == DX_CH_ESS) {
+#pragma unroll
+        for (int e = 0; e < V; ++e) r[e] = 0.0;
+        dx_chains_each<0>(par.K, [&](auto kc) {
+            constexpr int k = decltype(kc)::value;
+            double m[V], q[V], pv[V], f[V], P[V];
+            ChV<V>::ld(a->mean[p][k] + i, m); ChV<V>::ld(a->m2[p][k] + i, q); ChV<V>::ld(a->prev[p][k] + i, pv);
+            ChV<V>::ld(a->first[p][k] + i, f); ChV<V>::ld(a->P[p][k] + i, P);
+#pragma unroll
+            for (int e = 0; e < V; ++e) r[e] = dx_chains_ess_add(r[e], m[e], q[e], pv[e], f[e], P[e], par.cnt[k]);
+        });
+    } else {
+        double mean[V][DX_CHAINS_MAX] = {}, m2[V][DX_CHAINS_MAX] = {};
+        const bool nm = dx_chains_needs_mean(stat), nq = dx_chains_needs_m2(stat);
+        dx_chains_each<0>(par.K, [&](auto kc) {
+            constexpr int k = decltype(kc)::value;
+            double m[V] = {}, q[V] = {};
+            if (nm) ChV<V>::ld(a->mean[p][k] + i, m);
+            if (nq) ChV<V>::ld(a->m2[p][k] + i, q);
+#pragma unroll
+            for (int e = 0; e < V; ++e) { mean[e][k] = m[e]; m2[e][k] = q[e]; }
+        });
+#pragma unroll
+        for (int e = 0; e < V; ++e) r[e] = dx_chains_stat(stat, par, mean[e], m2[e]);
+    }
+    ChV<V>::st(a->out[p] + i, r);
+}
+
+__global__ __launch_bounds__(BLOCK) void k_chains_stat(ChainsArgs, DxChainsPar par, long long n, int stat) {
+    const chains_kptr a = (chains_kptr)__builtin_amdgcn_kernarg_segment_ptr();
+    const int p = blockIdx.y;
+    const long long gid = (long long)blockIdx.x * BLOCK + threadIdx.x, stride = (long long)gridDim.x * BLOCK;
+    const uintptr_t ao = addr(a->out[p]);
+    uintptr_t diff = ao & 7;   // out not even at a double's alignment: element by element
+    const bool ess = stat == DX_CH_ESS;
+    dx_chains_each<0>(par.K, [&](auto kc) {
+        constexpr int k = decltype(kc)::value;
+        diff |= (ao ^ addr(a->mean[p][k])) | (ao ^ addr(a->m2[p][k]));
+        if (ess) diff |= (ao ^ addr(a->prev[p][k])) | (ao ^ addr(a->first[p][k])) | (ao ^ addr(a->P[p][k]));
+    });
+    // dx_stream's loop written out: through dx_stream this kernel compiled to fewer instructions (5618 for 5788) at the same
+    // registers and occupancy, but its R-hat and ESS read-outs at Nside 1024 measured 2 % slower than this form, more than the
+    // spread of this form's rounds ("Posterior moments on the device")
+    if ((diff & 15) != 0) {
+        for (long long i = gid; i < n; i += stride) chains_item<1>(a, par, stat, p, i);
+        return;
+    }
+    const long long head = ((ao & 15) != 0 && n > 0) ? 1 : 0;
+    const long long npair = (n - head) / 2, tail = head + 2 * npair;   // tail < n: one element after the last pair
+    if (gid == 0 && head) chains_item<1>(a, par, stat, p, 0);
+    if (gid == 1 && tail < n) chains_item<1>(a, par, stat, p, tail);
+    for (long long t = gid; t < npair; t += stride) chains_item<2>(a, par, stat, p, head + 2 * t);
+}
+
+struct ChainsPairArgs {
+    const double* ma[DX_CHAINS_MAX];
+    const double* mb[DX_CHAINS_MAX];
+    const double* qa[DX_CHAINS_MAX];
+    const double* qb[DX_CHAINS_MAX];
+    const double* C[DX_CHAINS_MAX];
+    double* out;
+};
+
+template <int V>
+__device__ __forceinline__ void chains_pair_item(const ChainsPairArgs& a, const DxChainsPar& par, int stat, long long i) {
+    double ma[V][DX_CHAINS_MAX] = {}, mb[V][DX_CHAINS_MAX] = {}, qa[V][DX_CHAINS_MAX] = {}, qb[V][DX_CHAINS_MAX] = {}, C[V][DX_CHAINS_MAX] = {};
+    dx_chains_each<0>(par.K, [&](auto kc) {
+        constexpr int k = decltype(kc)::value;
+        double va[V], vb[V], vc[V], wa[V] = {}, wb[V] = {};
+        ChV<V>::ld(a.ma[k] + i, va); ChV<V>::ld(a.mb[k] + i, vb); ChV<V>::ld(a.C[k] + i, vc);
+        if (stat) { ChV<V>::ld(a.qa[k] + i, wa); ChV<V>::ld(a.qb[k] + i, wb); }
+#pragma unroll
+        for (int e = 0; e < V; ++e) { ma[e][k] = va[e]; mb[e][k] = vb[e]; qa[e][k] = wa[e]; qb[e][k] = wb[e]; C[e][k] = vc[e]; }
+    });
+    double r[V];
+#pragma unroll
+    for (int e = 0; e < V; ++e) r[e] = dx_chains_pair(stat, par, ma[e], mb[e], qa[e], qb[e], C[e]);
+    ChV<V>::st(a.out + i, r);
+}
+
+__global__ __launch_bounds__(BLOCK) void k_chains_pair(ChainsPairArgs a, DxChainsPar par, long long n, int stat) {
+    const uintptr_t ao = addr(a.out);
+    uintptr_t diff = ao & 7;
+    dx_chains_each<0>(par.K, [&](auto kc) {
+        constexpr int k = decltype(kc)::value;
+        diff |= (ao ^ addr(a.ma[k])) | (ao ^ addr(a.mb[k])) | (ao ^ addr(a.qa[k])) | (ao ^ addr(a.qb[k])) | (ao ^ addr(a.C[k]));
+    });
+    // element by element where the two planes (or a chain's adopted buffers) are at different 16-byte phases
+    dx_stream(n, (diff & 15) == 0, ao, [&](long long i) { chains_pair_item<1>(a, par, stat, i); },
+              [&](long long i) { chains_pair_item<2>(a, par, stat, i); });
+}
+
+struct ChainsHistArgs {
+    const uint32_t* rec[DX_CHAINS_MAX];
+    double q[DX_HIST_MAX_Q];
+    double* out;          // [nq][n] (stat 0) or [n]
+    double lo, hi;
+    long long n;
+    int K, nbins, bits, stat, nq;
+};
+
+// hist_walk over the SUM of the K records of pixel i: a 16-byte piece of every chain, its 4 or 8 counters summed in 64 bits,
+// then f(count, bin) per bin in bin order until f says stop
+template <class F>
+__device__ __forceinline__ void chains_hist_walk(const ChainsHistArgs& a, long long i, int pieces, F f) {
+    int b = 0;
+    for (int p = 0; p < pieces; ++p) {
+        unsigned long long c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (int k = 0; k < DX_CHAINS_MAX; ++k)
+            if (k < a.K) {
+                const u32x4 v = ((const GU4*)a.rec[k])[i * pieces + p];
+                const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (a.bits == 16) { c[2 * j] += w[j] & 0xffffu; c[2 * j + 1] += w[j] >> 16; }
+                    else c[j] += w[j];
+                }
+            }
+        const int nb = a.bits == 16 ? 8 : 4;
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (j < nb && f(c[j], b + j)) return;
+        b += nb;
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void k_chains_hist(ChainsHistArgs a) {
+    const int pieces = dx_hist_words(a.nbins, a.bits) / 4;
+    dx_hist_readout<unsigned long long>(a, [&](long long i, auto f) { chains_hist_walk(a, i, pieces, f); });
+}
+
+// ---- host side
+
+struct ChainSet {
+    dangx_ctx* const* c;
+    int K;
+    long long cnt[DX_CHAINS_MAX];
+};
+
+int chains_fail(dangx_ctx* const* ctxs, const std::string& msg) { return fail(ctxs[0], "posterior chains: " + msg); }
+
+// the checks every read-out shares; on success cs describes the set
+int chains_open(dangx_ctx* const* ctxs, int nchains, ChainSet& cs) {
+    if (!ctxs || !ctxs[0]) return 1;
+    if (nchains < 2 || nchains > DX_CHAINS_MAX)
+        return chains_fail(ctxs, "nchains must be 2 .. DANGX_MAX_CHAINS (" + std::to_string(DX_CHAINS_MAX) + "), not " + std::to_string(nchains));
+    for (int k = 1; k < nchains; ++k)
+        if (!ctxs[k]) return chains_fail(ctxs, "chain " + std::to_string(k) + " is a null context");
+    const dangx_ctx* c0 = ctxs[0];
+    for (int k = 1; k < nchains; ++k) {
+        const dangx_ctx* c = ctxs[k];
+        const std::string at = "chain " + std::to_string(k);
+        for (int o = 0; o < k; ++o)
+            if (ctxs[o] == c) return chains_fail(ctxs, at + " is the same context as chain " + std::to_string(o) + " (a context listed twice)");
+        if (c->device != c0->device)
+            return chains_fail(ctxs, at + " lives on device " + std::to_string(c->device) + ", chain 0 on device " + std::to_string(c0->device) +
+                                         ": chains on different devices are not supported");
+        if (c->dims.npix != c0->dims.npix || c->dims.pix0 != c0->dims.pix0 || c->dims.nmaps != c0->dims.nmaps)
+            return chains_fail(ctxs, at + " differs from chain 0 in npix / pix0 / nmaps");
+    }
+    for (int k = 0; k < nchains; ++k) {
+        if (!ctxs[k]->mom) return chains_fail(ctxs, "chain " + std::to_string(k) + ": dangx_moments_begin was not called");
+        if (ctxs[k]->mom->count == 0) return chains_fail(ctxs, "chain " + std::to_string(k) + ": no sample accumulated");
+        cs.cnt[k] = ctxs[k]->mom->count;
+    }
+    cs.c = ctxs;
+    cs.K = nchains;
+    return 0;
+}
+
+int chains_counts(const ChainSet& cs, int stat, int ddof, bool is_pair) {
+    const std::string why = dx_chains_count_check(cs.K, cs.cnt, stat, ddof, is_pair);
+    return why.empty() ? 0 : chains_fail(cs.c, why);
+}
+
+int chains_need_lag(const ChainSet& cs) {
+    for (int k = 0; k < cs.K; ++k)
+        if (!cs.c[k]->mom->lag1)
+            return chains_fail(cs.c, "chain " + std::to_string(k) + ": the lag-1 autocorrelation is not tracked (dangx_moments_pairs with lag1 != 0 was not called)");
+    return 0;
+}
+
+// the selected planes of (comp, what): those of chain 0, which every other chain must have selected too
+int chains_planes(const ChainSet& cs, int comp, int what, int stat, unsigned& planes) {
+    if (what < 0 || what > DANGX_MAX_IND) return chains_fail(cs.c, "what must be 0 (amplitude) or 1 + index number");
+    if (stat < DX_CH_MEAN || stat > DX_CH_ESS)
+        return chains_fail(cs.c, "stat must be 0 (pooled mean), 1 (pooled std), 2 (R-hat), 3 (W), 4 (B/n) or 5 (pooled ESS)");
+    for (int k = 0; k < cs.K; ++k) {
+        const dangx_ctx* c = cs.c[k];
+        if (comp < 0 || comp >= c->dims.ncomp) return chains_fail(cs.c, "chain " + std::to_string(k) + ": component index out of range");
+        const unsigned pk = (unsigned)(c->mom->sel[comp] >> (what == 0 ? 0 : 3 + 3 * (what - 1))) & 7u;
+        if (k == 0) planes = pk;
+        if (!pk || (pk & planes) != planes)
+            return chains_fail(cs.c, "chain " + std::to_string(k) + ": a plane of this component and what is not selected");
+        if (is_global_type(c->desc[comp].type) != is_global_type(cs.c[0]->desc[comp].type))
+            return chains_fail(cs.c, "chain " + std::to_string(k) + ": the component is of another kind than in chain 0");
+    }
+    if (stat == DX_CH_ESS && chains_need_lag(cs)) return 1;
+    return 0;
+}
+
+// every other chain's stream before stream 0 ...
+int chains_join(const ChainSet& cs) {
+    dangx_ctx* c0 = cs.c[0];
+    for (int k = 1; k < cs.K; ++k) {
+        dangx_ctx* c = cs.c[k];
+        if (c->stream == c0->stream) continue;
+        DxMoments* m = c->mom;
+        if (!m->chain_ev) HIPCHK(c0, hipEventCreateWithFlags(&m->chain_ev, hipEventDisableTiming));
+        HIPCHK(c0, hipEventRecord(m->chain_ev, c->stream));
+        HIPCHK(c0, hipStreamWaitEvent(c0->stream, m->chain_ev, 0));
+    }
+    return 0;
+}
+
+// ... and stream 0 before whatever the other streams do next: a following accumulation cannot overwrite what the kernel reads
+int chains_release(const ChainSet& cs) {
+    dangx_ctx* c0 = cs.c[0];
+    DxMoments* m0 = c0->mom;
+    bool any = false;
+    for (int k = 1; k < cs.K; ++k) any = any || cs.c[k]->stream != c0->stream;
+    if (!any) return 0;
+    if (!m0->chain_ev) HIPCHK(c0, hipEventCreateWithFlags(&m0->chain_ev, hipEventDisableTiming));
+    HIPCHK(c0, hipEventRecord(m0->chain_ev, c0->stream));
+    for (int k = 1; k < cs.K; ++k)
+        if (cs.c[k]->stream != c0->stream) HIPCHK(c0, hipStreamWaitEvent(cs.c[k]->stream, m0->chain_ev, 0));
+    return 0;
+}
+
+// k_chains_stat on stream 0 between the two joins; a.mean .. a.out of np planes are filled in
+int chains_launch(const ChainSet& cs, const ChainsArgs& a, int np, int stat, int ddof) {
+    dangx_ctx* c0 = cs.c[0];
+    const long long n = c0->dims.npix;
+    const DxChainsPar par = dx_chains_par(cs.K, cs.cnt, ddof);
+    if (chains_join(cs)) return 1;
+    {
+        Timed tm(c0, DANGX_K_CHAINS);
+        hipLaunchKernelGGL(k_chains_stat, dim3(c0->mom->grid_for((n + 1) / 2, np), np), dim3(BLOCK), 0, c0->stream, a, par, n, stat);
+        HIPCHK(c0, hipGetLastError());
+    }
+    return chains_release(cs);
+}
+
+// Every read-out is one implementation; `out` is a device buffer, or with to_host a host array staged through chain 0 (ReadOut).
+int chains_get_impl(dangx_ctx* const* ctxs, int nchains, int comp, int what, int stat, int ddof, double* out, bool to_host) {
+    if (!ctxs || !ctxs[0] || !out) return 1;
+    ChainSet cs{};
+    unsigned planes = 0;
+    if (chains_open(ctxs, nchains, cs) || chains_planes(cs, comp, what, stat, planes) || chains_counts(cs, stat, ddof, false)) return 1;
+    dangx_ctx* c0 = ctxs[0];
+    if (what == 0 && is_global_type(c0->desc[comp].type))
+        return chains_fail(ctxs, "a template / monopole / hi_fit amplitude is read with dangx_chains_get_template");
+    (void)hipSetDevice(c0->device);
+    const long long np = c0->dims.npix;
+    ReadOut ro{c0, out, to_host};
+    if (ro.open(sizeof(double) * (size_t)np * c0->dims.nmaps)) return 1;
+    ChainsArgs a{};
+    int n = 0;
+    for (int k = 0; k < c0->dims.nmaps; ++k) {
+        if (!((planes >> k) & 1u)) continue;
+        for (int j = 0; j < cs.K; ++j) {
+            const DxMoments* m = ctxs[j]->mom;
+            const int i = m->find_seg(comp, what, k);
+            if (i < 0) return chains_fail(ctxs, "chain " + std::to_string(j) + ": a plane of this component and what is not selected");
+            const auto& s = m->segs[i];
+            a.mean[n][j] = m->mean(s);
+            a.m2[n][j] = m->m2(s);
+            if (stat == DX_CH_ESS) { a.prev[n][j] = m->prev(s); a.first[n][j] = m->first(s); a.P[n][j] = m->P(s); }
+        }
+        a.out[n] = ro.dst + (long long)k * np;
+        ++n;
+    }
+    if (chains_launch(cs, a, n, stat, ddof)) return 1;
+    return ro.close(planes, c0->dims.nmaps, np, c0->host_stride > 0 ? c0->host_stride : np);
+}
+
+int chains_signal_impl(dangx_ctx* const* ctxs, int nchains, int sig, int stat, int ddof, double* out, bool to_host) {
+    if (!ctxs || !ctxs[0] || !out) return 1;
+    ChainSet cs{};
+    if (chains_open(ctxs, nchains, cs)) return 1;
+    if (stat < DX_CH_MEAN || stat > DX_CH_BN)
+        return chains_fail(ctxs, "the stat of a signal must be 0 (pooled mean), 1 (pooled std), 2 (R-hat), 3 (W) or 4 (B/n)");
+    const auto& s0 = ctxs[0]->mom->sigs;
+    if (sig < 0 || sig >= (int)s0.size())
+        return chains_fail(ctxs, "chain 0: signal index out of range (" + std::to_string(s0.size()) + " signals registered)");
+    for (int k = 1; k < nchains; ++k) {
+        const auto& sk = ctxs[k]->mom->sigs;
+        if (sig >= (int)sk.size() || sk[sig].comp != s0[sig].comp || sk[sig].band != s0[sig].band || sk[sig].kind != s0[sig].kind)
+            return chains_fail(ctxs, "chain " + std::to_string(k) + ": signal " + std::to_string(sig) + " is not the registration of chain 0");
+    }
+    if (chains_counts(cs, stat, ddof, false)) return 1;
+    dangx_ctx* c0 = ctxs[0];
+    (void)hipSetDevice(c0->device);
+    const long long n = c0->dims.npix;
+    ReadOut ro{c0, out, to_host};
+    if (ro.open(sizeof(double) * (size_t)n)) return 1;
+    ChainsArgs a{};
+    for (int j = 0; j < cs.K; ++j) {
+        const DxMoments* m = ctxs[j]->mom;
+        a.mean[0][j] = m->mean(m->sigs[sig]);
+        a.m2[0][j] = m->m2(m->sigs[sig]);
+    }
+    a.out[0] = ro.dst;
+    if (chains_launch(cs, a, 1, stat, ddof)) return 1;
+    return ro.close(n);
+}
+
+int chains_pair_impl(dangx_ctx* const* ctxs, int nchains, int pair, int stat, int ddof, double* out, bool to_host) {
+    if (!ctxs || !ctxs[0] || !out) return 1;
+    ChainSet cs{};
+    if (chains_open(ctxs, nchains, cs)) return 1;
+    if (stat != 0 && stat != 1) return chains_fail(ctxs, "the stat of a pair must be 0 (covariance) or 1 (correlation)");
+    const DxMoments* m0 = ctxs[0]->mom;
+    if (pair < 0 || pair >= (int)m0->pairs.size())
+        return chains_fail(ctxs, "chain 0: pair index out of range (" + std::to_string(m0->pairs.size()) + " pairs registered)");
+    for (int k = 1; k < nchains; ++k) {
+        const DxMoments* m = ctxs[k]->mom;
+        if (pair >= (int)m->pairs.size() || !same_plane(m->segs[m->pairs[pair].a], m0->segs[m0->pairs[pair].a]) ||
+            !same_plane(m->segs[m->pairs[pair].b], m0->segs[m0->pairs[pair].b]))
+            return chains_fail(ctxs, "chain " + std::to_string(k) + ": pair " + std::to_string(pair) + " is not the registration of chain 0");
+    }
+    if (chains_counts(cs, stat, ddof, true)) return 1;
+    dangx_ctx* c0 = ctxs[0];
+    (void)hipSetDevice(c0->device);
+    const long long n = c0->dims.npix;
+    ReadOut ro{c0, out, to_host};
+    if (ro.open(sizeof(double) * (size_t)n)) return 1;
+    ChainsPairArgs a{};
+    for (int j = 0; j < cs.K; ++j) {
+        const DxMoments* m = ctxs[j]->mom;
+        const auto& p = m->pairs[pair];
+        const auto &sa = m->segs[p.a], &sb = m->segs[p.b];
+        a.ma[j] = m->mean(sa); a.mb[j] = m->mean(sb);
+        a.qa[j] = m->m2(sa); a.qb[j] = m->m2(sb);
+        a.C[j] = m->C(p);
+    }
+    a.out = ro.dst;
+    const DxChainsPar par = dx_chains_par(cs.K, cs.cnt, ddof);
+    if (chains_join(cs)) return 1;
+    {
+        Timed tm(c0, DANGX_K_CHAINS);
+        hipLaunchKernelGGL(k_chains_pair, dim3(c0->mom->grid_for((n + 1) / 2, 1)), dim3(BLOCK), 0, c0->stream, a, par, n, stat);
+        HIPCHK(c0, hipGetLastError());
+    }
+    if (chains_release(cs)) return 1;
+    return ro.close(n);
+}
+
+int chains_hist_impl(dangx_ctx* const* ctxs, int nchains, int reg, int stat, int nq, const double* q, double* out, bool to_host) {
+    if (!ctxs || !ctxs[0] || !out) return 1;
+    ChainSet cs{};
+    if (chains_open(ctxs, nchains, cs)) return 1;
+    const DxMoments* m0 = ctxs[0]->mom;
+    if (reg < 0 || reg >= (int)m0->hists.size())
+        return chains_fail(ctxs, "chain 0: histogram registration out of range (" + std::to_string(m0->hists.size()) + " registered)");
+    for (int k = 1; k < nchains; ++k) {
+        const DxMoments* m = ctxs[k]->mom;
+        bool same = reg < (int)m->hists.size() && m->hbins == m0->hbins && m->hbits == m0->hbits;
+        if (same) {
+            const auto &h = m->hists[reg], &h0 = m0->hists[reg];
+            same = same_plane(m->segs[h.seg], m0->segs[h0.seg]) && h.lo == h0.lo && h.hi == h0.hi;
+        }
+        if (!same)
+            return chains_fail(ctxs, "chain " + std::to_string(k) + ": histogram registration " + std::to_string(reg) +
+                                         " is not the registration of chain 0 (plane, lo, hi, nbins and bits must agree)");
+    }
+    dangx_ctx* c0 = ctxs[0];
+    if (dx_hist_stat_check(c0, reg, stat, nq, q)) return 1;
+    (void)hipSetDevice(c0->device);
+    const long long total = (long long)c0->dims.npix * (stat == 0 ? nq : 1);
+    ReadOut ro{c0, out, to_host};
+    if (ro.open(sizeof(double) * (size_t)total)) return 1;
+    ChainsHistArgs a{};
+    for (int j = 0; j < cs.K; ++j) a.rec[j] = ctxs[j]->mom->records(ctxs[j]->mom->hists[reg]);
+    a.out = ro.dst; a.lo = m0->hists[reg].lo; a.hi = m0->hists[reg].hi; a.n = c0->dims.npix;
+    a.K = cs.K; a.nbins = m0->hbins; a.bits = m0->hbits; a.stat = stat; a.nq = stat == 0 ? nq : 0;
+    for (int j = 0; j < a.nq; ++j) a.q[j] = q[j];
+    if (chains_join(cs)) return 1;
+    {
+        Timed tm(c0, DANGX_K_CHAINS);
+        hipLaunchKernelGGL(k_chains_hist, dim3(c0->mom->grid_for(a.n, 1)), dim3(BLOCK), 0, c0->stream, a);
+        HIPCHK(c0, hipGetLastError());
+    }
+    if (chains_release(cs)) return 1;
+    return ro.close(total);
+}
+
+}  // namespace
+
+extern "C" {
+
+int dangx_chains_get_dev(dangx_ctx* const* ctxs, int nchains, int comp, int what, int stat, int ddof, double* out_dev) {
+    return chains_get_impl(ctxs, nchains, comp, what, stat, ddof, out_dev, false);
+}
+
+int dangx_chains_get(dangx_ctx* const* ctxs, int nchains, int comp, int what, int stat, int ddof, double* out) {
+    return chains_get_impl(ctxs, nchains, comp, what, stat, ddof, out, true);
+}
+
+int dangx_chains_get_template(dangx_ctx* const* ctxs, int nchains, int comp, int stat, int ddof, double* ta) {
+    if (!ctxs || !ctxs[0] || !ta) return 1;
+    ChainSet cs{};
+    unsigned planes = 0;
+    if (chains_open(ctxs, nchains, cs) || chains_planes(cs, comp, 0, stat, planes) || chains_counts(cs, stat, ddof, false)) return 1;
+    const dangx_ctx* c0 = ctxs[0];
+    if (!is_global_type(c0->desc[comp].type)) return chains_fail(ctxs, "not a template / monopole / hi_fit component");
+    for (int k = 1; k < nchains; ++k)
+        if (ctxs[k]->dims.nbands != c0->dims.nbands) return chains_fail(ctxs, "chain " + std::to_string(k) + " differs from chain 0 in nbands");
+    const DxChainsPar par = dx_chains_par(cs.K, cs.cnt, ddof);
+    for (int k = 0; k < c0->dims.nmaps; ++k) {
+        if (!((planes >> k) & 1u)) continue;
+        for (int j = 0; j < c0->dims.nbands; ++j) {
+            double v = 0.0;
+            if (stat == DX_CH_ESS) {
+                for (int i = 0; i < cs.K; ++i) {
+                    const DxMoments* m = ctxs[i]->mom;
+                    v = dx_chains_ess_add(v, m->tm_mean[comp][k][j], m->tm_m2[comp][k][j], m->tm_prev[comp][k][j], m->tm_first[comp][k][j],
+                                          m->tm_P[comp][k][j], par.cnt[i]);
+                }
+            } else {
+                double mean[DX_CHAINS_MAX] = {}, m2[DX_CHAINS_MAX] = {};
+                for (int i = 0; i < cs.K; ++i) {
+                    mean[i] = ctxs[i]->mom->tm_mean[comp][k][j];
+                    m2[i] = ctxs[i]->mom->tm_m2[comp][k][j];
+                }
+                v = dx_chains_stat(stat, par, mean, m2);
+            }
+            ta[k * c0->dims.nbands + j] = v;
+        }
+    }
+    return 0;
+}
+
+int dangx_chains_get_signal_dev(dangx_ctx* const* ctxs, int nchains, int sig, int stat, int ddof, double* out_dev) {
+    return chains_signal_impl(ctxs, nchains, sig, stat, ddof, out_dev, false);
+}
+
+int dangx_chains_get_signal(dangx_ctx* const* ctxs, int nchains, int sig, int stat, int ddof, double* out) {
+    return chains_signal_impl(ctxs, nchains, sig, stat, ddof, out, true);
+}
+
+int dangx_chains_get_pair_dev(dangx_ctx* const* ctxs, int nchains, int pair, int stat, int ddof, double* out_dev) {
+    return chains_pair_impl(ctxs, nchains, pair, stat, ddof, out_dev, false);
+}
+
+int dangx_chains_get_pair(dangx_ctx* const* ctxs, int nchains, int pair, int stat, int ddof, double* out) {
+    return chains_pair_impl(ctxs, nchains, pair, stat, ddof, out, true);
+}
+
+int dangx_chains_hist_stat_dev(dangx_ctx* const* ctxs, int nchains, int reg, int stat, int nq, const double* q, double* out_dev) {
+    return chains_hist_impl(ctxs, nchains, reg, stat, nq, q, out_dev, false);
+}
+
+int dangx_chains_hist_stat(dangx_ctx* const* ctxs, int nchains, int reg, int stat, int nq, const double* q, double* out) {
+    return chains_hist_impl(ctxs, nchains, reg, stat, nq, q, out, true);
+}
+
+}  // extern "C"

@@ -17,7 +17,7 @@
 #include "../../include/dangx.h"
 #include "dx_args.h"
 
-struct DxMoments;   // posterior-moment accumulators (dangx_moments.hip)
+struct DxMoments;   // posterior-moment accumulators (dx_moments_state.h: written by dangx_moments.hip, read by dangx_chains.hip)
 
 struct dangx_ctx {
     dangx_dims dims{};

@@ -1,0 +1,215 @@
+// dx_moments_state.h -- host: the state behind dangx_moments_* (dangx_moments.hip, which writes it) and dangx_chains_*
+// (dangx_chains.hip, which only reads it): the registrations, the device allocations that hold their accumulators and the one
+// vocabulary for the addresses inside them, plus the helpers every read-out shares.
+#pragma once
+#include "dx_host.h"
+#include "dx_signal_host.h"
+
+#include <cstdint>
+#include <utility>
+
+// ---- the tables the accumulation kernels read
+
+struct MomSeg {           // one selected plane: the chain's plane (resolved at accumulate time) and its two accumulators
+    const double* x;
+    double* mean;
+    double* m2;
+    long long n;
+};
+
+struct LagSeg {           // a selected plane with lag-1 tracking: MomSeg + previous sample, first sample, P
+    const double* x;
+    double* mean;
+    double* m2;
+    double* prev;
+    double* first;
+    double* P;
+    long long n;
+};
+
+struct PairSeg {          // a pair of selected planes and its cross-term accumulator
+    const double* xa;
+    const double* xb;
+    const double* ma;
+    const double* mb;
+    double* C;
+    long long n;
+};
+
+struct HistSeg {          // one registered histogram: the chain's plane (resolved at accumulate time) and its records
+    const double* x;
+    uint32_t* rec;        // [n][words] 32-bit words, 256-byte aligned
+    double lo, hi, scale;
+    long long n;
+    int nbins, bits;
+};
+
+struct SigBand {          // one band of a signal segment: the accumulators of its outputs (slot 0..2: T, or Q, U, P), null = not wanted
+    double* mean[3];
+    double* m2[3];
+    int band;
+    unsigned want;        // bit o: output slot o is registered
+};
+
+struct SigSeg {           // a (component, plane class) with up to DX_SIG_SEG_BANDS bands; the chain's planes resolved at accumulate time
+    const double* amp;    // the component's [nmaps][npix]: what the table is compared by
+    const double* idx;    // the component's [nind][nmaps][npix]
+    // src[k][0..2]: the amplitude and the two index planes of plane k of the class.  A plane the component does not have (an index
+    // beyond nindices) or no output needs points at a plane that IS read: the load hits the cache and its value is never used
+    const double* src[2][3];
+    long long n;
+    int comp, k0, np, nb; // k0: first plane (1-based) of the class, np: planes of the class (1: T, 2: Q+U)
+    int vec, nind;        // nind: indices of the component (load_theta: an index beyond it is 0.0).  vec 0: element by element; 1 / 2: pairs of pixels, every plane read and every accumulator at 16-byte phase 0 / 8
+    SigBand b[DX_SIG_SEG_BANDS];
+};
+
+// ---- device memory that belongs to its holder: freed when the holder goes, handed on by move
+
+struct DevStatus {        // the first HIP call of a sequence that failed (`what` names it); later calls of the sequence do nothing
+    hipError_t e = hipSuccess;
+    const char* what = "";
+    bool ok() const { return e == hipSuccess; }
+    void sync(hipStream_t s) {
+        if (!ok()) return;
+        what = "hipStreamSynchronize";
+        e = hipStreamSynchronize(s);
+    }
+    int fail(dangx_ctx* ctx, const char* where) const {   // where: "" or "dangx_moments_xyz: "
+        ctx->err = std::string("posterior moments: ") + where + what + ": " + hipGetErrorString(e);
+        return 1;
+    }
+};
+
+template <class T>
+struct DevBuf {
+    T* p = nullptr;
+    DevBuf() = default;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    DevBuf(DevBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
+    DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p, o.p); return *this; }   // what this held dies with o
+    operator T*() const { return p; }
+    void alloc(size_t count, DevStatus& st) {
+        if (!st.ok()) return;
+        st.what = "hipMalloc";
+        st.e = hipMalloc(&p, sizeof(T) * count);
+    }
+    void zeros(size_t count, hipStream_t s, DevStatus& st) {   // the fill is enqueued on s: the caller waits (DevStatus::sync)
+        alloc(count, st);
+        if (!st.ok()) return;
+        st.what = "hipMemsetAsync";
+        st.e = hipMemsetAsync(p, 0, sizeof(T) * count, s);
+    }
+};
+
+struct DxMoments {
+    int32_t sel[MAXC] = {};          // effective selection (bits as in include/dangx.h)
+    int type[MAXC] = {}, nind[MAXC] = {};  // shape key recorded at begin
+    struct Seg { int comp, what, plane; long long off; };
+    std::vector<Seg> segs;
+    std::vector<MomSeg> table;       // the table as last uploaded
+    DevBuf<MomSeg> d_table;
+    DevBuf<double> acc;              // [mean: acc_half doubles | m2: acc_half doubles]
+    long long acc_half = 0;
+    long long count = 0;
+    double tm_mean[MAXC][3][MAXB] = {}, tm_m2[MAXC][3][MAXB] = {};
+    DevBuf<double> scratch;          // what the host form of a read-out copies from; grows on demand (ReadOut)
+    size_t scratch_bytes = 0;
+    unsigned grid_target = 0;        // blocks of a full-machine launch
+    // dangx_moments_pairs
+    bool lag1 = false;
+    DevBuf<double> lag;              // [prev | first | P], acc_half doubles each, planes at the offsets of acc
+    DevBuf<LagSeg> d_lag;
+    struct Pair { int a, b; long long off; };   // indices into segs; off: the pair's plane in pc (at the phase of a's mean)
+    std::vector<Pair> pairs;
+    DevBuf<double> pc;
+    DevBuf<PairSeg> d_pairs;
+    double tm_prev[MAXC][3][MAXB] = {}, tm_first[MAXC][3][MAXB] = {}, tm_P[MAXC][3][MAXB] = {};
+    // dangx_moments_hist
+    struct Hist { int seg; double lo, hi; long long off; };   // seg: index into segs; off: the records' first word in hrec
+    std::vector<Hist> hists;
+    int hbins = 0, hbits = 0;
+    DevBuf<uint32_t> hrec;           // every registration's records, each block at a multiple of 256 bytes
+    DevBuf<HistSeg> d_hist;
+    // dangx_moments_signals
+    struct Sig { int comp, band, kind; long long off; };   // off: the signal's mean plane in sacc
+    std::vector<Sig> sigs;
+    std::vector<DxSigSeg> sig_plan;
+    int sig_type[MAXC] = {}, sig_nind[MAXC] = {};   // shape key of the registered components at registration
+    bool sig_used[MAXC] = {};
+    std::vector<SigSeg> sig_table;   // the table as last uploaded
+    DevBuf<SigSeg> d_sig;
+    DevBuf<double> sacc;             // [mean: sacc_half doubles | m2: sacc_half doubles]
+    long long sacc_half = 0;
+    // dangx_chains_*: orders this chain's stream against the stream of the chain set's first context (created on first use)
+    hipEvent_t chain_ev = nullptr;
+
+    DxMoments() = default;
+    DxMoments(const DxMoments&) = delete;
+    DxMoments& operator=(const DxMoments&) = delete;
+    ~DxMoments() { if (chain_ev) (void)hipEventDestroy(chain_ev); }
+
+    // where things are
+    double* mean(const Seg& s) const { return acc + s.off; }
+    double* m2(const Seg& s) const { return acc + acc_half + s.off; }
+    double* prev(const Seg& s) const { return lag + s.off; }
+    double* first(const Seg& s) const { return lag + acc_half + s.off; }
+    double* P(const Seg& s) const { return lag + 2 * acc_half + s.off; }
+    double* C(const Pair& p) const { return pc + p.off; }
+    double* mean(const Sig& s) const { return sacc + s.off; }
+    double* m2(const Sig& s) const { return sacc + sacc_half + s.off; }
+    uint32_t* records(const Hist& h) const { return hrec + h.off; }
+    int find_seg(int comp, int what, int plane) const {   // index into segs, -1: not selected
+        for (size_t i = 0; i < segs.size(); ++i)
+            if (segs[i].comp == comp && segs[i].what == what && segs[i].plane == plane) return (int)i;
+        return -1;
+    }
+    // blocks per row of a launch of `rows` rows (blockIdx.y) over `items` items each: together about one full machine
+    unsigned grid_for(long long items, unsigned rows) const { return std::max(1u, std::min(nblocks(items), (grid_target + rows - 1) / rows)); }
+};
+
+inline bool same_plane(const DxMoments::Seg& x, const DxMoments::Seg& y) { return x.comp == y.comp && x.what == y.what && x.plane == y.plane; }
+
+// A read-out's destination.  Device form: the caller's buffer, and close() does nothing.  Host form: the context's scratch buffer
+// (grown here to `bytes` when it is smaller, after a wait for whatever still reads the old one), which close() copies to the
+// caller's array and waits for.
+struct ReadOut {
+    dangx_ctx* ctx;
+    double* out;
+    bool to_host;
+    double* dst = nullptr;   // where the kernel writes: valid after open()
+    int open(size_t bytes) {
+        dst = out;
+        if (!to_host) return 0;
+        DxMoments* m = ctx->mom;
+        if (bytes > m->scratch_bytes) {
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+            m->scratch = DevBuf<double>();
+            m->scratch_bytes = 0;
+            HIPCHK(ctx, hipMalloc(&m->scratch.p, bytes));
+            m->scratch_bytes = bytes;
+        }
+        dst = m->scratch;
+        return 0;
+    }
+    // the planes named by `planes` (bit k) of dst's [nplanes][n], host_stride doubles apart in the caller's array
+    int close(unsigned planes, int nplanes, long long n, long long host_stride) {
+        if (!to_host) return 0;
+        for (int k = 0; k < nplanes; ++k)
+            if ((planes >> k) & 1u)
+                HIPCHK(ctx, hipMemcpyAsync(out + (long long)k * host_stride, dst + (long long)k * n, sizeof(double) * (size_t)n,
+                                           hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        return 0;
+    }
+    int close(long long n) { return close(1u, 1, n, n); }   // one run of n doubles
+};
+
+// "no sample accumulated", and for a stat that divides by n - ddof (noun names it in the message) the range of ddof
+inline int count_check(dangx_ctx* ctx, const char* noun, int ddof) {
+    const long long n = ctx->mom->count;
+    if (n == 0) return fail(ctx, "posterior moments: no sample accumulated");
+    if (noun && (ddof < 0 || n - ddof <= 0)) return fail(ctx, std::string("posterior moments: ") + noun + " needs 0 <= ddof < n");
+    return 0;
+}
+
+int dx_hist_stat_check(dangx_ctx* ctx, int reg, int stat, int nq, const double* q);   // dangx_moments.hip: the checks of a histogram read-out
