@@ -112,9 +112,7 @@ __global__ __launch_bounds__(BLOCK, (FAST && NG <= 4) ? 3 : 1) void k_amp_direct
                 // holding the LAST component's SED product
                 f0 += (eta * is) * mrow[NG - 1];
             } else {
-                double u1, u2;
-                uniform2(a.seed, a.stream, gpix, (uint32_t)(k + 4 * (j + 1)), u1, u2);
-                const double ej = rand_normal(0.0, 1.0, u1, u2) * is;
+                const double ej = fluct_band(a.seed, a.stream, gpix, k, j, is);   // dx_rng.h: the draw every kernel shares
 #pragma unroll
                 for (int g = 0; g < NG; ++g) bv[g] += ej * mrow[g];
             }

@@ -1005,8 +1005,12 @@ int device_schur(dangx_ctx* const* cs, int nc, const GroupArgs* as, const long l
     // consistent; the free directions keep their current value (d = 0 there), which is what the reference's CG does
     // with them too (a Krylov iterate never moves along the null space).  nullity is reported through cg_iters.
     std::vector<double> S(rows.begin(), rows.begin() + (size_t)R * R), t(rows.begin() + (size_t)R * R, rows.begin() + (size_t)R * R + R);
-    std::vector<double> fl(R, 0.0);  // fluctuation term of every row, through the running-counter mapping
-    if (a.ml_mode == DANGX_ML_SAMPLE)
+    // fluctuation term of every row: the reference's through the running-counter mapping of compute_sample_vector, the textbook
+    // one (DANGX_FLUCT_CORRECT) on the natural rows
+    std::vector<double> fl(R, 0.0);
+    if (a.ml_mode == DANGX_ML_SAMPLE && a.fluct != DANGX_FLUCT_REFERENCE)
+        for (int r = 0; r < R; ++r) fl[r] = rows[(size_t)R * R + R + r];
+    else if (a.ml_mode == DANGX_ML_SAMPLE)
         for (int r = 0; r < R; ++r)
             if (sa.ftarget[r] >= 0) fl[sa.ftarget[r]] += rows[(size_t)R * R + R + r];
     for (int r = 0; r < R; ++r) t[r] += fl[r];

@@ -126,6 +126,15 @@ int dx_set_chi_after(dangx_ctx* ctx, int k, double chi) {
     ctx->chi_after_valid[k - 1] = true;
     return 0;
 }
+// The textbook fluctuation term (DANGX_FLUCT_CORRECT) on a group with global-amplitude members: the Schur passes carry it where
+// every global member is a `template` (dangx_schur.hip).  A monopole (row weight 1, src/dang_cg_mod.f90:857) or hi_fit member
+// makes the system unsymmetric: "posterior draw" has no agreed meaning there, and the mode stays refused.
+static bool textbook_refused(dangx_ctx* ctx, const GroupArgs& a, int ml_mode, int fluct_mode) {
+    if (ml_mode != DANGX_ML_SAMPLE || fluct_mode == DANGX_FLUCT_REFERENCE) return false;
+    for (int t = 0; t < a.nt; ++t)
+        if (ctx->desc[a.tc[t]].type != DANGX_TEMPLATE) return true;
+    return false;
+}
 extern "C" {
 
 int dangx_amp_sample(dangx_ctx* ctx, int group, int flag, int ml_mode, int solver, int fluct_mode, uint64_t seed,
@@ -147,8 +156,7 @@ int dangx_amp_sample(dangx_ctx* ctx, int group, int flag, int ml_mode, int solve
     if (cg_iters) *cg_iters = 0;
     if (n_not_spd) *n_not_spd = 0;
     if (a.nt > 0 && solver != DANGX_SOLVER_CG) {
-        if (fluct_mode != DANGX_FLUCT_REFERENCE && ml_mode == DANGX_ML_SAMPLE)
-            return fail(ctx, "groups with template / monopole / hi_fit members reproduce the reference's fluctuation term only");
+        if (textbook_refused(ctx, a, ml_mode, fluct_mode)) return fail(ctx, "the textbook fluctuation term (DANGX_FLUCT_CORRECT) is refused for a group with a monopole or hi_fit member: its system is not symmetric, use DANGX_FLUCT_REFERENCE");
         int nullity = 0;
         dangx_ctx* one[1] = {ctx};
         if (device_schur(one, 1, &a, &SN, n_not_spd, &nullity)) return 1;
@@ -157,7 +165,7 @@ int dangx_amp_sample(dangx_ctx* ctx, int group, int flag, int ml_mode, int solve
     }
     if (solver == DANGX_SOLVER_CG) {
         if (fluct_mode != DANGX_FLUCT_REFERENCE && ml_mode == DANGX_ML_SAMPLE)
-            return fail(ctx, "the CG solver reproduces the reference's fluctuation term only");
+            return fail(ctx, "the textbook fluctuation term (DANGX_FLUCT_CORRECT) is refused with the CG solver (DANGX_SOLVER_CG), which reproduces the reference's term only: use DANGX_SOLVER_DIRECT");
         return device_cg(ctx, a, i_max, converge, cg_iters);
     }
     if (ctx->defer_amp) {  // dangx_amp_index_sample: the launch waits for the index sweep it is fused with
@@ -166,10 +174,10 @@ int dangx_amp_sample(dangx_ctx* ctx, int group, int flag, int ml_mode, int solve
     }
     // The amplitude phase with chi^2 of the state it leaves as a by-product (src/dang_cg_mod.f90:172-173 asks for it after every
     // group): the plane-set kernel without sweep items forms the residual of the new amplitudes anyway -- where it covers the
-    // model (delta bands, the group's members the only components on the planes, reference fluctuation term) the statistics need
-    // no pass of their own over the maps.  DANGX_AMP_CHI=0: the stand-alone amplitude kernel (A/B timing).
+    // model (the group's members the only components on the planes; either fluctuation term: SOLVE = 1 / 2 of the kernel) the
+    // statistics need no pass of their own over the maps.  DANGX_AMP_CHI=0: the stand-alone amplitude kernel (A/B timing).
     static const bool with_chi = [] { const char* e = getenv("DANGX_AMP_CHI"); return !(e && e[0] == '0'); }();
-    if (with_chi && (ml_mode == DANGX_ML_OPTIMIZE || fluct_mode == DANGX_FLUCT_REFERENCE)) {
+    if (with_chi) {
         SweepList sl;
         std::memset(&sl, 0, sizeof(sl));
         sl.s1 = (flag & DANGX_FLAG_QU) ? 2 : (flag & DANGX_FLAG_T) ? 1 : (flag & DANGX_FLAG_Q) ? 2 : 3;
@@ -230,8 +238,7 @@ int dangx_sky_amp_sample(dangx_ctx* const* ctxs, int nctx, int group, int flag, 
     }
     if (solver == DANGX_SOLVER_CG)
         return fail(c0, "the device CG (DANGX_SOLVER_CG) iterates on ONE context per process: use DANGX_SOLVER_DIRECT, or one process per GPU with dangx_set_allreduce");
-    if (fluct_mode != DANGX_FLUCT_REFERENCE && ml_mode == DANGX_ML_SAMPLE)
-        return fail(c0, "groups with template / monopole / hi_fit members reproduce the reference's fluctuation term only");
+    if (textbook_refused(c0, probe, ml_mode, fluct_mode)) return fail(c0, "the textbook fluctuation term (DANGX_FLUCT_CORRECT) is refused for a group with a monopole or hi_fit member: its system is not symmetric, use DANGX_FLUCT_REFERENCE");
     std::vector<GroupArgs> as((size_t)nctx);
     std::vector<long long> SNs((size_t)nctx);
     for (int r = 0; r < nctx; ++r) {
@@ -625,8 +632,8 @@ int dangx_plane_set_sample(dangx_ctx* ctx, int group, int flag, int ml_mode, int
     if (n_not_spd) *n_not_spd = 0;
     static const bool enabled = [] { const char* e = getenv("DANGX_FUSE"); return !(e && e[0] == '0'); }();
     // ---- does the one-launch form cover this?  (the conditions of dangx_amp_index_sample, for every sweep of the list)
+    // (either fluctuation term: the launch carries the textbook one as SOLVE = 2, dangx_planeset.hip)
     bool can = enabled && nsweeps <= 2 * DX_MAX_SWEEPS && solver == DANGX_SOLVER_DIRECT &&
-               (ml_mode == DANGX_ML_OPTIMIZE || fluct_mode == DANGX_FLUCT_REFERENCE) &&
                (ml_mode == DANGX_ML_SAMPLE || ml_mode == DANGX_ML_OPTIMIZE);
     GroupArgs g;
     SweepList sl;
@@ -717,15 +724,16 @@ int dangx_sky_plane_set_sample(dangx_ctx* const* ctxs, int nctx, int group, int 
     const int map_n = (flag == DANGX_FLAG_T) ? 1 : (flag == DANGX_FLAG_Q) ? 2 : (flag == DANGX_FLAG_U) ? 3 : (flag == DANGX_FLAG_QU) ? -1 : 0;
     if (map_n == 0) return fail(c0, "flag must be exactly one of T(1), Q(2), U(4), Q+U(8)");
     if (ml_mode != DANGX_ML_SAMPLE && ml_mode != DANGX_ML_OPTIMIZE) return fail(c0, "bad ml_mode");
-    if (fluct_mode != DANGX_FLUCT_REFERENCE && ml_mode == DANGX_ML_SAMPLE)
-        return fail(c0, "groups with template / monopole / hi_fit members reproduce the reference's fluctuation term only");
+    if (textbook_refused(c0, probe, ml_mode, fluct_mode)) return fail(c0, "the textbook fluctuation term (DANGX_FLUCT_CORRECT) is refused for a group with a monopole or hi_fit member: its system is not symmetric, use DANGX_FLUCT_REFERENCE");
+    // with the textbook term the back-substitution is not deferred into the plane-set launch: the full Schur solve, then the sweeps
+    const bool textbook = ml_mode == DANGX_ML_SAMPLE && fluct_mode != DANGX_FLUCT_REFERENCE;
     static const bool enabled = [] { const char* e = getenv("DANGX_FUSE"); return !(e && e[0] == '0'); }();
     const int s1 = (map_n == -1) ? 2 : map_n, s2 = (map_n == -1) ? 3 : map_n;
     std::vector<GroupArgs> as((size_t)nctx), gs((size_t)nctx);
     std::vector<SweepList> sls((size_t)nctx);
     std::vector<long long> SNs((size_t)nctx);
     std::vector<int> lanes((size_t)nctx, 0);
-    bool fuse = enabled && nsweeps <= 2 * DX_MAX_SWEEPS;
+    bool fuse = enabled && nsweeps <= 2 * DX_MAX_SWEEPS && !textbook;
     for (int r = 0; r < nctx; ++r) {
         dangx_ctx* c = ctxs[r];
         (void)hipSetDevice(c->device);

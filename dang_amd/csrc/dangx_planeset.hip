@@ -68,6 +68,8 @@ static int planeset_bp(dangx_ctx* ctx) {
 static bool planeset_builtin(int nb, int ng, int lanes, int solve, const SweepList& sl) {
     int c[4];
     item_codes(sl, c);
+    if (solve == 2)   // the textbook fluctuation term: the C3 shape, the solve alone and the whole iteration of a plane set
+        return lanes == 1 && nb == 10 && ng == 4 && (sl.n == 0 || (c[0] == CH_POW && c[1] == CH_MBB_BETA + 8 && c[2] == 0 && c[3] == 0));
     if (nb == 20 && ng == 6 && lanes == 2) return solve && c[0] == CH_POW && c[1] == CH_MBB_BETA + 8 && c[2] == CH_LOGN_NUP && c[3] == 0;
     if (lanes == 1 && nb == 10 && ng == 4 && solve && sl.n == 0) return true;
     if (lanes == 1 && nb == 10 && ng == 4 && c[0] == CH_POW + 16)   // C3 with the synchrotron index on the Jeffreys prior
@@ -89,13 +91,28 @@ static void launch_builtin(dangx_ctx* ctx, const GroupArgs& ga, const FusedArgs&
 // the Jeffreys instantiations of the C3 shape are a translation unit of their own (-DDX_PS_JEFF), built beside this one
 void dx_launch_planeset_jeff(dangx_ctx* ctx, const GroupArgs& ga, const FusedArgs& fa, const SweepList& sl, int Sp, int solve, unsigned nblk,
                              size_t ldsz, unsigned long long* accp);
-#ifdef DX_PS_JEFF
+// ... and so are the C3 instantiations with the textbook fluctuation term, SOLVE = 2 (-DDX_PS_FLUCT)
+void dx_launch_planeset_fluct(dangx_ctx* ctx, const GroupArgs& ga, const FusedArgs& fa, const SweepList& sl, int Sp, unsigned nblk, size_t ldsz,
+                              unsigned long long* accp);
+#if defined(DX_PS_JEFF)
 void dx_launch_planeset_jeff(dangx_ctx* ctx, const GroupArgs& ga, const FusedArgs& fa, const SweepList& sl, int Sp, int solve, unsigned nblk,
                              size_t ldsz, unsigned long long* accp) {
     if (solve) launch_builtin<10, 4, 1, 1, CH_POW + 16, CH_MBB_BETA + 8, 0>(ctx, ga, fa, sl, Sp, nblk, ldsz, accp);
     else launch_builtin<10, 4, 1, 0, CH_POW + 16, CH_MBB_BETA + 8, 0>(ctx, ga, fa, sl, Sp, nblk, ldsz, accp);
 }
+#elif defined(DX_PS_FLUCT)
+void dx_launch_planeset_fluct(dangx_ctx* ctx, const GroupArgs& ga, const FusedArgs& fa, const SweepList& sl, int Sp, unsigned nblk, size_t ldsz,
+                              unsigned long long* accp) {
+    if (sl.n == 0) launch_builtin<10, 4, 1, 2, 0, 0, 0>(ctx, ga, fa, sl, Sp, nblk, ldsz, accp);
+    else launch_builtin<10, 4, 1, 2, CH_POW, CH_MBB_BETA + 8, 0>(ctx, ga, fa, sl, Sp, nblk, ldsz, accp);
+}
 #else
+
+// SOLVE of the launch: 0 = the sweeps alone; 1 = the solve with the reference's fluctuation term (or none: ml_mode 'optimize');
+// 2 = the solve with the textbook term, one normal per band (ml_mode 'sample' with DANGX_FLUCT_CORRECT)
+static int planeset_solve(const GroupArgs& ga, int solve) {
+    return (solve && ga.ml_mode == DANGX_ML_SAMPLE && ga.fluct != DANGX_FLUCT_REFERENCE) ? 2 : (solve ? 1 : 0);
+}
 
 // members' roles (as the fused kernel's), and the conditions the kernel relies on
 static bool planeset_args(dangx_ctx* ctx, const GroupArgs& ga, const SweepList& sl, FusedArgs& fa) {
@@ -131,7 +148,8 @@ static bool planeset_args(dangx_ctx* ctx, const GroupArgs& ga, const SweepList& 
 // one lane is 5 % slower than as lane pairs, 15 slower than the separate launches), lane pairs above (even counts).
 // solve: the launch starts with the group's amplitude solve (sl.n = 0: nothing else); 0: the sweeps alone.
 // Specialises the kernel when there is no built-in instantiation.
-int dx_planeset_lanes(dangx_ctx* ctx, const GroupArgs& ga, const SweepList& sl, int solve) {
+int dx_planeset_lanes(dangx_ctx* ctx, const GroupArgs& ga, const SweepList& sl, int solve_in) {
+    const int solve = planeset_solve(ga, solve_in);
     static const bool enabled = [] { const char* e = getenv("DANGX_PLANESET"); return !(e && e[0] == '0'); }();
     // DANGX_PLANESET=pairs: only for the shapes that run as lane pairs (A/B switch)
     static const bool small_too = [] { const char* e = getenv("DANGX_PLANESET"); return !(e && e[0] == 'p'); }();
@@ -164,7 +182,8 @@ int dx_planeset_lanes(dangx_ctx* ctx, const GroupArgs& ga, const SweepList& sl, 
 }
 
 // accp: per-sweep counters (sum over items of 1 + pair entries) or null
-bool dx_launch_planeset(dangx_ctx* ctx, const GroupArgs& ga, const SweepList& sl_in, int lanes, int solve, unsigned nblk, unsigned long long* accp) {
+bool dx_launch_planeset(dangx_ctx* ctx, const GroupArgs& ga, const SweepList& sl_in, int lanes, int solve_in, unsigned nblk, unsigned long long* accp) {
+    const int solve = planeset_solve(ga, solve_in);
     FusedArgs fa;
     if (lanes < 1 || lanes > 2 || !planeset_args(ctx, ga, sl_in, fa)) return false;
     SweepList sl = sl_in;
@@ -173,7 +192,8 @@ bool dx_launch_planeset(dangx_ctx* ctx, const GroupArgs& ga, const SweepList& sl
     sl.keep = planeset_keep(sl, fa, ng, nb, lanes, Sp, bp);
     const size_t ldsz = planeset_lds(ng, nb, fa.nv, lanes, Sp, planeset_jeff(sl), sl.keep);
     if (!bp && planeset_builtin(nb, ng, lanes, solve, sl)) {
-        if (planeset_jeff(sl)) dx_launch_planeset_jeff(ctx, ga, fa, sl, Sp, solve, nblk, ldsz, accp);
+        if (solve == 2) dx_launch_planeset_fluct(ctx, ga, fa, sl, Sp, nblk, ldsz, accp);
+        else if (planeset_jeff(sl)) dx_launch_planeset_jeff(ctx, ga, fa, sl, Sp, solve, nblk, ldsz, accp);
         else if (nb == 20) launch_builtin<20, 6, 2, 1, CH_POW, CH_MBB_BETA + 8, CH_LOGN_NUP>(ctx, ga, fa, sl, Sp, nblk, ldsz, accp);
         else if (nb == 10 && sl.n == 0) launch_builtin<10, 4, 1, 1, 0, 0, 0>(ctx, ga, fa, sl, Sp, nblk, ldsz, accp);
         else if (nb == 10 && !solve) launch_builtin<10, 4, 1, 0, CH_POW, CH_MBB_BETA + 8, 0>(ctx, ga, fa, sl, Sp, nblk, ldsz, accp);
@@ -195,7 +215,7 @@ bool dx_launch_planeset(dangx_ctx* ctx, const GroupArgs& ga, const SweepList& sl
 
 #endif  // DX_PS_JEFF
 
-#if defined(DX_LNL_DIAG) && !defined(DX_PS_JEFF)
+#if defined(DX_LNL_DIAG) && !defined(DX_PS_JEFF) && !defined(DX_PS_FLUCT)
 // the certified likelihood's diagnostic counters (dx_chain.h: g_lnl_diag): copied to out[2], then cleared
 extern "C" int dangx_lnl_diag(unsigned long long* out) {
     if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_lnl_diag), 2 * sizeof(unsigned long long)) != hipSuccess) return 1;

@@ -20,9 +20,11 @@ struct MixedUnit {
 };
 
 // data prep of compute_rhs for groups with global members + per-unit normal equations.  When lds != nullptr the
-// per-band vectors W_j = M_j/s_j^2 (NG), d_j/s_j^2 and eta/s_j of the bands that carry a global row are parked
+// per-band vectors W_j = M_j/s_j^2 (NG), d_j/s_j^2 and eta/s_j (textbook term: eta_j/s_j) of the bands that carry a global row are parked
 // in LDS columns [(bslot[j]*(NG+2)+q)*BLOCK].
-template <int NG, bool SUBTRACT_MEMBERS>
+// TB: the textbook fluctuation term (ml_mode 'sample' with DANGX_FLUCT_CORRECT), compile-time: the instances without it are the
+// kernels they were before the term existed.
+template <int NG, bool SUBTRACT_MEMBERS, bool TB>
 __device__ __forceinline__ void mixed_normal_eq(const Model& M, const GroupArgs& a, const UnitId& q, double* lds,
                                                 const signed char* bslot, MixedUnit<NG>& U) {
     constexpr int NA = NG > 0 ? NG : 1;
@@ -38,8 +40,10 @@ __device__ __forceinline__ void mixed_normal_eq(const Model& M, const GroupArgs&
 #pragma unroll
     for (int g = 0; g < NG; ++g) U.bv[g] = 0.0;
     const bool sample = (a.ml_mode == DANGX_ML_SAMPLE);
+    // the textbook fluctuation term (DANGX_FLUCT_CORRECT; groups whose global members are all templates): one normal per band,
+    // every member its own SED -- the diffuse rows here, the global rows from the parked eta_j / s_j of the row's own band
     double eta = 0.0, f0 = 0.0;
-    if (sample) {
+    if (sample && !TB) {
         double u1, u2;
         uniform2(a.seed, a.stream, (unsigned long long)(M.pix0 + q.i), (uint32_t)q.k, u1, u2);
         eta = rand_normal(0.0, 1.0, u1, u2);
@@ -70,10 +74,18 @@ __device__ __forceinline__ void mixed_normal_eq(const Model& M, const GroupArgs&
             for (int h = 0; h <= g; ++h) U.A[g * (g + 1) / 2 + h] += t2 * mrow[h];
             if (lds && bslot[j] >= 0) lds[(bslot[j] * (NG + 2) + g) * BLOCK] = t2;
         }
-        if (NG > 0 && sample) f0 += (eta * is) * mrow[NG > 0 ? NG - 1 : 0];  // :1033-1040 (reference fluctuation term)
+        double es;
+        if constexpr (TB) {
+            es = fluct_band(a.seed, a.stream, (unsigned long long)(M.pix0 + q.i), q.k, j, is);
+#pragma unroll
+            for (int g = 0; g < NG; ++g) U.bv[g] += es * mrow[g];
+        } else {
+            if (NG > 0 && sample) f0 += (eta * is) * mrow[NG > 0 ? NG - 1 : 0];  // :1033-1040 (reference fluctuation term)
+            es = eta * is;
+        }
         if (lds && bslot[j] >= 0) {
             lds[(bslot[j] * (NG + 2) + NG) * BLOCK] = d * inv;
-            lds[(bslot[j] * (NG + 2) + NG + 1) * BLOCK] = eta * is;
+            lds[(bslot[j] * (NG + 2) + NG + 1) * BLOCK] = es;
         }
     }
     if (NG > 0) U.bv[0] += f0;
@@ -109,7 +121,7 @@ __device__ __forceinline__ void fwd_subst(const double* A, double* v) {
 
 // rowpartial rows: [0, R*R): S[r][r'] ; [R*R, R*R+R): t[r] ; [R*R+R, R*R+2R): fluctuation sum of natural row r ;
 // [R*R+2R, R*R+3R): G[r][r], the diagonal before elimination (scale for the degeneracy test on the host)
-template <int NG>
+template <int NG, bool TB>
 __global__ __launch_bounds__(BLOCK, NG <= 4 ? 3 : 1) void k_schur_pass1(const Model* __restrict__ Mp, GroupArgs a, SchurArgs sa,
                                                        double* __restrict__ rowpartial, unsigned long long* __restrict__ not_spd) {
     extern __shared__ double ldsall[];  // [nb*(NG+2)][BLOCK] columns + reduction scratch
@@ -123,7 +135,7 @@ __global__ __launch_bounds__(BLOCK, NG <= 4 ? 3 : 1) void k_schur_pass1(const Mo
     double yh[NG > 0 ? NG : 1];
     bool live = !q.msk;
     if (live) {
-        mixed_normal_eq<NG, false>(M, a, q, lds, sa.bslot, U);
+        mixed_normal_eq<NG, false, TB>(M, a, q, lds, sa.bslot, U);
         if (!U.ok) { live = false; atomicAdd(not_spd, 1ull); }
     }
     if (live) {
@@ -157,7 +169,9 @@ __global__ __launch_bounds__(BLOCK, NG <= 4 ? 3 : 1) void k_schur_pass1(const Mo
 #pragma unroll
             for (int g = 0; g < NG; ++g) dot += lds[(sl * (NG + 2) + g) * BLOCK] * yh[g];
             tv = lds[(sl * (NG + 2) + NG) * BLOCK] * s_r - w_r * dot;
-            fv = lds[(sl * (NG + 2) + NG + 1) * BLOCK] * w_r;
+            // reference term: eta / s_j times the row weight; textbook term: compute_rhs' row operator on s_j eta_j, i.e. times
+            // the member's SED (the same number for a template, the only member type that mode admits)
+            fv = lds[(sl * (NG + 2) + NG + 1) * BLOCK] * (TB ? s_r : w_r);
             const double rms = M.rms[((long long)jr * M.nmaps + (q.k - 1)) * M.npix + q.i];
             inv_r = 1.0 / (rms * rms);
         }
@@ -181,13 +195,13 @@ __global__ __launch_bounds__(BLOCK, NG <= 4 ? 3 : 1) void k_schur_pass1(const Mo
 }
 
 // pass 2: block solve with the global members' (new) signal removed from the data; writes the amplitudes
-template <int NG>
+template <int NG, bool TB>
 __global__ __launch_bounds__(BLOCK) void k_schur_pass2(const Model* __restrict__ Mp, GroupArgs a) {
     const Model& M = *Mp;
     const UnitId q = unit_of(M, a.flag);
     if (q.msk) return;
     MixedUnit<NG> U;
-    mixed_normal_eq<NG, true>(M, a, q, nullptr, nullptr, U);
+    mixed_normal_eq<NG, true, TB>(M, a, q, nullptr, nullptr, U);
     if (!U.ok) return;
     double v[NG > 0 ? NG : 1];
 #pragma unroll
@@ -282,6 +296,7 @@ template <int NG>
 struct LaunchSchur {
     static int run(dangx_ctx* ctx, const GroupArgs& a, const SchurArgs* sa, long long SN, double* rows_dev, bool resid = false) {
         const unsigned nblk = nblocks(SN);
+        const bool tb = a.ml_mode == DANGX_ML_SAMPLE && a.fluct != DANGX_FLUCT_REFERENCE;   // the textbook fluctuation term
         if (sa && resid) {
             const int nrows = 3 * sa->nrows;
             if (ensure_partial(ctx, (long long)nrows * nblk)) return 1;
@@ -293,11 +308,13 @@ struct LaunchSchur {
             const size_t lds = ((size_t)sa->nslots * (NG + 2) + R) * BLOCK * sizeof(double);
             if (lds > 150 * 1024) return fail(ctx, "too many bands x components for the direct solve of a template group: use DANGX_SOLVER_CG");
             HIPCHK(ctx, hipMemsetAsync(ctx->counters, 0, sizeof(unsigned long long), ctx->stream));
-            hipLaunchKernelGGL(k_schur_pass1<NG>, dim3(nblk), dim3(BLOCK), lds, ctx->stream, ctx->dm, a, *sa, ctx->partial, ctx->counters);
+            if (tb) hipLaunchKernelGGL((k_schur_pass1<NG, true>), dim3(nblk), dim3(BLOCK), lds, ctx->stream, ctx->dm, a, *sa, ctx->partial, ctx->counters);
+            else hipLaunchKernelGGL((k_schur_pass1<NG, false>), dim3(nblk), dim3(BLOCK), lds, ctx->stream, ctx->dm, a, *sa, ctx->partial, ctx->counters);
             dx_reduce_rows_to(ctx, ctx->partial, nblk, nrows, rows_dev);
         } else {
             Timed t(ctx, DANGX_K_AMP_DIRECT);
-            hipLaunchKernelGGL(k_schur_pass2<NG>, dim3(nblk), dim3(BLOCK), 0, ctx->stream, ctx->dm, a);
+            if (tb) hipLaunchKernelGGL((k_schur_pass2<NG, true>), dim3(nblk), dim3(BLOCK), 0, ctx->stream, ctx->dm, a);
+            else hipLaunchKernelGGL((k_schur_pass2<NG, false>), dim3(nblk), dim3(BLOCK), 0, ctx->stream, ctx->dm, a);
         }
         HIPCHK(ctx, hipGetLastError());
         return 0;

@@ -8,6 +8,8 @@
 //                               pass of its own (dangx_amp_sample)
 //   SOLVE = 0, sweep items      the index phase alone on the amplitudes in memory (dangx_plane_sweeps_sample: the two-call
 //                               seam's sample_spectral_parameters)
+//   SOLVE = 2                   as SOLVE = 1, with or without items: the solve with the textbook fluctuation term (ml_mode 'sample',
+//                               DANGX_FLUCT_CORRECT: one normal per band, every member its own SED -- dx_rng.h: fluct_band)
 //
 // Resident residual.  The members' SED columns are evaluated once into the lane's LDS column; the solve uses them; then the
 // lane forms the FULL residual (d - sum over every member) / rms of its bands in registers and parks 1 / rms in its LDS column
@@ -20,7 +22,7 @@
 // where |diff - ln u| is of that size (none in 3.8e8 decisions of a full-size run), chi^2 sums agree to rounding -- the parity
 // tolerance of the index maps.  Same device, tools/ab_bench.sh: C5 126.6 -> 112.5 ms per iteration, C3 11.7 -> 11.1 ms, C2 +4 %.
 //
-// Requirements checked by the launcher (dangx_planeset.hip): delta bands, direct solver with the reference fluctuation term,
+// Requirements checked by the launcher (dangx_planeset.hip): direct solver (either fluctuation term: SOLVE = 1 / 2),
 // every swept component an amplitude-sampled member of the group with a register-chain mode (chisq likelihood, gaussian /
 // uniform prior), no other component on the planes, and -- for Q+U -- index maps that are equal on the two planes for every
 // member that varies (true once a Q+U sweep has written them, :465; tracked on the host).  Band calibration: the T launch reads
@@ -242,11 +244,15 @@ __global__ __launch_bounds__(BLOCK, DX_PS_WAVES(SP, NB, LP, SOLVE, C0)) void k_p
             double bv[NG];
             if (SOLVE) {
                 // ---- the block solve of unit (i, k) (k_amp_index's), amplitudes stored for the sweeps
+                // SOLVE == 1: the reference's fluctuation term, ONE eta per unit through f0 into slot 0; SOLVE == 2 (launched for
+                // ml_mode 'sample' with DANGX_FLUCT_CORRECT only): the textbook term, a normal per band in the band loop
                 double eta = 0.0, f0 = 0.0;
-                if (sample) {
-                    double u1, u2;
-                    uniform2(ga.seed, ga.stream, gpix, (uint32_t)k, u1, u2);
-                    eta = rand_normal(0.0, 1.0, u1, u2);
+                if constexpr (SOLVE != 2) {
+                    if (sample) {
+                        double u1, u2;
+                        uniform2(ga.seed, ga.stream, gpix, (uint32_t)k, u1, u2);
+                        eta = rand_normal(0.0, 1.0, u1, u2);
+                    }
                 }
                 double A[NG * (NG + 1) / 2];
 #pragma unroll
@@ -261,8 +267,45 @@ __global__ __launch_bounds__(BLOCK, DX_PS_WAVES(SP, NB, LP, SOLVE, C0)) void k_p
                     mp[g] = var ? col + (fa.vslot[g] * NBL) * BLOCK : tab + (TROWS * g + 2 + k) * NB + jb;  // else csed of plane k
                     ms[g] = var ? BLOCK : 1;
                 }
+                if constexpr (SOLVE == 2) {
+                    // The band loop with the textbook term, ROLLED: per band the data term, then the band's own normal (fluct_band,
+                    // keyed by the model's band number jb + j: a lane of a pair draws for its own bands) times every member's own
+                    // SED -- the order of k_amp_direct's CORRECT branch; the halves of a pair meet in bv below.  One copy of the
+                    // Philox rounds and the Box-Muller polynomials: unrolled like the loop below, their constants and the hoisted
+                    // SED loads of all bands are live together and the C3 kernels spill 280 .. 656 bytes per lane.  The band's d
+                    // and rms leave the register arrays, and 1 / rms returns to them, through selects over compile-time
+                    // subscripts (a run-time subscript would move the arrays to scratch).
+#pragma unroll 1
+                    for (int j = 0; j < NBL; ++j) {
+                        double d = 0.0, r = 0.0;
 #pragma unroll
-                for (int j = 0; j < NBL; ++j) {
+                        for (int jj = 0; jj < NBL; ++jj) {
+                            d = (jj == j) ? R0.D[kk][jj] : d;
+                            r = (jj == j) ? R0.ISr[kk][jj] : r;
+                        }
+                        if (SP == 1 && fa.cal) d = d / tab[(TROWS * NG + 1) * NB + jb + j];  // T / gain, no offset (:371)
+                        const double is = fast_rcp(r);
+#pragma unroll
+                        for (int jj = 0; jj < NBL; ++jj) R0.set_is(kk, jj, (jj == j) ? is : R0.ISr[kk][jj]);
+                        const double inv = is * is;
+                        double mrow[NG];
+#pragma unroll
+                        for (int g = 0; g < NG; ++g) mrow[g] = mp[g][j * ms[g]];
+#pragma unroll
+                        for (int g = 0; g < NG; ++g) {
+                            const double t2 = mrow[g] * inv;
+                            bv[g] += d * t2;
+#pragma unroll
+                            for (int h = 0; h <= g; ++h) A[g * (g + 1) / 2 + h] += t2 * mrow[h];
+                        }
+                        const double ej = fluct_band(ga.seed, ga.stream, gpix, k, jb + j, is);
+#pragma unroll
+                        for (int g = 0; g < NG; ++g) bv[g] += ej * mrow[g];
+                    }
+                }
+                // SOLVE == 1: the unrolled band loop (no trip under SOLVE == 2, whose bands are done)
+#pragma unroll
+                for (int j = 0; j < (SOLVE == 2 ? 0 : NBL); ++j) {
                     double d = R0.D[kk][j];
                     if (SP == 1 && fa.cal) d = d / tab[(TROWS * NG + 1) * NB + jb + j];  // T / gain, no offset (:371)
                     const double is = fast_rcp(R0.ISr[kk][j]);
@@ -286,9 +329,9 @@ __global__ __launch_bounds__(BLOCK, DX_PS_WAVES(SP, NB, LP, SOLVE, C0)) void k_p
                     for (int q = 0; q < NG * (NG + 1) / 2; ++q) A[q] += __shfl_xor(A[q], 1, 64);
 #pragma unroll
                     for (int g = 0; g < NG; ++g) bv[g] += __shfl_xor(bv[g], 1, 64);
-                    f0 += __shfl_xor(f0, 1, 64);
+                    if constexpr (SOLVE != 2) f0 += __shfl_xor(f0, 1, 64);
                 }
-                bv[0] += f0;
+                if constexpr (SOLVE != 2) bv[0] += f0;
                 bool ok = true;
                 double ri[NG];
 #pragma unroll

@@ -81,4 +81,15 @@ __device__ __forceinline__ double rand_normal(double mean, double stdev, double 
     return fma(stdev * r, sin_2pi(u2), mean);
 }
 
+// The textbook fluctuation term of unit (global pixel, plane k) at band j (0-based, the model's band number): eta_j / sigma_j
+// with eta_j the band's own standard normal (draw slot k + 4 * (j + 1)) and is = 1 / sigma_j.  Member g's right-hand side takes
+// fluct_band(...) * m_gj after band j's data term.  ONE function for every kernel that carries the term, so that they agree bit
+// for bit on the draw (rand_normal ends in an fma of its own; the product with `is` cannot be contracted into it).
+__device__ __forceinline__ double fluct_band(unsigned long long seed, unsigned long long stream, unsigned long long pix, int k,
+                                             int j, double is) {
+    double u1, u2;
+    uniform2(seed, stream, pix, (uint32_t)(k + 4 * (j + 1)), u1, u2);
+    return rand_normal(0.0, 1.0, u1, u2) * is;
+}
+
 }  // namespace dx

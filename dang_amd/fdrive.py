@@ -128,12 +128,14 @@ def read_result(path, comps, meta, maps=True, posterior=False, pairs=False, hist
     return res
 
 
-def run(problem, result, nctx=1, mode="twocall", tile=1, timeout=900, posterior=None, pairs=False, hist=None, signal=False):
+def run(problem, result, nctx=1, mode="twocall", tile=1, timeout=900, posterior=None, pairs=False, hist=None, signal=False,
+        fluct_mode="reference"):
     """Run the driver; returns its stdout.  Raises when flang is absent or the run fails (no fallback).
     posterior=(burn_in, thin): accumulate the posterior moments (DANG_POSTERIOR) and append them to the result file.
     pairs (with posterior): also the lag-1 and default pair statistics (DANG_POSTERIOR_PAIRS=1), appended after them.
     hist=nbins (with posterior): also the default per-pixel histograms (DANG_POSTERIOR_HIST=nbins), their quantiles appended behind them.
-    signal (with posterior): also the default component signals (DANG_POSTERIOR_SIGNAL=1), their mean and std appended last."""
+    signal (with posterior): also the default component signals (DANG_POSTERIOR_SIGNAL=1), their mean and std appended last.
+    fluct_mode: 'correct' runs the amplitude solves with the textbook fluctuation term (DANG_FLUCT=correct -> gpu_fluct_mode)."""
     exe = _build.build_reference_drive()
     if exe is None:
         raise RuntimeError("flang is not available: the Fortran driver cannot be built")
@@ -142,6 +144,9 @@ def run(problem, result, nctx=1, mode="twocall", tile=1, timeout=900, posterior=
     env.pop("DANG_POSTERIOR_PAIRS", None)
     env.pop("DANG_POSTERIOR_HIST", None)
     env.pop("DANG_POSTERIOR_SIGNAL", None)
+    env.pop("DANG_FLUCT", None)
+    if fluct_mode != "reference":
+        env["DANG_FLUCT"] = fluct_mode
     if posterior is not None:
         env["DANG_POSTERIOR"] = "%d,%d" % tuple(posterior)
         if pairs:

@@ -27,6 +27,8 @@
 ! DANG_POSTERIOR_SIGNAL=1 beside DANG_POSTERIOR: posterior_signal_gpu(dpar) after posterior_begin_gpu, and behind everything else the
 ! number of signals and per signal its (comp, band, kind), its mean and its standard deviation (ddof 0).  Without it the result
 ! file is what the other switches give.
+! DANG_FLUCT=correct: gpu_fluct_mode = DANGX_FLUCT_CORRECT, the amplitude solves draw with the textbook fluctuation term (one
+! normal per band); unset or anything else: the reference's term, as before.
 subroutine mpi_allreduce(sendbuf, recvbuf, count, datatype, op, comm, ierror)
   ! the wrapper's MPI branch is never taken here (numprocs = 1); the symbol only has to exist
   integer :: sendbuf, recvbuf(*), count, datatype, op, comm, ierror
@@ -89,6 +91,10 @@ program dang_gpu_drive
   dpar%ml_mode = ml_mode
   dpar%outdir = fout(1:index(fout, '/', back=.true.))
   gpu_seed = seed
+  call get_environment_variable('DANG_FLUCT', arg, post_len)
+  if (post_len > 0) then
+     if (arg(1:post_len) == 'correct') gpu_fluct_mode = DANGX_FLUCT_CORRECT
+  end if
   allocate(freqs(nbands), blabel(nbands), ifit(nbands), icorr(nbands))
   allocate(ddata%gain(nbands), ddata%offset(nbands), ddata%fit_gain(nbands), ddata%label(nbands), ddata%conversion(nbands))
   read(u) freqs, ddata%gain, ddata%offset, ifit, blabel

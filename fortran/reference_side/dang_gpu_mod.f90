@@ -36,6 +36,9 @@ module dang_gpu_mod
 
   type(dangx_sky), save :: gpu_sky
   integer(c_int64_t)    :: gpu_seed = 1234_c_int64_t   ! the reference calls RANDOM_SEED() unseeded (src/dang.f90:67)
+  ! the amplitude solves' fluctuation term: DANGX_FLUCT_REFERENCE reproduces compute_sample_vector (one eta per unit, written to
+  ! the first member's slot); DANGX_FLUCT_CORRECT draws one normal per band and is the mode whose samples are posterior draws
+  integer(c_int)        :: gpu_fluct_mode = DANGX_FLUCT_REFERENCE
   integer(i4b)          :: gpu_pix0 = 0                ! first pixel of this PROCESS (0 unless the driver is run under MPI)
   integer(c_int32_t), allocatable, target :: gpu_post_sel(:)   ! posterior_begin_gpu's selection words, one per component
   integer(c_int32_t), allocatable, target :: gpu_post_pairs(:,:)   ! posterior_pairs_gpu's pairs (6, gpu_post_npairs), 0-based as in C
@@ -400,18 +403,18 @@ contains
                 ls(q) = dangx_stream_id(iter, 1, int(sw_comp(e)), int(sw_nind(e)), flag)
              end do
              if (coupled) then   ! the Schur solve's account, as on the two-call path (the call waits for the small system anyway)
-                call dangx_sky_plane_set_sample(gpu_sky, i, flag, mode, DANGX_FLUCT_REFERENCE, gpu_seed, dangx_stream_id(iter, 0, i, 0, flag), &
+                call dangx_sky_plane_set_sample(gpu_sky, i, flag, mode, gpu_fluct_mode, gpu_seed, dangx_stream_id(iter, 0, i, 0, flag), &
                      nl, lc, ln, ls, nsample, gpu_seed, n_not_spd=nbad, nullity=nullity)
                 if (nbad > 0) write(*,*) 'warning: ', nbad, ' non-SPD pixel blocks left unchanged'
                 call dangx_check(gpu_sky%ctx(1), dangx_schur_info(gpu_sky%ctx(1), resid, refinements), 'schur_info')
                 write(*,fmt='(a,es10.2,a,i2,a)') '  global rows: |b - A x| / |b| = ', resid(1), ' after ', refinements, ' refinement(s)'
              else
-                call dangx_sky_plane_set_sample(gpu_sky, i, flag, mode, DANGX_FLUCT_REFERENCE, gpu_seed, dangx_stream_id(iter, 0, i, 0, flag), &
+                call dangx_sky_plane_set_sample(gpu_sky, i, flag, mode, gpu_fluct_mode, gpu_seed, dangx_stream_id(iter, 0, i, 0, flag), &
                      nl, lc, ln, ls, nsample, gpu_seed)
              end if
              deallocate(lc, ln, ls)
           else if (coupled .or. per_group_stats) then     ! with the count: the chi^2 pass below waits for the device anyway
-             call dangx_sky_amp_sample(gpu_sky, i, flag, mode, DANGX_FLUCT_REFERENCE, gpu_seed, &
+             call dangx_sky_amp_sample(gpu_sky, i, flag, mode, gpu_fluct_mode, gpu_seed, &
                   dangx_stream_id(iter, 0, i, 0, flag), nbad, nullity)
              if (nbad > 0) write(*,*) 'warning: ', nbad, ' non-SPD pixel blocks left unchanged'
              if (coupled) then
@@ -419,7 +422,7 @@ contains
                 write(*,fmt='(a,es10.2,a,i2,a)') '  global rows: |b - A x| / |b| = ', resid(1), ' after ', refinements, ' refinement(s)'
              end if
           else
-             call dangx_sky_amp_sample(gpu_sky, i, flag, mode, DANGX_FLUCT_REFERENCE, gpu_seed, dangx_stream_id(iter, 0, i, 0, flag))
+             call dangx_sky_amp_sample(gpu_sky, i, flag, mode, gpu_fluct_mode, gpu_seed, dangx_stream_id(iter, 0, i, 0, flag))
           end if
        end do
        if (coupled) call refresh_offsets(ddata)           ! update_sky_model: offset <- monopole amplitudes
