@@ -66,6 +66,9 @@ static int planeset_bp(dangx_ctx* ctx) {
 // iteration of a plane set (solve + sweeps); for C3 also the two halves the two-call seam launches (the solve alone with its
 // chi^2, the sweeps alone).  Everything else is compiled on first use.
 static bool planeset_builtin(int nb, int ng, int lanes, int solve, const SweepList& sl) {
+    // DANGX_PLANESET_RTC=1 sends the built-in shapes to the run-time compiler too: with DANGX_RTC_DEFS, a header switch A/B on
+    // the very shapes the library carries (read on every launch: a test sets it between two engines)
+    if (const char* e = getenv("DANGX_PLANESET_RTC"); e && e[0] == '1' && dx_rtc_enabled()) return false;
     int c[4];
     item_codes(sl, c);
     if (solve == 2)   // the textbook fluctuation term: the C3 shape, the solve alone and the whole iteration of a plane set

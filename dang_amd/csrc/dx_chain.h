@@ -46,23 +46,40 @@ template <bool V> struct BoolTag { static constexpr bool value = V; };
 
 namespace {
 
-// The accept test of a Metropolis step (:443-454): diff >= 0 or exp(diff) > u3, u3 in [2^-33, 1).  The full-precision exp
-// decides only where a cheap estimate cannot: e = v_exp_f32(float(diff) * float(log2e)).  Where exp(diff) is near some u3,
-// the exponent t = diff log2e lies in [-34, 0), and the three roundings to float (diff, log2e, the product; 2^-24 each) move
-// it by at most 34 * 3 * 2^-24, so e is within 5e-6 of exp(diff) (with v_exp_f32's 1 ulp); exp_nr_v is within 2^-52 of it
-// and float(u3) within 2^-24 of u3.  Hence e > u3 (1 + 2^-12) and e < u3 (1 - 2^-12) decide exactly as the full comparison
-// does; beyond t = -34 both say reject (e <= 2^-34 (1 + 5e-6), 0 once it underflows), and a NaN diff fails both bounds.
-// The remaining lanes (|e / u3 - 1| <= 2^-12, a band of relative width 2^-11 around the threshold) take exp_nr_v, in a
-// branch that the wavefront skips unless one of its lanes needs it.  Decisions are bit for bit those of the full test
-// (tests/test_accept_certificate.py): C3 +2.4 %.  -DDX_ACCEPT_FULL restores the full test.
+// The accept test of a Metropolis step (:443-454): diff >= 0 or exp(diff) > u3, u3 = u32(w) in [2^-33, 1).  The full-precision
+// exp decides only where a cheap estimate cannot: e = v_exp_f32(float(diff) * float(log2e)) against uf, a float form of u3, with
+// a relative margin M on either side.  What the margin has to cover, relative to exp(diff) / u3, where exp(diff) is near some u3:
+//   * the exponent t = diff log2e lies in [-34, 0), and the three roundings to float (diff, log2e, the product; 2^-24 each) move
+//     it by at most 34 * 3 * 2^-24 (1 + 2^-23) < 6.08e-6, i.e. e by a factor within 4.22e-6 of 1 (ln 2 of that);
+//   * v_exp_f32, specified to 1 ulp and counted at 2: 2^-22 < 2.39e-7;
+//   * uf = float(u3): 2^-24; with -DDX_ACCEPT_WORD, uf = fmaf(float(w), 2^-32, 2^-33) -- float(w) is within 2^-24 / (1 + 2^-24)
+//     of w, hence the exact fma argument within that of u3, and the fma rounds once more: |uf - u3| < 2^-23 u3 = 1.2e-7 u3
+//     (tests/test_gpu_draw_forms.py checks all 2^32 words): the larger of the two is counted;
+//   * the product uf (1 +- M) rounded to float: 2^-24 < 6e-8; the margin constants are floats.
+// In all < 4.64e-6 (second-order terms < 1e-10).  M = 2^-16 = 1.53e-5 is more than three times that -- the rule for M: the
+// smallest power of two that is at least 3x the proven error.  Hence e > uf (1 + 2^-16) and e < uf (1 - 2^-16) decide exactly as
+// the full comparison does (exp_nr_v is within 2^-52 of exp(diff)); beyond t = -34 both say reject (e <= 2^-34 (1 + 5e-6), 0 once
+// it underflows, against uf >= 2^-33), and a NaN diff fails both bounds.  The remaining lanes (|e / uf - 1| <= 2^-16) take
+// exp_nr_v against the fp64 u3, in a branch that the wavefront skips unless one of its lanes needs it.  Decisions are bit for
+// bit those of the full test (tests/test_accept_certificate.py, tests/test_accept_margin_cpu.py): C3 +2.4 % (DESIGN.md, round
+// 5).  The margin was 2^-12 until round 13 (-DDX_ACCEPT_MARGIN12 restores it): it adds to the likelihood bound W of mh_certain
+// on both sides of the threshold (C3: the exact-branch share of cheap wave-steps 4.97 -> 4.46 % in the T launch, 7.03 -> 6.71 %
+// in the Q+U launch; W is the larger part).  -DDX_ACCEPT_FULL restores the full test.
+#ifdef DX_ACCEPT_MARGIN12
+#define DX_ACC_UP 0x1.001p+0f
+#define DX_ACC_DOWN 0x1.ffep-1f
+#else
+#define DX_ACC_UP 0x1.0001p+0f
+#define DX_ACC_DOWN 0x1.fffep-1f
+#endif
 __device__ __forceinline__ bool mh_accept(double diff, double u3) {
 #if defined(DX_ACCEPT_FULL) || defined(DX_CHAIN_LIBEXP)
     return (diff >= 0.0) || (CEXP1(diff) > u3);
 #else
     const float e = __builtin_amdgcn_exp2f((float)diff * 0x1.715476p+0f);
     const float uf = (float)u3;
-    bool acc = (diff >= 0.0) || (e > uf * 0x1.001p+0f);
-    const bool unsure = !(acc || e < uf * 0x1.ffep-1f);
+    bool acc = (diff >= 0.0) || (e > uf * DX_ACC_UP);
+    const bool unsure = !(acc || e < uf * DX_ACC_DOWN);
     if (__builtin_amdgcn_ballot_w64(unsure) != 0ull) {
         if (unsure) acc = CEXP1(diff) > u3;
     }
@@ -71,15 +88,42 @@ __device__ __forceinline__ bool mh_accept(double diff, double u3) {
 }
 
 // The same test for a diff known only as an interval: the fp64 chain's diff d lies in [dlo, dhi].  Decided (returns true) when
-// every d in the interval takes the same decision by mh_accept's margins: dlo >= 0 or e(dlo) > u3 (1 + 2^-12) accepts
-// (exp is increasing), dhi < 0 and e(dhi) < u3 (1 - 2^-12) rejects; a NaN bound decides nothing.
-__device__ __forceinline__ bool mh_certain(double dlo, double dhi, double u3, bool& acc) {
-    const float uf = (float)u3;
+// every d in the interval takes the same decision by mh_accept's margins: dlo >= 0 or e(dlo) > uf (1 + 2^-16) accepts
+// (exp is increasing), dhi < 0 and e(dhi) < uf (1 - 2^-16) rejects; a NaN bound decides nothing.
+__device__ __forceinline__ bool mh_certain(double dlo, double dhi, float uf, bool& acc) {
     const float elo = __builtin_amdgcn_exp2f((float)dlo * 0x1.715476p+0f);
     const float ehi = __builtin_amdgcn_exp2f((float)dhi * 0x1.715476p+0f);
-    acc = (dlo >= 0.0) || (elo > uf * 0x1.001p+0f);
-    return acc || ((dhi < 0.0) && (ehi < uf * 0x1.ffep-1f));
+    acc = (dlo >= 0.0) || (elo > uf * DX_ACC_UP);
+    return acc || ((dhi < 0.0) && (ehi < uf * DX_ACC_DOWN));
 }
+__device__ __forceinline__ bool mh_certain(double dlo, double dhi, double u3, bool& acc) { return mh_certain(dlo, dhi, (float)u3, acc); }
+
+// The chain carries the accept uniform of a step as its Philox word.  u32f: the float of it that the cheap tests compare with.
+// -DDX_ACCEPT_WORD forms it from the word in two 32-bit instructions and u32(w) only in the exact branches; OFF: it lowers the
+// proposal loops by one or two vector instructions, but the addend 2^-33 takes a vector register for the whole kernel and the
+// 5-band Q+U instance then spills 74 registers against 72.
+__device__ __forceinline__ float u32f(uint32_t w) {
+#ifdef DX_ACCEPT_WORD
+    return u32f_word(w);
+#else
+    return (float)u32(w);
+#endif
+}
+__device__ __forceinline__ bool mh_accept(double diff, uint32_t w) {
+#if defined(DX_ACCEPT_WORD) && !defined(DX_ACCEPT_FULL) && !defined(DX_CHAIN_LIBEXP)
+    const float e = __builtin_amdgcn_exp2f((float)diff * 0x1.715476p+0f);
+    const float uf = u32f(w);
+    bool acc = (diff >= 0.0) || (e > uf * DX_ACC_UP);
+    const bool unsure = !(acc || e < uf * DX_ACC_DOWN);
+    if (__builtin_amdgcn_ballot_w64(unsure) != 0ull) {
+        if (unsure) acc = CEXP1(diff) > u32(w);
+    }
+    return acc;
+#else
+    return mh_accept(diff, u32(w));
+#endif
+}
+__device__ __forceinline__ bool mh_certain(double dlo, double dhi, uint32_t w, bool& acc) { return mh_certain(dlo, dhi, u32f(w), acc); }
 
 
 #ifdef DX_LNL_DIAG
@@ -651,8 +695,8 @@ __device__ __forceinline__ unsigned long long chain_finish(const Model& M, const
             const bool ok = R.cheap_bound(M, c, lo, hi, -2.0 * lnl, wA, wG) && !ml_opt;
             cert = __builtin_amdgcn_ballot_w64(!ok) == 0ull;   // one decision per wavefront
         }
-        // one step from the proposal and the accept uniform (:414-454)
-        auto mh_step = [&](double prop, double u3) {
+        // one step from the proposal and the accept uniform (:414-454; u3: the uniform's word)
+        auto mh_step = [&](double prop, uint32_t u3) {
             if (prop < lo || prop > hi) return;                        // :415
             if constexpr (!kCert) {
                 lnl = R.template lnl<B>(M, c, prop, other, c0, c1);
@@ -706,21 +750,23 @@ __device__ __forceinline__ unsigned long long chain_finish(const Model& M, const
                 }
             }
         };
+        // (the draw from the Philox words, the accept uniform as word 3: dx_rng.h, mh_accept)
         if (LP == 1 || DX_CHAIN_PAIR_RNG == 0) {
             for (int l = 1; l <= a.nsample; ++l) {
-                double u1, u2, u3;
-                uniform3(a.seed, a.stream, gpix, (uint32_t)l, u1, u2, u3);
-                mh_step(cur + rand_normal(0.0, step, u1, u2), u3);    // :414
+                uint32_t o[4];
+                draw_words(a.seed, a.stream, gpix, (uint32_t)l, o);
+                mh_step(cur + rand_normal_w(0.0, step, o[0], o[1], o[2]), o[3]);    // :414
             }
         } else {
             // Lane pairs: both lanes of a pixel would draw the SAME numbers for every step (a third of a proposal's instructions).
             // Instead lane h draws for step l + h, and the two steps take their numbers from the lane that made them: the random
             // numbers of a pixel are computed once per TWO steps -- the same draws, the same arithmetic, half the instructions.
             for (int l = 1; l <= a.nsample; l += 2) {
-                double u1, u2, u3;
-                uniform3(a.seed, a.stream, gpix, (uint32_t)(l + half), u1, u2, u3);
-                const double g = rand_normal(0.0, step, u1, u2);
-                const double go = __shfl_xor(g, 1, 64), uo = __shfl_xor(u3, 1, 64);
+                uint32_t o[4];
+                draw_words(a.seed, a.stream, gpix, (uint32_t)(l + half), o);
+                const double g = rand_normal_w(0.0, step, o[0], o[1], o[2]);
+                const double go = __shfl_xor(g, 1, 64);
+                const uint32_t u3 = o[3], uo = (uint32_t)__shfl_xor((int)u3, 1, 64);
                 mh_step(cur + (half == 0 ? g : go), half == 0 ? u3 : uo);                          // step l: the even lane's numbers
                 if (l + 1 <= a.nsample) mh_step(cur + (half == 0 ? go : g), half == 0 ? uo : u3);  // step l + 1: the odd lane's
             }

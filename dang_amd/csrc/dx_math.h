@@ -159,6 +159,7 @@ static __device__ const LogRow log_tab[128] = {
     {0x1.7800000000000p-1, 0x1.3c25277333000p-2, 0x1.83b54b606bd5cp-46, 0.0}, {0x1.7600000000000p-1, 0x1.419b423d5f000p-2, -0x1.ce379226de3ecp-44, 0.0},
 };
 
+__device__ __forceinline__ double log_pos_scaled(double v, int e);
 __device__ __forceinline__ double log_pos(double x) {
 #ifdef DX_LOG_TABLE
     const unsigned long long ix = (unsigned long long)__double_as_longlong(x);
@@ -180,12 +181,25 @@ __device__ __forceinline__ double log_pos(double x) {
     q = fma_vc(r, q, -0.5);
     return hi + fma(r * r, q, tl);
 #else
+    return log_pos_scaled(x, 0);   // (the constant folds away: the operations of the form below)
+#endif
+}
+
+// log(v 2^e) for v > 0, finite and NORMAL, and an integer e with |e| < 2^20 (the product itself need not be formed, nor be
+// normal): log_pos's default form (log_pos is this with e = 0) with e added to the integer exponent it reads from v's bits.
+// The mantissa of v 2^e is v's, so every operation after that sees the operands log_pos(ldexp(v, e)) sees: the same bits
+// wherever v 2^e is normal.  The Metropolis draw passes its 53-bit uniform as the integer-valued v = m + 1/2 >= 1/2 with
+// e = -53 and saves the scaling (dx_rng.h: log_u53; tests/test_gpu_draw_forms.py compares it with log_pos(u53) on the device).
+__device__ __forceinline__ double log_pos_scaled(double v, int e) {
+#ifdef DX_LOG_TABLE
+    return log_pos(ldexp(v, e));
+#else
     constexpr double ln2_hi = 6.93147180369123816490e-01, ln2_lo = 1.90821492927058770002e-10;
     constexpr double Lg1 = 6.666666666666735130e-01, Lg2 = 3.999999999940941908e-01, Lg3 = 2.857142874366239149e-01,
                      Lg4 = 2.222219843214978396e-01, Lg5 = 1.818357216161805012e-01, Lg6 = 1.531383769920937332e-01,
                      Lg7 = 1.479819860511658591e-01;
-    unsigned long long ix = (unsigned long long)__double_as_longlong(x);
-    int k = (int)(ix >> 52) - 1023;
+    unsigned long long ix = (unsigned long long)__double_as_longlong(v);
+    int k = (int)(ix >> 52) - 1023 + e;
     ix = (ix & 0x000FFFFFFFFFFFFFull) | 0x3FF0000000000000ull;  // m in [1,2)
     double m = __longlong_as_double((long long)ix);
     if (m > 1.4142135623730951) { m *= 0.5; k += 1; }

@@ -81,6 +81,85 @@ __device__ __forceinline__ double rand_normal(double mean, double stdev, double 
     return fma(stdev * r, sin_2pi(u2), mean);
 }
 
+// ---- The Metropolis step's draw, formed from the Philox words themselves.  The conversions u32 / u53,
+// the reduction of sin_2pi and the scalings by powers of two are exact operations on integers that the forms above carry out
+// in fp64, at twice the issue cost of a 32-bit instruction; the forms below reach the same bits with fewer of them.
+// -DDX_DRAW_FP64 restores the forms above everywhere (or one by one: -DDX_SIN_FP64, -DDX_U1_LDEXP, -DDX_DRAW_BRANCH).
+#ifdef DX_DRAW_FP64
+#define DX_SIN_FP64 1
+#define DX_U1_LDEXP 1
+#define DX_DRAW_BRANCH 1
+#endif
+
+// the four words of one draw slot: u1 = words(0,1), u2 = word 2, u3 = word 3 (uniform3)
+__device__ __forceinline__ void draw_words(unsigned long long seed, unsigned long long stream, unsigned long long pix, uint32_t draw,
+                                           uint32_t o[4]) {
+    philox4x32_10((uint32_t)pix, draw ^ ((uint32_t)(pix >> 32) << 16), (uint32_t)stream, (uint32_t)(stream >> 32),
+                  (uint32_t)seed, (uint32_t)(seed >> 32), o);
+}
+
+// sin_2pi(u32(w)), bit for bit, for every word.  t = 2 u32(w) = (2w + 1) 2^-32 has an odd numerator, so rint never meets a
+// tie and r = t - rint(t) is never 0: r 2^32 = (2w + 1) - k 2^32 lies in (-2^31, 2^31) and is congruent to 2w + 1, i.e. it is
+// the 32-bit pattern (w << 1) | 1 read as a signed integer -- one v_cvt_f64_i32 and an exact scaling.  k == 1 where
+// 2^31 < 2w + 1 < 3 2^31, i.e. 2^30 <= w < 3 2^30: bit 31 of w + 2^30; there r changes its sign (r != 0: a flip of the sign
+// bit is the negation).  From z = r r on, the operations of sin_2pi.
+__device__ __forceinline__ double sin_2pi_w(uint32_t w) {
+#ifdef DX_SIN_FP64
+    return sin_2pi(u32(w));
+#else
+    const double r0 = (double)(int)((w << 1) | 1u) * 0x1p-32;
+    const uint32_t flip = (w + 0x40000000u) & 0x80000000u;
+    const double r = __longlong_as_double(__double_as_longlong(r0) ^ (long long)((unsigned long long)flip << 32));
+    const double z = r * r;
+    double p = fma_vc(z, 0x1.2877020d52cf0p-31, -0x1.8a404211f9547p-26);
+    p = fma_vc(z, p, 0x1.aaec32af93359p-21);
+    p = fma_vc(z, p, -0x1.6fadb9f155744p-16);
+    p = fma_vc(z, p, 0x1.e8f434d018d63p-12);
+    p = fma_vc(z, p, -0x1.e3074fde8871fp-8);
+    p = fma_vc(z, p, 0x1.50783487ee782p-4);
+    p = fma_vc(z, p, -0x1.32d2cce62bd86p-1);
+    p = fma_vc(z, p, 0x1.466bc6775aae2p+1);
+    p = fma_vc(z, p, -0x1.4abbce625be53p+2);
+    p = fma_vc(z, p, 0x1.921fb54442d18p+1);
+    return r * p;
+#endif
+}
+
+// u32(w) as a float, from the word in two 32-bit instructions: float(w) is within 2^-24 / (1 + 2^-24) of w, so the exact fma
+// argument is within that of u32(w), and the fma rounds once more: |u32f_word(w) - u32(w)| < 2^-23 u32(w); 2^-33 for w = 0.
+__device__ __forceinline__ float u32f_word(uint32_t w) { return fmaf((float)w, 0x1p-32f, 0x1p-33f); }
+
+// 2^53 u53(hi, lo) = m + 1/2 with m = x >> 11 (the one rounding of u53 is that of this sum: m has 53 bits).  m's two words
+// convert exactly and fma(m_hi, 2^32, m_lo) is exact, where the conversion of a 64-bit integer is two conversions and an ldexp.
+__device__ __forceinline__ double u53_unscaled(uint32_t hi, uint32_t lo) {
+    const uint32_t mh = hi >> 11, ml = (hi << 21) | (lo >> 11);
+    return fma((double)mh, 0x1p+32, (double)ml) + 0.5;
+}
+
+// log_pos(u53(hi, lo)), bit for bit: the scaling by 2^-53 goes into the logarithm's integer exponent (log_pos_scaled: v >= 1/2
+// is normal and its mantissa is u1's).  u1 == 1 is v == 2^53 and gives +0 as log_pos(1.0) does.
+__device__ __forceinline__ double log_u53(uint32_t hi, uint32_t lo) {
+#ifdef DX_U1_LDEXP
+    return log_pos(u53(hi, lo));
+#else
+    return log_pos_scaled(u53_unscaled(hi, lo), -53);
+#endif
+}
+
+// rand_normal(mean, stdev, u53(hi, lo), u32(w2)), bit for bit, from the words.  The radius is a select, not a branch: fast_sqrt
+// of the argument -0 (u1 == 1) is a NaN that the select drops, and the proposal loop keeps its execution mask
+// (-DDX_DRAW_BRANCH: the branch).
+__device__ __forceinline__ double rand_normal_w(double mean, double stdev, uint32_t hi, uint32_t lo, uint32_t w2) {
+    const double arg = -2.0 * log_u53(hi, lo);
+#ifdef DX_DRAW_BRANCH
+    const double r = (arg > 0.0) ? fast_sqrt(arg) : 0.0;
+#else
+    const double sq = fast_sqrt(arg);
+    const double r = (arg > 0.0) ? sq : 0.0;
+#endif
+    return fma(stdev * r, sin_2pi_w(w2), mean);
+}
+
 // The textbook fluctuation term of unit (global pixel, plane k) at band j (0-based, the model's band number): eta_j / sigma_j
 // with eta_j the band's own standard normal (draw slot k + 4 * (j + 1)) and is = 1 / sigma_j.  Member g's right-hand side takes
 // fluct_band(...) * m_gj after band j's data term.  ONE function for every kernel that carries the term, so that they agree bit
