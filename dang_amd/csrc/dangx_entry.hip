@@ -82,33 +82,49 @@ __global__ __launch_bounds__(BLOCK, 4) void k_sky_chisq(const Model* __restrict_
 
 }  // namespace
 
-// chi^2 of plane k as some sweep has just computed it on the host (the full-sky chain's sufficient statistics at the value it ended
-// on): the "after" slot of the cache, as a sweep's launch would leave it.  Pending launches are reduced first (their slots are
-// older).  Not on planes where a monopole has a signal (chi_byproduct_ok).
-int dx_set_chi_after(dangx_ctx* ctx, int k, double chi);
+namespace {
 
-extern "C" {
+const char* const MSG_TEXTBOOK_GLOBALS = "the textbook fluctuation term (DANGX_FLUCT_CORRECT) is refused for a group with a monopole or hi_fit member: its system is not symmetric, use DANGX_FLUCT_REFERENCE";
+const char* const MSG_CG_ONE_CONTEXT = "the device CG (DANGX_SOLVER_CG) iterates on ONE context per process: use DANGX_SOLVER_DIRECT, or one process per GPU with dangx_set_allreduce";
 
-static int planeset_launch(dangx_ctx* ctx, const GroupArgs& g, const SweepList& sl, int lanes, int solve, int64_t* n_not_spd, int64_t* accepted);
-static bool planeset_group(dangx_ctx* ctx, GroupArgs& g, int s1, int s2, int solve);
-static bool planeset_items(dangx_ctx* ctx, const GroupArgs& g, int map_n, int nsweeps, const int32_t* comp, const int32_t* nind, const uint64_t* stream, SweepList& sl);
+// a prepared amplitude solve (amp_prepare) handed to the index sweep on the same planes: the sweep launches it with itself
+// (dangx_fused.hip) or just before
+struct DeferredSolve { const GroupArgs* a; long long SN; };
+// the sweep of index nind + 1 of the same component rides along with the sweep of index nind where one launch covers both
+struct PairWith { uint64_t stream; };
+// what index_sweep did with them: solve_done -- the launch site was reached, the solve is the sweep's business from there on (it ran
+// or its failure is the call's); pair_ran -- index nind + 1 was swept too, its count waits in counters[2]
+struct SweepOut { bool solve_done = false, pair_ran = false; };
+
+// the sweep kernels take their [4][nblk] chi^2 partial buffer from ctx->partial: lend them the ring's, give the context's own back
+// on every way out of the launch section
+struct Lend {
+    dangx_ctx* c; double* saved;
+    Lend(dangx_ctx* c_, double* b) : c(c_), saved(c_->partial) { c->partial = b; }
+    void back() { if (c) { c->partial = saved; c = nullptr; } }
+    ~Lend() { back(); }
+};
+
+int planeset_launch(dangx_ctx* ctx, const GroupArgs& g, const SweepList& sl, int lanes, int solve, int64_t* n_not_spd, int64_t* accepted);
+bool planeset_group(dangx_ctx* ctx, GroupArgs& g, int s1, int s2, int solve);
+bool planeset_items(dangx_ctx* ctx, const GroupArgs& g, const PlaneSet& ps, int nsweeps, const int32_t* comp, const int32_t* nind, const uint64_t* stream, SweepList& sl);
 
 // Is index nind of this component a Jeffreys-prior index the register chains carry (dx_chain.h: RegChain<.., JF>)?  The power law
 // labelled 'synch' with the chisq likelihood: eval_jeffreys_prior's sum is non-trivial for that label only
 // (src/dang_lnl_mod.f90:289) -- under any other label the prior is log 0 and the chain never moves; those, and every other
 // component type, keep the run-time-typed chain.  Delta bands and the per-pixel mode are the callers' conditions.
-static bool jeffreys_fast(const dangx_comp_desc& d, int nind) {
+bool jeffreys_fast(const dangx_comp_desc& d, int nind) {
     return d.prior_type[nind] == DANGX_PRIOR_JEFFREYS && d.type == DANGX_POWERLAW && d.is_synch && d.lnl_type[nind] == DANGX_LNL_CHISQ;
 }
 // a prior the register chains cover: gaussian, uniform, or the Jeffreys case above
-static bool prior_fast(const dangx_comp_desc& d, int nind) {
+bool prior_fast(const dangx_comp_desc& d, int nind) {
     return d.prior_type[nind] != DANGX_PRIOR_JEFFREYS || jeffreys_fast(d, nind);
 }
 
 // The sums of squares a sweep leaves behind are chi^2 of update_sky_model's residual -- unless a monopole has a signal on the planes:
 // the chain removes it as one more component (eval_signal, src/dang_sample_mod.f90:180-196) ON TOP of the band offset it has
 // become (src/dang_data_mod.f90:357-361), while the sky model leaves it out.  Such planes take the explicit pass.
-static bool chi_byproduct_ok(const dangx_ctx* ctx, int s1, int s2) {
+bool chi_byproduct_ok(const dangx_ctx* ctx, int s1, int s2) {
     unsigned planes = 0;
     for (int k = s1; k <= s2; ++k) planes |= 1u << (k - 1);
     for (int l = 0; l < ctx->hm.ncomp; ++l)
@@ -116,47 +132,70 @@ static bool chi_byproduct_ok(const dangx_ctx* ctx, int s1, int s2) {
     return true;
 }
 
-}  // extern "C"
-int dx_set_chi_after(dangx_ctx* ctx, int k, double chi) {
-    if (k < 1 || k > ctx->dims.nmaps || !chi_byproduct_ok(ctx, k, k)) return 0;
-    (void)hipSetDevice(ctx->device);
-    if (chi_flush(ctx)) return 1;
-    ctx->chi_host[k - 1] = chi;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->chi_cache + 3 + (k - 1), &ctx->chi_host[k - 1], sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    ctx->chi_after_valid[k - 1] = true;
+// A solve on planes s1..s2 of group g is about to write: the planes' cached chi^2 is stale and no sweep has touched them since, the
+// degraded model channels are stale, the members' amplitude planes may be non-zero from now on.
+void solve_writes(dangx_ctx* ctx, const GroupArgs& g, int s1, int s2) {
+    ctx->cm_ok = false;
+    for (int k = s1; k <= s2; ++k) {
+        ctx->chi_before_valid[k - 1] = ctx->chi_after_valid[k - 1] = ctx->touched_since_amp[k - 1] = false;
+        for (int q = 0; q < g.ng; ++q) ctx->plane_nz[g.gc[q]] |= 1u << (k - 1);
+    }
+}
+
+// A launch that leaves chi^2 block partials of planes s1..s2 in the buffer chi_next gave has run: its entry in the ring (reduced when
+// a value is asked for: chi_flush), wb -- "before" is the launch's to write (the state the amplitude phase left) --, the validity of
+// both slots, and that a sweep has touched the planes.  items: the sweeps of a plane-set launch, whose masked index sums ride along
+// (rows 4 .., in the items' order) and stay on the device; null for one sweep of its own (ns = 0, as chi_next left it).
+void sweep_recorded(dangx_ctx* ctx, unsigned nblk, int s1, int s2, bool wb, const SweepList* items) {
+    auto& pend = ctx->chi_pend[ctx->chi_npend++];
+    pend.nblk = nblk; pend.s1 = s1; pend.s2 = s2; pend.wb = wb ? 1 : 0;
+    for (int q = 0; items && q < items->n; ++q)
+        for (int e = 0; e <= items->s[q].pair; ++e) {
+            const int comp = items->s[q].comp, nind = items->s[q].nind + e;
+            pend.slot[pend.ns++] = idx_slot(comp, nind, s1);
+            for (int k = s1; k <= s2; ++k) ctx->idxsum_dev[comp][nind][k - 1] = !ctx->idx_ext[comp];
+        }
+    const bool chi_ok = chi_byproduct_ok(ctx, s1, s2), swept = !items || items->n > 0;
+    for (int k = s1; k <= s2; ++k) {
+        if (wb) ctx->chi_before_valid[k - 1] = chi_ok;
+        ctx->chi_after_valid[k - 1] = chi_ok;
+        if (swept) ctx->touched_since_amp[k - 1] = true;   // (a solve without items: still false, from solve_writes)
+    }
+}
+
+int check_sweeps(dangx_ctx* ctx, int nsweeps, const int32_t* comp, const int32_t* nind) {
+    for (int s = 0; s < nsweeps; ++s)
+        if (check_comp(ctx, comp[s]) || nind[s] < 0 || nind[s] >= ctx->desc[comp[s]].nindices) return fail(ctx, "sweep list: component / index out of range");
     return 0;
 }
+
 // The textbook fluctuation term (DANGX_FLUCT_CORRECT) on a group with global-amplitude members: the Schur passes carry it where
 // every global member is a `template` (dangx_schur.hip).  A monopole (row weight 1, src/dang_cg_mod.f90:857) or hi_fit member
 // makes the system unsymmetric: "posterior draw" has no agreed meaning there, and the mode stays refused.
-static bool textbook_refused(dangx_ctx* ctx, const GroupArgs& a, int ml_mode, int fluct_mode) {
+bool textbook_refused(dangx_ctx* ctx, const GroupArgs& a, int ml_mode, int fluct_mode) {
     if (ml_mode != DANGX_ML_SAMPLE || fluct_mode == DANGX_FLUCT_REFERENCE) return false;
     for (int t = 0; t < a.nt; ++t)
         if (ctx->desc[a.tc[t]].type != DANGX_TEMPLATE) return true;
     return false;
 }
-extern "C" {
 
-int dangx_amp_sample(dangx_ctx* ctx, int group, int flag, int ml_mode, int solver, int fluct_mode, uint64_t seed,
-                     uint64_t stream, int i_max, double converge, int* cg_iters, int64_t* n_not_spd) {
-    DxRange rg_("dangx_amp_sample");
-    if (!ctx) return 1;
-    (void)hipSetDevice(ctx->device);
+// What every solve of (group, flag) does before anything is launched, on the context's device: the arguments, the model on the
+// device, and the bookkeeping of a solve that is about to write (solve_writes).  SN: units x pixels of the shard.
+int amp_prepare(dangx_ctx* ctx, int group, int flag, int ml_mode, int fluct_mode, uint64_t seed, uint64_t stream, GroupArgs& a, long long& SN) {
     if (ml_mode != DANGX_ML_SAMPLE && ml_mode != DANGX_ML_OPTIMIZE) return fail(ctx, "bad ml_mode");
-    GroupArgs a;
     if (make_group(ctx, group, flag, a) || sync_model(ctx)) return 1;
     a.ml_mode = ml_mode; a.fluct = fluct_mode; a.seed = seed; a.stream = stream;
-    const long long SN = (long long)flag_planes_h(flag) * ctx->hm.npix;
-    for (int pl = 0; pl < flag_planes_h(flag); ++pl) {  // the planes' cached chi^2 is stale now
-        const int k = (flag & DANGX_FLAG_QU) ? 2 + pl : (flag & DANGX_FLAG_T) ? 1 : (flag & DANGX_FLAG_Q) ? 2 : 3;
-        ctx->chi_before_valid[k - 1] = ctx->chi_after_valid[k - 1] = ctx->touched_since_amp[k - 1] = false;
-        ctx->cm_ok = false;   // amplitudes about to be written
-        for (int g = 0; g < a.ng; ++g) ctx->plane_nz[a.gc[g]] |= 1u << (k - 1);  // about to be written
-    }
-    if (cg_iters) *cg_iters = 0;
-    if (n_not_spd) *n_not_spd = 0;
+    const PlaneSet ps = plane_set_or_none(flag);   // (make_group has refused every other flag)
+    SN = (long long)(ps.s2 - ps.s1 + 1) * ctx->hm.npix;
+    solve_writes(ctx, a, ps.s1, ps.s2);
+    return 0;
+}
+
+// The launches of a prepared solve on ONE context: the Schur solve of a group with global members, the CG solver, or the per-pixel
+// direct solve -- with chi^2 of the state it leaves as a by-product where the plane-set kernel covers the model.
+int amp_launch(dangx_ctx* ctx, const GroupArgs& a, long long SN, int solver, int i_max, double converge, int* cg_iters, int64_t* n_not_spd) {
     if (a.nt > 0 && solver != DANGX_SOLVER_CG) {
-        if (textbook_refused(ctx, a, ml_mode, fluct_mode)) return fail(ctx, "the textbook fluctuation term (DANGX_FLUCT_CORRECT) is refused for a group with a monopole or hi_fit member: its system is not symmetric, use DANGX_FLUCT_REFERENCE");
+        if (textbook_refused(ctx, a, a.ml_mode, a.fluct)) return fail(ctx, MSG_TEXTBOOK_GLOBALS);
         int nullity = 0;
         dangx_ctx* one[1] = {ctx};
         if (device_schur(one, 1, &a, &SN, n_not_spd, &nullity)) return 1;
@@ -164,13 +203,9 @@ int dangx_amp_sample(dangx_ctx* ctx, int group, int flag, int ml_mode, int solve
         return 0;
     }
     if (solver == DANGX_SOLVER_CG) {
-        if (fluct_mode != DANGX_FLUCT_REFERENCE && ml_mode == DANGX_ML_SAMPLE)
+        if (a.fluct != DANGX_FLUCT_REFERENCE && a.ml_mode == DANGX_ML_SAMPLE)
             return fail(ctx, "the textbook fluctuation term (DANGX_FLUCT_CORRECT) is refused with the CG solver (DANGX_SOLVER_CG), which reproduces the reference's term only: use DANGX_SOLVER_DIRECT");
         return device_cg(ctx, a, i_max, converge, cg_iters);
-    }
-    if (ctx->defer_amp) {  // dangx_amp_index_sample: the launch waits for the index sweep it is fused with
-        ctx->pending = a; ctx->pending_SN = SN; ctx->have_pending = true;
-        return 0;
     }
     // The amplitude phase with chi^2 of the state it leaves as a by-product (src/dang_cg_mod.f90:172-173 asks for it after every
     // group): the plane-set kernel without sweep items forms the residual of the new amplitudes anyway -- where it covers the
@@ -178,97 +213,32 @@ int dangx_amp_sample(dangx_ctx* ctx, int group, int flag, int ml_mode, int solve
     // statistics need no pass of their own over the maps.  DANGX_AMP_CHI=0: the stand-alone amplitude kernel (A/B timing).
     static const bool with_chi = [] { const char* e = getenv("DANGX_AMP_CHI"); return !(e && e[0] == '0'); }();
     if (with_chi) {
+        const PlaneSet ps = plane_set_or_none(a.flag);
         SweepList sl;
         std::memset(&sl, 0, sizeof(sl));
-        sl.s1 = (flag & DANGX_FLAG_QU) ? 2 : (flag & DANGX_FLAG_T) ? 1 : (flag & DANGX_FLAG_Q) ? 2 : 3;
-        sl.s2 = (flag & DANGX_FLAG_QU) ? 3 : sl.s1;
-        sl.ml_mode = ml_mode;
-        GroupArgs ps = a;
-        if (planeset_group(ctx, ps, sl.s1, sl.s2, 1)) {
-            const int lanes = dx_planeset_lanes(ctx, ps, sl, 1);
-            if (lanes) return planeset_launch(ctx, ps, sl, lanes, 1, n_not_spd, nullptr);
+        sl.s1 = ps.s1; sl.s2 = ps.s2;
+        sl.ml_mode = a.ml_mode;
+        GroupArgs g = a;
+        if (planeset_group(ctx, g, sl.s1, sl.s2, 1)) {
+            const int lanes = dx_planeset_lanes(ctx, g, sl, 1);
+            if (lanes) return planeset_launch(ctx, g, sl, lanes, 1, n_not_spd, nullptr);
         }
     }
     if (n_not_spd) HIPCHK(ctx, hipMemsetAsync(ctx->counters, 0, sizeof(unsigned long long), ctx->stream));
     if (dx_launch_amp(ctx, a, SN)) return 1;
     HIPCHK(ctx, hipGetLastError());
-    if (n_not_spd) {
-        unsigned long long v = 0;
-        HIPCHK(ctx, hipMemcpyAsync(&v, ctx->counters, sizeof(v), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        *n_not_spd = (int64_t)v;
-    }
-    return 0;
+    return n_not_spd ? read_counters(ctx, 0, 1, n_not_spd) : 0;
 }
 
-// One (group, flag) pass of sample_cg_groups over several contexts of ONE process (include/dangx.h).  Independent per-pixel
-// work is enqueued on every device before the first result is awaited; a coupled group shares its Schur rows.
-int dangx_sky_amp_sample(dangx_ctx* const* ctxs, int nctx, int group, int flag, int ml_mode, int solver, int fluct_mode, uint64_t seed,
-                         uint64_t stream, int i_max, double converge, int* cg_iters, int64_t* n_not_spd) {
-    DxRange rg_("dangx_sky_amp_sample");
-    if (!ctxs || nctx < 1) return 1;
-    for (int r = 0; r < nctx; ++r) if (!ctxs[r]) return 1;
-    dangx_ctx* c0 = ctxs[0];
-    if (nctx == 1) return dangx_amp_sample(c0, group, flag, ml_mode, solver, fluct_mode, seed, stream, i_max, converge, cg_iters, n_not_spd);
-    if (nctx > 64) return fail(c0, "too many contexts");
-    auto bubble = [&](dangx_ctx* who) { if (who != c0) c0->err = who->err; return 1; };
-    if (ml_mode != DANGX_ML_SAMPLE && ml_mode != DANGX_ML_OPTIMIZE) return fail(c0, "bad ml_mode");
-    GroupArgs probe;
-    if (make_group(c0, group, flag, probe)) return 1;
-    if (cg_iters) *cg_iters = 0;
-    if (n_not_spd) *n_not_spd = 0;
-    if (probe.nt == 0 && solver != DANGX_SOLVER_CG) {  // block diagonal: every shard on its own
-        for (int r = 0; r < nctx; ++r) {
-            if (n_not_spd) {  // the amplitude kernels add to counters[0]: each context starts its launch from zero, on its own stream
-                (void)hipSetDevice(ctxs[r]->device);
-                HIPCHK(c0, hipMemsetAsync(ctxs[r]->counters, 0, sizeof(unsigned long long), ctxs[r]->stream));
-            }
-            if (dangx_amp_sample(ctxs[r], group, flag, ml_mode, solver, fluct_mode, seed, stream, i_max, converge, nullptr, nullptr))
-                return bubble(ctxs[r]);
-        }
-        if (n_not_spd)   // the counters are read after every device has its launch
-            for (int r = 0; r < nctx; ++r) {
-                unsigned long long v = 0;
-                (void)hipSetDevice(ctxs[r]->device);
-                HIPCHK(c0, hipMemcpyAsync(&v, ctxs[r]->counters, sizeof(v), hipMemcpyDeviceToHost, ctxs[r]->stream));
-                HIPCHK(c0, hipStreamSynchronize(ctxs[r]->stream));
-                *n_not_spd += (int64_t)v;
-            }
-        return 0;
-    }
-    if (solver == DANGX_SOLVER_CG)
-        return fail(c0, "the device CG (DANGX_SOLVER_CG) iterates on ONE context per process: use DANGX_SOLVER_DIRECT, or one process per GPU with dangx_set_allreduce");
-    if (textbook_refused(c0, probe, ml_mode, fluct_mode)) return fail(c0, "the textbook fluctuation term (DANGX_FLUCT_CORRECT) is refused for a group with a monopole or hi_fit member: its system is not symmetric, use DANGX_FLUCT_REFERENCE");
-    std::vector<GroupArgs> as((size_t)nctx);
-    std::vector<long long> SNs((size_t)nctx);
-    for (int r = 0; r < nctx; ++r) {
-        dangx_ctx* c = ctxs[r];
-        (void)hipSetDevice(c->device);
-        if (make_group(c, group, flag, as[r]) || sync_model(c)) return bubble(c);
-        as[r].ml_mode = ml_mode; as[r].fluct = fluct_mode; as[r].seed = seed; as[r].stream = stream;
-        SNs[r] = (long long)flag_planes_h(flag) * c->hm.npix;
-        for (int pl = 0; pl < flag_planes_h(flag); ++pl) {
-            const int k = (flag & DANGX_FLAG_QU) ? 2 + pl : (flag & DANGX_FLAG_T) ? 1 : (flag & DANGX_FLAG_Q) ? 2 : 3;
-            c->chi_before_valid[k - 1] = c->chi_after_valid[k - 1] = c->touched_since_amp[k - 1] = false;
-            c->cm_ok = false;
-            for (int g = 0; g < as[r].ng; ++g) c->plane_nz[as[r].gc[g]] |= 1u << (k - 1);
-        }
-        if (as[r].nglob != as[0].nglob || as[r].nt != as[0].nt) return fail(c0, "the contexts disagree on the group's global-amplitude members");
-    }
-    int nullity = 0;
-    if (device_schur(ctxs, nctx, as.data(), SNs.data(), n_not_spd, &nullity)) return 1;
-    if (cg_iters) *cg_iters = -nullity;
-    return 0;
-}
-
-int dangx_index_sample(dangx_ctx* ctx, int comp, int nind, int map_n, int nsample, int ml_mode, uint64_t seed,
-                       uint64_t stream, int64_t* accepted) {
-    DxRange rg_("dangx_index_sample");
-    if (!ctx || check_comp(ctx, comp)) return 1;
+// One Metropolis sweep of index nind of a component on map_n's planes (dangx_index_sample), and what may travel with it: `solve`, a
+// prepared amplitude solve on the same planes, runs in the sweep's launch where the fused kernel covers both and just before it
+// otherwise; `pair`, the sweep of index nind + 1, runs in the same launch where the register chain covers both.  The caller has
+// checked comp.  The sweep marks the index maps as varying BEFORE the model is synchronised and before any other validation.
+int index_sweep(dangx_ctx* ctx, int comp, int nind, int map_n, int nsample, int ml_mode, uint64_t seed, uint64_t stream, int64_t* accepted,
+                const DeferredSolve* solve, const PairWith* pair, SweepOut* out) {
     (void)hipSetDevice(ctx->device);
     {   // this sweep makes the component's index map pixel dependent on the touched planes
-        unsigned touched = 0;
-        if (map_n == -1) touched = 6u; else if (map_n >= 1 && map_n <= 3) touched = 1u << (map_n - 1);
+        const unsigned touched = map_bits(map_n);
         if (ctx->idx_const[comp] & touched) { ctx->idx_const[comp] &= ~touched; ctx->dirty = true; }
         idx_written(ctx, comp);
         if (nind >= 0 && nind < DANGX_MAX_IND) qu_written(ctx, comp, nind, map_n);
@@ -278,10 +248,7 @@ int dangx_index_sample(dangx_ctx* ctx, int comp, int nind, int map_n, int nsampl
     if (nind < 0 || nind >= d.nindices) return fail(ctx, "index number out of range");
     IndexArgs a;
     a.comp = comp; a.nind = nind; a.nsample = nsample; a.ml_mode = ml_mode; a.seed = seed; a.stream = stream; a.jeff = 0;
-    if (map_n == -1) { a.s1 = 2; a.s2 = 3; }                       // src/dang_sample_mod.f90:157-163
-    else if (map_n >= 1 && map_n <= 3) { a.s1 = a.s2 = map_n; }
-    else return fail(ctx, "There is something wrong with the poltype flag (map_n must be 1,2,3 or -1)");
-    if (a.s2 > ctx->dims.nmaps) return fail(ctx, "map_n exceeds nmaps");
+    if (map_planes(ctx, map_n, a.s1, a.s2)) return 1;                 // src/dang_sample_mod.f90:157-163
     if (d.lnl_type[nind] < DANGX_LNL_CHISQ || d.lnl_type[nind] > DANGX_LNL_PRIOR) return fail(ctx, "bad lnl_type");
     if (ml_mode != DANGX_ML_SAMPLE && ml_mode != DANGX_ML_OPTIMIZE) return fail(ctx, "bad ml_mode");
     const int Sp = a.s2 - a.s1 + 1;
@@ -311,79 +278,158 @@ int dangx_index_sample(dangx_ctx* ctx, int comp, int nind, int map_n, int nsampl
                         a.mode != CH_GENERIC && dx_mh_reg_supported(ctx, a.mode, ctx->hm.nbands, Sp, a.jeff);
     if (!reg_ok) a.jeff = 0;
     if (reg_ok) bs = BLOCK;  // register-resident form: no LDS columns
-    // lanes per pixel: of the chain's register form, or of the fused launch when a solve on these planes is waiting for this
+    // lanes per pixel: of the chain's register form, or of the fused launch when a solve on these planes travels with this
     // sweep and the model takes the one-launch form (decided now: the grid and the chi^2 buffers are sized by it)
     int lanes = reg_ok ? dx_mh_reg_lanes(ctx->hm.nbands, Sp) : 1;
-    const int fused_lanes = (ctx->have_pending && reg_ok) ? dx_fused_lanes(ctx, ctx->pending, a, Sp) : 0;
+    const int fused_lanes = (solve && reg_ok) ? dx_fused_lanes(ctx, *solve->a, a, Sp) : 0;
     if (fused_lanes) lanes = fused_lanes;
     const unsigned nblk = nblocks((long long)ctx->hm.npix * lanes, bs);
-    constexpr int RSTAGE = 128;  // blocks of the first reduction stage
     double* chi_buf = nullptr;
     if (chi_next(ctx, nblk, &chi_buf)) return 1;
-    // the sweep kernels take their [4][nblk] chi^2 partial buffer from ctx->partial: lend them the ring's, give the
-    // context's own back on every way out of the launch section
-    struct Lend {
-        dangx_ctx* c; double* saved;
-        Lend(dangx_ctx* c_, double* b) : c(c_), saved(c_->partial) { c->partial = b; }
-        void back() { if (c) { c->partial = saved; c = nullptr; } }
-        ~Lend() { back(); }
-    } lend(ctx, chi_buf);
+    Lend lend(ctx, chi_buf);
+    unsigned long long* accp = accepted ? ctx->counters + 1 : nullptr;  // counters[1], and counters[2] of a pair
     if (accepted) HIPCHK(ctx, hipMemsetAsync(ctx->counters + 1, 0, 2 * sizeof(unsigned long long), ctx->stream));
     bool fused = false;
-    if (ctx->have_pending) {  // an amplitude solve on these planes is waiting: one launch for both, or the solve first
-        ctx->have_pending = false;
-        unsigned long long* accp = accepted ? ctx->counters + 1 : nullptr;
+    if (solve) {  // one launch for the solve and the sweep, or the solve first
+        out->solve_done = true;
         if (fused_lanes) {
             Timed t(ctx, DANGX_K_AMP_INDEX, Sp);
-            fused = dx_launch_fused(ctx, ctx->pending, a, Sp, fused_lanes, nblk, accp);
+            fused = dx_launch_fused(ctx, *solve->a, a, Sp, fused_lanes, nblk, accp);
         }
         if (!fused) {
             if (fused_lanes) return fail(ctx, "the fused solve + sweep launch failed after its kernel was prepared");
-            if (dx_launch_amp(ctx, ctx->pending, ctx->pending_SN)) return 1;
+            if (dx_launch_amp(ctx, *solve->a, solve->SN)) return 1;
         }
     }
-    if (!fused && ctx->pair_on) {  // dangx_index_sample_pair: this sweep and the sweep of index nind + 1 in one launch
-        ctx->pair_on = false;
-        if (reg_ok && nind + 1 < d.nindices) {
-            IndexArgs b = a;
-            b.nind = nind + 1; b.stream = ctx->pair_stream; b.jeff = 0;
-            b.mode = (d.type == DANGX_MBB) ? CH_MBB_T : (d.type == DANGX_LOGNORMAL && all_delta) ? CH_LOGN_W : CH_GENERIC;
-            const bool ok_b = !a.jeff && d.lnl_type[nind + 1] == DANGX_LNL_CHISQ && d.prior_type[nind + 1] != DANGX_PRIOR_JEFFREYS;
-            unsigned long long* accp = accepted ? ctx->counters + 1 : nullptr;  // counters[1], counters[2]
-            if (ok_b) {
-                Timed t(ctx, DANGX_K_INDEX_MH, Sp);
-                fused = ctx->pair_done = dx_launch_mh_pair(ctx, a, b, Sp, nblk, accp);
-            }
+    if (!fused && pair && reg_ok && nind + 1 < d.nindices) {  // this sweep and the sweep of index nind + 1 in one launch
+        IndexArgs b = a;
+        b.nind = nind + 1; b.stream = pair->stream; b.jeff = 0;
+        b.mode = (d.type == DANGX_MBB) ? CH_MBB_T : (d.type == DANGX_LOGNORMAL && all_delta) ? CH_LOGN_W : CH_GENERIC;
+        const bool ok_b = !a.jeff && d.lnl_type[nind + 1] == DANGX_LNL_CHISQ && d.prior_type[nind + 1] != DANGX_PRIOR_JEFFREYS;
+        if (ok_b) {
+            Timed t(ctx, DANGX_K_INDEX_MH, Sp);
+            fused = out->pair_ran = dx_launch_mh_pair(ctx, a, b, Sp, nblk, accp);
         }
     }
     if (!fused) {
         Timed t(ctx, DANGX_K_INDEX_MH, Sp);
-        unsigned long long* accp = accepted ? ctx->counters + 1 : nullptr;
         const bool fast = d.lnl_type[nind] == DANGX_LNL_CHISQ &&
                           (a.mode == CH_POW || a.mode == CH_MBB_BETA || a.mode == CH_MBB_T);
         if (!(reg_ok && dx_launch_mh_reg(ctx, a, Sp, nblk, accp))) dx_launch_mh_lds(ctx, a, fast, Sp, nblk, bs, lds, accp);
     }
     lend.back();
     HIPCHK(ctx, hipGetLastError());  // a failed launch must not leave a pending entry over partials nobody wrote
-    {   // fused chi^2 of the touched planes (before = state left by the amplitude phase, after = new state): the block
-        // partials wait in the ring (chi_flush) until a value is asked for
-        const bool wb = !ctx->touched_since_amp[a.s1 - 1];
-        auto& pend = ctx->chi_pend[ctx->chi_npend++];
-        pend.nblk = nblk; pend.s1 = a.s1; pend.s2 = a.s2; pend.wb = wb ? 1 : 0;
-        const bool chi_ok = chi_byproduct_ok(ctx, a.s1, a.s2);
-        for (int k = a.s1; k <= a.s2; ++k) {
-            if (wb) ctx->chi_before_valid[k - 1] = chi_ok;
-            ctx->chi_after_valid[k - 1] = chi_ok;
-            ctx->touched_since_amp[k - 1] = true;
+    // fused chi^2 of the touched planes (before = state left by the amplitude phase, after = new state)
+    sweep_recorded(ctx, nblk, a.s1, a.s2, !ctx->touched_since_amp[a.s1 - 1], nullptr);
+    return accepted ? read_counters(ctx, 1, 1, accepted) : 0;
+}
+
+// dangx_index_sample per sweep from `first` on, consecutive indices of a component through dangx_index_sample_pair
+int sweeps_one_by_one(dangx_ctx* ctx, int first, int map_n, int nsweeps, const int32_t* comp, const int32_t* nind, const uint64_t* stream,
+                      int nsample, int ml_mode, uint64_t seed, int64_t* accepted) {
+    int64_t acc = 0, acc2 = 0;
+    for (int s = first; s < nsweeps; ++s) {
+        if (s + 1 < nsweeps && comp[s + 1] == comp[s] && nind[s + 1] == nind[s] + 1) {
+            const int rc = dangx_index_sample_pair(ctx, comp[s], nind[s], map_n, nsample, ml_mode, seed, stream[s], stream[s + 1],
+                                                   accepted ? &acc : nullptr, accepted ? &acc2 : nullptr);
+            if (rc) return rc;
+            if (accepted) { accepted[s] = acc; accepted[s + 1] = acc2; }
+            ++s;
+        } else {
+            const int rc = dangx_index_sample(ctx, comp[s], nind[s], map_n, nsample, ml_mode, seed, stream[s], accepted ? &acc : nullptr);
+            if (rc) return rc;
+            if (accepted) accepted[s] = acc;
         }
     }
-    if (accepted) {
-        unsigned long long v = 0;
-        HIPCHK(ctx, hipMemcpyAsync(&v, ctx->counters + 1, sizeof(v), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        *accepted = (int64_t)v;
-    }
     return 0;
+}
+
+}  // namespace
+
+// chi^2 of plane k as some sweep has just computed it on the host (the full-sky chain's sufficient statistics at the value it ended
+// on): the "after" slot of the cache, as a sweep's launch would leave it.  Pending launches are reduced first (their slots are
+// older).  Not on planes where a monopole has a signal (chi_byproduct_ok).
+int dx_set_chi_after(dangx_ctx* ctx, int k, double chi) {
+    if (k < 1 || k > ctx->dims.nmaps || !chi_byproduct_ok(ctx, k, k)) return 0;
+    (void)hipSetDevice(ctx->device);
+    if (chi_flush(ctx)) return 1;
+    ctx->chi_host[k - 1] = chi;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->chi_cache + 3 + (k - 1), &ctx->chi_host[k - 1], sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    ctx->chi_after_valid[k - 1] = true;
+    return 0;
+}
+
+extern "C" {
+
+int dangx_amp_sample(dangx_ctx* ctx, int group, int flag, int ml_mode, int solver, int fluct_mode, uint64_t seed,
+                     uint64_t stream, int i_max, double converge, int* cg_iters, int64_t* n_not_spd) {
+    DxRange rg_("dangx_amp_sample");
+    if (!ctx) return 1;
+    (void)hipSetDevice(ctx->device);
+    GroupArgs a;
+    long long SN = 0;
+    if (amp_prepare(ctx, group, flag, ml_mode, fluct_mode, seed, stream, a, SN)) return 1;
+    if (cg_iters) *cg_iters = 0;
+    if (n_not_spd) *n_not_spd = 0;
+    return amp_launch(ctx, a, SN, solver, i_max, converge, cg_iters, n_not_spd);
+}
+
+// One (group, flag) pass of sample_cg_groups over several contexts of ONE process (include/dangx.h).  Independent per-pixel
+// work is enqueued on every device before the first result is awaited; a coupled group shares its Schur rows.
+int dangx_sky_amp_sample(dangx_ctx* const* ctxs, int nctx, int group, int flag, int ml_mode, int solver, int fluct_mode, uint64_t seed,
+                         uint64_t stream, int i_max, double converge, int* cg_iters, int64_t* n_not_spd) {
+    DxRange rg_("dangx_sky_amp_sample");
+    if (!ctxs || nctx < 1) return 1;
+    for (int r = 0; r < nctx; ++r) if (!ctxs[r]) return 1;
+    dangx_ctx* c0 = ctxs[0];
+    if (nctx == 1) return dangx_amp_sample(c0, group, flag, ml_mode, solver, fluct_mode, seed, stream, i_max, converge, cg_iters, n_not_spd);
+    if (nctx > 64) return fail(c0, "too many contexts");
+    auto bubble = [&](dangx_ctx* who) { if (who != c0) c0->err = who->err; return 1; };
+    if (ml_mode != DANGX_ML_SAMPLE && ml_mode != DANGX_ML_OPTIMIZE) return fail(c0, "bad ml_mode");
+    GroupArgs probe;
+    if (make_group(c0, group, flag, probe)) return 1;
+    if (cg_iters) *cg_iters = 0;
+    if (n_not_spd) *n_not_spd = 0;
+    if (probe.nt == 0 && solver != DANGX_SOLVER_CG) {  // block diagonal: every shard on its own
+        for (int r = 0; r < nctx; ++r) {
+            if (n_not_spd) {  // the amplitude kernels add to counters[0]: each context starts its launch from zero, on its own stream
+                (void)hipSetDevice(ctxs[r]->device);
+                HIPCHK(c0, hipMemsetAsync(ctxs[r]->counters, 0, sizeof(unsigned long long), ctxs[r]->stream));
+            }
+            if (dangx_amp_sample(ctxs[r], group, flag, ml_mode, solver, fluct_mode, seed, stream, i_max, converge, nullptr, nullptr))
+                return bubble(ctxs[r]);
+        }
+        if (n_not_spd)   // the counters are read after every device has its launch
+            for (int r = 0; r < nctx; ++r) {
+                int64_t v = 0;
+                (void)hipSetDevice(ctxs[r]->device);
+                if (read_counters(ctxs[r], 0, 1, &v)) return bubble(ctxs[r]);
+                *n_not_spd += v;
+            }
+        return 0;
+    }
+    if (solver == DANGX_SOLVER_CG) return fail(c0, MSG_CG_ONE_CONTEXT);
+    if (textbook_refused(c0, probe, ml_mode, fluct_mode)) return fail(c0, MSG_TEXTBOOK_GLOBALS);
+    std::vector<GroupArgs> as((size_t)nctx);
+    std::vector<long long> SNs((size_t)nctx);
+    for (int r = 0; r < nctx; ++r) {
+        dangx_ctx* c = ctxs[r];
+        (void)hipSetDevice(c->device);
+        if (amp_prepare(c, group, flag, ml_mode, fluct_mode, seed, stream, as[r], SNs[r])) return bubble(c);
+        if (as[r].nglob != as[0].nglob || as[r].nt != as[0].nt) return fail(c0, "the contexts disagree on the group's global-amplitude members");
+    }
+    int nullity = 0;
+    if (device_schur(ctxs, nctx, as.data(), SNs.data(), n_not_spd, &nullity)) return 1;
+    if (cg_iters) *cg_iters = -nullity;
+    return 0;
+}
+
+int dangx_index_sample(dangx_ctx* ctx, int comp, int nind, int map_n, int nsample, int ml_mode, uint64_t seed,
+                       uint64_t stream, int64_t* accepted) {
+    DxRange rg_("dangx_index_sample");
+    if (!ctx || check_comp(ctx, comp)) return 1;
+    SweepOut out;
+    return index_sweep(ctx, comp, nind, map_n, nsample, ml_mode, seed, stream, accepted, nullptr, nullptr, &out);
 }
 
 // dangx_index_sample(comp, nind, ...) followed by dangx_index_sample(comp, nind + 1, ...) on the same planes: two
@@ -395,24 +441,17 @@ int dangx_index_sample_pair(dangx_ctx* ctx, int comp, int nind, int map_n, int n
                             uint64_t stream_first, uint64_t stream_second, int64_t* accepted_first, int64_t* accepted_second) {
     DxRange rg_("dangx_index_sample_pair");
     if (!ctx || check_comp(ctx, comp)) return 1;
-    static const bool enabled = [] { const char* e = getenv("DANGX_FUSE"); return !(e && e[0] == '0'); }();
     const bool want_counts = accepted_first || accepted_second;
     int64_t acc1 = 0;
-    ctx->pair_on = enabled; ctx->pair_done = false; ctx->pair_stream = stream_second;
-    int rc = dangx_index_sample(ctx, comp, nind, map_n, nsample, ml_mode, seed, stream_first, want_counts ? &acc1 : nullptr);
-    ctx->pair_on = false;
+    const PairWith pair{stream_second};
+    SweepOut out;
+    const int rc = index_sweep(ctx, comp, nind, map_n, nsample, ml_mode, seed, stream_first, want_counts ? &acc1 : nullptr, nullptr,
+                               dx_fuse_enabled() ? &pair : nullptr, &out);
     if (rc) return rc;
     if (accepted_first) *accepted_first = acc1;
-    if (!ctx->pair_done) return dangx_index_sample(ctx, comp, nind + 1, map_n, nsample, ml_mode, seed, stream_second, accepted_second);
-    ctx->pair_done = false;
-    if (nind + 1 < DANGX_MAX_IND) qu_written(ctx, comp, nind + 1, map_n);
-    if (accepted_second) {
-        unsigned long long v = 0;
-        HIPCHK(ctx, hipMemcpyAsync(&v, ctx->counters + 2, sizeof(v), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        *accepted_second = (int64_t)v;
-    }
-    return 0;
+    if (!out.pair_ran) return dangx_index_sample(ctx, comp, nind + 1, map_n, nsample, ml_mode, seed, stream_second, accepted_second);
+    if (nind + 1 < DANGX_MAX_IND) qu_written(ctx, comp, nind + 1, map_n);   // the sweep itself has recorded index nind only
+    return accepted_second ? read_counters(ctx, 2, 1, accepted_second) : 0;
 }
 
 // dangx_amp_sample(group, flag, ...) followed by dangx_index_sample(comp, nind, map_n, ...) -- the amplitude solve of a CG
@@ -427,21 +466,19 @@ int dangx_amp_index_sample(dangx_ctx* ctx, int group, int flag, int ml_mode, int
     DxRange rg_("dangx_amp_index_sample");
     if (!ctx || check_comp(ctx, comp)) return 1;
     if (cg_iters) *cg_iters = 0;
-    static const bool enabled = [] { const char* e = getenv("DANGX_FUSE"); return !(e && e[0] == '0'); }();  // A/B switch
     (void)hipSetDevice(ctx->device);
     if (sync_model(ctx)) return 1;  // all_delta and the constant-plane flags the decision below reads are set there
-    bool can = enabled && solver == DANGX_SOLVER_DIRECT && ctx->hm.all_delta != 0 &&
+    bool can = dx_fuse_enabled() && solver == DANGX_SOLVER_DIRECT && ctx->hm.all_delta != 0 &&
                (ml_mode == DANGX_ML_OPTIMIZE || fluct_mode == DANGX_FLUCT_REFERENCE);
     // the planes of the sweep are the planes of the solve
-    const int want = (flag == DANGX_FLAG_T) ? 1 : (flag == DANGX_FLAG_Q) ? 2 : (flag == DANGX_FLAG_U) ? 3 : (flag == DANGX_FLAG_QU) ? -1 : 0;
+    const int want = plane_set_or_none(flag).map_n;
     can = can && want != 0 && want == map_n;
     if (can) {
         const dangx_comp_desc& d = ctx->desc[comp];
-        const unsigned touched = (map_n == -1) ? 6u : 1u << (map_n - 1);
         // a sweep that turns a spatially constant index map into a varying one changes which SED route the SOLVE takes
         // (host-evaluated row against per-pixel evaluation) if it is launched after the descriptor update: first sweeps
         // on constant maps go the two-call way
-        can = nind >= 0 && nind < d.nindices && !(ctx->idx_const[comp] & touched) && d.cg_group == group && d.sample_amplitude &&
+        can = nind >= 0 && nind < d.nindices && !(ctx->idx_const[comp] & map_bits(map_n)) && d.cg_group == group && d.sample_amplitude &&
               d.lnl_type[nind] == DANGX_LNL_CHISQ && prior_fast(d, nind) &&
               (d.type == DANGX_POWERLAW || d.type == DANGX_MBB);
     }
@@ -457,89 +494,57 @@ int dangx_amp_index_sample(dangx_ctx* ctx, int group, int flag, int ml_mode, int
         const int rc = dangx_amp_sample(ctx, group, flag, ml_mode, solver, fluct_mode, seed_amp, stream_amp, i_max, converge, cg_iters, n_not_spd);
         return rc ? rc : dangx_index_sample(ctx, comp, nind, map_n, nsample, ml_mode, seed_index, stream_index, accepted);
     }
+    // (can: the plain direct solve of a diffuse group -- no Schur rows, no CG, no refusal between the preparation and the launch)
     if (n_not_spd) HIPCHK(ctx, hipMemsetAsync(ctx->counters, 0, sizeof(unsigned long long), ctx->stream));
-    ctx->defer_amp = true;
-    int rc = dangx_amp_sample(ctx, group, flag, ml_mode, solver, fluct_mode, seed_amp, stream_amp, i_max, converge, nullptr, nullptr);
-    ctx->defer_amp = false;
-    if (rc) { ctx->have_pending = false; return rc; }
-    rc = dangx_index_sample(ctx, comp, nind, map_n, nsample, ml_mode, seed_index, stream_index, accepted);
-    if (ctx->have_pending) {  // the sweep failed before its launch site: the solve still happens, as with the two calls
-        ctx->have_pending = false;
-        if (dx_launch_amp(ctx, ctx->pending, ctx->pending_SN)) return 1;
-    }
+    GroupArgs a;
+    long long SN = 0;
+    if (amp_prepare(ctx, group, flag, ml_mode, fluct_mode, seed_amp, stream_amp, a, SN)) return 1;
+    const DeferredSolve solve{&a, SN};
+    SweepOut out;
+    const int rc = index_sweep(ctx, comp, nind, map_n, nsample, ml_mode, seed_index, stream_index, accepted, &solve, nullptr, &out);
+    // the sweep failed before its launch site: the solve still happens, as with the two calls
+    if (!out.solve_done && dx_launch_amp(ctx, a, SN)) return 1;
     if (rc) return rc;
-    if (n_not_spd) {
-        unsigned long long v = 0;
-        HIPCHK(ctx, hipMemcpyAsync(&v, ctx->counters, sizeof(v), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        *n_not_spd = (int64_t)v;
-    }
-    return 0;
+    return n_not_spd ? read_counters(ctx, 0, 1, n_not_spd) : 0;   // (the fused kernel and dx_launch_amp both count in counters[0])
 }
 
-// One k_plane_set launch (dx_kern_planeset.h) with its bookkeeping: solve = 1 starts with the group's amplitude solve (what
-// dangx_amp_sample records: the planes' cached chi^2 is stale, the members' amplitudes are about to be written), sl.n sweep items
-// follow (what dangx_index_sample records per sweep).  The chi^2 by-products go to the ring: with a solve "before" = the state the
-// solve leaves and "after" = the last sweep's (both the same value without sweeps); without, as for any sweep.
-static int planeset_launch(dangx_ctx* ctx, const GroupArgs& g, const SweepList& sl, int lanes, int solve, int64_t* n_not_spd, int64_t* accepted) {
-    const bool qu = sl.s2 > sl.s1;
-    bool wb = true;
-    if (solve) {
-        for (int k = sl.s1; k <= sl.s2; ++k) {
-            ctx->chi_before_valid[k - 1] = ctx->chi_after_valid[k - 1] = ctx->touched_since_amp[k - 1] = false;
-            ctx->cm_ok = false;   // amplitudes about to be written
-            for (int q = 0; q < g.ng; ++q) ctx->plane_nz[g.gc[q]] |= 1u << (k - 1);
-        }
-    } else {
-        wb = !ctx->touched_since_amp[sl.s1 - 1];
-    }
+}  // extern "C"
+
+namespace {
+
+// One k_plane_set launch (dx_kern_planeset.h) with its bookkeeping: solve = 1 starts with the group's amplitude solve (solve_writes),
+// sl.n sweep items follow (what index_sweep records per sweep).  The chi^2 by-products go to the ring: with a solve "before" = the
+// state the solve leaves and "after" = the last sweep's (both the same value without sweeps); without, as for any sweep.
+int planeset_launch(dangx_ctx* ctx, const GroupArgs& g, const SweepList& sl, int lanes, int solve, int64_t* n_not_spd, int64_t* accepted) {
+    const int map_n = sl.s2 > sl.s1 ? -1 : sl.s1;   // two planes are Q+U
+    const bool wb = solve || !ctx->touched_since_amp[sl.s1 - 1];
+    if (solve) solve_writes(ctx, g, sl.s1, sl.s2);
     for (int q = 0; q < sl.n; ++q)
         for (int e = 0; e <= sl.s[q].pair; ++e) {
             idx_written(ctx, sl.s[q].comp);
-            if (qu) ctx->qu_equal[sl.s[q].comp] |= 1u << (sl.s[q].nind + e);
-            else if (sl.s1 == 2 || sl.s1 == 3) ctx->qu_equal[sl.s[q].comp] &= ~(1u << (sl.s[q].nind + e));
+            qu_written(ctx, sl.s[q].comp, sl.s[q].nind + e, map_n);
         }
     const unsigned nblk = nblocks((long long)ctx->hm.npix * lanes, BLOCK);
     double* chi_buf = nullptr;
     if (chi_next(ctx, nblk, &chi_buf)) return 1;
     HIPCHK(ctx, hipMemsetAsync(ctx->counters, 0, 16 * sizeof(unsigned long long), ctx->stream));
+    bool ok;
     {
-        double* saved = ctx->partial;
-        ctx->partial = chi_buf;
-        bool ok;
-        {
-            Timed t(ctx, !solve ? DANGX_K_INDEX_MH : sl.n ? DANGX_K_AMP_INDEX : DANGX_K_AMP_DIRECT, sl.s2 - sl.s1 + 1);
-            ok = dx_launch_planeset(ctx, g, sl, lanes, solve, nblk, accepted ? ctx->counters + 4 : nullptr);
-        }
-        ctx->partial = saved;
-        if (!ok) return fail(ctx, "the plane-set launch failed after its kernel was prepared");
+        Lend lend(ctx, chi_buf);
+        Timed t(ctx, !solve ? DANGX_K_INDEX_MH : sl.n ? DANGX_K_AMP_INDEX : DANGX_K_AMP_DIRECT, sl.s2 - sl.s1 + 1);
+        ok = dx_launch_planeset(ctx, g, sl, lanes, solve, nblk, accepted ? ctx->counters + 4 : nullptr);
     }
+    if (!ok) return fail(ctx, "the plane-set launch failed after its kernel was prepared");
     HIPCHK(ctx, hipGetLastError());
-    {
-        auto& pend = ctx->chi_pend[ctx->chi_npend++];
-        pend.nblk = nblk; pend.s1 = sl.s1; pend.s2 = sl.s2; pend.wb = wb ? 1 : 0;
-        pend.ns = 0;
-        for (int q = 0; q < sl.n; ++q)   // the masked sums of the swept index maps ride along (rows 4 ..), in the items' order
-            for (int e = 0; e <= sl.s[q].pair; ++e) {
-                pend.slot[pend.ns++] = idx_slot(sl.s[q].comp, sl.s[q].nind + e, sl.s1);
-                for (int k = sl.s1; k <= sl.s2; ++k) ctx->idxsum_dev[sl.s[q].comp][sl.s[q].nind + e][k - 1] = !ctx->idx_ext[sl.s[q].comp];
-            }
-        const bool chi_ok = chi_byproduct_ok(ctx, sl.s1, sl.s2);
-        for (int k = sl.s1; k <= sl.s2; ++k) {
-            if (wb) ctx->chi_before_valid[k - 1] = chi_ok;
-            ctx->chi_after_valid[k - 1] = chi_ok;
-            ctx->touched_since_amp[k - 1] = sl.n > 0 || (!solve && ctx->touched_since_amp[k - 1]);
-        }
-    }
+    sweep_recorded(ctx, nblk, sl.s1, sl.s2, wb, &sl);
     if (n_not_spd || accepted) {
-        unsigned long long v[16];
-        HIPCHK(ctx, hipMemcpyAsync(v, ctx->counters, sizeof(v), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        if (n_not_spd) *n_not_spd = (int64_t)v[0];
+        int64_t v[16];
+        if (read_counters(ctx, 0, 16, v)) return 1;
+        if (n_not_spd) *n_not_spd = v[0];
         if (accepted) {   // the kernel counts per item (1 + pair entries each); the items follow the list's order
             int slot = 4, s = 0;
             for (int q = 0; q < sl.n; ++q)
-                for (int e = 0; e <= sl.s[q].pair; ++e) accepted[s++] = (int64_t)v[slot++];
+                for (int e = 0; e <= sl.s[q].pair; ++e) accepted[s++] = v[slot++];
         }
     }
     return 0;
@@ -547,9 +552,9 @@ static int planeset_launch(dangx_ctx* ctx, const GroupArgs& g, const SweepList& 
 
 // the sweeps (comp[s], nind[s]), s = 0 .. nsweeps-1, as the items of a plane-set launch over group g's members: consecutive
 // indices of a component travel in one item.  false: some sweep has no register-chain form, or the list is too long
-static bool planeset_items(dangx_ctx* ctx, const GroupArgs& g, int map_n, int nsweeps, const int32_t* comp, const int32_t* nind,
-                           const uint64_t* stream, SweepList& sl) {
-    const unsigned touched = (map_n == -1) ? 6u : 1u << (map_n - 1);
+bool planeset_items(dangx_ctx* ctx, const GroupArgs& g, const PlaneSet& ps, int nsweeps, const int32_t* comp, const int32_t* nind,
+                    const uint64_t* stream, SweepList& sl) {
+    const unsigned touched = map_bits(ps.map_n);
     std::memset(&sl, 0, sizeof(sl));
     for (int s = 0; s < nsweeps; ++s) {
         const dangx_comp_desc& d = ctx->desc[comp[s]];
@@ -570,7 +575,7 @@ static bool planeset_items(dangx_ctx* ctx, const GroupArgs& g, int map_n, int ns
         it.comp = comp[s]; it.nind = nind[s]; it.mode = mode; it.pair = 0; it.gmember = gm; it.stream = stream[s]; it.stream2 = 0;
         it.jeff = jeffreys_fast(d, nind[s]) ? 1 : 0;
     }
-    sl.s1 = (map_n == -1) ? 2 : map_n; sl.s2 = (map_n == -1) ? 3 : map_n;
+    sl.s1 = ps.s1; sl.s2 = ps.s2;
     return true;
 }
 
@@ -584,7 +589,7 @@ static bool planeset_items(dangx_ctx* ctx, const GroupArgs& g, int map_n, int ns
 // solve = 2: the back-substitution of a template group's Schur solve (dangx_sky_plane_set_sample) followed by the sweeps: every
 // template with a signal on the planes must then be a global member of THIS group (its new amplitudes, on every band, are what pass 2
 // removes from the data: dx_ampreg.h, HT form), and the group has no monopole / hi_fit member.
-static bool planeset_group(dangx_ctx* ctx, GroupArgs& g, int s1, int s2, int solve) {
+bool planeset_group(dangx_ctx* ctx, GroupArgs& g, int s1, int s2, int solve) {
     unsigned planes = 0;
     for (int k = s1; k <= s2; ++k) planes |= 1u << (k - 1);
     int ntg = 0, tg[MAXC];
@@ -611,6 +616,10 @@ static bool planeset_group(dangx_ctx* ctx, GroupArgs& g, int s1, int s2, int sol
     return true;
 }
 
+}  // namespace
+
+extern "C" {
+
 // dangx_amp_sample(group, flag, ...) followed by dangx_index_sample(comp[s], nind[s], map_n of the flag, ...) for s = 0 ..
 // nsweeps-1 -- everything one iteration of the main loop does on ONE plane set of a CG group: the solve of sample_cg_groups
 // (src/dang_cg_mod.f90:166-171) and the passes of sample_spectral_parameters that touch these planes (src/dang_sample_mod.f90:
@@ -624,23 +633,20 @@ int dangx_plane_set_sample(dangx_ctx* ctx, int group, int flag, int ml_mode, int
     if (!ctx || nsweeps < 1 || !comp || !nind || !stream) return 1;
     (void)hipSetDevice(ctx->device);
     if (sync_model(ctx)) return 1;
-    const int map_n = (flag == DANGX_FLAG_T) ? 1 : (flag == DANGX_FLAG_Q) ? 2 : (flag == DANGX_FLAG_U) ? 3 : (flag == DANGX_FLAG_QU) ? -1 : 0;
-    if (map_n == 0) return fail(ctx, "flag must be exactly one of T(1), Q(2), U(4), Q+U(8)");
-    for (int s = 0; s < nsweeps; ++s)
-        if (check_comp(ctx, comp[s]) || nind[s] < 0 || nind[s] >= ctx->desc[comp[s]].nindices) return fail(ctx, "sweep list: component / index out of range");
+    PlaneSet ps;
+    if (plane_set_of(ctx, flag, ps) || check_sweeps(ctx, nsweeps, comp, nind)) return 1;
     if (cg_iters) *cg_iters = 0;
     if (n_not_spd) *n_not_spd = 0;
-    static const bool enabled = [] { const char* e = getenv("DANGX_FUSE"); return !(e && e[0] == '0'); }();
     // ---- does the one-launch form cover this?  (the conditions of dangx_amp_index_sample, for every sweep of the list)
     // (either fluctuation term: the launch carries the textbook one as SOLVE = 2, dangx_planeset.hip)
-    bool can = enabled && nsweeps <= 2 * DX_MAX_SWEEPS && solver == DANGX_SOLVER_DIRECT &&
+    bool can = dx_fuse_enabled() && nsweeps <= 2 * DX_MAX_SWEEPS && solver == DANGX_SOLVER_DIRECT &&
                (ml_mode == DANGX_ML_SAMPLE || ml_mode == DANGX_ML_OPTIMIZE);
     GroupArgs g;
     SweepList sl;
     std::memset(&sl, 0, sizeof(sl));
     if (can) {
         if (make_group(ctx, group, flag, g)) return 1;
-        can = planeset_group(ctx, g, (map_n == -1) ? 2 : map_n, (map_n == -1) ? 3 : map_n, 1) && planeset_items(ctx, g, map_n, nsweeps, comp, nind, stream, sl);
+        can = planeset_group(ctx, g, ps.s1, ps.s2, 1) && planeset_items(ctx, g, ps, nsweeps, comp, nind, stream, sl);
     }
     int lanes = 0;
     if (can) {
@@ -648,43 +654,28 @@ int dangx_plane_set_sample(dangx_ctx* ctx, int group, int flag, int ml_mode, int
         g.ml_mode = ml_mode; g.fluct = fluct_mode; g.seed = seed_amp; g.stream = stream_amp;
         lanes = dx_planeset_lanes(ctx, g, sl, 1);
     }
-    if (!lanes) {  // the calls this entry point stands for, through the two-step fusions where they apply
-        {   // template / monopole / hi_fit components in the model: the solve is the Schur path (or sees them as other components),
-            // and the sweeps beside them go together where the sweeps-only launch covers them (dangx_plane_sweeps_sample)
-            GroupArgs gq;
-            if (make_group(ctx, group, flag, gq)) return 1;
-            if (gq.nt != 0 && solver == DANGX_SOLVER_DIRECT) {   // a coupled group: the Schur solve, its back-substitution with the sweeps
-                dangx_ctx* one[1] = {ctx};
-                return dangx_sky_plane_set_sample(one, 1, group, flag, ml_mode, solver, fluct_mode, seed_amp, stream_amp, i_max, converge, nsweeps,
-                                                  comp, nind, stream, nsample, seed_index, cg_iters, n_not_spd, accepted);
-            }
-            if (gq.nt != 0 || gq.nuc != 0) {
-                const int rc = dangx_amp_sample(ctx, group, flag, ml_mode, solver, fluct_mode, seed_amp, stream_amp, i_max, converge, cg_iters, n_not_spd);
-                return rc ? rc : dangx_plane_sweeps_sample(ctx, flag, nsweeps, comp, nind, stream, nsample, ml_mode, seed_index, accepted);
-            }
-        }
-        int s = 0;
-        int64_t acc = 0, acc2 = 0;
-        int rc = dangx_amp_index_sample(ctx, group, flag, ml_mode, solver, fluct_mode, seed_amp, stream_amp, i_max, converge, comp[0], nind[0],
-                                        map_n, nsample, seed_index, stream[0], cg_iters, n_not_spd, accepted ? &acc : nullptr);
-        if (rc) return rc;
-        if (accepted) accepted[0] = acc;
-        for (s = 1; s < nsweeps; ++s) {
-            if (s + 1 < nsweeps && comp[s + 1] == comp[s] && nind[s + 1] == nind[s] + 1) {
-                rc = dangx_index_sample_pair(ctx, comp[s], nind[s], map_n, nsample, ml_mode, seed_index, stream[s], stream[s + 1],
-                                             accepted ? &acc : nullptr, accepted ? &acc2 : nullptr);
-                if (rc) return rc;
-                if (accepted) { accepted[s] = acc; accepted[s + 1] = acc2; }
-                ++s;
-            } else {
-                rc = dangx_index_sample(ctx, comp[s], nind[s], map_n, nsample, ml_mode, seed_index, stream[s], accepted ? &acc : nullptr);
-                if (rc) return rc;
-                if (accepted) accepted[s] = acc;
-            }
-        }
-        return 0;
+    if (lanes) return planeset_launch(ctx, g, sl, lanes, 1, n_not_spd, accepted);
+    // ---- the calls this entry point stands for, through the two-step fusions where they apply
+    // template / monopole / hi_fit components in the model: the solve is the Schur path (or sees them as other components),
+    // and the sweeps beside them go together where the sweeps-only launch covers them (dangx_plane_sweeps_sample)
+    GroupArgs gq;
+    if (make_group(ctx, group, flag, gq)) return 1;
+    if (gq.nt != 0 && solver == DANGX_SOLVER_DIRECT) {   // a coupled group: the Schur solve, its back-substitution with the sweeps
+        dangx_ctx* one[1] = {ctx};
+        return dangx_sky_plane_set_sample(one, 1, group, flag, ml_mode, solver, fluct_mode, seed_amp, stream_amp, i_max, converge, nsweeps,
+                                          comp, nind, stream, nsample, seed_index, cg_iters, n_not_spd, accepted);
     }
-    return planeset_launch(ctx, g, sl, lanes, 1, n_not_spd, accepted);
+    if (gq.nt != 0 || gq.nuc != 0) {
+        const int rc = dangx_amp_sample(ctx, group, flag, ml_mode, solver, fluct_mode, seed_amp, stream_amp, i_max, converge, cg_iters, n_not_spd);
+        return rc ? rc : dangx_plane_sweeps_sample(ctx, flag, nsweeps, comp, nind, stream, nsample, ml_mode, seed_index, accepted);
+    }
+    int64_t acc = 0;
+    const int rc = dangx_amp_index_sample(ctx, group, flag, ml_mode, solver, fluct_mode, seed_amp, stream_amp, i_max, converge, comp[0], nind[0],
+                                          ps.map_n, nsample, seed_index, stream[0], cg_iters, n_not_spd, accepted ? &acc : nullptr);
+    if (rc) return rc;
+    if (accepted) accepted[0] = acc;
+    // (the loop, not dangx_plane_sweeps_sample: that call would try the sweeps-only launch, which is another route)
+    return sweeps_one_by_one(ctx, 1, ps.map_n, nsweeps, comp, nind, stream, nsample, ml_mode, seed_index, accepted);
 }
 
 // dangx_plane_set_sample over several contexts of ONE process (include/dangx.h).  Diffuse groups: that call on every context.  A
@@ -709,8 +700,7 @@ int dangx_sky_plane_set_sample(dangx_ctx* const* ctxs, int nctx, int group, int 
     if (accepted) for (int s = 0; s < nsweeps; ++s) accepted[s] = 0;
     auto add_acc = [&]() { if (accepted) for (int s = 0; s < nsweeps; ++s) accepted[s] += acc[(size_t)s]; };
     if (probe.nt == 0 || solver != DANGX_SOLVER_DIRECT) {
-        if (probe.nt != 0 && nctx > 1)
-            return fail(c0, "the device CG (DANGX_SOLVER_CG) iterates on ONE context per process: use DANGX_SOLVER_DIRECT, or one process per GPU with dangx_set_allreduce");
+        if (probe.nt != 0 && nctx > 1) return fail(c0, MSG_CG_ONE_CONTEXT);
         for (int r = 0; r < nctx; ++r) {
             int64_t bad = 0;
             if (dangx_plane_set_sample(ctxs[r], group, flag, ml_mode, solver, fluct_mode, seed_amp, stream_amp, i_max, converge, nsweeps, comp, nind,
@@ -721,37 +711,27 @@ int dangx_sky_plane_set_sample(dangx_ctx* const* ctxs, int nctx, int group, int 
         }
         return 0;
     }
-    const int map_n = (flag == DANGX_FLAG_T) ? 1 : (flag == DANGX_FLAG_Q) ? 2 : (flag == DANGX_FLAG_U) ? 3 : (flag == DANGX_FLAG_QU) ? -1 : 0;
-    if (map_n == 0) return fail(c0, "flag must be exactly one of T(1), Q(2), U(4), Q+U(8)");
+    PlaneSet ps;
+    if (plane_set_of(c0, flag, ps)) return 1;
     if (ml_mode != DANGX_ML_SAMPLE && ml_mode != DANGX_ML_OPTIMIZE) return fail(c0, "bad ml_mode");
-    if (textbook_refused(c0, probe, ml_mode, fluct_mode)) return fail(c0, "the textbook fluctuation term (DANGX_FLUCT_CORRECT) is refused for a group with a monopole or hi_fit member: its system is not symmetric, use DANGX_FLUCT_REFERENCE");
+    if (textbook_refused(c0, probe, ml_mode, fluct_mode)) return fail(c0, MSG_TEXTBOOK_GLOBALS);
     // with the textbook term the back-substitution is not deferred into the plane-set launch: the full Schur solve, then the sweeps
     const bool textbook = ml_mode == DANGX_ML_SAMPLE && fluct_mode != DANGX_FLUCT_REFERENCE;
-    static const bool enabled = [] { const char* e = getenv("DANGX_FUSE"); return !(e && e[0] == '0'); }();
-    const int s1 = (map_n == -1) ? 2 : map_n, s2 = (map_n == -1) ? 3 : map_n;
     std::vector<GroupArgs> as((size_t)nctx), gs((size_t)nctx);
     std::vector<SweepList> sls((size_t)nctx);
     std::vector<long long> SNs((size_t)nctx);
     std::vector<int> lanes((size_t)nctx, 0);
-    bool fuse = enabled && nsweeps <= 2 * DX_MAX_SWEEPS && !textbook;
+    bool fuse = dx_fuse_enabled() && nsweeps <= 2 * DX_MAX_SWEEPS && !textbook;
     for (int r = 0; r < nctx; ++r) {
         dangx_ctx* c = ctxs[r];
         (void)hipSetDevice(c->device);
-        for (int s = 0; s < nsweeps; ++s)
-            if (check_comp(c, comp[s]) || nind[s] < 0 || nind[s] >= c->desc[comp[s]].nindices) { fail(c, "sweep list: component / index out of range"); return bubble(c); }
-        if (make_group(c, group, flag, as[r]) || sync_model(c)) return bubble(c);
-        as[r].ml_mode = ml_mode; as[r].fluct = fluct_mode; as[r].seed = seed_amp; as[r].stream = stream_amp;
-        SNs[r] = (long long)flag_planes_h(flag) * c->hm.npix;
-        for (int k = s1; k <= s2; ++k) {
-            c->chi_before_valid[k - 1] = c->chi_after_valid[k - 1] = c->touched_since_amp[k - 1] = false;
-            c->cm_ok = false;
-            for (int g = 0; g < as[r].ng; ++g) c->plane_nz[as[r].gc[g]] |= 1u << (k - 1);
-        }
+        if (check_sweeps(c, nsweeps, comp, nind)) return bubble(c);
+        if (amp_prepare(c, group, flag, ml_mode, fluct_mode, seed_amp, stream_amp, as[r], SNs[r])) return bubble(c);
         if (as[r].nglob != as[0].nglob || as[r].nt != as[0].nt) return fail(c0, "the contexts disagree on the group's global-amplitude members");
         if (fuse) {
             gs[r] = as[r];
             std::memset(&sls[r], 0, sizeof(SweepList));
-            fuse = planeset_group(c, gs[r], s1, s2, 2) && planeset_items(c, gs[r], map_n, nsweeps, comp, nind, stream, sls[r]);
+            fuse = planeset_group(c, gs[r], ps.s1, ps.s2, 2) && planeset_items(c, gs[r], ps, nsweeps, comp, nind, stream, sls[r]);
             if (fuse) {
                 sls[r].nsample = nsample; sls[r].ml_mode = ml_mode; sls[r].seed = seed_index;
                 lanes[r] = dx_planeset_lanes(c, gs[r], sls[r], 1);
@@ -786,12 +766,9 @@ int dangx_plane_sweeps_sample(dangx_ctx* ctx, int flag, int nsweeps, const int32
     if (!ctx || nsweeps < 1 || !comp || !nind || !stream) return 1;
     (void)hipSetDevice(ctx->device);
     if (sync_model(ctx)) return 1;
-    const int map_n = (flag == DANGX_FLAG_T) ? 1 : (flag == DANGX_FLAG_Q) ? 2 : (flag == DANGX_FLAG_U) ? 3 : (flag == DANGX_FLAG_QU) ? -1 : 0;
-    if (map_n == 0) return fail(ctx, "flag must be exactly one of T(1), Q(2), U(4), Q+U(8)");
-    for (int s = 0; s < nsweeps; ++s)
-        if (check_comp(ctx, comp[s]) || nind[s] < 0 || nind[s] >= ctx->desc[comp[s]].nindices) return fail(ctx, "sweep list: component / index out of range");
-    static const bool enabled = [] { const char* e = getenv("DANGX_FUSE"); return !(e && e[0] == '0'); }();
-    bool can = enabled && nsweeps <= 2 * DX_MAX_SWEEPS && (ml_mode == DANGX_ML_SAMPLE || ml_mode == DANGX_ML_OPTIMIZE);
+    PlaneSet ps;
+    if (plane_set_of(ctx, flag, ps) || check_sweeps(ctx, nsweeps, comp, nind)) return 1;
+    bool can = dx_fuse_enabled() && nsweeps <= 2 * DX_MAX_SWEEPS && (ml_mode == DANGX_ML_SAMPLE || ml_mode == DANGX_ML_OPTIMIZE);
     const int group = ctx->desc[comp[0]].cg_group;
     for (int s = 0; can && s < nsweeps; ++s) can = ctx->desc[comp[s]].cg_group == group && ctx->desc[comp[s]].sample_amplitude;
     GroupArgs g;
@@ -799,28 +776,14 @@ int dangx_plane_sweeps_sample(dangx_ctx* ctx, int flag, int nsweeps, const int32
     int lanes = 0;
     if (can) {
         if (make_group(ctx, group, flag, g)) return 1;
-        if (planeset_group(ctx, g, (map_n == -1) ? 2 : map_n, (map_n == -1) ? 3 : map_n, 0) && planeset_items(ctx, g, map_n, nsweeps, comp, nind, stream, sl)) {
+        if (planeset_group(ctx, g, ps.s1, ps.s2, 0) && planeset_items(ctx, g, ps, nsweeps, comp, nind, stream, sl)) {
             sl.nsample = nsample; sl.ml_mode = ml_mode; sl.seed = seed;
             g.ml_mode = ml_mode; g.fluct = DANGX_FLUCT_REFERENCE; g.seed = 0; g.stream = 0;
             lanes = dx_planeset_lanes(ctx, g, sl, 0);
         }
     }
     if (lanes) return planeset_launch(ctx, g, sl, lanes, 0, nullptr, accepted);
-    int64_t acc = 0, acc2 = 0;
-    for (int s = 0; s < nsweeps; ++s) {
-        if (s + 1 < nsweeps && comp[s + 1] == comp[s] && nind[s + 1] == nind[s] + 1) {
-            const int rc = dangx_index_sample_pair(ctx, comp[s], nind[s], map_n, nsample, ml_mode, seed, stream[s], stream[s + 1],
-                                                   accepted ? &acc : nullptr, accepted ? &acc2 : nullptr);
-            if (rc) return rc;
-            if (accepted) { accepted[s] = acc; accepted[s + 1] = acc2; }
-            ++s;
-        } else {
-            const int rc = dangx_index_sample(ctx, comp[s], nind[s], map_n, nsample, ml_mode, seed, stream[s], accepted ? &acc : nullptr);
-            if (rc) return rc;
-            if (accepted) accepted[s] = acc;
-        }
-    }
-    return 0;
+    return sweeps_one_by_one(ctx, 0, ps.map_n, nsweeps, comp, nind, stream, nsample, ml_mode, seed, accepted);
 }
 
 // chi^2 of planes pol_lo..pol_hi from the values fused into the index sweeps: which = 0 -> the state the

@@ -642,7 +642,6 @@ int dangx_moments_accumulate(dangx_ctx* ctx) {
     for (int l = 0; l < ctx->dims.ncomp; ++l)
         if (m->sig_used[l] && (!ctx->comp_set[l] || ctx->desc[l].type != m->sig_type[l] || ctx->desc[l].nindices != m->sig_nind[l]))
             return fail(ctx, "posterior moments: component " + std::to_string(l) + " changed type or nindices since dangx_moments_signals");
-    if (ctx->have_pending) return fail(ctx, "posterior moments: an amplitude solve is still pending");   // not at a call boundary
     if (!m->hists.empty()) {   // no counter ever wraps: refused before anything is touched
         const std::string why = dx_hist_limit_check(m->count + 1, m->hbits);
         if (!why.empty()) return fail(ctx, "posterior moments: dangx_moments_accumulate: " + why);

@@ -3,6 +3,10 @@
 // dangx_coarse.hip: full-sky / coarse-Nside device side; dangx_amp.hip: amplitude kernels of diffuse groups; dangx_mixed.hip /
 // dangx_schur.hip: groups with template-type members (mixed CG operators / direct Schur solve); dangx_mh.hip: LDS-form
 // Metropolis kernels; dangx_mhreg.hip: register-resident Metropolis kernels, compiled once per chain mode).
+// The context holds state that outlives a call: the model, the buffers, and what is known about them (which cached chi^2 values and
+// index sums are valid, which planes carry a signal, which index maps are constant or equal on Q and U).  Nothing in it passes
+// arguments from one function of a call to another.  The small helpers every entry point shares live here too: flag -> planes
+// (PlaneSet), map_n -> planes (map_planes, map_bits), the DANGX_FUSE switch (dx_fuse_enabled), the counter read-back (read_counters).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -117,13 +121,6 @@ struct dangx_ctx {
     // last DANGX_SOLVER_DIRECT solve of a group with global-amplitude members: largest |b - A x| of a global row relative
     // to that row of b after the last refinement, and the number of refinement steps taken
     double schur_resid = 0.0, schur_backward = 0.0;  // relative to the row of b / to the size of the row's terms
-    // dangx_amp_index_sample: an amplitude solve whose launch waits for the index sweep it is fused with
-    bool defer_amp = false, have_pending = false;
-    // dangx_index_sample_pair: the sweep of index nind is launched together with the sweep of index nind + 1
-    bool pair_on = false, pair_done = false;
-    unsigned long long pair_stream = 0;
-    GroupArgs pending{};
-    long long pending_SN = 0;
     int schur_refine = 0;
     // kernels specialised at run time for this context's model (dangx_rtc.hip)
     std::vector<std::pair<std::string, hipFunction_t>> rtc_fns;
@@ -265,6 +262,36 @@ inline int map_planes(dangx_ctx* ctx, int map_n, int& s1, int& s2) {
     else if (map_n >= 1 && map_n <= 3) { s1 = s2 = map_n; }
     else return fail(ctx, "There is something wrong with the poltype flag (map_n must be 1,2,3 or -1)");
     if (s2 > ctx->dims.nmaps) return fail(ctx, "map_n exceeds nmaps");
+    return 0;
+}
+// bit k-1 for every plane k that map_n names (0: not a map_n)
+inline unsigned map_bits(int map_n) { return map_n == -1 ? 6u : (map_n >= 1 && map_n <= 3) ? 1u << (map_n - 1) : 0u; }
+// the planes of a CG group's flag: map_n as the index sweeps on them take it, first and last plane
+struct PlaneSet { int map_n, s1, s2; };
+// ... of a flag that is exactly one of T / Q / U / Q+U; map_n = 0 for any other value, for callers that do not fail on it
+inline PlaneSet plane_set_or_none(int flag) {
+    switch (flag) {
+        case DANGX_FLAG_T: return {1, 1, 1};
+        case DANGX_FLAG_Q: return {2, 2, 2};
+        case DANGX_FLAG_U: return {3, 3, 3};
+        case DANGX_FLAG_QU: return {-1, 2, 3};
+    }
+    return {0, 0, 0};
+}
+inline int plane_set_of(dangx_ctx* ctx, int flag, PlaneSet& ps) {
+    ps = plane_set_or_none(flag);
+    return ps.map_n ? 0 : fail(ctx, "flag must be exactly one of T(1), Q(2), U(4), Q+U(8)");
+}
+// DANGX_FUSE=0: every fusion of two phases into one launch is off (A/B switch; read once)
+inline bool dx_fuse_enabled() {
+    static const bool on = [] { const char* e = getenv("DANGX_FUSE"); return !(e && e[0] == '0'); }();
+    return on;
+}
+// counters[first .. first+n) -> out (the ABI's type for a count), on the context's stream, awaited
+inline int read_counters(dangx_ctx* ctx, int first, int n, int64_t* out) {
+    static_assert(sizeof(int64_t) == sizeof(unsigned long long), "counter width");
+    HIPCHK(ctx, hipMemcpyAsync(out, ctx->counters + first, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return 0;
 }
 
