@@ -24,10 +24,10 @@ COARSE_REFERENCE, COARSE_DEGRADED = 0, 1
 COARSE_MODEL_CODES = {"reference": COARSE_REFERENCE, "degraded": COARSE_DEGRADED}
 A2T, A2F, F2T = 0, 1, 2
 UNIT_CODES = {"uK_RJ": 0, "uK_cmb": 1, "MJy/sr": 2}
-K_AMP_DIRECT, K_INDEX_MH, K_SKY_CHISQ, K_REDUCE, K_CG_AX, K_CG_VEC, K_AMP_INDEX, K_MOMENTS, K_HIST, K_SIGNAL, K_CHAINS = range(11)
+K_AMP_DIRECT, K_INDEX_MH, K_SKY_CHISQ, K_REDUCE, K_CG_AX, K_CG_VEC, K_AMP_INDEX, K_MOMENTS, K_HIST, K_SIGNAL, K_CHAINS, K_BATCH = range(12)
 KERNEL_NAMES = {K_AMP_DIRECT: "k_amp_direct", K_INDEX_MH: "k_index_mh", K_SKY_CHISQ: "k_sky_chisq",
                 K_REDUCE: "k_reduce", K_CG_AX: "k_Ax", K_CG_VEC: "k_cg_vec", K_AMP_INDEX: "k_amp_index", K_MOMENTS: "k_moments",
-                K_HIST: "k_hist", K_SIGNAL: "k_signal", K_CHAINS: "k_chains"}
+                K_HIST: "k_hist", K_SIGNAL: "k_signal", K_CHAINS: "k_chains", K_BATCH: "k_batch"}
 STAT_CODES = {"mean": 0, "std": 1, "rho1": 2, "ess": 3}
 PAIR_STAT_CODES = {"cov": 0, "corr": 1}
 MAX_PAIRS = 64
@@ -36,6 +36,8 @@ MAX_HIST, MAX_HIST_Q = 32, 16
 MAX_SIGNALS = 64
 MAX_CHAINS = 8
 CHAINS_STAT_CODES = {"mean": 0, "std": 1, "rhat": 2, "W": 3, "B": 4, "ess": 5}
+BATCH_STAT_CODES = {"mean": 0, "std": 1, "mcse": 2, "ess_bm": 3, "split_rhat": 4}
+MAX_BATCHES, MAX_BATCH_PLANES = 32, 32
 SIGNAL_KINDS = ("T", "Q", "U", "P")      # kind 0..3 of a signal spec (comp, band, kind)
 
 TYPE_CODES = {"power-law": POWERLAW, "mbb": MBB, "freefree": FREEFREE, "lognormal": LOGNORMAL, "cmb": CMB, "T_cmb": TCMB,
@@ -171,6 +173,12 @@ SYMBOLS = {
     "dangx_moments_get_signal": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
     "dangx_moments_get_signal_dev": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
     "dangx_moments_end": (C.c_int, [_P]),
+    "dangx_moments_batches": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int64]),
+    "dangx_moments_batches_info": (C.c_int, [_P, _P, _P, _P]),
+    "dangx_moments_batches_get": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "dangx_moments_batches_get_dev": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "dangx_moments_batches_raw": (C.c_int, [_P, C.c_int, C.c_int, _P, _P]),
+    "dangx_moments_batches_raw_dev": (C.c_int, [_P, C.c_int, C.c_int, _P, _P]),
     # read-outs over several chains: (ctxs, nchains, ...) = one context per chain
     "dangx_chains_get": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "dangx_chains_get_dev": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
@@ -181,6 +189,8 @@ SYMBOLS = {
     "dangx_chains_get_pair_dev": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "dangx_chains_hist_stat": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "dangx_chains_hist_stat_dev": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "dangx_chains_batches_get": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "dangx_chains_batches_get_dev": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "dangx_profile_enable": (C.c_int, [_P, C.c_int]),
     "dangx_profile_reset": (C.c_int, [_P]),
     "dangx_profile_get": (C.c_int, [_P, C.c_int, _D, C.POINTER(C.c_int64)]),

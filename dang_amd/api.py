@@ -645,6 +645,7 @@ class Engine:
         self._moment_pairs, self._moment_lag1 = [], False   # dangx_moments_begin drops what moments_pairs registered
         self._moment_hist = None                            # ... and what moments_hist registered
         self._moment_signals = None                         # ... and what moments_signals registered
+        self._moment_batches = None                         # ... and what moments_batches registered
         if sel is None:
             self._chk(self.lib.dangx_moments_begin(self.h, None))
             full = (1 << self.nmaps) - 1
@@ -783,8 +784,46 @@ class Engine:
             self.synchronize()
         return out
 
+    def moments_batches(self, planes, nbatch=16, batch_len=1):
+        """Register batched accumulators after moments_begin and before the first moments_accumulate: planes = [(l, what, plane),
+        ...] as in moments_hist, nbatch (even, 2..32) batches of initially batch_len samples, each with its own (mean, m2); when
+        all are full they are merged pairwise in place and the batch length doubles.  nbatch * 16 bytes per pixel and plane.
+        Independent of moments_pairs / _hist / _signals; a second call replaces the first.  Definitions: include/dangx.h."""
+        p = np.ascontiguousarray(np.asarray(list(planes), dtype=np.int32).reshape(-1, 3))
+        self._chk(self.lib.dangx_moments_batches(self.h, p.shape[0], p.ctypes.data if p.size else None, int(nbatch), int(batch_len)))
+        self._moment_batches = {"planes": [tuple(int(v) for v in r) for r in p], "nbatch": int(nbatch), "batch_len": int(batch_len)} if p.size else None
+
+    def moments_batches_info(self):
+        """{'batch_len': the current L, 'nfull': full batches, 'partial': samples in the open batch}"""
+        L_, nf, pa = C.c_int64(0), C.c_int32(0), C.c_int64(0)
+        self._chk(self.lib.dangx_moments_batches_info(self.h, C.byref(L_), C.byref(nf), C.byref(pa)))
+        return {"batch_len": L_.value, "nfull": nf.value, "partial": pa.value}
+
+    def moments_batches_get(self, reg, stat, first=0, ddof=0, device=False, out=None):
+        """Read-out of batch registration reg as [npix], the first `first` batches discarded as burn-in: 'mean' / 0 and 'std' / 1
+        over every later sample (open batch included), 'mcse' / 2 the batch-means Monte-Carlo standard error of the mean, 'ess_bm'
+        / 3 the batch-means effective sample size, 'split_rhat' / 4 R-hat of the two halves of the last full batches (NaN where
+        the pixel never moved).  device=True: a torch cuda tensor filled on the device."""
+        st = L.BATCH_STAT_CODES[stat] if isinstance(stat, str) else int(stat)
+        out, ptr = _readout_dest(self, (self.npix,), device, out)
+        self._chk((self.lib.dangx_moments_batches_get_dev if device else self.lib.dangx_moments_batches_get)(self.h, int(reg), st, int(first),
+                                                                                                         int(ddof), ptr))
+        if device:
+            self.synchronize()
+        return out
+
+    def moments_batches_raw(self, reg, batch, device=False):
+        """(mean, m2) of one batch of registration reg as it is, [npix] each: the batch-means trace."""
+        mean, pm = _readout_dest(self, (self.npix,), device)
+        m2, pq = _readout_dest(self, (self.npix,), device)
+        self._chk((self.lib.dangx_moments_batches_raw_dev if device else self.lib.dangx_moments_batches_raw)(self.h, int(reg), int(batch), pm, pq))
+        if device:
+            self.synchronize()
+        return mean, m2
+
     def moments_end(self):
         self._moment_signals = None
+        self._moment_batches = None
         self._chk(self.lib.dangx_moments_end(self.h))
 
     # -- profiling
@@ -1358,6 +1397,75 @@ def posterior_quantile_maps(ddata, q=(0.16, 0.5, 0.84), masked_value=None, engin
     return out
 
 
+BATCH_STATS = ("mean", "std", "mcse", "ess_bm", "split_rhat")
+
+
+def moments_batches(dpar, ddata, planes=None, nbatch=16, batch_len=1, engines=None):
+    """dangx_moments_batches on every context of this process, after moments_begin and before the first moments_accumulate;
+    planes=None: default_hist_planes of the selection moments_begin made (every sampled index).  Returns the plane list."""
+    engs = _engines_of(ddata, engines)
+    if planes is None:
+        sel = getattr(engs[0], "_moment_sel", None)
+        if sel is None:
+            raise DangxError("moments_batches: moments_begin was not called")
+        planes = default_hist_planes(dpar, engs[0].component_list, sel)
+    planes = [tuple(int(v) for v in p) for p in planes]
+    for e in engs:
+        e.moments_batches(planes, nbatch=nbatch, batch_len=batch_len)
+    return planes
+
+
+def _batch_stats(info, first):
+    """The statistics a chain with these batches carries after `first` are discarded: MCSE, ESS and split R-hat need two full
+    batches, split R-hat two samples per half."""
+    B = info["nfull"] - first
+    out = ("mean", "std")
+    if B >= 2:
+        out += ("mcse", "ess_bm")
+        if (B // 2) * info["batch_len"] >= 2:
+            out += ("split_rhat",)
+    return out
+
+
+def _batch_first_check(who, info, first):
+    """`first` leading batches can be discarded when they exist and a sample is left behind them"""
+    if not 0 <= first <= info["nfull"]:
+        raise DangxError("%s: first must be 0 .. %d full batches, not %d" % (who, info["nfull"], first))
+    if first == info["nfull"] and info["partial"] == 0:
+        raise DangxError("%s: first = %d discards every sample held (%d full batches, none in the open one)" % (who, first, info["nfull"]))
+
+
+def posterior_batch_maps(ddata, first=0, ddof=0, masked_value=None, engines=None):
+    """{(label, name, plane): {'mean', 'std', 'mcse', 'ess_bm', 'split_rhat', 'n', 'batch_len', 'nfull', 'partial', 'first'}} of
+    the planes moments_batches registered, the first `first` batches discarded as burn-in; keys as posterior_quantile_maps'.  A
+    statistic the batches held cannot give yet (fewer than two full ones after `first`) is left out.  Several contexts of this
+    process: their shards side by side.  masked_value: as in posterior_maps."""
+    engs = _engines_of(ddata, engines)
+    regs = [getattr(e, "_moment_batches", None) for e in engs]
+    if not regs[0]:
+        raise DangxError("posterior_batch_maps: moments_batches was not called")
+    if any(r != regs[0] for r in regs[1:]):
+        raise DangxError("posterior_batch_maps: the contexts hold different batch registrations")
+    counts = {e.moments_count() for e in engs}
+    if len(counts) != 1:
+        raise DangxError("posterior_batch_maps: the contexts hold different sample counts %s" % sorted(counts))
+    n = counts.pop()
+    info = engs[0].moments_batches_info()
+    _batch_first_check("posterior_batch_maps", info, first)
+    comps = engs[0].component_list
+    out = {}
+    for r, (l, what, k) in enumerate(regs[0]["planes"]):
+        entry = dict(info, n=n, first=int(first))
+        for stat in _batch_stats(info, first):
+            parts = []
+            for e in engs:
+                m = e.moments_batches_get(r, stat, first, ddof)
+                parts.append(_mask_fill(m, e.ddata.masks, masked_value) if masked_value is not None else m)
+            entry[stat] = np.concatenate(parts, axis=-1) if len(parts) > 1 else parts[0]
+        out[(comps[l].label, _plane_name(comps[l], what), k)] = entry
+    return out
+
+
 def default_signal_specs(dpar, component_list, bands):
     """[(l, band, kind), ...] for moments_signals: for every non-global component whose amplitude is sampled and that has at least
     one sampled index (without one its signal is a constant multiple of its amplitude), the signal at the band whose nu_c is
@@ -1597,6 +1705,40 @@ def chains_quantile_maps(chains, q=(0.16, 0.5, 0.84), masked_value=None):
         entry = {"range": reg0["ranges"][r], "nbins": reg0["nbins"]}
         for name, stat in (("q", "quantile"), ("mode", "mode"), ("n", "n")):
             entry[name] = _chains_map(shards, lambda col: chains_hist_stat(col, r, stat, q=q if stat == "quantile" else None), masked_value)
+        out[(comps[l].label, _plane_name(comps[l], what), k)] = entry
+    return out
+
+
+def chains_batches_get(engines, reg, stat, first=0, ddof=0, device=False, out=None):
+    """Engine.moments_batches_get over the chains `engines` (the same registration, batch length and count in each): 'mean' /
+    'std' pooled over chains and batches first.., 'mcse' = sqrt(sum MCSE_k^2) / K, 'ess_bm' = sum ESS_k, 'split_rhat' over the 2K
+    half-chains, as [npix].  device=True: written asynchronously on the first chain's stream."""
+    e = engines[0]
+    st = L.BATCH_STAT_CODES[stat] if isinstance(stat, str) else int(stat)
+    out, ptr = _readout_dest(e, (e.npix,), device, out)
+    _chains_call(engines, "dangx_chains_batches_get_dev" if device else "dangx_chains_batches_get", int(reg), st, int(first), int(ddof), ptr)
+    return out
+
+
+def chains_batch_maps(chains, first=0, ddof=0, masked_value=None):
+    """posterior_batch_maps over several chains: the same keys, every entry with chains_batches_get's statistics + 'n' (samples per
+    chain), 'nchains', 'batch_len', 'nfull', 'partial', 'first'.  Every chain must hold the same registration and batch state."""
+    shards, counts = _chains_shards(chains, "chains_batch_maps")
+    reg0 = getattr(shards[0][0], "_moment_batches", None)
+    if not reg0:
+        raise DangxError("chains_batch_maps: moments_batches was not called")
+    if any(getattr(e, "_moment_batches", None) != reg0 for col in shards for e in col):
+        raise DangxError("chains_batch_maps: the contexts hold different batch registrations")
+    if len(set(counts)) != 1:
+        raise DangxError("chains_batch_maps: the chains hold different sample counts %s" % list(counts))
+    info = shards[0][0].moments_batches_info()
+    _batch_first_check("chains_batch_maps", info, first)
+    comps = shards[0][0].component_list
+    out = {}
+    for r, (l, what, k) in enumerate(reg0["planes"]):
+        entry = dict(info, n=counts[0], nchains=len(counts), first=int(first))
+        for stat in _batch_stats(info, first):
+            entry[stat] = _chains_map(shards, lambda col: chains_batches_get(col, r, stat, first, ddof), masked_value)
         out[(comps[l].label, _plane_name(comps[l], what), k)] = entry
     return out
 

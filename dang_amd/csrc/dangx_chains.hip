@@ -1,5 +1,6 @@
 // dangx_chains.hip -- dangx_chains_*: read-outs over the accumulators of SEVERAL chains of one device (definitions in dx_chains_host.h).  Nothing here
-// touches an accumulator, a chain or a cache: three read-only kernels combine the per-chain planes and write only the map asked for.
+// touches an accumulator, a chain or a cache: four read-only kernels combine the per-chain planes and write only the map asked for.
+//   k_chains_batches  the batched accumulators (dx_batches_host.h): every chain's slots in one pass from one base pointer per chain.
 //   k_chains_stat  planes and signals (blockIdx.y = plane, up to three): pooled mean / std, R-hat, W, B/n read K x (mean, m2) --
 //                  a stat that does not use one of the two does not load it -- and write one f64: at most (2 K + 1) x 8 B per
 //                  element; the pooled ESS reads K x (mean, m2, prev, first, P), (5 K + 1) x 8 B.
@@ -12,6 +13,7 @@
 #include "dx_moments_state.h"
 #include "dx_hist_host.h"
 #include "dx_chains_host.h"
+#include "dx_batches_host.h"
 #include "dx_stream.h"
 
 static_assert(DX_CHAINS_MAX == DANGX_MAX_CHAINS, "dx_chains_host.h and include/dangx.h disagree");
@@ -165,6 +167,46 @@ __device__ __forceinline__ void chains_hist_walk(const ChainsHistArgs& a, long l
 __global__ __launch_bounds__(BLOCK) void k_chains_hist(ChainsHistArgs a) {
     const int pieces = dx_hist_words(a.nbins, a.bits) / 4;
     dx_hist_readout<unsigned long long>(a, [&](long long i, auto f) { chains_hist_walk(a, i, pieces, f); });
+}
+
+struct ChainsBatchArgs {   // one base pointer per chain (slot 0's mean plane of the registration) plus the stride of the regular layout
+    const double* base[DX_CHAINS_MAX];
+    double* out;
+    long long pitch, n;
+    DxBatchPar par;
+};
+static_assert(sizeof(ChainsBatchArgs) <= 2048, "the arguments must stay well inside the 4 KB kernel-argument segment");
+
+// read where the kernel arguments lie (scalar loads at a computed offset: base[k], the ratio tables), never copied
+typedef const ChainsBatchArgs __attribute__((address_space(4))) * batch_kptr;
+
+template <int V>
+__device__ __forceinline__ void chains_batch_item(batch_kptr a, long long i) {
+    double r[V];
+    const long long pitch = a->pitch;
+    dx_chains_batches_stat<V>(a->par, [&](int k, int b, bool want_m2, double (&m)[V], double (&q)[V]) DX_LAMBDA_INLINE {
+        const double* base = a->base[k];
+        ChV<V>::ld(base + (2LL * b) * pitch + i, m);
+        if (want_m2) ChV<V>::ld(base + (2LL * b + 1) * pitch + i, q);
+        else {
+#pragma unroll
+            for (int e = 0; e < V; ++e) q[e] = 0.0;
+        }
+    }, r);
+    ChV<V>::st(a->out + i, r);
+}
+
+// k_batches_stat over K chains: every chain's slots in one pass with running values, at most (2 K nbatch + 1) x 8 B per element;
+// the 2K half-means of split R-hat stay in registers (constant subscripts through dx_chains_each)
+// ChainsBatchArgs must stay the FIRST and ONLY explicit parameter: the kernel reads it at offset 0 of the kernel-argument segment,
+// not through the (unnamed) parameter.  A parameter put in front of it would shift what `a` points at; one added behind it is
+// harmless but must be read the same way or by name.
+__global__ __launch_bounds__(BLOCK) void k_chains_batches(ChainsBatchArgs) {
+    const batch_kptr a = (batch_kptr)__builtin_amdgcn_kernarg_segment_ptr();
+    const uintptr_t ao = addr(a->out);
+    uintptr_t diff = ao & 7;
+    for (int k = 0; k < a->par.K; ++k) diff |= (ao ^ addr(a->base[k])) & 15;
+    dx_stream(a->n, diff == 0, ao, [&](long long i) { chains_batch_item<1>(a, i); }, [&](long long i) { chains_batch_item<2>(a, i); });
 }
 
 // ---- host side
@@ -423,9 +465,64 @@ int chains_hist_impl(dangx_ctx* const* ctxs, int nchains, int reg, int stat, int
     return ro.close(total);
 }
 
+int chains_batches_impl(dangx_ctx* const* ctxs, int nchains, int reg, int stat, int first, int ddof, double* out, bool to_host) {
+    if (!ctxs || !ctxs[0] || !out) return 1;
+    ChainSet cs{};
+    if (chains_open(ctxs, nchains, cs)) return 1;
+    const DxMoments* m0 = ctxs[0]->mom;
+    if (m0->batches.empty()) return chains_fail(ctxs, "chain 0: no batches are registered (dangx_moments_batches was not called)");
+    if (reg < 0 || reg >= (int)m0->batches.size())
+        return chains_fail(ctxs, "chain 0: batch registration out of range (" + std::to_string(m0->batches.size()) + " registered)");
+    for (int k = 1; k < nchains; ++k) {
+        const DxMoments* m = ctxs[k]->mom;
+        const std::string at = "chain " + std::to_string(k) + ": ";
+        if (reg >= (int)m->batches.size() || !same_plane(m->segs[m->batches[reg].seg], m0->segs[m0->batches[reg].seg]))
+            return chains_fail(ctxs, at + "batch registration " + std::to_string(reg) + " is not the registration of chain 0");
+        if (m->nbatch != m0->nbatch)
+            return chains_fail(ctxs, at + "nbatch is " + std::to_string(m->nbatch) + ", chain 0 has " + std::to_string(m0->nbatch));
+        if (m->count != m0->count)
+            return chains_fail(ctxs, at + "batch read-outs need equal sample counts: it holds " + std::to_string(m->count) + ", chain 0 holds " +
+                                         std::to_string(m0->count));
+        if (m->batch_len != m0->batch_len)
+            return chains_fail(ctxs, at + "the batch length is " + std::to_string(m->batch_len) + ", chain 0 has " + std::to_string(m0->batch_len));
+    }
+    const DxBatchPos p = dx_batches_pos(m0->count, m0->batch_len);
+    std::string why = dx_batches_stat_check(stat, first, 0, p.L, p.nfull, p.partial);
+    if (why.empty() && stat == DX_BT_STD) {
+        const long long N = (long long)nchains * ((p.nfull - first) * p.L + p.partial);
+        if (ddof < 0 || N - ddof <= 0) why = "standard deviation needs 0 <= ddof < N (N = " + std::to_string(N) + ")";
+    }
+    if (!why.empty()) return chains_fail(ctxs, "dangx_chains_batches_get: " + why);
+    dangx_ctx* c0 = ctxs[0];
+    (void)hipSetDevice(c0->device);
+    const long long n = c0->dims.npix;
+    ReadOut ro{c0, out, to_host};
+    if (ro.open(sizeof(double) * (size_t)n)) return 1;
+    ChainsBatchArgs a{};
+    for (int j = 0; j < cs.K; ++j) a.base[j] = ctxs[j]->mom->bmean(ctxs[j]->mom->batches[reg], 0);
+    a.out = ro.dst; a.pitch = m0->bpitch; a.n = n;
+    a.par = dx_batches_par(stat, first, ddof, p.L, p.nfull, p.partial, cs.K);
+    if (chains_join(cs)) return 1;
+    {
+        Timed tm(c0, DANGX_K_CHAINS);
+        hipLaunchKernelGGL(k_chains_batches, dim3(c0->mom->grid_for((n + 1) / 2, 1)), dim3(BLOCK), 0, c0->stream, a);
+        HIPCHK(c0, hipGetLastError());
+    }
+    if (chains_release(cs)) return 1;
+    return ro.close(n);
+}
+
 }  // namespace
 
 extern "C" {
+
+int dangx_chains_batches_get_dev(dangx_ctx* const* ctxs, int nchains, int reg, int stat, int first, int ddof, double* out_dev) {
+    return chains_batches_impl(ctxs, nchains, reg, stat, first, ddof, out_dev, false);
+}
+
+int dangx_chains_batches_get(dangx_ctx* const* ctxs, int nchains, int reg, int stat, int first, int ddof, double* out) {
+    return chains_batches_impl(ctxs, nchains, reg, stat, first, ddof, out, true);
+}
 
 int dangx_chains_get_dev(dangx_ctx* const* ctxs, int nchains, int comp, int what, int stat, int ddof, double* out_dev) {
     return chains_get_impl(ctxs, nchains, comp, what, stat, ddof, out_dev, false);

@@ -38,11 +38,19 @@
 // and updates the f64 mean / m2 planes of every registered output of every band of the segment.  Segments with an integrated
 // band go to a second launch of the kernel's BP form (the streaming form carries no bandpass code).  Nothing registered: no launch.
 //
+// dangx_moments_batches adds batched accumulators of registered pixel planes (definitions in dx_batches_host.h): nbatch slots of
+// (mean, m2) per plane in an allocation of the library's own.  An accumulation adds ONE launch of k_moments_accum behind the
+// others, on the table row of the slot the sample belongs to (inv_n = 1 / its number within the slot); when every slot is full
+// k_batches_merge first folds the slots pairwise in place and the batch length doubles.  k_batches_stat reads the slots in one
+// pass with running values (discarded burn-in, MCSE, batch-means ESS, split R-hat).  Nothing registered: no launch.
+//
 // The state (DxMoments) and the host helpers are in dx_moments_state.h, the loop over a plane (dx_stream) in dx_stream.h; the
 // read-outs over several chains (dangx_chains_*) are a translation unit of their own, dangx_chains.hip.
 #include "dx_moments_state.h"
 #include "dx_moments_host.h"
 #include "dx_hist_host.h"
+#define DX_BATCH_UNROLL 4   // k_batches_stat: four slots' loads in flight (79 VGPRs, occupancy 6)
+#include "dx_batches_host.h"
 #include "dx_stream.h"
 
 #include <memory>
@@ -50,6 +58,7 @@
 static_assert(DX_MOM_MAX_PAIRS == DANGX_MAX_PAIRS, "dx_moments_host.h and include/dangx.h disagree");
 static_assert(DX_HIST_MAX == DANGX_MAX_HIST, "dx_hist_host.h and include/dangx.h disagree");
 static_assert(DX_SIG_MAX == DANGX_MAX_SIGNALS, "dx_signal_host.h and include/dangx.h disagree");
+static_assert(DX_BATCH_MAX == DANGX_MAX_BATCHES && DX_BATCH_MAX_PLANES == DANGX_MAX_BATCH_PLANES, "dx_batches_host.h and include/dangx.h disagree");
 
 namespace {
 
@@ -350,6 +359,66 @@ __global__ __launch_bounds__(BLOCK) void k_moments_finish(FinishArgs a) {
     double* __restrict__ out = a.out[p];
     for (long long i = (long long)blockIdx.x * BLOCK + threadIdx.x; i < a.n; i += (long long)gridDim.x * BLOCK)
         out[i] = a.stat == 0 ? mean[i] : sqrt(m2[i] / a.dn);
+}
+
+// ---- batched accumulators
+
+// V consecutive elements of every slot of a registration: slots (2t, 2t+1) folded into slot t for t ascending, the upper half zeroed
+template <int V>
+__device__ __forceinline__ void merge_item(double* base, long long pitch, int nbatch, double halfL, long long i) {
+    const int half = nbatch / 2;
+    for (int t = 0; t < half; ++t) {
+        double mu[V], M[V], m[V], q[V];
+        ChV<V>::ld(base + (4LL * t) * pitch + i, mu); ChV<V>::ld(base + (4LL * t + 1) * pitch + i, M);
+        ChV<V>::ld(base + (4LL * t + 2) * pitch + i, m); ChV<V>::ld(base + (4LL * t + 3) * pitch + i, q);
+#pragma unroll
+        for (int e = 0; e < V; ++e) dx_batches_merge(m[e], q[e], halfL, mu[e], M[e]);
+        ChV<V>::st(base + (2LL * t) * pitch + i, mu); ChV<V>::st(base + (2LL * t + 1) * pitch + i, M);
+    }
+    double z[V];
+#pragma unroll
+    for (int e = 0; e < V; ++e) z[e] = 0.0;
+    for (int t = 2 * half; t < 2 * nbatch; ++t) ChV<V>::st(base + (long long)t * pitch + i, z);
+}
+
+// blockIdx.y = registration; segs: the table row of slot 0, whose mean is the registration's first plane (planes `pitch` apart:
+// mean_0, m2_0, mean_1, ...).  The merge is IN PLACE: one thread owns an element (a pair of elements) in every slot, and walks
+// t ascending -- it reads slots 2t and 2t+1 before it writes slot t, and a later step t' > t reads slots 2t', 2t'+1 >= 2t + 2 > t,
+// so no step overwrites a source that is still unread (destination t <= 2t).  No second buffer, no atomics, no other thread
+// touches the element.
+__global__ __launch_bounds__(BLOCK) void k_batches_merge(const MomSeg* __restrict__ segs, long long pitch, int nbatch, double halfL) {
+    const MomSeg s = segs[blockIdx.y];
+    dx_stream(s.n, true, addr(s.mean), [&](long long i) { merge_item<1>(s.mean, pitch, nbatch, halfL, i); },
+              [&](long long i) { merge_item<2>(s.mean, pitch, nbatch, halfL, i); });
+}
+
+struct BatchStatArgs {
+    const double* base;   // slot 0's mean plane of the registration
+    double* out;
+    long long pitch, n;
+    DxBatchPar par;
+};
+
+template <int V>
+__device__ __forceinline__ void batch_stat_item(const BatchStatArgs& a, long long i) {
+    double r[V];
+    dx_batches_stat<V>(a.par, [&](int b, bool want_m2, double (&m)[V], double (&q)[V]) DX_LAMBDA_INLINE {
+        ChV<V>::ld(a.base + (2LL * b) * a.pitch + i, m);
+        if (want_m2) ChV<V>::ld(a.base + (2LL * b + 1) * a.pitch + i, q);
+        else {
+#pragma unroll
+            for (int e = 0; e < V; ++e) q[e] = 0.0;
+        }
+    }, r);
+    ChV<V>::st(a.out + i, r);
+}
+
+// one registration's slots in ONE pass with running values: at most (2 nbatch + 1) x 8 B per element; a stat that does not use
+// m2 (mean, MCSE) does not load it.  16-byte accesses where out shares the slots' phase, element by element otherwise.
+__global__ __launch_bounds__(BLOCK) void k_batches_stat(BatchStatArgs a) {
+    const uintptr_t ao = addr(a.out);
+    const bool vec = ((ao & 7) | ((ao ^ addr(a.base)) & 15)) == 0;
+    dx_stream(a.n, vec, ao, [&](long long i) { batch_stat_item<1>(a, i); }, [&](long long i) { batch_stat_item<2>(a, i); });
 }
 
 void host_welford(double x, double& mean, double& m2, double inv_n) {
@@ -681,6 +750,12 @@ int dangx_moments_accumulate(dangx_ctx* ctx) {
                                          m->hbins, m->hbits});
                 HIPCHK(ctx, hipMemcpyAsync(m->d_hist, th.data(), sizeof(HistSeg) * th.size(), hipMemcpyHostToDevice, ctx->stream));
             }
+            std::vector<MomSeg> tb;
+            if (m->d_batch) {   // every slot's row at once: moving on to the next slot needs no upload
+                for (int b = 0; b < m->nbatch; ++b)
+                    for (const auto& r : m->batches) tb.push_back(MomSeg{t[r.seg].x, m->bmean(r, b), m->bm2(r, b), (long long)ctx->dims.npix});
+                HIPCHK(ctx, hipMemcpyAsync(m->d_batch, tb.data(), sizeof(MomSeg) * tb.size(), hipMemcpyHostToDevice, ctx->stream));
+            }
             HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
             m->table = t;
         }
@@ -729,6 +804,20 @@ int dangx_moments_accumulate(dangx_ctx* ctx) {
                                (const SigSeg*)(m->d_sig + ndelta), inv_n);
             HIPCHK(ctx, hipGetLastError());
         }
+    }
+    if (!m->batches.empty()) {   // the batched accumulators: k_moments_accum on the row of the slot this sample belongs to
+        const unsigned nreg = (unsigned)m->batches.size(), gx = m->grid_for(pairs, nreg);
+        if (m->count / m->batch_len == m->nbatch) {   // every slot is full: merged pairwise in place, and the batch length doubles
+            Timed tm(ctx, DANGX_K_BATCH, 2);   // the profile tells a merge from an accumulation by this mark
+            hipLaunchKernelGGL(k_batches_merge, dim3(gx, nreg), dim3(BLOCK), 0, ctx->stream, (const MomSeg*)m->d_batch, m->bpitch, m->nbatch,
+                               0.5 * (double)m->batch_len);
+            HIPCHK(ctx, hipGetLastError());
+            m->batch_len *= 2;
+        }
+        const long long b = m->count / m->batch_len, j = m->count % m->batch_len + 1;
+        Timed tm(ctx, DANGX_K_BATCH);
+        hipLaunchKernelGGL(k_moments_accum, dim3(gx, nreg), dim3(BLOCK), 0, ctx->stream, (const MomSeg*)(m->d_batch + b * nreg), 1.0 / (double)j);
+        HIPCHK(ctx, hipGetLastError());
     }
     for (int l = 0; l < ctx->dims.ncomp; ++l) {
         if (!m->sel[l] || !is_global_type(ctx->desc[l].type)) continue;
@@ -995,6 +1084,119 @@ int dangx_moments_get_signal_dev(dangx_ctx* ctx, int sig, int stat, int ddof, do
 
 int dangx_moments_get_signal(dangx_ctx* ctx, int sig, int stat, int ddof, double* out) {
     return get_signal_impl(ctx, sig, stat, ddof, out, true);
+}
+
+int dangx_moments_batches(dangx_ctx* ctx, int nreg, const int32_t* planes, int nbatch, int64_t batch_len) {
+    if (!ctx || need(ctx)) return 1;
+    DxMoments* m = ctx->mom;
+    if (m->count != 0)
+        return fail(ctx, "posterior moments: dangx_moments_batches is legal only before the first dangx_moments_accumulate after dangx_moments_begin");
+    const int ncomp = ctx->dims.ncomp;
+    int nind[MAXC] = {}, global[MAXC] = {};
+    for (int l = 0; l < ncomp; ++l) {
+        nind[l] = m->nind[l];
+        global[l] = is_global_type(m->type[l]) ? 1 : 0;
+    }
+    const std::string why = dx_batches_check(nreg, planes, nbatch, batch_len, ncomp, ctx->dims.nmaps, m->sel, nind, global);
+    if (!why.empty()) return fail(ctx, "posterior moments: dangx_moments_batches: " + why);
+    const long long pitch = ctx->dims.npix + (ctx->dims.npix & 1);   // even: every plane of a registration at the phase of its first
+    std::vector<DxMoments::Batch> nb;
+    long long off = 0;
+    for (int r = 0; r < nreg; ++r) {
+        const int seg = m->find_seg(planes[3 * r], planes[3 * r + 1], planes[3 * r + 2]);
+        if (seg < 0) return fail(ctx, "posterior moments: dangx_moments_batches: registration " + std::to_string(r) + ": a plane that is not selected");
+        if ((off & 1) != (m->segs[seg].off & 1)) ++off;
+        nb.push_back(DxMoments::Batch{seg, off});
+        off += 2LL * nbatch * pitch;
+    }
+    (void)hipSetDevice(ctx->device);
+    // everything new is allocated before anything old is dropped: a failure leaves the registration as it was
+    DevBuf<double> bacc;
+    DevBuf<MomSeg> d_batch;
+    DevStatus st;
+    if (!nb.empty()) {
+        bacc.zeros((size_t)off, ctx->stream, st);
+        d_batch.alloc(nb.size() * (size_t)nbatch, st);
+        st.sync(ctx->stream);
+    }
+    if (!st.ok()) return st.fail(ctx, "dangx_moments_batches: ");
+    m->bacc = std::move(bacc); m->d_batch = std::move(d_batch);
+    m->batches = nb;
+    m->nbatch = nb.empty() ? 0 : nbatch;
+    m->batch_len = nb.empty() ? 0 : (long long)batch_len;
+    m->bpitch = pitch;
+    m->table.clear();   // the next accumulation uploads the tables
+    return 0;
+}
+
+static int batches_need(dangx_ctx* ctx, int reg) {
+    if (need(ctx)) return 1;
+    const DxMoments* m = ctx->mom;
+    if (m->batches.empty()) return fail(ctx, "posterior moments: no batches are registered (dangx_moments_batches was not called)");
+    if (reg < 0 || reg >= (int)m->batches.size())
+        return fail(ctx, "posterior moments: batch registration out of range (" + std::to_string(m->batches.size()) + " registered)");
+    return 0;
+}
+
+int dangx_moments_batches_info(dangx_ctx* ctx, int64_t* batch_len, int32_t* nfull, int64_t* partial) {
+    if (!ctx || batches_need(ctx, 0)) return 1;
+    const DxMoments* m = ctx->mom;
+    const DxBatchPos p = dx_batches_pos(m->count, m->batch_len);
+    if (batch_len) *batch_len = p.L;
+    if (nfull) *nfull = p.nfull;
+    if (partial) *partial = p.partial;
+    return 0;
+}
+
+static int batches_get_impl(dangx_ctx* ctx, int reg, int stat, int first, int ddof, double* out, bool to_host) {
+    if (!ctx || !out || batches_need(ctx, reg)) return 1;
+    const DxMoments* m = ctx->mom;
+    if (count_check(ctx, nullptr, 0)) return 1;
+    const DxBatchPos p = dx_batches_pos(m->count, m->batch_len);
+    const std::string why = dx_batches_stat_check(stat, first, ddof, p.L, p.nfull, p.partial);
+    if (!why.empty()) return fail(ctx, "posterior moments: dangx_moments_batches_get: " + why);
+    (void)hipSetDevice(ctx->device);
+    const long long n = ctx->dims.npix;
+    ReadOut ro{ctx, out, to_host};
+    if (ro.open(sizeof(double) * (size_t)n)) return 1;
+    BatchStatArgs a{};
+    a.base = m->bmean(m->batches[reg], 0); a.out = ro.dst; a.pitch = m->bpitch; a.n = n;
+    a.par = dx_batches_par(stat, first, ddof, p.L, p.nfull, p.partial);
+    hipLaunchKernelGGL(k_batches_stat, dim3(m->grid_for((n + 1) / 2, 1)), dim3(BLOCK), 0, ctx->stream, a);
+    HIPCHK(ctx, hipGetLastError());
+    return ro.close(n);
+}
+
+int dangx_moments_batches_get_dev(dangx_ctx* ctx, int reg, int stat, int first, int ddof, double* out_dev) {
+    return batches_get_impl(ctx, reg, stat, first, ddof, out_dev, false);
+}
+
+int dangx_moments_batches_get(dangx_ctx* ctx, int reg, int stat, int first, int ddof, double* out) {
+    return batches_get_impl(ctx, reg, stat, first, ddof, out, true);
+}
+
+// one slot's two planes as they are: copies on the stream, which the host form waits for
+static int batches_raw_impl(dangx_ctx* ctx, int reg, int batch, double* mean_out, double* m2_out, bool to_host) {
+    if (!ctx || batches_need(ctx, reg)) return 1;
+    const DxMoments* m = ctx->mom;
+    if (batch < 0 || batch >= m->nbatch)
+        return fail(ctx, "posterior moments: dangx_moments_batches_raw: batch out of range (nbatch = " + std::to_string(m->nbatch) + ")");
+    (void)hipSetDevice(ctx->device);
+    const size_t bytes = sizeof(double) * (size_t)ctx->dims.npix;
+    const hipMemcpyKind kind = to_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    const auto& r = m->batches[reg];
+    if (mean_out) HIPCHK(ctx, hipMemcpyAsync(mean_out, m->bmean(r, batch), bytes, kind, ctx->stream));
+    if (m2_out) HIPCHK(ctx, hipMemcpyAsync(m2_out, m->bm2(r, batch), bytes, kind, ctx->stream));
+    if (to_host) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+int dangx_moments_batches_raw_dev(dangx_ctx* ctx, int reg, int batch, double* mean_out_dev, double* m2_out_dev) {
+    return batches_raw_impl(ctx, reg, batch, mean_out_dev, m2_out_dev, false);
+}
+
+int dangx_moments_batches_raw(dangx_ctx* ctx, int reg, int batch, double* mean_out, double* m2_out) {
+    return batches_raw_impl(ctx, reg, batch, mean_out, m2_out, true);
 }
 
 int dangx_moments_end(dangx_ctx* ctx) {

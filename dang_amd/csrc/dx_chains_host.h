@@ -60,11 +60,12 @@ inline DxChainsPar dx_chains_par(int K, const long long* n, int ddof) {
 // f(std::integral_constant<int, k>) for k0 <= k < min(K, DX_CHAINS_MAX), unrolled by recursion: whatever f indexes by k is indexed
 // by a constant from the start, so the small arrays below live in registers on the device and a by-value DxChainsPar is read
 // where it lies
-template <int k, class F>
+// (MAX: the bound of the arrays, DX_CHAINS_MAX unless the caller holds more entries -- the 2K half-chains of dx_batches_host.h)
+template <int k, int MAX = DX_CHAINS_MAX, class F>
 DX_HD void dx_chains_each(int K, F&& f) {
-    if constexpr (k < DX_CHAINS_MAX) {
+    if constexpr (k < MAX) {
         if (k < K) f(std::integral_constant<int, k>());
-        dx_chains_each<k + 1>(K, f);
+        dx_chains_each<k + 1, MAX>(K, f);
     }
 }
 
@@ -91,17 +92,22 @@ DX_HD double dx_chains_W(const DxChainsPar& p, const double (&m2)[DX_CHAINS_MAX]
     return s / p.kn1;
 }
 
-DX_HD double dx_chains_Bn(const DxChainsPar& p, const double (&mean)[DX_CHAINS_MAX]) {
+// B/n of the first K of N means, referred to mean[0]; kd = K, km1 = K - 1 as f64.  The one definition: the chains' (N =
+// DX_CHAINS_MAX) and the half-chains' of dx_batches_host.h (N = 2 DX_CHAINS_MAX)
+template <int N>
+DX_HD double dx_chains_Bn_of(int K, double kd, double km1, const double (&mean)[N]) {
     double sum = 0.0;   // d_0 = 0
-    dx_chains_each<1>(p.K, [&](auto kc) { sum += mean[decltype(kc)::value] - mean[0]; });
-    const double dbar = sum / p.kd;
+    dx_chains_each<1, N>(K, [&](auto kc) { sum += mean[decltype(kc)::value] - mean[0]; });
+    const double dbar = sum / kd;
     double acc = dbar * dbar;   // (d_0 - dbar)^2
-    dx_chains_each<1>(p.K, [&](auto kc) {
+    dx_chains_each<1, N>(K, [&](auto kc) {
         const double e = (mean[decltype(kc)::value] - mean[0]) - dbar;
         acc = fma(e, e, acc);
     });
-    return acc / p.km1;
+    return acc / km1;
 }
+
+DX_HD double dx_chains_Bn(const DxChainsPar& p, const double (&mean)[DX_CHAINS_MAX]) { return dx_chains_Bn_of(p.K, p.kd, p.km1, mean); }
 
 DX_HD double dx_chains_rhat(const DxChainsPar& p, double W, double Bn) { return sqrt(fma(p.f, W, Bn) / W); }
 

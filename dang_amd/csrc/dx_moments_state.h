@@ -140,6 +140,15 @@ struct DxMoments {
     DevBuf<SigSeg> d_sig;
     DevBuf<double> sacc;             // [mean: sacc_half doubles | m2: sacc_half doubles]
     long long sacc_half = 0;
+    // dangx_moments_batches: [reg][batch][mean | m2][bpitch] in bacc, every plane at the 16-byte phase of its segment's main
+    // accumulator (bpitch is even, so a registration's planes share the phase of its first)
+    struct Batch { int seg; long long off; };   // seg: index into segs; off: batch 0's mean plane in bacc
+    std::vector<Batch> batches;
+    int nbatch = 0;
+    long long batch_len = 0;         // the current L
+    long long bpitch = 0;            // doubles between two planes of a registration
+    DevBuf<double> bacc;
+    DevBuf<MomSeg> d_batch;          // [nbatch][nreg]: row b is the table of a launch into batch b (uploaded with the main table)
     // dangx_chains_*: orders this chain's stream against the stream of the chain set's first context (created on first use)
     hipEvent_t chain_ev = nullptr;
 
@@ -158,6 +167,8 @@ struct DxMoments {
     double* mean(const Sig& s) const { return sacc + s.off; }
     double* m2(const Sig& s) const { return sacc + sacc_half + s.off; }
     uint32_t* records(const Hist& h) const { return hrec + h.off; }
+    double* bmean(const Batch& r, int b) const { return bacc + r.off + 2LL * b * bpitch; }
+    double* bm2(const Batch& r, int b) const { return bmean(r, b) + bpitch; }
     int find_seg(int comp, int what, int plane) const {   // index into segs, -1: not selected
         for (size_t i = 0; i < segs.size(); ++i)
             if (segs[i].comp == comp && segs[i].what == what && segs[i].plane == plane) return (int)i;

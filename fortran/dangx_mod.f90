@@ -613,6 +613,46 @@ module dangx_mod
        type(c_ptr), value :: ctx, out_dev
        integer(c_int), value :: sig, stat, ddof
      end function
+     ! batched accumulators: planes(3, nreg) = (comp, what, plane), 0-based as in C; nbatch even, 2..32 batches of initially
+     ! batch_len samples, merged pairwise in place when all are full.  Only between dangx_moments_begin and the first
+     ! dangx_moments_accumulate.  stat: 0 = mean, 1 = std (ddof), 2 = MCSE, 3 = batch-means ESS, 4 = split R-hat, the first
+     ! `first` batches discarded; out: (0:npix-1) of this shard.
+     integer(c_int) function dangx_moments_batches(ctx, nreg, planes, nbatch, batch_len) bind(C, name='dangx_moments_batches')
+       import :: c_int, c_ptr, c_int64_t
+       type(c_ptr), value :: ctx, planes            ! planes: integer(c_int32_t)(3, nreg) or c_null_ptr
+       integer(c_int), value :: nreg, nbatch
+       integer(c_int64_t), value :: batch_len
+     end function
+     integer(c_int) function dangx_moments_batches_info(ctx, batch_len, nfull, partial) &
+          bind(C, name='dangx_moments_batches_info')
+       import :: c_int, c_ptr, c_int32_t, c_int64_t
+       type(c_ptr), value :: ctx
+       integer(c_int64_t), intent(out) :: batch_len, partial
+       integer(c_int32_t), intent(out) :: nfull
+     end function
+     integer(c_int) function dangx_moments_batches_get(ctx, reg, stat, first, ddof, out) bind(C, name='dangx_moments_batches_get')
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx, out
+       integer(c_int), value :: reg, stat, first, ddof
+     end function
+     integer(c_int) function dangx_moments_batches_get_dev(ctx, reg, stat, first, ddof, out_dev) &
+          bind(C, name='dangx_moments_batches_get_dev')
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx, out_dev
+       integer(c_int), value :: reg, stat, first, ddof
+     end function
+     ! one batch's (mean, m2) planes as they are; either output may be c_null_ptr
+     integer(c_int) function dangx_moments_batches_raw(ctx, reg, batch, mean_out, m2_out) bind(C, name='dangx_moments_batches_raw')
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx, mean_out, m2_out
+       integer(c_int), value :: reg, batch
+     end function
+     integer(c_int) function dangx_moments_batches_raw_dev(ctx, reg, batch, mean_out_dev, m2_out_dev) &
+          bind(C, name='dangx_moments_batches_raw_dev')
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx, mean_out_dev, m2_out_dev
+       integer(c_int), value :: reg, batch
+     end function
      integer(c_int) function dangx_moments_end(ctx) bind(C, name='dangx_moments_end')
        import :: c_int, c_ptr
        type(c_ptr), value :: ctx
@@ -679,6 +719,21 @@ module dangx_mod
        type(c_ptr), intent(in) :: ctxs(*)
        integer(c_int), value :: nchains, reg, stat, nq
        type(c_ptr), value :: q, out_dev
+     end function
+     ! dangx_moments_batches_get over the chains (the same registration, batch length and count in each)
+     integer(c_int) function dangx_chains_batches_get(ctxs, nchains, reg, stat, first, ddof, out) &
+          bind(C, name='dangx_chains_batches_get')
+       import :: c_int, c_ptr
+       type(c_ptr), intent(in) :: ctxs(*)
+       integer(c_int), value :: nchains, reg, stat, first, ddof
+       type(c_ptr), value :: out
+     end function
+     integer(c_int) function dangx_chains_batches_get_dev(ctxs, nchains, reg, stat, first, ddof, out_dev) &
+          bind(C, name='dangx_chains_batches_get_dev')
+       import :: c_int, c_ptr
+       type(c_ptr), intent(in) :: ctxs(*)
+       integer(c_int), value :: nchains, reg, stat, first, ddof
+       type(c_ptr), value :: out_dev
      end function
      integer(c_int) function dangx_profile_enable(ctx, on) bind(C, name='dangx_profile_enable')
        import :: c_int, c_ptr

@@ -76,7 +76,8 @@ enum {
     DANGX_K_AMP_DIRECT = 0, DANGX_K_INDEX_MH = 1, DANGX_K_SKY_CHISQ = 2, DANGX_K_REDUCE = 3,
     DANGX_K_CG_AX = 4, DANGX_K_CG_VEC = 5, DANGX_K_AMP_INDEX = 6, DANGX_K_MOMENTS = 7, DANGX_K_HIST = 8, DANGX_K_SIGNAL = 9,
     DANGX_K_CHAINS = 10,   /* the read-outs over several chains (dangx_chains_*): nothing else is ever counted here */
-    DANGX_K_COUNT = 11
+    DANGX_K_BATCH = 11,    /* the batched accumulators (dangx_moments_batches): one launch per accumulation, one more per merge */
+    DANGX_K_COUNT = 12
 };
 
 typedef struct dangx_ctx dangx_ctx;
@@ -589,6 +590,42 @@ int dangx_moments_hist_stat_dev(dangx_ctx *ctx, int reg, int stat, int nq, const
 int dangx_moments_signals(dangx_ctx *ctx, int nsig, const int32_t *spec);
 int dangx_moments_get_signal(dangx_ctx *ctx, int sig, int stat, int ddof, double *out);
 int dangx_moments_get_signal_dev(dangx_ctx *ctx, int sig, int stat, int ddof, double *out_dev);
+/* Batched accumulators of registered pixel planes: the run cut into nbatch consecutive batches of L samples, each with its own
+ * (mean, m2), so that burn-in can be discarded AFTER the run and one chain gets a batch-means Monte-Carlo error, a model-free
+ * effective sample size and split R-hat.  One launch of k_moments_accum's update per accumulation (DANGX_K_BATCH) behind the
+ * others, only when something is registered.  Definitions (dang_amd/csrc/dx_batches_host.h):
+ *   with c samples held, sample c + 1 goes to batch c / L as its sample c % L + 1 (Welford; a batch's first sample lands on zeros).
+ *   When all nbatch batches are full they are merged in place before the sample is taken (k_batches_merge, one launch): batch i
+ *     = batches (2i, 2i+1) folded with Chan's update (w = 1/2, c = L/2), the upper half zeroed, L doubled -- the run length need
+ *     not be known.  Merges happen at count = nbatch * batch_len * 2^k.
+ *   nfull = count / L full batches, p = count % L samples in the open one; `first` leading batches discarded; B' = nfull - first.
+ *   stat 0 mean, 1 std: over the samples [first L, count), open batch included; sqrt(M / (N' - ddof)), N' = B'L + p.
+ *   stat 2 MCSE = sqrt(S / (B'(B'-1))), S the M2 of the full batches' means (Welford in batch order).        B' >= 2
+ *   stat 3 batch-means ESS = (M_f / (B'L - 1)) / MCSE^2, M_f the folded M2 of the full batches; unclamped.    B' >= 2
+ *   stat 4 split R-hat: h = B'/2, the halves are the LAST 2h full batches (an odd B' drops its oldest), each folded to (mu, M);
+ *     W, B/n and R-hat as dangx_chains_get's with K = 2, n = hL.  NaN where the element never moved, +inf where only the
+ *     half-means differ.                                                                                        h >= 1, hL >= 2
+ * dangx_moments_batches: planes[r] = {comp, what, plane} as in dangx_moments_hist; nbatch even, 2 .. DANGX_MAX_BATCHES;
+ *   batch_len >= 1 the initial L.  Legal after dangx_moments_begin and before the first dangx_moments_accumulate, independent of
+ *   dangx_moments_pairs / _hist / _signals (either order, none drops another); a second call replaces the first (nreg = 0: none),
+ *   dangx_moments_begin / _end drop it.  Errors (nothing changes, an earlier registration stays): count > 0, a plane that is not
+ *   selected, a template / monopole / hi_fit amplitude, the same plane twice, an odd or out-of-range nbatch, batch_len < 1, nreg >
+ *   DANGX_MAX_BATCH_PLANES, a failed allocation.  Memory: [reg][batch][mean | m2][npix] f64 of the library's own, zero-filled =
+ *   nreg * nbatch * 16 B * npix (one plane x 16 batches at Nside 1024, 12.6 M pixels: 3.2 GB; the main accumulators take 16 B
+ *   * npix per plane).
+ * dangx_moments_batches_info: the current L, the number of full batches and the samples in the open batch.
+ * dangx_moments_batches_get: out[npix] of this shard.  Errors: nothing registered, reg out of range, a bad stat, first outside
+ *   0 .. nfull, too few batches or samples for the stat (named), a bad ddof.
+ * dangx_moments_batches_raw: one batch's (mean, m2) planes as they are -- the batch-means trace (either output may be NULL).
+ * The _dev forms write device arrays of this shard, asynchronously on the context's stream. */
+#define DANGX_MAX_BATCHES 32
+#define DANGX_MAX_BATCH_PLANES 32
+int dangx_moments_batches(dangx_ctx *ctx, int nreg, const int32_t *planes, int nbatch, int64_t batch_len);
+int dangx_moments_batches_info(dangx_ctx *ctx, int64_t *batch_len, int32_t *nfull, int64_t *partial);
+int dangx_moments_batches_get(dangx_ctx *ctx, int reg, int stat, int first, int ddof, double *out);
+int dangx_moments_batches_get_dev(dangx_ctx *ctx, int reg, int stat, int first, int ddof, double *out_dev);
+int dangx_moments_batches_raw(dangx_ctx *ctx, int reg, int batch, double *mean_out, double *m2_out);
+int dangx_moments_batches_raw_dev(dangx_ctx *ctx, int reg, int batch, double *mean_out_dev, double *m2_out_dev);
 /* frees the accumulators */
 int dangx_moments_end(dangx_ctx *ctx);
 
@@ -627,6 +664,12 @@ int dangx_chains_get_pair(dangx_ctx *const *ctxs, int nchains, int pair, int sta
 int dangx_chains_get_pair_dev(dangx_ctx *const *ctxs, int nchains, int pair, int stat, int ddof, double *out_dev);
 int dangx_chains_hist_stat(dangx_ctx *const *ctxs, int nchains, int reg, int stat, int nq, const double *q, double *out);
 int dangx_chains_hist_stat_dev(dangx_ctx *const *ctxs, int nchains, int reg, int stat, int nq, const double *q, double *out_dev);
+/* dangx_moments_batches_get over the chains (k_chains_batches): every chain must hold the same registration, L, nbatch and count
+ * (anything else is refused, naming the chain).  stat 0 / 1: pooled over chains and over batches first.., the chains folded in
+ * list order from each chain's own fold, sqrt(M / (K N' - ddof)); stat 2: sqrt(sum_k MCSE_k^2) / K; stat 3: sum_k ESS_k; stat 4:
+ * split R-hat over the 2K half-chains, W and B/n as for one chain with 2K for K, the half-means referred to half 0 of chain 0. */
+int dangx_chains_batches_get(dangx_ctx *const *ctxs, int nchains, int reg, int stat, int first, int ddof, double *out);
+int dangx_chains_batches_get_dev(dangx_ctx *const *ctxs, int nchains, int reg, int stat, int first, int ddof, double *out_dev);
 
 /* ---- per-kernel timing with HIP events on the context's stream ----------------- */
 int dangx_profile_enable(dangx_ctx *ctx, int on);

@@ -3,7 +3,7 @@
 iterations of the C3 model: blocks of iterations without and with accumulation after every iteration, alternating in one process;
 then the k_moments kernel time from the profile and its bandwidth in algorithmic bytes (5 x 8 B per selected element) against the
 6.29 TB/s measured copy ceiling of the MI355X.
-    python3 tools/bench_moments.py [nside=1024] [steps per block=10] [rounds=5] [--lag1] [--pairs default] [--hist [nbins=64]] [--signals [--bandpass]] [--chains K]
+    python3 tools/bench_moments.py [nside=1024] [steps per block=10] [rounds=5] [--lag1] [--pairs default] [--hist [nbins=64]] [--signals [--bandpass]] [--chains K] [--batches NB]
 --lag1 / --pairs default: after the above, `rounds` alternating rounds of `steps` accumulations each of (a) the plain accumulate,
 (b) with lag-1 tracking (k_moments_accum_lag: 10 x 8 B per selected element) and (c) with the default pairs (k_moments_pairs: 6 x 8 B
 per pair element, timed apart from the mean launch that follows it); per launch the algorithmic bytes, the achieved bytes/s and
@@ -22,7 +22,13 @@ iteration is run.
 `rounds` alternating rounds of `steps` read-outs each, timed with events on the stream: (y) the single-chain std read-out
 (k_moments_finish: 2 x 8 B per element), (r) R-hat over the chains ((2 K + 1) x 8 B), (e) the pooled ESS ((5 K + 1) x 8 B) and (q)
 three pooled quantiles (K x 128 B + 3 x 8 B per pixel); per read-out its bytes/s and the ratio to (y) in the same round.  Nothing
-else of the above is run."""
+else of the above is run.
+--batches NB: the batched accumulators (dangx_moments_batches) with NB batches on up to four of the default index planes, two chains.
+`rounds` alternating rounds in one process of (a) the plain k_moments_accum launch and (b) the batch launch of the same
+accumulations (5 x 8 B per element each; batches long enough that no merge falls into the round), per byte; then, after NB
+samples with batches of one sample (every batch full), rounds of (y) the single-chain std read-out, (s) split R-hat of one chain
+(k_batches_stat: (2 NB + 1) x 8 B per element) and (c) of two chains (k_chains_batches: (4 NB + 1) x 8 B); then the time of the
+merges the next 3 NB + 1 accumulations cause.  Nothing else of the above is run."""
 import os
 import sys
 import time
@@ -47,6 +53,10 @@ nchains = 0
 if "--chains" in argv:
     i = argv.index("--chains")
     nchains = int(argv.pop(i + 1))
+nbat = 0
+if "--batches" in argv:
+    i = argv.index("--batches")
+    nbat = int(argv.pop(i + 1))
 args = [a for a in argv if not a.startswith("--") and a != "default"]
 want_lag1 = "--lag1" in sys.argv
 want_pairs = "--pairs" in sys.argv
@@ -129,6 +139,87 @@ if nchains:
     for key, name, _, _ in forms[1:]:
         print("(%s) %s / (y): median %.3f (spread %.3f .. %.3f)%s" % (key, name, float(np.median(ratios[key])), min(ratios[key]), max(ratios[key]),
                                                                      "" if key == "q" else "; expected >= 0.8"))
+    sys.exit(0)
+if nbat:
+    npx = meta["npix"]
+    runs = [(dpar, ddata), da.open_chain(dpar, ddata, dpar.seed + 1)]
+    engs = [d.engine for _, d in runs]
+    for p, d in runs:
+        da.gibbs_iteration(p, d, 1, want_counts=False)
+    sel = da.moments_begin(dpar, ddata)
+    nsel = sum(bin(int(w) & 7).count("1") + bin(int(w) >> 3).count("1") for w in sel)
+    bp = da.default_hist_planes(dpar, comps, sel)[:4]
+    da.moments_batches(dpar, ddata, planes=bp, nbatch=nbat, batch_len=1 << 40)
+    da.moments_accumulate(ddata)   # table upload
+    print("C3 at Nside %d: %d selected planes, %d batch planes x %d batches of %d pixels = %.2f GB of batch accumulators"
+          % (nside, nsel, len(bp), nbat, npx, 16.0 * npx * len(bp) * nbat * 1e-9))
+    ratios = []
+    for r in range(rounds):
+        eng.profile(True)
+        for _ in range(steps):
+            da.moments_accumulate(ddata)
+        prof = eng.profile_get()
+        eng.profile(False)
+        a_ms, b_ms = (prof[k]["total_ms"] / prof[k]["launches"] for k in ("k_moments", "k_batch"))
+        a_bw, b_bw = 40.0 * nsel * npx / a_ms * 1e-9, 40.0 * len(bp) * npx / b_ms * 1e-9
+        ratios.append(b_bw / a_bw)
+        print("round %d: (a) plain %.3f ms, %.2f GB -> %.2f TB/s; (b) batch launch %.3f ms, %.2f GB -> %.2f TB/s = %.3f of (a)"
+              % (r + 1, a_ms, 40.0 * nsel * npx * 1e-9, a_bw, b_ms, 40.0 * len(bp) * npx * 1e-9, b_bw, b_bw / a_bw))
+    print("(b) / (a) per byte: median %.3f (spread %.3f .. %.3f)" % (float(np.median(ratios)), min(ratios), max(ratios)))
+    for p, d in runs:
+        da.moments_begin(p, d, sel=sel)
+        da.moments_batches(p, d, planes=bp, nbatch=nbat, batch_len=1)
+    for it in range(nbat):
+        for p, d in runs:
+            da.moments_accumulate(d)
+    assert eng.moments_batches_info() == {"batch_len": 1, "nfull": nbat, "partial": 0}
+    l, what, _ = bp[0]
+    nplanes = bin((int(sel[l]) >> (3 + 3 * (what - 1))) & 7).count("1")
+    out3 = torch.zeros((meta["nmaps"], npx), dtype=torch.float64, device=dev)
+    out1 = torch.zeros((npx,), dtype=torch.float64, device=dev)
+
+    def timed(fn):
+        fn()   # first use: scratch, events
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(steps):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / steps
+
+    forms = [("y", "single-chain std", 2 * 8 * nplanes, lambda: eng._chk(eng.lib.dangx_moments_get_dev(eng.h, l, what, 1, 0, out3.data_ptr()))),
+             ("s", "split R-hat, one chain", (2 * nbat + 1) * 8, lambda: eng._chk(eng.lib.dangx_moments_batches_get_dev(eng.h, 0, 4, 0, 0, out1.data_ptr()))),
+             ("c", "split R-hat, two chains", (4 * nbat + 1) * 8, lambda: da.chains_batches_get(engs, 0, "split_rhat", device=True, out=out1))]
+    ratios = {k: [] for k, _, _, _ in forms[1:]}
+    rates = {k: [] for k, _, _, _ in forms}
+    for r in range(rounds):
+        line, y_bw = "round %d:" % (r + 1), None
+        for key, name, per_pix, fn in forms:
+            ms = timed(fn)
+            bw = per_pix * npx / ms * 1e-9
+            if key == "y":
+                y_bw = bw
+            else:
+                ratios[key].append(bw / y_bw)
+            rates[key].append(bw)
+            line += " (%s) %s %.3f ms, %.3f GB -> %.2f TB/s%s;" % (key, name, ms, per_pix * npx * 1e-9, bw, "" if key == "y" else " = %.3f of (y)" % (bw / y_bw))
+        print(line)
+    for key, name, _, _ in forms[1:]:
+        print("(%s) %s / (y): median %.3f (spread %.3f .. %.3f); expected >= 0.8" % (key, name, float(np.median(ratios[key])), min(ratios[key]), max(ratios[key])))
+    # (y) moves 0.2 GB that the accumulations just wrote: where it reads above the copy ceiling it is partly served from cache, and
+    # the ratios to it are ratios to an inflated denominator -- hence the ratios to the ceiling as well
+    for key, name, _, _ in forms:
+        print("(%s) %s / the %.2f TB/s copy ceiling: %.3f .. %.3f" % (key, name, COPY_CEILING_TBS, min(rates[key]) / COPY_CEILING_TBS,
+                                                                  max(rates[key]) / COPY_CEILING_TBS))
+    eng.profile(True)
+    for _ in range(3 * nbat + 1):
+        da.moments_accumulate(ddata)
+    mg = eng.profile_get(by_planes=True).get(("k_batch", 2))
+    eng.profile(False)
+    print("k_batches_merge: %.3f ms per merge (%d merges of %d planes x %d batches, %.2f GB read + written each)"
+          % (mg["total_ms"] / mg["launches"], mg["launches"], len(bp), nbat, (2 + 1 + 1) * 8.0 * nbat * len(bp) * npx * 1e-9))
     sys.exit(0)
 it = 1
 for _ in range(2):
