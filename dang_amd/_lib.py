@@ -32,6 +32,7 @@ STAT_CODES = {"mean": 0, "std": 1, "rho1": 2, "ess": 3}
 PAIR_STAT_CODES = {"cov": 0, "corr": 1}
 MAX_PAIRS = 64
 HIST_STAT_CODES = {"quantile": 0, "mode": 1, "n": 2}
+RANK_STAT_CODES = {"bulk": 0, "folded": 1, "max": 2}
 MAX_HIST, MAX_HIST_Q = 32, 16
 MAX_SIGNALS = 64
 MAX_CHAINS = 8
@@ -189,6 +190,8 @@ SYMBOLS = {
     "dangx_chains_get_pair_dev": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "dangx_chains_hist_stat": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "dangx_chains_hist_stat_dev": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "dangx_chains_hist_rank": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int, C.c_int, _P]),
+    "dangx_chains_hist_rank_dev": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int, C.c_int, _P]),
     "dangx_chains_batches_get": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "dangx_chains_batches_get_dev": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "dangx_profile_enable": (C.c_int, [_P, C.c_int]),

@@ -1595,6 +1595,19 @@ def chains_hist_stat(engines, reg, stat, q=None, device=False, out=None):
     return out
 
 
+def chains_hist_rank(engines, reg, stat, device=False, out=None):
+    """Rank-normalised R-hat (Vehtari et al. 2021) of histogram registration reg over the chains `engines`, read from their
+    records: 'bulk' / 0 = rank-normalised, 'folded' / 1 = of the fold around the pooled median bin (chains that differ in spread),
+    'max' / 2 = the larger of the two, the number to report; [npix].  The samples of a bin are ties, so this is the statistic of
+    the binned trace.  NaN where the chains hold different numbers of counted samples in a pixel, fewer than 2, or one bin only.
+    Not split: drift inside a chain is 'split_rhat' of moments_batches."""
+    e = engines[0]
+    st = L.RANK_STAT_CODES[stat] if isinstance(stat, str) else int(stat)
+    out, ptr = _readout_dest(e, (e.npix,), device, out)
+    _chains_call(engines, "dangx_chains_hist_rank_dev" if device else "dangx_chains_hist_rank", int(reg), st, ptr)
+    return out
+
+
 def open_chain(dpar, ddata, seed, stream=None, tcmb=None):
     """A further chain over the same data: (dpar_k, ddata_k).  dpar_k is a copy of dpar with its own seed.  ddata_k shares ddata's
     sig_map / rms_map / masks objects -- for device tensors its Engine adopts the same HBM, host arrays are uploaded once more --
@@ -1705,6 +1718,26 @@ def chains_quantile_maps(chains, q=(0.16, 0.5, 0.84), masked_value=None):
         entry = {"range": reg0["ranges"][r], "nbins": reg0["nbins"]}
         for name, stat in (("q", "quantile"), ("mode", "mode"), ("n", "n")):
             entry[name] = _chains_map(shards, lambda col: chains_hist_stat(col, r, stat, q=q if stat == "quantile" else None), masked_value)
+        out[(comps[l].label, _plane_name(comps[l], what), k)] = entry
+    return out
+
+
+def chains_rank_maps(chains, masked_value=None):
+    """The rank-normalised R-hat of every registered histogram plane over several chains: {'rhat_rank', 'rhat_folded', 'rhat_max',
+    'range', 'nbins'} per plane (chains_hist_rank's 'bulk', 'folded' and 'max').  Shards side by side; masked_value as in
+    posterior_maps."""
+    shards, _ = _chains_shards(chains, "chains_rank_maps")
+    reg0 = getattr(shards[0][0], "_moment_hist", None)
+    if not reg0:
+        raise DangxError("chains_rank_maps: moments_hist was not called")
+    if any(getattr(e, "_moment_hist", None) != reg0 for col in shards for e in col):
+        raise DangxError("chains_rank_maps: the contexts hold different histogram registrations")
+    comps = shards[0][0].component_list
+    out = {}
+    for r, (l, what, k) in enumerate(reg0["planes"]):
+        entry = {"range": reg0["ranges"][r], "nbins": reg0["nbins"]}
+        for name, stat in (("rhat_rank", "bulk"), ("rhat_folded", "folded"), ("rhat_max", "max")):
+            entry[name] = _chains_map(shards, lambda col: chains_hist_rank(col, r, stat), masked_value)
         out[(comps[l].label, _plane_name(comps[l], what), k)] = entry
     return out
 

@@ -1,11 +1,14 @@
 // dangx_chains.hip -- dangx_chains_*: read-outs over the accumulators of SEVERAL chains of one device (definitions in dx_chains_host.h).  Nothing here
-// touches an accumulator, a chain or a cache: four read-only kernels combine the per-chain planes and write only the map asked for.
+// touches an accumulator, a chain or a cache: five read-only kernels combine the per-chain planes and write only the map asked for.
 //   k_chains_batches  the batched accumulators (dx_batches_host.h): every chain's slots in one pass from one base pointer per chain.
 //   k_chains_stat  planes and signals (blockIdx.y = plane, up to three): pooled mean / std, R-hat, W, B/n read K x (mean, m2) --
 //                  a stat that does not use one of the two does not load it -- and write one f64: at most (2 K + 1) x 8 B per
 //                  element; the pooled ESS reads K x (mean, m2, prev, first, P), (5 K + 1) x 8 B.
 //   k_chains_pair  one pair: K x (mean_a, mean_b, C) for the covariance, + K x (m2_a, m2_b) for the correlation.
 //   k_chains_hist  a lane sums its pixel's K records piece by piece in 64-bit integers and takes k_hist_stat's steps on the sums.
+//   k_chains_rank  the rank-normalised / folded R-hat of the binned traces (dx_rank_host.h): a lane walks its pixel's K records for
+//                  the pooled total, once more for the scores and the K running (n, mean, m2), and for the fold a third time by
+//                  32-bit word around the pooled median bin; it writes one f64.
 // The pointers of all chains travel by value (ChainsArgs + DxChainsPar: 1.3 KB of the 4 KB kernel-argument segment).  Pairs of elements are read
 // as 16 bytes where every pointer of a plane shares out's 16-byte phase, element by element otherwise (chains whose buffers were
 // adopted at different alignments; dx_stream.h); both forms evaluate the same header functions.  No LDS, no atomics, no scratch.
@@ -14,6 +17,7 @@
 #include "dx_hist_host.h"
 #include "dx_chains_host.h"
 #include "dx_batches_host.h"
+#include "dx_rank_host.h"
 #include "dx_stream.h"
 
 static_assert(DX_CHAINS_MAX == DANGX_MAX_CHAINS, "dx_chains_host.h and include/dangx.h disagree");
@@ -140,8 +144,9 @@ struct ChainsHistArgs {
 
 // hist_walk over the SUM of the K records of pixel i: a 16-byte piece of every chain, its 4 or 8 counters summed in 64 bits,
 // then f(count, bin) per bin in bin order until f says stop
-template <class F>
-__device__ __forceinline__ void chains_hist_walk(const ChainsHistArgs& a, long long i, int pieces, F f) {
+// (A: ChainsHistArgs or ChainsRankArgs -- rec, K, bits)
+template <class A, class F>
+__device__ __forceinline__ void chains_hist_walk(const A& a, long long i, int pieces, F f) {
     int b = 0;
     for (int p = 0; p < pieces; ++p) {
         unsigned long long c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -167,6 +172,72 @@ __device__ __forceinline__ void chains_hist_walk(const ChainsHistArgs& a, long l
 __global__ __launch_bounds__(BLOCK) void k_chains_hist(ChainsHistArgs a) {
     const int pieces = dx_hist_words(a.nbins, a.bits) / 4;
     dx_hist_readout<unsigned long long>(a, [&](long long i, auto f) { chains_hist_walk(a, i, pieces, f); });
+}
+
+struct ChainsRankArgs {
+    const uint32_t* rec[DX_CHAINS_MAX];
+    double* out;          // [n]
+    long long n;
+    int K, nbins, bits, stat;
+};
+
+// the rank-normalised R-hat of pixel i (S > 0 pooled samples): chains_hist_walk with every chain's piece kept, so that a non-empty
+// bin's score is formed once and goes into the triples of the chains that hold samples of it.  raw[k] and the triples are
+// indexed by constants only (the k and j loops are unrolled): registers, no scratch
+__device__ __forceinline__ double chains_rank_bulk(const ChainsRankArgs& a, long long i, int pieces, unsigned long long S) {
+    DxRankState s;
+    dx_rank_reset(s);
+    unsigned long long cum = 0;
+    const int nb = a.bits == 16 ? 8 : 4;
+    for (int p = 0; p < pieces; ++p) {
+        u32x4 raw[DX_CHAINS_MAX];
+        unsigned long long c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (int k = 0; k < DX_CHAINS_MAX; ++k)
+            if (k < a.K) {
+                raw[k] = ((const GU4*)a.rec[k])[i * pieces + p];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (a.bits == 16) { c[2 * j] += raw[k][j] & 0xffffu; c[2 * j + 1] += raw[k][j] >> 16; }
+                    else c[j] += raw[k][j];
+                }
+            }
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (j < nb)
+                dx_rank_bin(a.K, c[j], cum, S, s, [&](auto kc) -> unsigned long long {
+                    const u32x4 v = raw[decltype(kc)::value];
+                    return a.bits == 16 ? (v[j >> 1] >> ((j & 1) * 16)) & 0xffffu : v[j & 3];
+                });
+    }
+    return dx_rank_finish(a.K, s);
+}
+
+// A lane per pixel.  The walks after the first hit the cache lines the first brought in; the fold reads its counters by 32-bit
+// word at m +- e (dx_hist_count), m being known only after the second walk.
+__global__ __launch_bounds__(BLOCK) void k_chains_rank(ChainsRankArgs a) {
+    const int words = dx_hist_words(a.nbins, a.bits), pieces = words / 4;
+    for (long long i = (long long)blockIdx.x * BLOCK + threadIdx.x; i < a.n; i += (long long)gridDim.x * BLOCK) {
+        unsigned long long S = 0;
+        int first = -1, last = -1;
+        chains_hist_walk(a, i, pieces, [&](unsigned long long c, int b) { dx_rank_total_step(c, b, S, first, last); return false; });
+        double r = (double)NAN;
+        if (S > 0) {
+            double bulk = 0.0, folded = 0.0;
+            if (a.stat != DX_RK_FOLDED) bulk = chains_rank_bulk(a, i, pieces, S);
+            if (a.stat != DX_RK_BULK) {
+                unsigned long long cum = 0;
+                int m = 0;
+                const double half = 0.5 * (double)S;
+                chains_hist_walk(a, i, pieces, [&](unsigned long long c, int b) { return dx_rank_median_step(c, b, half, cum, m); });
+                folded = dx_rank_folded_of(a.K, a.nbins, m, first, last, S, [&](auto kc, int b) {   // 0 <= b < nbins: inside pixel i's record
+                    return dx_hist_count(a.rec[decltype(kc)::value] + i * words, b, a.bits);
+                });
+            }
+            r = a.stat == DX_RK_BULK ? bulk : a.stat == DX_RK_FOLDED ? folded : dx_rank_larger(bulk, folded);
+        }
+        a.out[i] = r;
+    }
 }
 
 struct ChainsBatchArgs {   // one base pointer per chain (slot 0's mean plane of the registration) plus the stride of the regular layout
@@ -426,10 +497,8 @@ int chains_pair_impl(dangx_ctx* const* ctxs, int nchains, int pair, int stat, in
     return ro.close(n);
 }
 
-int chains_hist_impl(dangx_ctx* const* ctxs, int nchains, int reg, int stat, int nq, const double* q, double* out, bool to_host) {
-    if (!ctxs || !ctxs[0] || !out) return 1;
-    ChainSet cs{};
-    if (chains_open(ctxs, nchains, cs)) return 1;
+// histogram registration reg is the same in every chain (after chains_open)
+int chains_hist_same(dangx_ctx* const* ctxs, int nchains, int reg) {
     const DxMoments* m0 = ctxs[0]->mom;
     if (reg < 0 || reg >= (int)m0->hists.size())
         return chains_fail(ctxs, "chain 0: histogram registration out of range (" + std::to_string(m0->hists.size()) + " registered)");
@@ -444,6 +513,14 @@ int chains_hist_impl(dangx_ctx* const* ctxs, int nchains, int reg, int stat, int
             return chains_fail(ctxs, "chain " + std::to_string(k) + ": histogram registration " + std::to_string(reg) +
                                          " is not the registration of chain 0 (plane, lo, hi, nbins and bits must agree)");
     }
+    return 0;
+}
+
+int chains_hist_impl(dangx_ctx* const* ctxs, int nchains, int reg, int stat, int nq, const double* q, double* out, bool to_host) {
+    if (!ctxs || !ctxs[0] || !out) return 1;
+    ChainSet cs{};
+    if (chains_open(ctxs, nchains, cs) || chains_hist_same(ctxs, nchains, reg)) return 1;
+    const DxMoments* m0 = ctxs[0]->mom;
     dangx_ctx* c0 = ctxs[0];
     if (dx_hist_stat_check(c0, reg, stat, nq, q)) return 1;
     (void)hipSetDevice(c0->device);
@@ -463,6 +540,32 @@ int chains_hist_impl(dangx_ctx* const* ctxs, int nchains, int reg, int stat, int
     }
     if (chains_release(cs)) return 1;
     return ro.close(total);
+}
+
+int chains_rank_impl(dangx_ctx* const* ctxs, int nchains, int reg, int stat, double* out, bool to_host) {
+    if (!ctxs || !ctxs[0] || !out) return 1;
+    ChainSet cs{};
+    if (chains_open(ctxs, nchains, cs) || chains_hist_same(ctxs, nchains, reg)) return 1;
+    const DxMoments* m0 = ctxs[0]->mom;
+    dangx_ctx* c0 = ctxs[0];
+    if (dx_hist_stat_check(c0, reg, 2, 0, nullptr)) return 1;   // the registration and the sample count, as for a pooled count
+    const std::string why = dx_rank_check(cs.K, m0->hbins, m0->hbits, stat);
+    if (!why.empty()) return chains_fail(ctxs, "dangx_chains_hist_rank: " + why);
+    (void)hipSetDevice(c0->device);
+    const long long n = c0->dims.npix;
+    ReadOut ro{c0, out, to_host};
+    if (ro.open(sizeof(double) * (size_t)n)) return 1;
+    ChainsRankArgs a{};
+    for (int j = 0; j < cs.K; ++j) a.rec[j] = ctxs[j]->mom->records(ctxs[j]->mom->hists[reg]);
+    a.out = ro.dst; a.n = n; a.K = cs.K; a.nbins = m0->hbins; a.bits = m0->hbits; a.stat = stat;
+    if (chains_join(cs)) return 1;
+    {
+        Timed tm(c0, DANGX_K_CHAINS);
+        hipLaunchKernelGGL(k_chains_rank, dim3(c0->mom->grid_for(n, 1)), dim3(BLOCK), 0, c0->stream, a);
+        HIPCHK(c0, hipGetLastError());
+    }
+    if (chains_release(cs)) return 1;
+    return ro.close(n);
 }
 
 int chains_batches_impl(dangx_ctx* const* ctxs, int nchains, int reg, int stat, int first, int ddof, double* out, bool to_host) {
@@ -588,6 +691,14 @@ int dangx_chains_hist_stat_dev(dangx_ctx* const* ctxs, int nchains, int reg, int
 
 int dangx_chains_hist_stat(dangx_ctx* const* ctxs, int nchains, int reg, int stat, int nq, const double* q, double* out) {
     return chains_hist_impl(ctxs, nchains, reg, stat, nq, q, out, true);
+}
+
+int dangx_chains_hist_rank_dev(dangx_ctx* const* ctxs, int nchains, int reg, int stat, double* out_dev) {
+    return chains_rank_impl(ctxs, nchains, reg, stat, out_dev, false);
+}
+
+int dangx_chains_hist_rank(dangx_ctx* const* ctxs, int nchains, int reg, int stat, double* out) {
+    return chains_rank_impl(ctxs, nchains, reg, stat, out, true);
 }
 
 }  // extern "C"

@@ -720,6 +720,20 @@ module dangx_mod
        integer(c_int), value :: nchains, reg, stat, nq
        type(c_ptr), value :: q, out_dev
      end function
+     ! rank-normalised R-hat of the binned traces: stat 0 = bulk, 1 = folded, 2 = the larger of the two; out(npix)
+     integer(c_int) function dangx_chains_hist_rank(ctxs, nchains, reg, stat, out) bind(C, name='dangx_chains_hist_rank')
+       import :: c_int, c_ptr
+       type(c_ptr), intent(in) :: ctxs(*)
+       integer(c_int), value :: nchains, reg, stat
+       type(c_ptr), value :: out
+     end function
+     integer(c_int) function dangx_chains_hist_rank_dev(ctxs, nchains, reg, stat, out_dev) &
+          bind(C, name='dangx_chains_hist_rank_dev')
+       import :: c_int, c_ptr
+       type(c_ptr), intent(in) :: ctxs(*)
+       integer(c_int), value :: nchains, reg, stat
+       type(c_ptr), value :: out_dev
+     end function
      ! dangx_moments_batches_get over the chains (the same registration, batch length and count in each)
      integer(c_int) function dangx_chains_batches_get(ctxs, nchains, reg, stat, first, ddof, out) &
           bind(C, name='dangx_chains_batches_get')

@@ -664,6 +664,26 @@ int dangx_chains_get_pair(dangx_ctx *const *ctxs, int nchains, int pair, int sta
 int dangx_chains_get_pair_dev(dangx_ctx *const *ctxs, int nchains, int pair, int stat, int ddof, double *out_dev);
 int dangx_chains_hist_stat(dangx_ctx *const *ctxs, int nchains, int reg, int stat, int nq, const double *q, double *out);
 int dangx_chains_hist_stat_dev(dangx_ctx *const *ctxs, int nchains, int reg, int stat, int nq, const double *q, double *out_dev);
+/* Rank-normalised and folded R-hat (Vehtari, Gelman, Simpson, Carpenter and Buerkner 2021) of histogram registration reg, read
+ * from the chains' records (k_chains_rank; definitions in dang_amd/csrc/dx_rank_host.h).  The samples of one bin are ties and take
+ * the average rank, so the records are a sufficient statistic of the statistic of the BINNED trace: nothing is approximated
+ * beyond the bin width.  Unlike stat 2 of dangx_chains_get it needs no finite variance (heavy tails do not hide a difference in
+ * location) and its folded form sees chains that agree in the mean and differ in spread.  Per pixel, c[k][b] the counter of chain
+ * k and bin b, C[b] = sum_k c[k][b] (64-bit), S = sum_b C[b], cum[b] = sum_{b' < b} C[b']:
+ *   score of a non-empty bin: u = 2 cum[b] + C[b] + 1 (twice the mid-rank), u' = min(u, 2S + 2 - u), p = (u' - 0.75) / (2S + 0.5)
+ *     (Blom), z[b] = -|Phi^-1(p)| where u' == u, +|Phi^-1(p)| otherwise; |Phi^-1| to 1e-12 absolute.
+ *   chain k's (n_k, mean_k, m2_k) of its scores by the weighted Welford update over its non-empty bins in ascending order.
+ *   W, B/n and R-hat as for dangx_chains_get from these, where n_0 = .. = n_{K-1} = n >= 2 IN THIS PIXEL; NaN otherwise (the
+ *     chains' samples left the range a different number of times), NaN where S = 0 or every sample lies in one bin, +inf where
+ *     every chain stayed in one bin and the bins differ.
+ *   folded: m = the pooled median bin (dangx_moments_hist_stat's quantile rule at q = 0.5); f[k][e] = c[k][m - e] + c[k][m + e]
+ *     (f[k][0] = c[k][m]; terms outside the record are 0); the same statistic with f for c and e = 0 .. nbins-1 for b.
+ * stat: 0 = bulk (rank-normalised), 1 = folded, 2 = the larger of the two, the number to report (NaN if either is NaN).
+ * out[npix] of this shard.  Not split: the histograms are not batched, drift inside a chain is stat 4 of
+ * dangx_moments_batches_get.  Errors as for dangx_chains_hist_stat, and a bad stat; dangx_moments_count may differ between the
+ * chains (the rule per pixel decides). */
+int dangx_chains_hist_rank(dangx_ctx *const *ctxs, int nchains, int reg, int stat, double *out);
+int dangx_chains_hist_rank_dev(dangx_ctx *const *ctxs, int nchains, int reg, int stat, double *out_dev);
 /* dangx_moments_batches_get over the chains (k_chains_batches): every chain must hold the same registration, L, nbatch and count
  * (anything else is refused, naming the chain).  stat 0 / 1: pooled over chains and over batches first.., the chains folded in
  * list order from each chain's own fold, sqrt(M / (K N' - ddof)); stat 2: sqrt(sum_k MCSE_k^2) / K; stat 3: sum_k ESS_k; stat 4:

@@ -3,7 +3,7 @@
 iterations of the C3 model: blocks of iterations without and with accumulation after every iteration, alternating in one process;
 then the k_moments kernel time from the profile and its bandwidth in algorithmic bytes (5 x 8 B per selected element) against the
 6.29 TB/s measured copy ceiling of the MI355X.
-    python3 tools/bench_moments.py [nside=1024] [steps per block=10] [rounds=5] [--lag1] [--pairs default] [--hist [nbins=64]] [--signals [--bandpass]] [--chains K] [--batches NB]
+    python3 tools/bench_moments.py [nside=1024] [steps per block=10] [rounds=5] [--lag1] [--pairs default] [--hist [nbins=64]] [--signals [--bandpass]] [--chains K [--samples N]] [--batches NB]
 --lag1 / --pairs default: after the above, `rounds` alternating rounds of `steps` accumulations each of (a) the plain accumulate,
 (b) with lag-1 tracking (k_moments_accum_lag: 10 x 8 B per selected element) and (c) with the default pairs (k_moments_pairs: 6 x 8 B
 per pair element, timed apart from the mean launch that follows it); per launch the algorithmic bytes, the achieved bytes/s and
@@ -21,8 +21,11 @@ iteration is run.
 --chains K: K chains over the same data (open_chain), three samples each with lag-1 and one histogram plane (64 bins x 16 bit);
 `rounds` alternating rounds of `steps` read-outs each, timed with events on the stream: (y) the single-chain std read-out
 (k_moments_finish: 2 x 8 B per element), (r) R-hat over the chains ((2 K + 1) x 8 B), (e) the pooled ESS ((5 K + 1) x 8 B) and (q)
-three pooled quantiles (K x 128 B + 3 x 8 B per pixel); per read-out its bytes/s and the ratio to (y) in the same round.  Nothing
-else of the above is run.
+three pooled quantiles (K x 128 B + 3 x 8 B per pixel); per read-out its bytes/s and the ratio to (y) in the same round; then the
+rank-normalised R-hat of the same histograms (k_chains_rank: K x 128 B + 8 B per pixel) as (b) bulk, (f) folded and (m) the
+larger of the two, each also as its time over (q)'s of the same round.  --samples N: N samples per chain instead of three (the
+rank read-outs form one score per non-empty bin, so their time grows with the bins the samples reach).  Nothing else of the above
+is run.
 --batches NB: the batched accumulators (dangx_moments_batches) with NB batches on up to four of the default index planes, two chains.
 `rounds` alternating rounds in one process of (a) the plain k_moments_accum launch and (b) the batch launch of the same
 accumulations (5 x 8 B per element each; batches long enough that no merge falls into the round), per byte; then, after NB
@@ -53,6 +56,10 @@ nchains = 0
 if "--chains" in argv:
     i = argv.index("--chains")
     nchains = int(argv.pop(i + 1))
+nsamples = 3
+if "--samples" in argv:
+    i = argv.index("--samples")
+    nsamples = int(argv.pop(i + 1))
 nbat = 0
 if "--batches" in argv:
     i = argv.index("--batches")
@@ -96,7 +103,7 @@ if nchains:
         sel = da.moments_begin(p, d)
         da.moments_pairs(p, d, pairs=[], lag1=True)
         hp = da.moments_hist(p, d, planes=da.default_hist_planes(p, comps, sel)[:1], nbins=64, bits=16)
-    for it in (1, 2, 3):
+    for it in range(1, nsamples + 1):
         for p, d in runs:
             da.gibbs_iteration(p, d, it, want_counts=False)
             da.moments_accumulate(d)
@@ -118,15 +125,19 @@ if nchains:
         torch.cuda.synchronize()
         return e0.elapsed_time(e1) / steps
 
+    out1 = torch.zeros((npx,), dtype=torch.float64, device=dev)
     forms = [("y", "single-chain std", 2 * 8 * nplanes, lambda: eng._chk(eng.lib.dangx_moments_get_dev(eng.h, l, what, 1, 0, out.data_ptr()))),
              ("r", "R-hat", (2 * nchains + 1) * 8 * nplanes, lambda: da.chains_get(engs, l, what, "rhat", device=True, out=out)),
              ("e", "pooled ESS", (5 * nchains + 1) * 8 * nplanes, lambda: da.chains_get(engs, l, what, "ess", device=True, out=out)),
              ("q", "3 pooled quantiles", nchains * 128 + 3 * 8, lambda: da.chains_hist_stat(engs, 0, "quantile", q=q3, device=True, out=outq))]
+    forms += [(key, "%s rank R-hat" % stat, nchains * 128 + 8, lambda stat=stat: da.chains_hist_rank(engs, 0, stat, device=True, out=out1))
+              for key, stat in (("b", "bulk"), ("f", "folded"), ("m", "max"))]
     ratios = {k: [] for k, _, _, _ in forms[1:]}
+    to_q = {k: [] for k in "bfm"}                       # the time of a rank read-out over the quantile read-out's of the same round
     print("C3 at Nside %d, %d chains of %d samples, %s index %d: %d planes of %d pixels" % (nside, nchains, engs[0].moments_count(),
                                                                                           comps[l].label, what, nplanes, npx))
     for r in range(rounds):
-        line, y_bw = "round %d:" % (r + 1), None
+        line, y_bw, q_ms = "round %d:" % (r + 1), None, None
         for key, name, per_pix, fn in forms:
             ms = timed(fn)
             bw = per_pix * npx / ms * 1e-9
@@ -134,11 +145,17 @@ if nchains:
                 y_bw = bw
             else:
                 ratios[key].append(bw / y_bw)
+            if key == "q":
+                q_ms = ms
+            if key in to_q:
+                to_q[key].append(ms / q_ms)
             line += " (%s) %s %.3f ms, %.3f GB -> %.2f TB/s%s;" % (key, name, ms, per_pix * npx * 1e-9, bw, "" if key == "y" else " = %.3f of (y)" % (bw / y_bw))
         print(line)
     for key, name, _, _ in forms[1:]:
         print("(%s) %s / (y): median %.3f (spread %.3f .. %.3f)%s" % (key, name, float(np.median(ratios[key])), min(ratios[key]), max(ratios[key]),
-                                                                     "" if key == "q" else "; expected >= 0.8"))
+                                                                     "" if key in "qbfm" else "; expected >= 0.8"))
+    for key, name, _, _ in forms[-3:]:
+        print("(%s) %s, time / (q)'s: median %.3f (spread %.3f .. %.3f)" % (key, name, float(np.median(to_q[key])), min(to_q[key]), max(to_q[key])))
     sys.exit(0)
 if nbat:
     npx = meta["npix"]
