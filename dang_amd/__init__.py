@@ -14,6 +14,7 @@ from .api import (BandInfo, DangCGGroup, DangComps, DangData, DangParams, DangxE
                   default_signal_specs, moments_signals, posterior_signal_maps,
                   chains_get, chains_get_template, chains_get_signal, chains_get_pair, chains_hist_stat, open_chain,
                   chains_posterior_maps, chains_pair_maps, chains_quantile_maps, chains_signal_maps, chains_hist_rank, chains_rank_maps,
-                  moments_batches, posterior_batch_maps, chains_batches_get, chains_batch_maps)
+                  moments_batches, posterior_batch_maps, chains_batches_get, chains_batch_maps,
+                  dist_chains, moments_save, moments_load)
 
 __version__ = "0.1.0"

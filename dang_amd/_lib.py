@@ -39,6 +39,9 @@ MAX_CHAINS = 8
 CHAINS_STAT_CODES = {"mean": 0, "std": 1, "rhat": 2, "W": 3, "B": 4, "ess": 5}
 BATCH_STAT_CODES = {"mean": 0, "std": 1, "mcse": 2, "ess_bm": 3, "split_rhat": 4}
 MAX_BATCHES, MAX_BATCH_PLANES = 32, 32
+SEC_HEAD, SEC_PLANES, SEC_PAIR, SEC_HIST, SEC_SIGNAL, SEC_BATCHES = range(6)   # family of a section
+SECTION_NAMES = ("HEAD", "PLANES", "PAIR", "HIST", "SIGNAL", "BATCHES")
+SECTION_HEAD_BYTES = 104
 SIGNAL_KINDS = ("T", "Q", "U", "P")      # kind 0..3 of a signal spec (comp, band, kind)
 
 TYPE_CODES = {"power-law": POWERLAW, "mbb": MBB, "freefree": FREEFREE, "lognormal": LOGNORMAL, "cmb": CMB, "T_cmb": TCMB,
@@ -180,6 +183,14 @@ SYMBOLS = {
     "dangx_moments_batches_get_dev": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "dangx_moments_batches_raw": (C.c_int, [_P, C.c_int, C.c_int, _P, _P]),
     "dangx_moments_batches_raw_dev": (C.c_int, [_P, C.c_int, C.c_int, _P, _P]),
+    # sections of the accumulator state: (ctx, family, a, b, ...)
+    "dangx_moments_section_bytes": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "dangx_moments_section_get": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int64]),
+    "dangx_moments_section_get_dev": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int64]),
+    "dangx_moments_section_put": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int64]),
+    "dangx_moments_section_put_dev": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int64]),
+    "dangx_moments_begin_like": (C.c_int, [_P, _P]),
+    "dangx_moments_held_bytes": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     # read-outs over several chains: (ctxs, nchains, ...) = one context per chain
     "dangx_chains_get": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "dangx_chains_get_dev": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),

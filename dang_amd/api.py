@@ -12,6 +12,8 @@ Arrays keep the Fortran memory order, i.e. numpy/torch shape [band][map][pix] fo
 sig_map/rms_map, [map][pix] for masks/amplitude and [ind][map][pix] for indices.
 """
 import ctypes as C
+import os
+import struct
 from dataclasses import dataclass, field
 from typing import List, Optional
 
@@ -166,6 +168,19 @@ def _readout_dest(e, shape, device, out=None, dtype=np.float64):
         out = np.zeros(shape, dtype=dtype)
     assert isinstance(out, np.ndarray) and out.dtype == dtype and out.flags.c_contiguous and out.shape == shape
     return out, out.ctypes.data
+
+
+def _sec_family(family):
+    return L.SECTION_NAMES.index(family) if isinstance(family, str) else int(family)
+
+
+def _sec_buffer(x, device):
+    """(pointer, bytes) of a section payload: a contiguous torch cuda tensor (device) or numpy array"""
+    if device:
+        assert _is_torch(x) and x.is_cuda and x.is_contiguous()
+        return x.data_ptr(), x.numel() * x.element_size()
+    assert isinstance(x, np.ndarray) and x.flags.c_contiguous
+    return x.ctypes.data, x.nbytes
 
 
 class Engine:
@@ -820,6 +835,69 @@ class Engine:
         if device:
             self.synchronize()
         return mean, m2
+
+    # -- sections: one part of the accumulator state in its packed layout (include/dangx.h); family = L.SEC_* or its name
+    def moments_section_bytes(self, family, a=0, b=0):
+        n = C.c_int64(0)
+        self._chk(self.lib.dangx_moments_section_bytes(self.h, _sec_family(family), int(a), int(b), C.byref(n)))
+        return n.value
+
+    def moments_section_get(self, family, a=0, b=0, device=False, out=None):
+        """The payload of section (family, a, b) as uint8: a numpy array, or with device=True a torch cuda tensor written
+        asynchronously on the context's stream (synchronize this engine, or use that stream, before reading it)."""
+        f = _sec_family(family)
+        if out is None:
+            n = self.moments_section_bytes(f, a, b)
+            if device:
+                import torch
+                dev = self._device if self._device is not None and self._device >= 0 else torch.cuda.current_device()
+                out = torch.empty(n, dtype=torch.uint8, device=torch.device("cuda", dev))
+            else:
+                out = np.empty(n, dtype=np.uint8)
+        ptr, n = _sec_buffer(out, device)
+        self._chk((self.lib.dangx_moments_section_get_dev if device else self.lib.dangx_moments_section_get)(self.h, f, int(a), int(b), ptr, n))
+        return out
+
+    def moments_section_put(self, family, a, b, data):
+        """Write a payload (a contiguous numpy array -> the host form, a torch cuda tensor -> the device form, asynchronous on the
+        context's stream: keep the tensor alive and unchanged until this engine is synchronized) into section (family, a, b)."""
+        device = _is_torch(data)
+        if device and not data.is_cuda:
+            data, device = data.numpy(), False
+        ptr, n = _sec_buffer(data, device)
+        self._chk((self.lib.dangx_moments_section_put_dev if device else self.lib.dangx_moments_section_put)(self.h, _sec_family(family), int(a),
+                                                                                                         int(b), ptr, n))
+
+    def moments_sections(self):
+        """[(family, a, b), ...] of every section of this engine's registration except HEAD, in the order moments_save writes them."""
+        sel = getattr(self, "_moment_sel", None)
+        if sel is None:
+            raise DangxError("moments_begin was not called")
+        out = []
+        for l, c in enumerate(self.component_list):
+            for what in range(1 + c.nindices):
+                if (int(sel[l]) >> (0 if what == 0 else 3 + 3 * (what - 1))) & 7:
+                    out.append((L.SEC_PLANES, l, what))
+        out += [(L.SEC_PAIR, p, 0) for p in range(len(getattr(self, "_moment_pairs", None) or []))]
+        out += [(L.SEC_HIST, r, 0) for r in range(len((getattr(self, "_moment_hist", None) or {}).get("planes", [])))]
+        out += [(L.SEC_SIGNAL, s, 0) for s in range(len(getattr(self, "_moment_signals", None) or []))]
+        out += [(L.SEC_BATCHES, r, 0) for r in range(len((getattr(self, "_moment_batches", None) or {}).get("planes", [])))]
+        return out
+
+    def moments_begin_like(self, like):
+        """Make this engine a holder: it takes over the registrations of Engine `like` (same shard, same components) and
+        allocates no accumulators; sections put into it (moments_section_put) serve the chains_* read-outs, at any position of
+        their list.  moments_accumulate and the single-chain read-outs refuse a holder.  Calling it again drops what is held."""
+        self._chk(self.lib.dangx_moments_begin_like(self.h, like.h))
+        import copy
+        for name in ("_moment_sel", "_moment_pairs", "_moment_lag1", "_moment_hist", "_moment_signals", "_moment_batches"):
+            setattr(self, name, copy.deepcopy(getattr(like, name, None)))
+
+    def moments_held_bytes(self):
+        """Device bytes of the sections a holder holds (0 for an engine with accumulators of its own)."""
+        n = C.c_int64(0)
+        self._chk(self.lib.dangx_moments_held_bytes(self.h, C.byref(n)))
+        return n.value
 
     def moments_end(self):
         self._moment_signals = None
@@ -1650,6 +1728,31 @@ def _chains_shards(chains, who):
     return [list(col) for col in zip(*chs)], counts
 
 
+class _LocalChains:
+    """The chains of this process as the chains_*_maps read them: nothing to fetch, the maps are made here."""
+    here = True
+
+    def __init__(self, chains, who):
+        self.shards, self.counts = _chains_shards(chains, who)
+
+    def fetch(self, sections):
+        pass
+
+    def batches_info(self):
+        return self.shards[0][0].moments_batches_info()
+
+    def finish(self, out):
+        return out
+
+
+def _chains_source(chains, who):
+    """what a chains_*_maps call reads its chains through: a list of chains of this process, or dist_chains' object"""
+    if isinstance(chains, DistChains):
+        chains.begin(who)
+        return chains
+    return _LocalChains(chains, who)
+
+
 def _chains_map(shards, get, masked_value):
     parts = []
     for col in shards:
@@ -1669,7 +1772,8 @@ def chains_posterior_maps(chains, ddof=0, masked_value=None):
     every entry {'n', 'nchains', 'mean', 'std', 'rhat', 'W', 'B'} (+ 'ess' when every chain tracks lag-1) with the pooled mean and
     standard deviation, R-hat, the within-chain variance and B/n of chains_get.  'n' is the samples per chain -- a list, and no
     'rhat' / 'W' / 'B', when the chains hold different counts.  Shards side by side; masked_value as in posterior_maps."""
-    shards, counts = _chains_shards(chains, "chains_posterior_maps")
+    src = _chains_source(chains, "chains_posterior_maps")
+    shards, counts = src.shards, src.counts
     first = shards[0]
     sel = getattr(first[0], "_moment_sel", None)
     if sel is None:
@@ -1680,19 +1784,24 @@ def chains_posterior_maps(chains, ddof=0, masked_value=None):
         for what in range(1 + c.nindices):
             if not (int(sel[l]) >> (0 if what == 0 else 3 + 3 * (what - 1))) & 7:
                 continue
+            stats = _chains_stats(counts, lag1)
+            src.fetch([(L.SEC_PLANES, l, what, "ess" in stats)])
+            if not src.here:
+                continue
             entry = {"n": counts[0] if len(set(counts)) == 1 else list(counts), "nchains": len(counts)}
-            for stat in _chains_stats(counts, lag1):
+            for stat in stats:
                 if what == 0 and c.type in GLOBAL_TYPES:
                     entry[stat] = chains_get_template(first, l, stat, ddof)
                 else:
                     entry[stat] = _chains_map(shards, lambda col: chains_get(col, l, what, stat, ddof), masked_value)
             out[(c.label, _plane_name(c, what))] = entry
-    return out
+    return src.finish(out)
 
 
 def chains_pair_maps(chains, stat="corr", ddof=0, masked_value=None):
     """posterior_pair_maps over several chains: the pooled correlation ('corr') or covariance ('cov', with ddof) of every pair."""
-    shards, _ = _chains_shards(chains, "chains_pair_maps")
+    src = _chains_source(chains, "chains_pair_maps")
+    shards = src.shards
     pairs = getattr(shards[0][0], "_moment_pairs", None)
     if pairs is None:
         raise DangxError("chains_pair_maps: moments_pairs was not called")
@@ -1700,13 +1809,16 @@ def chains_pair_maps(chains, stat="corr", ddof=0, masked_value=None):
     out = {}
     for p, (a, b) in enumerate(pairs):
         key = tuple((comps[l].label, _plane_name(comps[l], what), k) for l, what, k in (a, b))
-        out[key] = _chains_map(shards, lambda col: chains_get_pair(col, p, stat, ddof), masked_value)
-    return out
+        src.fetch([(L.SEC_PAIR, p, 0, False)] + sorted({(L.SEC_PLANES, l, what, False) for l, what, _ in (a, b)}))
+        if src.here:
+            out[key] = _chains_map(shards, lambda col: chains_get_pair(col, p, stat, ddof), masked_value)
+    return src.finish(out)
 
 
 def chains_quantile_maps(chains, q=(0.16, 0.5, 0.84), masked_value=None):
     """posterior_quantile_maps over several chains: 'q', 'mode' and 'n' of the bins of all chains summed (+ 'range', 'nbins')."""
-    shards, _ = _chains_shards(chains, "chains_quantile_maps")
+    src = _chains_source(chains, "chains_quantile_maps")
+    shards = src.shards
     reg0 = getattr(shards[0][0], "_moment_hist", None)
     if not reg0:
         raise DangxError("chains_quantile_maps: moments_hist was not called")
@@ -1715,18 +1827,22 @@ def chains_quantile_maps(chains, q=(0.16, 0.5, 0.84), masked_value=None):
     comps = shards[0][0].component_list
     out = {}
     for r, (l, what, k) in enumerate(reg0["planes"]):
+        src.fetch([(L.SEC_HIST, r, 0, False)])
+        if not src.here:
+            continue
         entry = {"range": reg0["ranges"][r], "nbins": reg0["nbins"]}
         for name, stat in (("q", "quantile"), ("mode", "mode"), ("n", "n")):
             entry[name] = _chains_map(shards, lambda col: chains_hist_stat(col, r, stat, q=q if stat == "quantile" else None), masked_value)
         out[(comps[l].label, _plane_name(comps[l], what), k)] = entry
-    return out
+    return src.finish(out)
 
 
 def chains_rank_maps(chains, masked_value=None):
     """The rank-normalised R-hat of every registered histogram plane over several chains: {'rhat_rank', 'rhat_folded', 'rhat_max',
     'range', 'nbins'} per plane (chains_hist_rank's 'bulk', 'folded' and 'max').  Shards side by side; masked_value as in
     posterior_maps."""
-    shards, _ = _chains_shards(chains, "chains_rank_maps")
+    src = _chains_source(chains, "chains_rank_maps")
+    shards = src.shards
     reg0 = getattr(shards[0][0], "_moment_hist", None)
     if not reg0:
         raise DangxError("chains_rank_maps: moments_hist was not called")
@@ -1735,11 +1851,14 @@ def chains_rank_maps(chains, masked_value=None):
     comps = shards[0][0].component_list
     out = {}
     for r, (l, what, k) in enumerate(reg0["planes"]):
+        src.fetch([(L.SEC_HIST, r, 0, False)])
+        if not src.here:
+            continue
         entry = {"range": reg0["ranges"][r], "nbins": reg0["nbins"]}
         for name, stat in (("rhat_rank", "bulk"), ("rhat_folded", "folded"), ("rhat_max", "max")):
             entry[name] = _chains_map(shards, lambda col: chains_hist_rank(col, r, stat), masked_value)
         out[(comps[l].label, _plane_name(comps[l], what), k)] = entry
-    return out
+    return src.finish(out)
 
 
 def chains_batches_get(engines, reg, stat, first=0, ddof=0, device=False, out=None):
@@ -1756,7 +1875,8 @@ def chains_batches_get(engines, reg, stat, first=0, ddof=0, device=False, out=No
 def chains_batch_maps(chains, first=0, ddof=0, masked_value=None):
     """posterior_batch_maps over several chains: the same keys, every entry with chains_batches_get's statistics + 'n' (samples per
     chain), 'nchains', 'batch_len', 'nfull', 'partial', 'first'.  Every chain must hold the same registration and batch state."""
-    shards, counts = _chains_shards(chains, "chains_batch_maps")
+    src = _chains_source(chains, "chains_batch_maps")
+    shards, counts = src.shards, src.counts
     reg0 = getattr(shards[0][0], "_moment_batches", None)
     if not reg0:
         raise DangxError("chains_batch_maps: moments_batches was not called")
@@ -1764,21 +1884,25 @@ def chains_batch_maps(chains, first=0, ddof=0, masked_value=None):
         raise DangxError("chains_batch_maps: the contexts hold different batch registrations")
     if len(set(counts)) != 1:
         raise DangxError("chains_batch_maps: the chains hold different sample counts %s" % list(counts))
-    info = shards[0][0].moments_batches_info()
+    info = src.batches_info()
     _batch_first_check("chains_batch_maps", info, first)
     comps = shards[0][0].component_list
     out = {}
     for r, (l, what, k) in enumerate(reg0["planes"]):
+        src.fetch([(L.SEC_BATCHES, r, 0, False)])
+        if not src.here:
+            continue
         entry = dict(info, n=counts[0], nchains=len(counts), first=int(first))
         for stat in _batch_stats(info, first):
             entry[stat] = _chains_map(shards, lambda col: chains_batches_get(col, r, stat, first, ddof), masked_value)
         out[(comps[l].label, _plane_name(comps[l], what), k)] = entry
-    return out
+    return src.finish(out)
 
 
 def chains_signal_maps(chains, ddof=0, masked_value=None):
     """posterior_signal_maps over several chains: {'n', 'nchains', 'mean', 'std', 'rhat', 'W', 'B'} per registered signal."""
-    shards, counts = _chains_shards(chains, "chains_signal_maps")
+    src = _chains_source(chains, "chains_signal_maps")
+    shards, counts = src.shards, src.counts
     reg0 = getattr(shards[0][0], "_moment_signals", None)
     if reg0 is None:
         raise DangxError("chains_signal_maps: moments_signals was not called")
@@ -1787,11 +1911,315 @@ def chains_signal_maps(chains, ddof=0, masked_value=None):
     comps, bands = shards[0][0].component_list, shards[0][0].bands
     out = {}
     for s, (l, j, kind) in enumerate(reg0):
+        src.fetch([(L.SEC_SIGNAL, s, 0, False)])
+        if not src.here:
+            continue
         entry = {"n": counts[0] if len(set(counts)) == 1 else list(counts), "nchains": len(counts)}
         for stat in _chains_stats(counts, False):
             entry[stat] = _chains_map(shards, lambda col: chains_get_signal(col, s, stat, ddof), masked_value)
         out[(comps[l].label, bands[j].label, L.SIGNAL_KINDS[kind])] = entry
-    return out
+    return src.finish(out)
+
+
+# --------------------------------------------------------------------------- chains in other processes, save / restore
+# Both are thin layers over the sections of the accumulator state (Engine.moments_section_*, include/dangx.h): a chain that ran in
+# another process reaches the chains_* read-outs as a HOLDER on this device (Engine.moments_begin_like) given the few sections a
+# read-out needs, so the read-outs stay the one implementation they are and give bit for bit what the same chains give inside
+# one process; a saved run is HEAD plus every section, streamed one at a time.
+
+_HEAD_STRUCT = struct.Struct("<IIqiiqiiqQ6Q")
+_HEAD_GROUPS = ("the shard (npix, pix0 or nmaps)", "the selection (selection words, type or nindices of a selected component)",
+                "the pair list", "the histogram registrations (planes, lo / hi range, nbins or bits)", "the signal registrations",
+                "the batch registrations (planes)")
+
+
+def head_unpack(raw):
+    """The fields of a HEAD section (include/dangx.h) as a dict; `raw`: its DANGX_SECTION_HEAD_BYTES bytes."""
+    raw = bytes(raw)
+    if len(raw) != L.SECTION_HEAD_BYTES:
+        raise DangxError("a HEAD section is %d bytes, not %d (truncated or foreign)" % (L.SECTION_HEAD_BYTES, len(raw)))
+    v = _HEAD_STRUCT.unpack(raw)
+    if v[0] != 0x48535844:
+        raise DangxError("not a HEAD section (foreign bytes: the magic word is missing)")
+    return {"version": v[1], "count": v[2], "lag1": v[3], "nbatch": v[4], "batch_len": v[5], "nfull": v[6], "partial": v[8],
+            "fingerprint": v[9], "groups": tuple(v[10:16])}
+
+
+def head_diff(got, own):
+    """'' when two unpacked HEADs describe the same registration, else what differs (dx_section_head_diff's words)"""
+    why = []
+    if got["lag1"] != own["lag1"]:
+        why.append("lag-1 is tracked there and missing here" if got["lag1"] else "lag-1 is missing there and tracked here")
+    if got["nbatch"] != own["nbatch"]:
+        why.append("nbatch is %d there and %d here" % (got["nbatch"], own["nbatch"]))
+    for i, name in enumerate(_HEAD_GROUPS):
+        if got["groups"][i] == own["groups"][i] or (i == 2 and got["lag1"] != own["lag1"]) or (i == 5 and got["nbatch"] != own["nbatch"]):
+            continue
+        why.append(name + " differ")
+    if not why and got["fingerprint"] != own["fingerprint"]:
+        why.append("the fingerprints differ")
+    return "; ".join(why)
+
+
+def dist_verdict(metas):
+    """What every rank concludes from the gathered metadata of dist_chains, metas[r] = {'error': str or None, 'heads': [chain]
+    [shard] HEAD bytes, 'shape': [chain][shard] (pix0, npix)} of rank r: (error message or None, the chains in global order as
+    (rank, local index), their sample counts).  A pure function of its argument: every rank reaches the same verdict."""
+    for r, m in enumerate(metas):
+        if m.get("error"):
+            return "rank %d: %s" % (r, m["error"]), [], []
+    order = [(r, i) for r, m in enumerate(metas) for i in range(len(m["heads"]))]
+    if not 2 <= len(order) <= L.MAX_CHAINS:
+        return "takes 2 to %d chains in all, not %d" % (L.MAX_CHAINS, len(order)), [], []
+    nsh = {len(metas[r]["heads"][i]) for r, i in order}
+    if len(nsh) != 1:
+        return "the chains hold different numbers of shards %s" % sorted(nsh), [], []
+    r0, i0 = order[0]
+    counts = []
+    for r, i in order:
+        who = "rank %d chain %d" % (r, i)
+        heads = [head_unpack(h) for h in metas[r]["heads"][i]]
+        for s, h in enumerate(heads):
+            if tuple(metas[r]["shape"][i][s]) != tuple(metas[r0]["shape"][i0][s]):
+                return "%s shard %d holds pixels %s, the first chain %s: the ranks of one group must hold the same pixel range" % (
+                    who, s, tuple(metas[r]["shape"][i][s]), tuple(metas[r0]["shape"][i0][s])), [], []
+            why = head_diff(h, head_unpack(metas[r0]["heads"][i0][s]))
+            if why:
+                return "%s shard %d is registered differently from the first chain: %s" % (who, s, why), [], []
+        ns = {h["count"] for h in heads}
+        if len(ns) != 1:
+            return "the contexts of %s hold different sample counts %s" % (who, sorted(ns)), [], []
+        if heads[0]["count"] == 0:
+            return "%s: no sample accumulated" % who, [], []
+        counts.append(heads[0]["count"])
+    return None, order, counts
+
+
+def _holder_engine(src):
+    """An Engine on src's shard and device with src's model and no chain state of its own: what moments_begin_like makes a holder of."""
+    import copy
+    import dataclasses
+    comps = []
+    for c in src.component_list:
+        k = copy.copy(c)
+        k.amplitude, k.indices = None, None
+        comps.append(k)
+    dd = dataclasses.replace(src.ddata, engine=None, sky_model=None, res_map=None, chi_map=None)
+    return Engine(src.bands, comps, dd, npix_global=src.npix_global, pix0=src.pix0, device=src._device)
+
+
+class DistChains:
+    """dist_chains' object: the chains of every rank of a process group, which the chains_*_maps take in place of a list."""
+
+    def __init__(self, chains, group=None, dst=0):
+        import torch.distributed as td
+        if not (td.is_available() and td.is_initialized()):
+            raise DangxError("dist_chains: torch.distributed is not initialised")
+        self.local = [_chain_engines(c) for c in chains]          # [local chain][shard]
+        self.group, self.dst = group, dst
+        self.rank, self.nranks = td.get_rank(group), td.get_world_size(group)
+        if dst is not None and not 0 <= int(dst) < self.nranks:
+            raise DangxError("dist_chains: dst must be a rank of the group (0..%d) or None" % (self.nranks - 1))
+        self.here = dst is None or self.rank == int(dst)
+        self._holders = {}                                       # (rank, local index) -> [holder Engine per shard]
+        self.peak_held = 0                                       # most device bytes the holders held at once during the last call
+        self.fetched = []                                        # the sections the last call moved, in order
+        self.begin("dist_chains")
+
+    def _meta(self):
+        try:
+            return {"error": None,
+                    "heads": [[bytes(e.moments_section_get(L.SEC_HEAD)) for e in ch] for ch in self.local],
+                    "shape": [[(e.pix0, e.npix) for e in ch] for ch in self.local]}
+        except (DangxError, AssertionError) as ex:
+            return {"error": str(ex) or type(ex).__name__, "heads": [], "shape": []}
+
+    def begin(self, who):
+        """The one all_gather of metadata in front of every call: shard ranges, HEADs (fingerprint, counts, batch state) and the
+        number of local chains.  Every rank reaches the same verdict, so a mismatch raises on every rank before a section moves."""
+        import torch.distributed as td
+        metas = [None] * self.nranks
+        td.all_gather_object(metas, self._meta(), group=self.group)
+        err, self.order, self.counts = dist_verdict(metas)
+        if err:
+            raise DangxError("%s: %s" % (who, err))
+        self.heads = {(r, i): metas[r]["heads"][i] for r, i in self.order}
+        self.nlocal = [len(m["heads"]) for m in metas]
+        self.peak_held, self.fetched = 0, []
+        nsh = len(self.local[0]) if self.local else len(next(iter(self.heads.values())))
+        if self.here and not self.local:
+            raise DangxError("%s: the rank that makes the maps must hold a chain of its own (the model of the holders is taken from it)" % who)
+        cols = []
+        for s in range(nsh):
+            col = []
+            for r, i in (self.order if self.here else [(self.rank, j) for j in range(len(self.local))]):
+                if r == self.rank:
+                    col.append(self.local[i][s])
+                else:
+                    hs = self._holders.setdefault((r, i), [])
+                    while len(hs) <= s:                           # a holder from its first moment: it carries the registration
+                        hs.append(_holder_engine(self.local[0][len(hs)]))
+                        hs[-1].moments_begin_like(self.local[0][len(hs) - 1])
+                    col.append(hs[s])
+            cols.append(col)
+        self.shards = cols
+        if not self.here:
+            self.counts = list(self.counts)
+
+    def batches_info(self):
+        h = head_unpack(self.heads[self.order[0]][0])
+        if h["nbatch"] == 0:
+            raise DangxError("no batches are registered (moments_batches was not called)")
+        return {"batch_len": h["batch_len"], "nfull": h["nfull"], "partial": h["partial"]}
+
+    def _payload(self, e, f, a, b, lag):
+        """this rank's bytes of a section: a device tensor under nccl, a host tensor under gloo (staged through the host form)"""
+        import torch
+        import torch.distributed as td
+        if td.get_backend(self.group) == "nccl":
+            t = e.moments_section_get(f, a, b, device=True)
+            e.synchronize()
+        else:
+            t = torch.from_numpy(e.moments_section_get(f, a, b))
+        pixel_planes = f == L.SEC_PLANES and not (b == 0 and e.component_list[a].type in GLOBAL_TYPES)
+        if pixel_planes and getattr(e, "_moment_lag1", False) and not lag:
+            t = t[:t.numel() * 2 // 5]                           # mean and m2 are the first two of the five parts
+        return t
+
+    def fetch(self, sections):
+        """Collective: the sections [(family, a, b, with lag-1 parts), ...] of every chain reach the holders on the ranks that make
+        the maps.  What the holders held before is dropped first: they never hold more than one call's sections."""
+        import torch
+        import torch.distributed as td
+        nccl = td.get_backend(self.group) == "nccl"
+        rows = max(self.nlocal)
+        remote = [(r, i) for r, i in self.order if r != self.rank]
+        for s in range(len(self.shards)):
+            if self.here:
+                for key in remote:
+                    h = self._holders[key][s]
+                    h.moments_begin_like(self.local[0][s])
+                    h.moments_section_put(L.SEC_HEAD, 0, 0, np.frombuffer(self.heads[key][s], dtype=np.uint8).copy())
+            keep = []
+            for f, a, b, lag in sections:
+                mine = [self._payload(ch[s], f, a, b, lag) for ch in self.local]
+                send = torch.stack(mine + [torch.zeros_like(mine[0])] * (rows - len(mine))).contiguous()
+                parts = _dist.gather_equal(send, self.group, self.dst)
+                self.fetched.append((s, f, a, b, bool(lag)))
+                if not self.here:
+                    continue
+                if nccl:
+                    torch.cuda.current_stream().synchronize()     # the gathered bytes exist before a holder's stream copies them
+                for r, i in remote:
+                    self._holders[(r, i)][s].moments_section_put(f, a, b, parts[r][i] if nccl else parts[r][i].numpy())
+                keep.append(parts)
+            if self.here:
+                for key in remote:
+                    self._holders[key][s].synchronize()           # the copies out of `keep` are over
+                held = sum(h.moments_held_bytes() for hs in self._holders.values() for h in hs)
+                self.peak_held = max(self.peak_held, held)
+
+    def finish(self, out):
+        for key, hs in self._holders.items():                    # nothing stays held between calls
+            for s, h in enumerate(hs):
+                h.moments_begin_like(self.local[0][s])
+        return out if self.here else None
+
+
+def dist_chains(chains, group=None, dst=0):
+    """The chains of every rank of `group` (None: the default process group) as ONE set: every rank passes its local chain or
+    chains (each a ddata, or the list of that chain's shard engines), and the object returned is accepted by chains_posterior_maps,
+    chains_pair_maps, chains_quantile_maps, chains_rank_maps, chains_batch_maps and chains_signal_maps in place of the list.  Those
+    calls are then collective -- every rank of the group makes the same call -- and return the maps on rank `dst` of the group and
+    None elsewhere; dst=None: on every rank.  The chain order is rank order, and list order within a rank; 2 to 8 chains in all.
+    The ranks of one group hold the same pixel range (a sharded run makes one group per shard).  A rank whose registration, shard
+    or chain count does not fit raises DangxError on EVERY rank before anything moves.  For each map only the sections it needs
+    travel (mean and m2 of a plane; the lag-1 parts for 'ess' only; one histogram or batch registration at a time), as device
+    tensors under nccl and through the host under gloo, into holders (Engine.moments_begin_like) beside the local chains."""
+    return DistChains(chains, group=group, dst=dst)
+
+
+_SAVE_MAGIC = b"DANGXSEC"
+_SAVE_HEAD = struct.Struct("<8sIIqq")            # magic, format version, number of sections, pix0, npix
+_SAVE_ENTRY = struct.Struct("<iiiiqq")           # family, a, b, reserved, offset of the payload in the file, its bytes
+
+
+def _save_paths(path, engines):
+    return [path] if len(engines) == 1 else ["%s.%d" % (path, s) for s in range(len(engines))]
+
+
+def moments_save(ddata, path, engines=None):
+    """Write the accumulator state of every shard engine to `path` (several shards: path.0, path.1, ...): one self-describing file
+    per shard -- a fixed header, an index of (family, a, b, offset, bytes), then the raw section payloads (include/dangx.h), HEAD
+    first.  Sections are streamed one at a time: host memory is one section.  Together with the chain state this resumes a run:
+
+        # save                                             # restore, in a fresh process
+        state = ddata.engine.pull_state()                  initialize(...); moments_begin / _pairs / _hist / _signals / _batches as before
+        np.savez(p + ".chain", it=it, **state arrays)      put_amplitude / put_indices / put_template_amplitudes of the saved state
+        da.moments_save(ddata, p + ".moments")             da.moments_load(ddata, p + ".moments"); continue at iteration it + 1
+
+    (the random streams are keyed by seed, iteration and global pixel, so the resumed chain is the uninterrupted one)."""
+    engines = _engines_of(ddata, engines)
+    for e, fn in zip(engines, _save_paths(path, engines)):
+        secs = [(L.SEC_HEAD, 0, 0)] + e.moments_sections()
+        sizes = [e.moments_section_bytes(*s) for s in secs]
+        off = _SAVE_HEAD.size + _SAVE_ENTRY.size * len(secs)
+        tmp = fn + ".tmp"
+        with open(tmp, "wb") as f:
+            f.write(_SAVE_HEAD.pack(_SAVE_MAGIC, 1, len(secs), e.pix0, e.npix))
+            for (fam, a, b), n in zip(secs, sizes):
+                f.write(_SAVE_ENTRY.pack(fam, a, b, 0, off, n))
+                off += n
+            for (fam, a, b), n in zip(secs, sizes):
+                f.write(memoryview(np.ascontiguousarray(e.moments_section_get(fam, a, b))).cast("B"))
+        os.replace(tmp, fn)
+
+
+def moments_load(ddata, path, engines=None):
+    """Read what moments_save wrote into engines on which the same registrations were made first: HEAD decides (its fingerprint
+    must be that of the engine's registration; the error names what differs) before any accumulator is written.  A file that is
+    truncated, foreign or of another shard is refused whole.  The next moments_accumulate continues the saved run."""
+    engines = _engines_of(ddata, engines)
+    for e, fn in zip(engines, _save_paths(path, engines)):
+        size = os.path.getsize(fn)
+        with open(fn, "rb") as f:
+            raw = f.read(_SAVE_HEAD.size)
+            if len(raw) != _SAVE_HEAD.size or raw[:8] != _SAVE_MAGIC:
+                raise DangxError("moments_load: %s is not a file of moments_save" % fn)
+            _, ver, nsec, pix0, npix = _SAVE_HEAD.unpack(raw)
+            if ver != 1:
+                raise DangxError("moments_load: %s has format version %d, this library reads version 1" % (fn, ver))
+            if (pix0, npix) != (e.pix0, e.npix):
+                raise DangxError("moments_load: %s holds pixels (%d, %d), the engine (%d, %d)" % (fn, pix0, npix, e.pix0, e.npix))
+            raw = f.read(_SAVE_ENTRY.size * nsec) if 0 < nsec < 1 << 20 else b""
+            if nsec < 1 or len(raw) != _SAVE_ENTRY.size * nsec:
+                raise DangxError("moments_load: %s is truncated (its index is incomplete)" % fn)
+            index = [_SAVE_ENTRY.unpack_from(raw, _SAVE_ENTRY.size * i) for i in range(nsec)]
+            end = _SAVE_HEAD.size + _SAVE_ENTRY.size * nsec
+            for fam, a, b, _, off, n in index:
+                if off != end or n < 0:
+                    raise DangxError("moments_load: %s is damaged (its index does not describe consecutive payloads)" % fn)
+                end += n
+            if end != size:
+                raise DangxError("moments_load: %s is truncated (%d bytes, its index describes %d)" % (fn, size, end))
+            if index[0][0] != L.SEC_HEAD:
+                raise DangxError("moments_load: %s does not begin with a HEAD section" % fn)
+            f.seek(index[0][4])
+            head = np.frombuffer(f.read(index[0][5]), dtype=np.uint8).copy()
+            why = head_diff(head_unpack(head), head_unpack(e.moments_section_get(L.SEC_HEAD)))
+            if why:
+                raise DangxError("moments_load: %s does not fit the engine's registration: %s" % (fn, why))
+            want = e.moments_sections()
+            if [tuple(t[:3]) for t in index[1:]] != want:
+                raise DangxError("moments_load: %s holds other sections than the engine's registration has" % fn)
+            for fam, a, b, _, off, n in index[1:]:
+                if n != e.moments_section_bytes(fam, a, b):
+                    raise DangxError("moments_load: %s: section %s(%d, %d) is %d bytes, the engine's %d" % (
+                        fn, L.SECTION_NAMES[fam], a, b, n, e.moments_section_bytes(fam, a, b)))
+            e.moments_section_put(L.SEC_HEAD, 0, 0, head)        # the library checks the fingerprint once more
+            for fam, a, b, _, off, n in index[1:]:
+                f.seek(off)
+                e.moments_section_put(fam, a, b, np.frombuffer(f.read(n), dtype=np.uint8).copy())
 
 
 # --------------------------------------------------------------------------- full-sky mode, tuner, calibrators

@@ -12,7 +12,9 @@
 // The pointers of all chains travel by value (ChainsArgs + DxChainsPar: 1.3 KB of the 4 KB kernel-argument segment).  Pairs of elements are read
 // as 16 bytes where every pointer of a plane shares out's 16-byte phase, element by element otherwise (chains whose buffers were
 // adopted at different alignments; dx_stream.h); both forms evaluate the same header functions.  No LDS, no atomics, no scratch.
-// The chains' state is read through DxMoments' accessors (dx_moments_state.h); dangx_moments.hip accumulates it.
+// The chains' state is read through DxMoments' accessors (dx_moments_state.h); dangx_moments.hip accumulates it.  A chain may be a
+// holder (dangx_moments_begin_like): the accessors then answer from the sections put into it, null for one that was not, which the
+// host side refuses by name before a launch.
 #include "dx_moments_state.h"
 #include "dx_hist_host.h"
 #include "dx_chains_host.h"
@@ -290,6 +292,13 @@ struct ChainSet {
 
 int chains_fail(dangx_ctx* const* ctxs, const std::string& msg) { return fail(ctxs[0], "posterior chains: " + msg); }
 
+// a holder (dangx_moments_begin_like) that was not given the section a read-out needs: refused before anything is launched
+int chains_missing(dangx_ctx* const* ctxs, int k, const std::string& section) {
+    return chains_fail(ctxs, "chain " + std::to_string(k) + ": section " + section + " was not put into this holder (dangx_moments_section_put)");
+}
+
+std::string planes_section(int comp, int what) { return "PLANES(" + std::to_string(comp) + ", " + std::to_string(what) + ")"; }
+
 // the checks every read-out shares; on success cs describes the set
 int chains_open(dangx_ctx* const* ctxs, int nchains, ChainSet& cs) {
     if (!ctxs || !ctxs[0]) return 1;
@@ -311,6 +320,7 @@ int chains_open(dangx_ctx* const* ctxs, int nchains, ChainSet& cs) {
     }
     for (int k = 0; k < nchains; ++k) {
         if (!ctxs[k]->mom) return chains_fail(ctxs, "chain " + std::to_string(k) + ": dangx_moments_begin was not called");
+        if (ctxs[k]->mom->holder && !ctxs[k]->mom->head_put) return chains_missing(ctxs, k, "HEAD");
         if (ctxs[k]->mom->count == 0) return chains_fail(ctxs, "chain " + std::to_string(k) + ": no sample accumulated");
         cs.cnt[k] = ctxs[k]->mom->count;
     }
@@ -417,6 +427,9 @@ int chains_get_impl(dangx_ctx* const* ctxs, int nchains, int comp, int what, int
             a.mean[n][j] = m->mean(s);
             a.m2[n][j] = m->m2(s);
             if (stat == DX_CH_ESS) { a.prev[n][j] = m->prev(s); a.first[n][j] = m->first(s); a.P[n][j] = m->P(s); }
+            if (!a.mean[n][j] || !a.m2[n][j]) return chains_missing(ctxs, j, planes_section(comp, what));
+            if (stat == DX_CH_ESS && (!a.prev[n][j] || !a.first[n][j] || !a.P[n][j]))
+                return chains_missing(ctxs, j, planes_section(comp, what) + " with its lag-1 parts");
         }
         a.out[n] = ro.dst + (long long)k * np;
         ++n;
@@ -450,6 +463,7 @@ int chains_signal_impl(dangx_ctx* const* ctxs, int nchains, int sig, int stat, i
         const DxMoments* m = ctxs[j]->mom;
         a.mean[0][j] = m->mean(m->sigs[sig]);
         a.m2[0][j] = m->m2(m->sigs[sig]);
+        if (!a.mean[0][j]) return chains_missing(ctxs, j, "SIGNAL(" + std::to_string(sig) + ")");
     }
     a.out[0] = ro.dst;
     if (chains_launch(cs, a, 1, stat, ddof)) return 1;
@@ -484,6 +498,9 @@ int chains_pair_impl(dangx_ctx* const* ctxs, int nchains, int pair, int stat, in
         a.ma[j] = m->mean(sa); a.mb[j] = m->mean(sb);
         a.qa[j] = m->m2(sa); a.qb[j] = m->m2(sb);
         a.C[j] = m->C(p);
+        if (!a.C[j]) return chains_missing(ctxs, j, "PAIR(" + std::to_string(pair) + ")");
+        if (!a.ma[j] || !a.qa[j]) return chains_missing(ctxs, j, planes_section(sa.comp, sa.what));
+        if (!a.mb[j] || !a.qb[j]) return chains_missing(ctxs, j, planes_section(sb.comp, sb.what));
     }
     a.out = ro.dst;
     const DxChainsPar par = dx_chains_par(cs.K, cs.cnt, ddof);
@@ -528,7 +545,10 @@ int chains_hist_impl(dangx_ctx* const* ctxs, int nchains, int reg, int stat, int
     ReadOut ro{c0, out, to_host};
     if (ro.open(sizeof(double) * (size_t)total)) return 1;
     ChainsHistArgs a{};
-    for (int j = 0; j < cs.K; ++j) a.rec[j] = ctxs[j]->mom->records(ctxs[j]->mom->hists[reg]);
+    for (int j = 0; j < cs.K; ++j) {
+        a.rec[j] = ctxs[j]->mom->records(ctxs[j]->mom->hists[reg]);
+        if (!a.rec[j]) return chains_missing(ctxs, j, "HIST(" + std::to_string(reg) + ")");
+    }
     a.out = ro.dst; a.lo = m0->hists[reg].lo; a.hi = m0->hists[reg].hi; a.n = c0->dims.npix;
     a.K = cs.K; a.nbins = m0->hbins; a.bits = m0->hbits; a.stat = stat; a.nq = stat == 0 ? nq : 0;
     for (int j = 0; j < a.nq; ++j) a.q[j] = q[j];
@@ -556,7 +576,10 @@ int chains_rank_impl(dangx_ctx* const* ctxs, int nchains, int reg, int stat, dou
     ReadOut ro{c0, out, to_host};
     if (ro.open(sizeof(double) * (size_t)n)) return 1;
     ChainsRankArgs a{};
-    for (int j = 0; j < cs.K; ++j) a.rec[j] = ctxs[j]->mom->records(ctxs[j]->mom->hists[reg]);
+    for (int j = 0; j < cs.K; ++j) {
+        a.rec[j] = ctxs[j]->mom->records(ctxs[j]->mom->hists[reg]);
+        if (!a.rec[j]) return chains_missing(ctxs, j, "HIST(" + std::to_string(reg) + ")");
+    }
     a.out = ro.dst; a.n = n; a.K = cs.K; a.nbins = m0->hbins; a.bits = m0->hbits; a.stat = stat;
     if (chains_join(cs)) return 1;
     {
@@ -602,7 +625,10 @@ int chains_batches_impl(dangx_ctx* const* ctxs, int nchains, int reg, int stat, 
     ReadOut ro{c0, out, to_host};
     if (ro.open(sizeof(double) * (size_t)n)) return 1;
     ChainsBatchArgs a{};
-    for (int j = 0; j < cs.K; ++j) a.base[j] = ctxs[j]->mom->bmean(ctxs[j]->mom->batches[reg], 0);
+    for (int j = 0; j < cs.K; ++j) {
+        a.base[j] = ctxs[j]->mom->bmean(ctxs[j]->mom->batches[reg], 0);
+        if (!a.base[j]) return chains_missing(ctxs, j, "BATCHES(" + std::to_string(reg) + ")");
+    }
     a.out = ro.dst; a.pitch = m0->bpitch; a.n = n;
     a.par = dx_batches_par(stat, first, ddof, p.L, p.nfull, p.partial, cs.K);
     if (chains_join(cs)) return 1;
@@ -644,6 +670,8 @@ int dangx_chains_get_template(dangx_ctx* const* ctxs, int nchains, int comp, int
     if (!is_global_type(c0->desc[comp].type)) return chains_fail(ctxs, "not a template / monopole / hi_fit component");
     for (int k = 1; k < nchains; ++k)
         if (ctxs[k]->dims.nbands != c0->dims.nbands) return chains_fail(ctxs, "chain " + std::to_string(k) + " differs from chain 0 in nbands");
+    for (int k = 0; k < nchains; ++k)
+        if (ctxs[k]->mom->holder && !ctxs[k]->mom->h_rows[comp]) return chains_missing(ctxs, k, planes_section(comp, 0));
     const DxChainsPar par = dx_chains_par(cs.K, cs.cnt, ddof);
     for (int k = 0; k < c0->dims.nmaps; ++k) {
         if (!((planes >> k) & 1u)) continue;

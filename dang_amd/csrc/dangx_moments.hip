@@ -44,6 +44,11 @@
 // k_batches_merge first folds the slots pairwise in place and the batch length doubles.  k_batches_stat reads the slots in one
 // pass with running values (discarded burn-in, MCSE, batch-means ESS, split R-hat).  Nothing registered: no launch.
 //
+// dangx_moments_section_* read and write one section of all this state in a packed layout (dx_section_host.h: HEAD, the planes of a
+// (component, what), a pair, a histogram, a signal, a batch registration) with one hipMemcpyAsync per plane and no kernel, and
+// dangx_moments_begin_like makes a context a HOLDER of sections put into it, which the read-outs over several chains accept in
+// place of a live chain: what saving / restoring a run and chains in other processes are made of.
+//
 // The state (DxMoments) and the host helpers are in dx_moments_state.h, the loop over a plane (dx_stream) in dx_stream.h; the
 // read-outs over several chains (dangx_chains_*) are a translation unit of their own, dangx_chains.hip.
 #include "dx_moments_state.h"
@@ -51,6 +56,7 @@
 #include "dx_hist_host.h"
 #define DX_BATCH_UNROLL 4   // k_batches_stat: four slots' loads in flight (79 VGPRs, occupancy 6)
 #include "dx_batches_host.h"
+#include "dx_section_host.h"
 #include "dx_stream.h"
 
 #include <memory>
@@ -58,6 +64,7 @@
 static_assert(DX_MOM_MAX_PAIRS == DANGX_MAX_PAIRS, "dx_moments_host.h and include/dangx.h disagree");
 static_assert(DX_HIST_MAX == DANGX_MAX_HIST, "dx_hist_host.h and include/dangx.h disagree");
 static_assert(DX_SIG_MAX == DANGX_MAX_SIGNALS, "dx_signal_host.h and include/dangx.h disagree");
+static_assert(DX_SEC_HEAD_BYTES == DANGX_SECTION_HEAD_BYTES, "dx_section_host.h and include/dangx.h disagree");
 static_assert(DX_BATCH_MAX == DANGX_MAX_BATCHES && DX_BATCH_MAX_PLANES == DANGX_MAX_BATCH_PLANES, "dx_batches_host.h and include/dangx.h disagree");
 
 namespace {
@@ -439,6 +446,15 @@ int need(dangx_ctx* ctx) {
     return 0;
 }
 
+// an entry point that reads or writes accumulators of the context's own
+int need_live(dangx_ctx* ctx, const char* who) {
+    if (need(ctx)) return 1;
+    if (ctx->mom->holder)
+        return fail(ctx, std::string("posterior moments: ") + who + ": the context is a holder (dangx_moments_begin_like): it has no accumulators of its own, "
+                         "only dangx_moments_section_* and dangx_chains_* take it");
+    return 0;
+}
+
 // the resident plane of a segment as it is now (adopted buffers may have been replaced since begin)
 const double* seg_plane(const dangx_ctx* ctx, const DxMoments::Seg& s) {
     const long long np = ctx->dims.npix;
@@ -448,7 +464,7 @@ const double* seg_plane(const dangx_ctx* ctx, const DxMoments::Seg& s) {
 
 // checks of a get: planes of (comp, what) that are selected -> bit k = plane k+1
 int get_planes(dangx_ctx* ctx, int comp, int what, int stat, int ddof, unsigned& planes) {
-    if (need(ctx)) return 1;
+    if (need_live(ctx, "dangx_moments_get")) return 1;
     DxMoments* m = ctx->mom;
     if (comp < 0 || comp >= ctx->dims.ncomp) return fail(ctx, "posterior moments: component index out of range");
     if (what < 0 || what > DANGX_MAX_IND) return fail(ctx, "posterior moments: what must be 0 (amplitude) or 1 + index number");
@@ -562,7 +578,7 @@ int finish_plane(dangx_ctx* ctx, const double* mean, const double* m2, int stat,
 }
 
 int signal_get_check(dangx_ctx* ctx, int sig, int stat, int ddof) {
-    if (need(ctx)) return 1;
+    if (need_live(ctx, "dangx_moments_get_signal")) return 1;
     const DxMoments* m = ctx->mom;
     if (sig < 0 || sig >= (int)m->sigs.size())
         return fail(ctx, "posterior moments: signal index out of range (" + std::to_string(m->sigs.size()) + " signals registered)");
@@ -631,6 +647,7 @@ int dangx_moments_begin(dangx_ctx* ctx, const int32_t* sel) {
                 const long long phase = (long long)((reinterpret_cast<uintptr_t>(seg_plane(ctx, s)) >> 3) & 1);
                 if ((off & 1) != phase) ++off;
                 s.off = off;
+                s.id = (int)m->segs.size();
                 off += ctx->dims.npix;
                 m->segs.push_back(s);
             }
@@ -652,7 +669,7 @@ int dangx_moments_begin(dangx_ctx* ctx, const int32_t* sel) {
 }
 
 int dangx_moments_pairs(dangx_ctx* ctx, int lag1, int npairs, const int32_t* pairs) {
-    if (!ctx || need(ctx)) return 1;
+    if (!ctx || need_live(ctx, "dangx_moments_pairs")) return 1;
     DxMoments* m = ctx->mom;
     if (m->count != 0)
         return fail(ctx, "posterior moments: dangx_moments_pairs is legal only before the first dangx_moments_accumulate after dangx_moments_begin");
@@ -672,6 +689,7 @@ int dangx_moments_pairs(dangx_ctx* ctx, int lag1, int npairs, const int32_t* pai
         if (pr.a < 0 || pr.b < 0) return fail(ctx, "posterior moments: dangx_moments_pairs: pair " + std::to_string(p) + ": a plane that is not selected");
         if ((off & 1) != (m->segs[pr.a].off & 1)) ++off;
         pr.off = off;
+        pr.id = p;
         off += ctx->dims.npix;
         np.push_back(pr);
     }
@@ -703,7 +721,7 @@ int dangx_moments_pairs(dangx_ctx* ctx, int lag1, int npairs, const int32_t* pai
 }
 
 int dangx_moments_accumulate(dangx_ctx* ctx) {
-    if (!ctx || need(ctx)) return 1;
+    if (!ctx || need_live(ctx, "dangx_moments_accumulate")) return 1;
     DxMoments* m = ctx->mom;
     for (int l = 0; l < ctx->dims.ncomp; ++l)
         if (m->sel[l] && (!ctx->comp_set[l] || ctx->desc[l].type != m->type[l] || ctx->desc[l].nindices != m->nind[l]))
@@ -889,7 +907,7 @@ int dangx_moments_get_template(dangx_ctx* ctx, int comp, int stat, int ddof, dou
 }
 
 static int get_pair_impl(dangx_ctx* ctx, int pair, int stat, int ddof, double* out, bool to_host) {
-    if (!ctx || !out || need(ctx)) return 1;
+    if (!ctx || !out || need_live(ctx, "dangx_moments_get_pair")) return 1;
     const DxMoments* m = ctx->mom;
     if (pair < 0 || pair >= (int)m->pairs.size())
         return fail(ctx, "posterior moments: pair index out of range (" + std::to_string(m->pairs.size()) + " pairs registered)");
@@ -916,7 +934,7 @@ int dangx_moments_get_pair(dangx_ctx* ctx, int pair, int stat, int ddof, double*
 }
 
 int dangx_moments_hist(dangx_ctx* ctx, int nreg, const int32_t* planes, const double* range, int nbins, int bits) {
-    if (!ctx || need(ctx)) return 1;
+    if (!ctx || need_live(ctx, "dangx_moments_hist")) return 1;
     DxMoments* m = ctx->mom;
     if (m->count != 0)
         return fail(ctx, "posterior moments: dangx_moments_hist is legal only before the first dangx_moments_accumulate after dangx_moments_begin");
@@ -950,7 +968,7 @@ int dangx_moments_hist(dangx_ctx* ctx, int nreg, const int32_t* planes, const do
     for (int r = 0; r < nreg; ++r) {
         const int seg = m->find_seg(planes[3 * r], planes[3 * r + 1], planes[3 * r + 2]);
         if (seg < 0) return fail(ctx, "posterior moments: dangx_moments_hist: registration " + std::to_string(r) + ": a plane that is not selected");
-        nh.push_back(DxMoments::Hist{seg, rg[2 * r], rg[2 * r + 1], off});
+        nh.push_back(DxMoments::Hist{seg, rg[2 * r], rg[2 * r + 1], off, r});
         off += (np * words + 63) / 64 * 64;
     }
     (void)hipSetDevice(ctx->device);
@@ -973,7 +991,7 @@ int dangx_moments_hist(dangx_ctx* ctx, int nreg, const int32_t* planes, const do
 
 // the raw records: a copy on the stream, which the host form waits for
 static int hist_get_impl(dangx_ctx* ctx, int reg, void* counts, bool to_host) {
-    if (!ctx || !counts || hist_reg(ctx, reg)) return 1;
+    if (!ctx || !counts || need_live(ctx, "dangx_moments_hist_get") || hist_reg(ctx, reg)) return 1;
     const DxMoments* m = ctx->mom;
     (void)hipSetDevice(ctx->device);
     const size_t bytes = sizeof(uint32_t) * (size_t)ctx->dims.npix * dx_hist_words(m->hbins, m->hbits);
@@ -987,7 +1005,7 @@ int dangx_moments_hist_get_dev(dangx_ctx* ctx, int reg, void* counts_dev) { retu
 int dangx_moments_hist_get(dangx_ctx* ctx, int reg, void* counts) { return hist_get_impl(ctx, reg, counts, true); }
 
 static int hist_stat_impl(dangx_ctx* ctx, int reg, int stat, int nq, const double* q, double* out, bool to_host) {
-    if (!ctx || !out || dx_hist_stat_check(ctx, reg, stat, nq, q)) return 1;
+    if (!ctx || !out || need_live(ctx, "dangx_moments_hist_stat") || dx_hist_stat_check(ctx, reg, stat, nq, q)) return 1;
     const DxMoments* m = ctx->mom;
     (void)hipSetDevice(ctx->device);
     const long long total = (long long)ctx->dims.npix * (stat == 0 ? nq : 1);
@@ -1013,7 +1031,7 @@ int dangx_moments_hist_stat(dangx_ctx* ctx, int reg, int stat, int nq, const dou
 }
 
 int dangx_moments_signals(dangx_ctx* ctx, int nsig, const int32_t* spec) {
-    if (!ctx || need(ctx)) return 1;
+    if (!ctx || need_live(ctx, "dangx_moments_signals")) return 1;
     DxMoments* m = ctx->mom;
     if (m->count != 0)
         return fail(ctx, "posterior moments: dangx_moments_signals is legal only before the first dangx_moments_accumulate after dangx_moments_begin");
@@ -1040,6 +1058,7 @@ int dangx_moments_signals(dangx_ctx* ctx, int nsig, const int32_t* spec) {
         const long long phase = (long long)((reinterpret_cast<uintptr_t>(plane) >> 3) & 1);
         if ((off & 1) != phase) ++off;
         sg.off = off;
+        sg.id = s;
         off += ctx->dims.npix;
         ns.push_back(sg);
     }
@@ -1087,7 +1106,7 @@ int dangx_moments_get_signal(dangx_ctx* ctx, int sig, int stat, int ddof, double
 }
 
 int dangx_moments_batches(dangx_ctx* ctx, int nreg, const int32_t* planes, int nbatch, int64_t batch_len) {
-    if (!ctx || need(ctx)) return 1;
+    if (!ctx || need_live(ctx, "dangx_moments_batches")) return 1;
     DxMoments* m = ctx->mom;
     if (m->count != 0)
         return fail(ctx, "posterior moments: dangx_moments_batches is legal only before the first dangx_moments_accumulate after dangx_moments_begin");
@@ -1106,7 +1125,7 @@ int dangx_moments_batches(dangx_ctx* ctx, int nreg, const int32_t* planes, int n
         const int seg = m->find_seg(planes[3 * r], planes[3 * r + 1], planes[3 * r + 2]);
         if (seg < 0) return fail(ctx, "posterior moments: dangx_moments_batches: registration " + std::to_string(r) + ": a plane that is not selected");
         if ((off & 1) != (m->segs[seg].off & 1)) ++off;
-        nb.push_back(DxMoments::Batch{seg, off});
+        nb.push_back(DxMoments::Batch{seg, off, r});
         off += 2LL * nbatch * pitch;
     }
     (void)hipSetDevice(ctx->device);
@@ -1149,7 +1168,7 @@ int dangx_moments_batches_info(dangx_ctx* ctx, int64_t* batch_len, int32_t* nful
 }
 
 static int batches_get_impl(dangx_ctx* ctx, int reg, int stat, int first, int ddof, double* out, bool to_host) {
-    if (!ctx || !out || batches_need(ctx, reg)) return 1;
+    if (!ctx || !out || need_live(ctx, "dangx_moments_batches_get") || batches_need(ctx, reg)) return 1;
     const DxMoments* m = ctx->mom;
     if (count_check(ctx, nullptr, 0)) return 1;
     const DxBatchPos p = dx_batches_pos(m->count, m->batch_len);
@@ -1177,7 +1196,7 @@ int dangx_moments_batches_get(dangx_ctx* ctx, int reg, int stat, int first, int 
 
 // one slot's two planes as they are: copies on the stream, which the host form waits for
 static int batches_raw_impl(dangx_ctx* ctx, int reg, int batch, double* mean_out, double* m2_out, bool to_host) {
-    if (!ctx || batches_need(ctx, reg)) return 1;
+    if (!ctx || need_live(ctx, "dangx_moments_batches_raw") || batches_need(ctx, reg)) return 1;
     const DxMoments* m = ctx->mom;
     if (batch < 0 || batch >= m->nbatch)
         return fail(ctx, "posterior moments: dangx_moments_batches_raw: batch out of range (nbatch = " + std::to_string(m->nbatch) + ")");
@@ -1197,6 +1216,291 @@ int dangx_moments_batches_raw_dev(dangx_ctx* ctx, int reg, int batch, double* me
 
 int dangx_moments_batches_raw(dangx_ctx* ctx, int reg, int batch, double* mean_out, double* m2_out) {
     return batches_raw_impl(ctx, reg, batch, mean_out, m2_out, true);
+}
+
+}  // extern "C"
+
+// ---- sections: one part of the accumulator state in its packed layout (dx_section_host.h), read or written by copies on the
+// context's stream, and holders (dangx_moments_begin_like), which keep sections put into them for dangx_chains_*
+
+static DxSecReg section_reg(const dangx_ctx* ctx, const DxMoments* m) {
+    DxSecReg r;
+    r.npix = ctx->dims.npix; r.pix0 = ctx->dims.pix0; r.nmaps = ctx->dims.nmaps;
+    for (int l = 0; l < ctx->dims.ncomp; ++l) { r.sel.push_back(m->sel[l]); r.type.push_back(m->type[l]); r.nind.push_back(m->nind[l]); }
+    r.lag1 = m->lag1 ? 1 : 0;
+    auto plane = [&](std::vector<int32_t>& v, int seg) { const auto& s = m->segs[seg]; v.push_back(s.comp); v.push_back(s.what); v.push_back(s.plane); };
+    for (const auto& p : m->pairs) { plane(r.pairs, p.a); plane(r.pairs, p.b); }
+    for (const auto& h : m->hists) { plane(r.hist_planes, h.seg); r.hist_range.push_back(h.lo); r.hist_range.push_back(h.hi); }
+    r.nbins = m->hbins; r.bits = m->hbits;
+    for (const auto& s : m->sigs) { r.signals.push_back(s.comp); r.signals.push_back(s.band); r.signals.push_back(s.kind); }
+    for (const auto& b : m->batches) plane(r.batch_planes, b.seg);
+    r.nbatch = m->nbatch;
+    return r;
+}
+
+namespace {
+
+struct SecRun { void* dev; void* host; long long off, bytes; };   // a run of the payload at `off`: in HBM (dev) or a host row of the state
+
+struct SecShape {          // a section of this context's registration
+    long long bytes = 0;   // the payload
+    int nsel = 0;          // PLANES: selected planes
+    unsigned planes = 0;
+    bool global = false;   // PLANES: the host rows of a template / monopole / hi_fit member
+};
+
+std::string section_name(int family, int a, int b) {
+    std::string s = dx_section_family_name(family);
+    if (family == DX_SEC_PLANES) s += "(" + std::to_string(a) + ", " + std::to_string(b) + ")";
+    else if (family != DX_SEC_HEAD) s += "(" + std::to_string(a) + ")";
+    return s;
+}
+
+int section_shape(dangx_ctx* ctx, const char* who, int family, int a, int b, SecShape& sh) {
+    if (need(ctx)) return 1;
+    const DxMoments* m = ctx->mom;
+    const long long np = ctx->dims.npix;
+    auto range = [&](size_t n, const char* noun) {
+        if (a >= 0 && a < (int)n) return 0;
+        return fail(ctx, std::string("posterior moments: ") + who + ": " + noun + " out of range (" + std::to_string(n) + " registered)");
+    };
+    switch (family) {
+    case DX_SEC_HEAD: sh.bytes = DX_SEC_HEAD_BYTES; return 0;
+    case DX_SEC_PLANES: {
+        if (a < 0 || a >= ctx->dims.ncomp) return fail(ctx, std::string("posterior moments: ") + who + ": component index out of range");
+        if (b < 0 || b > DANGX_MAX_IND) return fail(ctx, std::string("posterior moments: ") + who + ": what must be 0 (amplitude) or 1 + index number");
+        sh.planes = (unsigned)(m->sel[a] >> (b == 0 ? 0 : 3 + 3 * (b - 1))) & 7u;
+        sh.nsel = __builtin_popcount(sh.planes);
+        if (!sh.nsel) return fail(ctx, std::string("posterior moments: ") + who + ": nothing selected for this component and what");
+        sh.global = b == 0 && is_global_type(m->type[a]);
+        sh.bytes = dx_section_planes_bytes(sh.global ? ctx->dims.nbands : np, sh.nsel, m->lag1);
+        return 0;
+    }
+    case DX_SEC_PAIR: if (range(m->pairs.size(), "pair index")) return 1; sh.bytes = dx_section_pair_bytes(np); return 0;
+    case DX_SEC_HIST: if (range(m->hists.size(), "histogram registration")) return 1; sh.bytes = dx_section_hist_bytes(np, m->hbins, m->hbits); return 0;
+    case DX_SEC_SIGNAL: if (range(m->sigs.size(), "signal index")) return 1; sh.bytes = dx_section_signal_bytes(np); return 0;
+    case DX_SEC_BATCHES: if (range(m->batches.size(), "batch registration")) return 1; sh.bytes = dx_section_batches_bytes(np, m->nbatch); return 0;
+    }
+    return fail(ctx, std::string("posterior moments: ") + who + ": family must be 0 (HEAD) .. 5 (BATCHES)");
+}
+
+// a holder's buffer for a section of `bytes` payload bytes, and its planes entered into the tables
+int holder_take(dangx_ctx* ctx, int family, int a, int b, const SecShape& sh, long long bytes) {
+    DxMoments* m = ctx->mom;
+    // batches at the pitch of a live context (the kernels over several chains take ONE pitch, chain 0's), everything else packed
+    const size_t want = (size_t)dx_section_round256(family == DX_SEC_BATCHES ? 16LL * m->nbatch * m->bpitch : bytes);
+    DxMoments::Held* h = nullptr;
+    for (auto& x : m->held)
+        if (x.family == family && x.a == a && x.b == b) h = &x;
+    if (!h || h->bytes != want) {
+        DevBuf<unsigned char> nb;
+        DevStatus st;
+        nb.alloc(want, st);
+        if (!st.ok()) return st.fail(ctx, "dangx_moments_section_put: ");
+        if (h) {
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // nothing may still read the buffer that goes
+            h->buf = std::move(nb);
+            h->bytes = want;
+        } else {
+            m->held.push_back(DxMoments::Held{family, a, b, std::move(nb), want});
+            h = &m->held.back();
+        }
+    }
+    const long long np = ctx->dims.npix;
+    double* base = reinterpret_cast<double*>(h->buf.p);
+    switch (family) {
+    case DX_SEC_PLANES: {
+        const bool lag = bytes == dx_section_planes_bytes(np, sh.nsel, 1);
+        int r = 0;
+        for (int k = 0; k < ctx->dims.nmaps; ++k) {
+            if (!((sh.planes >> k) & 1u)) continue;
+            DxMoments::HeldSeg& t = m->h_seg[m->find_seg(a, b, k)];
+            t.mean = base + (long long)r * np;
+            t.m2 = base + (long long)(sh.nsel + r) * np;
+            t.prev = lag ? base + (long long)(2 * sh.nsel + r) * np : nullptr;
+            t.first = lag ? base + (long long)(3 * sh.nsel + r) * np : nullptr;
+            t.P = lag ? base + (long long)(4 * sh.nsel + r) * np : nullptr;
+            ++r;
+        }
+        break;
+    }
+    case DX_SEC_PAIR: m->h_pair[a] = base; break;
+    case DX_SEC_HIST: m->h_hist[a] = reinterpret_cast<uint32_t*>(h->buf.p); break;
+    case DX_SEC_SIGNAL: m->h_sig[a].mean = base; m->h_sig[a].m2 = base + np; break;
+    case DX_SEC_BATCHES: m->h_batch[a] = base; break;
+    }
+    return 0;
+}
+
+// the runs of a section's payload where the context keeps them; nparts: the parts of a PLANES payload that travel
+int section_runs(dangx_ctx* ctx, const char* who, int family, int a, int b, const SecShape& sh, int nparts, bool put, std::vector<SecRun>& runs) {
+    DxMoments* m = ctx->mom;
+    const long long np = ctx->dims.npix, plane = 8 * np;
+    auto add = [&](void* dev, long long off, long long bytes) { runs.push_back(SecRun{dev, nullptr, off, bytes}); };
+    switch (family) {
+    case DX_SEC_PLANES: {
+        int r = 0;
+        for (int k = 0; k < ctx->dims.nmaps; ++k) {
+            if (!((sh.planes >> k) & 1u)) continue;
+            if (sh.global) {
+                double* rows[5] = {m->tm_mean[a][k], m->tm_m2[a][k], m->tm_prev[a][k], m->tm_first[a][k], m->tm_P[a][k]};
+                const long long row = 8LL * ctx->dims.nbands;
+                for (int p = 0; p < nparts; ++p) runs.push_back(SecRun{nullptr, rows[p], ((long long)p * sh.nsel + r) * row, row});
+            } else {
+                const auto& s = m->segs[m->find_seg(a, b, k)];
+                double* part[5] = {m->mean(s), m->m2(s), nparts > 2 ? m->prev(s) : nullptr, nparts > 2 ? m->first(s) : nullptr, nparts > 2 ? m->P(s) : nullptr};
+                for (int p = 0; p < nparts; ++p) add(part[p], ((long long)p * sh.nsel + r) * plane, plane);
+            }
+            ++r;
+        }
+        break;
+    }
+    case DX_SEC_PAIR: add(m->C(m->pairs[a]), 0, plane); break;
+    case DX_SEC_HIST: add(m->records(m->hists[a]), 0, sh.bytes); break;
+    case DX_SEC_SIGNAL: add(m->mean(m->sigs[a]), 0, plane); add(m->m2(m->sigs[a]), plane, plane); break;
+    case DX_SEC_BATCHES:
+        for (int t = 0; t < m->nbatch; ++t) {
+            add(m->bmean(m->batches[a], t), 2LL * t * plane, plane);
+            add(m->bm2(m->batches[a], t), (2LL * t + 1) * plane, plane);
+        }
+        break;
+    }
+    bool missing = !put && m->holder && family == DX_SEC_PLANES && sh.global && !m->h_rows[a];
+    for (const SecRun& r : runs) missing = missing || (!r.dev && !r.host);
+    if (missing)
+            return fail(ctx, std::string("posterior moments: ") + who + ": section " + section_name(family, a, b) + " was not put into this holder");
+    return 0;
+}
+
+int section_head_own(dangx_ctx* ctx, DxSecHead& h) {
+    const DxMoments* m = ctx->mom;
+    h = dx_section_head(section_reg(ctx, m), m->count, m->batch_len);
+    return 0;
+}
+
+int section_move(dangx_ctx* ctx, const char* who, int family, int a, int b, void* user, long long bytes, bool put, bool user_dev) {
+    if (!ctx || !user) return 1;
+    SecShape sh;
+    if (section_shape(ctx, who, family, a, b, sh)) return 1;
+    DxMoments* m = ctx->mom;
+    const std::string name = section_name(family, a, b);
+    int nparts = (int)dx_section_planes_parts(m->lag1);
+    // a holder takes the first two parts (mean, m2) of a PLANES section alone: what R-hat and the pooled moments need
+    const bool short_put = put && m->holder && family == DX_SEC_PLANES && !sh.global && m->lag1 && bytes == dx_section_planes_bytes(ctx->dims.npix, sh.nsel, 0);
+    if (short_put) nparts = 2;
+    else if (bytes != sh.bytes)
+        return fail(ctx, std::string("posterior moments: ") + who + ": section " + name + " is " + std::to_string(sh.bytes) + " bytes, not " + std::to_string(bytes));
+    if (family == DX_SEC_HEAD) {
+        if (user_dev) return fail(ctx, std::string("posterior moments: ") + who + ": HEAD is a host section (use the host form)");
+        DxSecHead own;
+        section_head_own(ctx, own);
+        if (!put) {
+            if (m->holder && !m->head_put) return fail(ctx, std::string("posterior moments: ") + who + ": section HEAD was not put into this holder");
+            dx_section_head_pack(own, static_cast<unsigned char*>(user));
+            return 0;
+        }
+        DxSecHead got;
+        std::string why = dx_section_head_unpack(static_cast<const unsigned char*>(user), (size_t)bytes, got);
+        if (why.empty()) {
+            why = dx_section_head_diff(got, own);
+            if (!why.empty()) why = "HEAD does not fit this context's registration: " + why;
+        }
+        if (why.empty() && !m->hists.empty() && got.count > 0) why = dx_hist_limit_check(got.count, m->hbits);
+        if (!why.empty()) return fail(ctx, std::string("posterior moments: ") + who + ": " + why);
+        m->count = got.count;
+        if (!m->batches.empty()) m->batch_len = got.batch_len;
+        if (m->holder) m->head_put = true;
+        return 0;
+    }
+    (void)hipSetDevice(ctx->device);
+    if (put && m->holder && !sh.global && holder_take(ctx, family, a, b, sh, bytes)) return 1;
+    std::vector<SecRun> runs;
+    if (section_runs(ctx, who, family, a, b, sh, nparts, put, runs)) return 1;
+    char* u = static_cast<char*>(user);
+    bool wait = !user_dev;
+    for (const SecRun& r : runs) {
+        if (r.host && !user_dev) {   // host rows and a host array: no device involved
+            if (put) std::memcpy(r.host, u + r.off, (size_t)r.bytes);
+            else std::memcpy(u + r.off, r.host, (size_t)r.bytes);
+            continue;
+        }
+        void* mine = r.host ? r.host : r.dev;
+        const hipMemcpyKind kind = r.host ? (put ? hipMemcpyDeviceToHost : hipMemcpyHostToDevice)
+                                          : user_dev ? hipMemcpyDeviceToDevice : put ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
+        if (put) HIPCHK(ctx, hipMemcpyAsync(mine, u + r.off, (size_t)r.bytes, kind, ctx->stream));
+        else HIPCHK(ctx, hipMemcpyAsync(u + r.off, mine, (size_t)r.bytes, kind, ctx->stream));
+        wait = wait || r.host;   // the host rows are the state itself: the copy is over when the call returns
+    }
+    if (wait) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (put && m->holder && sh.global) m->h_rows[a] = true;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dangx_moments_section_bytes(dangx_ctx* ctx, int family, int a, int b, int64_t* bytes) {
+    if (!ctx || !bytes) return 1;
+    SecShape sh;
+    if (section_shape(ctx, "dangx_moments_section_bytes", family, a, b, sh)) return 1;
+    *bytes = sh.bytes;
+    return 0;
+}
+
+int dangx_moments_section_get(dangx_ctx* ctx, int family, int a, int b, void* out, int64_t bytes) {
+    return section_move(ctx, "dangx_moments_section_get", family, a, b, out, bytes, false, false);
+}
+
+int dangx_moments_section_get_dev(dangx_ctx* ctx, int family, int a, int b, void* out_dev, int64_t bytes) {
+    return section_move(ctx, "dangx_moments_section_get_dev", family, a, b, out_dev, bytes, false, true);
+}
+
+int dangx_moments_section_put(dangx_ctx* ctx, int family, int a, int b, const void* in, int64_t bytes) {
+    return section_move(ctx, "dangx_moments_section_put", family, a, b, const_cast<void*>(in), bytes, true, false);
+}
+
+int dangx_moments_section_put_dev(dangx_ctx* ctx, int family, int a, int b, const void* in_dev, int64_t bytes) {
+    return section_move(ctx, "dangx_moments_section_put_dev", family, a, b, const_cast<void*>(in_dev), bytes, true, true);
+}
+
+int dangx_moments_begin_like(dangx_ctx* ctx, dangx_ctx* like) {
+    if (!ctx || !like) return 1;
+    if (ctx == like) return fail(ctx, "posterior moments: dangx_moments_begin_like: a context cannot be a holder like itself");
+    if (!like->mom) return fail(ctx, "posterior moments: dangx_moments_begin_like: dangx_moments_begin was not called on the other context");
+    const DxMoments* o = like->mom;
+    if (ctx->dims.npix != like->dims.npix || ctx->dims.pix0 != like->dims.pix0 || ctx->dims.nmaps != like->dims.nmaps ||
+        ctx->dims.ncomp != like->dims.ncomp || ctx->dims.nbands != like->dims.nbands)
+        return fail(ctx, "posterior moments: dangx_moments_begin_like: the contexts differ in npix / pix0 / nmaps / ncomp / nbands");
+    for (int l = 0; l < ctx->dims.ncomp; ++l)
+        if ((o->sel[l] || o->sig_used[l]) && (!ctx->comp_set[l] || ctx->desc[l].type != like->desc[l].type || ctx->desc[l].nindices != like->desc[l].nindices))
+            return fail(ctx, "posterior moments: dangx_moments_begin_like: component " + std::to_string(l) + " is not the other context's");
+    (void)hipSetDevice(ctx->device);
+    if (ctx->mom) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // no launch may still read what is dropped
+    std::unique_ptr<DxMoments> m(new DxMoments());
+    m->holder = true;
+    std::memcpy(m->sel, o->sel, sizeof m->sel); std::memcpy(m->type, o->type, sizeof m->type); std::memcpy(m->nind, o->nind, sizeof m->nind);
+    m->segs = o->segs; m->grid_target = o->grid_target;
+    m->lag1 = o->lag1; m->pairs = o->pairs;
+    m->hists = o->hists; m->hbins = o->hbins; m->hbits = o->hbits;
+    m->sigs = o->sigs; m->sig_plan = o->sig_plan;
+    std::memcpy(m->sig_type, o->sig_type, sizeof m->sig_type); std::memcpy(m->sig_nind, o->sig_nind, sizeof m->sig_nind);
+    std::memcpy(m->sig_used, o->sig_used, sizeof m->sig_used);
+    m->batches = o->batches; m->nbatch = o->nbatch; m->batch_len = o->batch_len; m->bpitch = o->bpitch;
+    m->h_seg.resize(m->segs.size()); m->h_pair.assign(m->pairs.size(), nullptr); m->h_hist.assign(m->hists.size(), nullptr);
+    m->h_sig.resize(m->sigs.size()); m->h_batch.assign(m->batches.size(), nullptr);
+    dx_moments_free(ctx);   // whatever the context held or accumulated goes
+    ctx->mom = m.release();
+    return 0;
+}
+
+int dangx_moments_held_bytes(dangx_ctx* ctx, int64_t* bytes) {
+    if (!ctx || !bytes || need(ctx)) return 1;
+    const DxMoments* m = ctx->mom;
+    long long total = 0;
+    for (const auto& h : m->held) total += (long long)h.bytes;
+    *bytes = total;   // a live context holds nothing: its accumulators are its own
+    return 0;
 }
 
 int dangx_moments_end(dangx_ctx* ctx) {

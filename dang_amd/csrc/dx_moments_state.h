@@ -104,7 +104,7 @@ struct DevBuf {
 struct DxMoments {
     int32_t sel[MAXC] = {};          // effective selection (bits as in include/dangx.h)
     int type[MAXC] = {}, nind[MAXC] = {};  // shape key recorded at begin
-    struct Seg { int comp, what, plane; long long off; };
+    struct Seg { int comp, what, plane; long long off; int id = 0; };   // id: its index in segs
     std::vector<Seg> segs;
     std::vector<MomSeg> table;       // the table as last uploaded
     DevBuf<MomSeg> d_table;
@@ -119,19 +119,19 @@ struct DxMoments {
     bool lag1 = false;
     DevBuf<double> lag;              // [prev | first | P], acc_half doubles each, planes at the offsets of acc
     DevBuf<LagSeg> d_lag;
-    struct Pair { int a, b; long long off; };   // indices into segs; off: the pair's plane in pc (at the phase of a's mean)
+    struct Pair { int a, b; long long off; int id = 0; };   // indices into segs; off: the pair's plane in pc (at the phase of a's mean); id: its index in pairs
     std::vector<Pair> pairs;
     DevBuf<double> pc;
     DevBuf<PairSeg> d_pairs;
     double tm_prev[MAXC][3][MAXB] = {}, tm_first[MAXC][3][MAXB] = {}, tm_P[MAXC][3][MAXB] = {};
     // dangx_moments_hist
-    struct Hist { int seg; double lo, hi; long long off; };   // seg: index into segs; off: the records' first word in hrec
+    struct Hist { int seg; double lo, hi; long long off; int id = 0; };   // seg: index into segs; off: the records' first word in hrec; id: its index in hists
     std::vector<Hist> hists;
     int hbins = 0, hbits = 0;
     DevBuf<uint32_t> hrec;           // every registration's records, each block at a multiple of 256 bytes
     DevBuf<HistSeg> d_hist;
     // dangx_moments_signals
-    struct Sig { int comp, band, kind; long long off; };   // off: the signal's mean plane in sacc
+    struct Sig { int comp, band, kind; long long off; int id = 0; };   // off: the signal's mean plane in sacc; id: its index in sigs
     std::vector<Sig> sigs;
     std::vector<DxSigSeg> sig_plan;
     int sig_type[MAXC] = {}, sig_nind[MAXC] = {};   // shape key of the registered components at registration
@@ -142,7 +142,7 @@ struct DxMoments {
     long long sacc_half = 0;
     // dangx_moments_batches: [reg][batch][mean | m2][bpitch] in bacc, every plane at the 16-byte phase of its segment's main
     // accumulator (bpitch is even, so a registration's planes share the phase of its first)
-    struct Batch { int seg; long long off; };   // seg: index into segs; off: batch 0's mean plane in bacc
+    struct Batch { int seg; long long off; int id = 0; };   // seg: index into segs; off: batch 0's mean plane in bacc; id: its index in batches
     std::vector<Batch> batches;
     int nbatch = 0;
     long long batch_len = 0;         // the current L
@@ -157,18 +157,35 @@ struct DxMoments {
     DxMoments& operator=(const DxMoments&) = delete;
     ~DxMoments() { if (chain_ev) (void)hipEventDestroy(chain_ev); }
 
+    // dangx_moments_begin_like: a HOLDER has the registrations of another context and none of the allocations above.  Every section
+    // (dx_section_host.h) put into it lives in a buffer of its own, allocated at its first put and packed as the section's payload
+    // is; the tables below say where each plane of it lies (null: that section was not put).  Batches keep the pitch bpitch of a
+    // live context, which the kernels over several chains take from chain 0.
+    bool holder = false;
+    bool head_put = false;            // a holder's count and batch bookkeeping were put
+    struct Held { int family, a, b; DevBuf<unsigned char> buf; size_t bytes; };   // bytes: as allocated (a multiple of 256)
+    std::vector<Held> held;
+    struct HeldSeg { double *mean = nullptr, *m2 = nullptr, *prev = nullptr, *first = nullptr, *P = nullptr; };
+    std::vector<HeldSeg> h_seg;       // by Seg::id
+    std::vector<double*> h_pair;      // by Pair::id
+    std::vector<uint32_t*> h_hist;    // by Hist::id
+    std::vector<HeldSeg> h_sig;       // by Sig::id (mean, m2)
+    std::vector<double*> h_batch;     // by Batch::id: batch 0's mean plane
+    bool h_rows[MAXC] = {};           // the host rows tm_* of a template / monopole / hi_fit member were put
+
     // where things are
-    double* mean(const Seg& s) const { return acc + s.off; }
-    double* m2(const Seg& s) const { return acc + acc_half + s.off; }
-    double* prev(const Seg& s) const { return lag + s.off; }
-    double* first(const Seg& s) const { return lag + acc_half + s.off; }
-    double* P(const Seg& s) const { return lag + 2 * acc_half + s.off; }
-    double* C(const Pair& p) const { return pc + p.off; }
-    double* mean(const Sig& s) const { return sacc + s.off; }
-    double* m2(const Sig& s) const { return sacc + sacc_half + s.off; }
-    uint32_t* records(const Hist& h) const { return hrec + h.off; }
-    double* bmean(const Batch& r, int b) const { return bacc + r.off + 2LL * b * bpitch; }
-    double* bm2(const Batch& r, int b) const { return bmean(r, b) + bpitch; }
+    double* mean(const Seg& s) const { return holder ? h_seg[s.id].mean : acc + s.off; }
+    double* m2(const Seg& s) const { return holder ? h_seg[s.id].m2 : acc + acc_half + s.off; }
+    double* prev(const Seg& s) const { return holder ? h_seg[s.id].prev : lag + s.off; }
+    double* first(const Seg& s) const { return holder ? h_seg[s.id].first : lag + acc_half + s.off; }
+    double* P(const Seg& s) const { return holder ? h_seg[s.id].P : lag + 2 * acc_half + s.off; }
+    double* C(const Pair& p) const { return holder ? h_pair[p.id] : pc + p.off; }
+    double* mean(const Sig& s) const { return holder ? h_sig[s.id].mean : sacc + s.off; }
+    double* m2(const Sig& s) const { return holder ? h_sig[s.id].m2 : sacc + sacc_half + s.off; }
+    uint32_t* records(const Hist& h) const { return holder ? h_hist[h.id] : hrec + h.off; }
+    double* bbase(const Batch& r) const { return holder ? h_batch[r.id] : bacc + r.off; }
+    double* bmean(const Batch& r, int b) const { double* p = bbase(r); return p ? p + 2LL * b * bpitch : nullptr; }
+    double* bm2(const Batch& r, int b) const { double* p = bbase(r); return p ? p + (2LL * b + 1) * bpitch : nullptr; }
     int find_seg(int comp, int what, int plane) const {   // index into segs, -1: not selected
         for (size_t i = 0; i < segs.size(); ++i)
             if (segs[i].comp == comp && segs[i].what == what && segs[i].plane == plane) return (int)i;

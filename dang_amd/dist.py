@@ -126,6 +126,24 @@ def allreduce_sum_(t):
     return t
 
 
+def gather_equal(send, group=None, dst=0):
+    """Gather one equal-shape tensor per rank of `group` (api.dist_chains: the rows of a section's bytes, padded by the caller as
+    gather_maps pads its shards): the list of every rank's tensor on rank `dst` of the group and None elsewhere; dst=None: on
+    every rank.  Device tensors under nccl, host tensors under gloo."""
+    n = td.get_world_size(group)
+    if send.is_cuda and td.get_backend(group) != "nccl":
+        send = send.cpu()
+    send = send.contiguous()
+    if dst is None:
+        parts = [torch.empty_like(send) for _ in range(n)]
+        td.all_gather(parts, send, group=group)
+        return parts
+    here = td.get_rank(group) == int(dst)
+    parts = [torch.empty_like(send) for _ in range(n)] if here else None
+    td.gather(send, parts, dst=int(dst) if group is None else td.get_global_rank(group, int(dst)), group=group)
+    return parts
+
+
 def gather_maps(local, npix_global, dst=0, bounds=None):
     """Gather pixel-sharded maps [..., npix_local] to `dst` as [..., npix_global] (map output; what the reference's write_maps
     consumes, src/dang_data_mod.f90:573-664).  `bounds`: the shard boundaries b[0..nranks] the sky was split by (shard_range's

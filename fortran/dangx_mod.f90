@@ -653,6 +653,50 @@ module dangx_mod
        type(c_ptr), value :: ctx, mean_out_dev, m2_out_dev
        integer(c_int), value :: reg, batch
      end function
+     ! sections of the accumulator state in their packed layout (include/dangx.h): family 0 = HEAD (host forms only), 1 = PLANES
+     ! (a = comp, b = what), 2 = PAIR, 3 = HIST, 4 = SIGNAL, 5 = BATCHES (a = index, b ignored); bytes as _section_bytes gives them
+     integer(c_int) function dangx_moments_section_bytes(ctx, family, a, b, bytes) bind(C, name='dangx_moments_section_bytes')
+       import :: c_int, c_ptr, c_int64_t
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: family, a, b
+       integer(c_int64_t), intent(out) :: bytes
+     end function
+     integer(c_int) function dangx_moments_section_get(ctx, family, a, b, out, bytes) bind(C, name='dangx_moments_section_get')
+       import :: c_int, c_ptr, c_int64_t
+       type(c_ptr), value :: ctx, out
+       integer(c_int), value :: family, a, b
+       integer(c_int64_t), value :: bytes
+     end function
+     integer(c_int) function dangx_moments_section_get_dev(ctx, family, a, b, out_dev, bytes) &
+          bind(C, name='dangx_moments_section_get_dev')
+       import :: c_int, c_ptr, c_int64_t
+       type(c_ptr), value :: ctx, out_dev
+       integer(c_int), value :: family, a, b
+       integer(c_int64_t), value :: bytes
+     end function
+     integer(c_int) function dangx_moments_section_put(ctx, family, a, b, src, bytes) bind(C, name='dangx_moments_section_put')
+       import :: c_int, c_ptr, c_int64_t
+       type(c_ptr), value :: ctx, src
+       integer(c_int), value :: family, a, b
+       integer(c_int64_t), value :: bytes
+     end function
+     integer(c_int) function dangx_moments_section_put_dev(ctx, family, a, b, src_dev, bytes) &
+          bind(C, name='dangx_moments_section_put_dev')
+       import :: c_int, c_ptr, c_int64_t
+       type(c_ptr), value :: ctx, src_dev
+       integer(c_int), value :: family, a, b
+       integer(c_int64_t), value :: bytes
+     end function
+     ! ctx becomes a holder with the registrations of `like` and no accumulators; _held_bytes: the device bytes put into it
+     integer(c_int) function dangx_moments_begin_like(ctx, like) bind(C, name='dangx_moments_begin_like')
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx, like
+     end function
+     integer(c_int) function dangx_moments_held_bytes(ctx, bytes) bind(C, name='dangx_moments_held_bytes')
+       import :: c_int, c_ptr, c_int64_t
+       type(c_ptr), value :: ctx
+       integer(c_int64_t), intent(out) :: bytes
+     end function
      integer(c_int) function dangx_moments_end(ctx) bind(C, name='dangx_moments_end')
        import :: c_int, c_ptr
        type(c_ptr), value :: ctx

@@ -626,6 +626,46 @@ int dangx_moments_batches_get(dangx_ctx *ctx, int reg, int stat, int first, int 
 int dangx_moments_batches_get_dev(dangx_ctx *ctx, int reg, int stat, int first, int ddof, double *out_dev);
 int dangx_moments_batches_raw(dangx_ctx *ctx, int reg, int batch, double *mean_out, double *m2_out);
 int dangx_moments_batches_raw_dev(dangx_ctx *ctx, int reg, int batch, double *mean_out_dev, double *m2_out_dev);
+/* Sections: one part of a context's accumulator state, read or written in a packed little-endian layout that does not depend on
+ * where the context keeps it -- what saving and restoring a run, and handing a chain's accumulators to another process, are
+ * made of (definitions in dang_amd/csrc/dx_section_host.h).  A section is addressed by (family, a, b):
+ *   family 0 HEAD    (a, b ignored)  DANGX_SECTION_HEAD_BYTES bytes, host forms only: layout version, count, lag-1 flag, nbatch,
+ *                                    the current batch length, the full batches, the fill of the open batch and a 64-bit
+ *                                    fingerprint of the registration, with one 64-bit value per part of it: the shard (npix,
+ *                                    pix0, nmaps); the selection words with type and nindices of the selected components; the
+ *                                    lag-1 flag and the pair list; the histogram planes with lo, hi, nbins, bits; the signal
+ *                                    specs; the batch planes with nbatch
+ *   family 1 PLANES  (comp, what)    parts mean, m2 (then prev, first, P when lag-1 is tracked), each [selected planes in T, Q, U
+ *                                    order][npix] f64; for a template / monopole / hi_fit member (what 0) its host rows in the
+ *                                    same part order, each [selected planes][nbands]
+ *   family 2 PAIR    (pair, -)       C[npix] f64
+ *   family 3 HIST    (reg, -)        the records as the raw histogram getter lays them out
+ *   family 4 SIGNAL  (sig, -)        mean, m2, each [npix] f64
+ *   family 5 BATCHES (reg, -)        [nbatch][mean, m2][npix] f64
+ * _section_bytes: the payload's size.  _section_get / _put: host arrays, returning after the copy; the _dev forms take device
+ * arrays and are asynchronous on the context's stream (the host rows of a template / monopole / hi_fit member: the call waits).
+ * Transport is one copy per plane; no kernel is launched.  Every get and put checks `bytes` against _section_bytes.
+ * A put overwrites that section of a context with live accumulators.  A put of HEAD is refused, naming what differs, unless its
+ * fingerprint is that of this context's registration (make the same registrations first); it sets the count and the batch
+ * bookkeeping, and a following dangx_moments_accumulate continues as if the samples had been taken on this context: the lag-1
+ * product uses the restored prev, the pair terms the restored means, the batch schedule the restored batch length and fill, the
+ * histogram limit the restored count.
+ * dangx_moments_begin_like makes ctx a HOLDER: it takes over the registrations of `like` (selection, pairs / lag-1 flag,
+ * histograms, signals, batches; the two contexts must agree in npix / pix0 / nmaps / ncomp / nbands and in the components
+ * concerned) and allocates NO accumulators; whatever ctx accumulated or held before is dropped.  A section's device memory
+ * (its payload rounded up to 256 bytes; batches at the plane pitch of a live context) is allocated when it is first put.  A
+ * holder with lag-1 also takes a PLANES payload of the first two parts (mean, m2) alone.  The read-outs over several chains
+ * below accept holders at any position; every single-context entry point of this group except _count, _batches_info, _end and
+ * the ones here refuses a holder by name.  dangx_moments_held_bytes: the device bytes a holder holds (0 for a live context).
+ * Not covered: merging a section into live accumulators, chains of one process on different devices. */
+#define DANGX_SECTION_HEAD_BYTES 104
+int dangx_moments_section_bytes(dangx_ctx *ctx, int family, int a, int b, int64_t *bytes);
+int dangx_moments_section_get(dangx_ctx *ctx, int family, int a, int b, void *out, int64_t bytes);
+int dangx_moments_section_get_dev(dangx_ctx *ctx, int family, int a, int b, void *out_dev, int64_t bytes);
+int dangx_moments_section_put(dangx_ctx *ctx, int family, int a, int b, const void *in, int64_t bytes);
+int dangx_moments_section_put_dev(dangx_ctx *ctx, int family, int a, int b, const void *in_dev, int64_t bytes);
+int dangx_moments_begin_like(dangx_ctx *ctx, dangx_ctx *like);
+int dangx_moments_held_bytes(dangx_ctx *ctx, int64_t *bytes);
 /* frees the accumulators */
 int dangx_moments_end(dangx_ctx *ctx);
 
@@ -633,7 +673,9 @@ int dangx_moments_end(dangx_ctx *ctx);
  * ctxs[0..nchains) are contexts of ONE device holding the same shard, each with its own chain and its own dangx_moments_*
  * accumulators (the data planes can be shared: dangx_adopt_device_data).  The read-outs combine the per-chain accumulators on the
  * device and write only the map asked for; they touch no accumulator, chain or cache, and a run that never calls them launches
- * what it launched before.  Definitions (dang_amd/csrc/dx_chains_host.h), per element, chain k with n_k samples, mean_k and
+ * what it launched before.  Any of the contexts, ctxs[0] included, may be a HOLDER (dangx_moments_begin_like) given the sections of
+ * a chain that ran elsewhere: the result is bit for bit that of the live chain; a read-out that needs a section a holder was not
+ * given fails, naming the chain and the section, before anything is written.  Definitions (dang_amd/csrc/dx_chains_host.h), per element, chain k with n_k samples, mean_k and
  * m2_k = sum_t (x_t - mean_k)^2, N = sum n_k:
  *   pooled mean / M2: the chains folded in list order from chain 0's own values, d = mean_k - mu, n' = n + n_k,
  *     mu += d (n_k / n'), M += m2_k + d^2 (n n_k / n') -- every added term >= 0.  Pooled std = sqrt(M / (N - ddof)).

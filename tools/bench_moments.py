@@ -3,7 +3,7 @@
 iterations of the C3 model: blocks of iterations without and with accumulation after every iteration, alternating in one process;
 then the k_moments kernel time from the profile and its bandwidth in algorithmic bytes (5 x 8 B per selected element) against the
 6.29 TB/s measured copy ceiling of the MI355X.
-    python3 tools/bench_moments.py [nside=1024] [steps per block=10] [rounds=5] [--lag1] [--pairs default] [--hist [nbins=64]] [--signals [--bandpass]] [--chains K [--samples N]] [--batches NB]
+    python3 tools/bench_moments.py [nside=1024] [steps per block=10] [rounds=5] [--lag1] [--pairs default] [--hist [nbins=64]] [--signals [--bandpass]] [--chains K [--samples N]] [--batches NB] [--sections]
 --lag1 / --pairs default: after the above, `rounds` alternating rounds of `steps` accumulations each of (a) the plain accumulate,
 (b) with lag-1 tracking (k_moments_accum_lag: 10 x 8 B per selected element) and (c) with the default pairs (k_moments_pairs: 6 x 8 B
 per pair element, timed apart from the mean launch that follows it); per launch the algorithmic bytes, the achieved bytes/s and
@@ -31,7 +31,11 @@ is run.
 accumulations (5 x 8 B per element each; batches long enough that no merge falls into the round), per byte; then, after NB
 samples with batches of one sample (every batch full), rounds of (y) the single-chain std read-out, (s) split R-hat of one chain
 (k_batches_stat: (2 NB + 1) x 8 B per element) and (c) of two chains (k_chains_batches: (4 NB + 1) x 8 B); then the time of the
-merges the next 3 NB + 1 accumulations cause.  Nothing else of the above is run."""
+merges the next 3 NB + 1 accumulations cause.  Nothing else of the above is run.
+--sections: one chain with lag-1 and one histogram plane (64 bins x 16 bit); three alternating rounds in one process of (c) a plain
+hipMemcpyAsync device to device, (s) the same on a stream of its own, (g) dangx_moments_section_get_dev and (p) _put_dev into a
+holder, of the same bytes: the histogram's records (one copy) and a PLANES section (one copy per plane and part); `steps` copies
+per timing, wall time around a device synchronisation.  Nothing else of the above is run."""
 import os
 import sys
 import time
@@ -95,6 +99,58 @@ if want_bandpass:
         eng.profile(False)
         print("round %d: bandpass form, %d signals at integrated bands of 9 samples: %.3f ms per launch (%d launches)"
               % (r + 1, len(specs), prof["total_ms"] / prof["launches"], prof["launches"]))
+    sys.exit(0)
+if "--sections" in sys.argv:
+    import ctypes
+    from dang_amd import api
+    hip = ctypes.CDLL("libamdhip64.so")
+    hip.hipMemcpyAsync.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
+    sel = da.moments_begin(dpar, ddata)
+    da.moments_pairs(dpar, ddata, pairs=[], lag1=True)
+    hp = da.moments_hist(dpar, ddata, planes=da.default_hist_planes(dpar, comps, sel)[:1], nbins=64, bits=16)
+    da.gibbs_iteration(dpar, ddata, 1, want_counts=False)
+    da.moments_accumulate(ddata)
+    holder = api._holder_engine(eng)
+    holder.moments_begin_like(eng)
+    side = torch.cuda.Stream()
+    l, what, _ = hp[0]
+    print("C3 at Nside %d, %d pixels: sections of one chain, get_dev / put_dev (into a holder) against hipMemcpyAsync device to device of the "
+          "same bytes, %d copies per timing" % (nside, meta["npix"], steps))
+    for name, sec in (("HIST(0), 64 bins x 16 bit", ("HIST", 0, 0)), ("PLANES(%s, %d), five parts" % (comps[l].label, what), ("PLANES", l, what))):
+        n = eng.moments_section_bytes(*sec)
+        a = torch.empty(n, dtype=torch.uint8, device=dev)
+        b = torch.empty(n, dtype=torch.uint8, device=dev)
+        eng.moments_section_get(*sec, device=True, out=a)
+        holder.moments_section_put(*sec, a)            # the holder's buffer exists from here on
+        torch.cuda.synchronize()
+
+        def timed(fn):
+            fn()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                fn()
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) / steps * 1e3
+
+        forms = [("c", "hipMemcpyAsync", lambda: hip.hipMemcpyAsync(b.data_ptr(), a.data_ptr(), n, 3, None)),
+                 ("s", "hipMemcpyAsync on a stream of its own", lambda: hip.hipMemcpyAsync(b.data_ptr(), a.data_ptr(), n, 3, side.cuda_stream)),
+                 ("g", "section_get_dev", lambda: eng.moments_section_get(*sec, device=True, out=b)),
+                 ("p", "section_put_dev", lambda: holder.moments_section_put(*sec, a))]
+        ratio = {"s": [], "g": [], "p": []}
+        print("%s: %.3f GB" % (name, n * 1e-9))
+        for r in range(3):
+            line, c_ms = "  round %d:" % (r + 1), None
+            for key, what_, fn in forms:
+                ms = timed(fn)
+                if key == "c":
+                    c_ms = ms
+                else:
+                    ratio[key].append(ms / c_ms)
+                line += " (%s) %s %.3f ms, %.0f GB/s copied%s;" % (key, what_, ms, n / ms * 1e-6, "" if key == "c" else " = %.3f x (c)'s time" % (ms / c_ms))
+            print(line)
+        for key in "sgp":
+            print("  (%s) time / (c)'s: median %.3f (spread %.3f .. %.3f)" % (key, float(np.median(ratio[key])), min(ratio[key]), max(ratio[key])))
     sys.exit(0)
 if nchains:
     runs = [(dpar, ddata)] + [da.open_chain(dpar, ddata, dpar.seed + k) for k in range(1, nchains)]
