@@ -41,6 +41,8 @@ BATCH_STAT_CODES = {"mean": 0, "std": 1, "mcse": 2, "ess_bm": 3, "split_rhat": 4
 MAX_BATCHES, MAX_BATCH_PLANES = 32, 32
 SEC_HEAD, SEC_PLANES, SEC_PAIR, SEC_HIST, SEC_SIGNAL, SEC_BATCHES = range(6)   # family of a section
 SECTION_NAMES = ("HEAD", "PLANES", "PAIR", "HIST", "SIGNAL", "BATCHES")
+# a PLANES section of pixel planes is equal parts: mean and m2, and with lag-1 tracking three more behind them (include/dangx.h)
+PLANES_MOMENT_PARTS, PLANES_LAG1_PARTS = 2, 5
 SECTION_HEAD_BYTES = 104
 SIGNAL_KINDS = ("T", "Q", "U", "P")      # kind 0..3 of a signal spec (comp, band, kind)
 

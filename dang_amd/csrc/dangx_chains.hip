@@ -388,18 +388,25 @@ int chains_release(const ChainSet& cs) {
     return 0;
 }
 
+// one launch on stream 0 between the two joins, timed as DANGX_K_CHAINS
+template <class Launch>
+int chains_run(const ChainSet& cs, Launch launch) {
+    dangx_ctx* c0 = cs.c[0];
+    if (chains_join(cs)) return 1;
+    {
+        Timed tm(c0, DANGX_K_CHAINS);
+        launch();
+        HIPCHK(c0, hipGetLastError());
+    }
+    return chains_release(cs);
+}
+
 // k_chains_stat on stream 0 between the two joins; a.mean .. a.out of np planes are filled in
 int chains_launch(const ChainSet& cs, const ChainsArgs& a, int np, int stat, int ddof) {
     dangx_ctx* c0 = cs.c[0];
     const long long n = c0->dims.npix;
     const DxChainsPar par = dx_chains_par(cs.K, cs.cnt, ddof);
-    if (chains_join(cs)) return 1;
-    {
-        Timed tm(c0, DANGX_K_CHAINS);
-        hipLaunchKernelGGL(k_chains_stat, dim3(c0->mom->grid_for((n + 1) / 2, np), np), dim3(BLOCK), 0, c0->stream, a, par, n, stat);
-        HIPCHK(c0, hipGetLastError());
-    }
-    return chains_release(cs);
+    return chains_run(cs, [&] { hipLaunchKernelGGL(k_chains_stat, dim3(c0->mom->grid_for((n + 1) / 2, np), np), dim3(BLOCK), 0, c0->stream, a, par, n, stat); });
 }
 
 // Every read-out is one implementation; `out` is a device buffer, or with to_host a host array staged through chain 0 (ReadOut).
@@ -504,13 +511,7 @@ int chains_pair_impl(dangx_ctx* const* ctxs, int nchains, int pair, int stat, in
     }
     a.out = ro.dst;
     const DxChainsPar par = dx_chains_par(cs.K, cs.cnt, ddof);
-    if (chains_join(cs)) return 1;
-    {
-        Timed tm(c0, DANGX_K_CHAINS);
-        hipLaunchKernelGGL(k_chains_pair, dim3(c0->mom->grid_for((n + 1) / 2, 1)), dim3(BLOCK), 0, c0->stream, a, par, n, stat);
-        HIPCHK(c0, hipGetLastError());
-    }
-    if (chains_release(cs)) return 1;
+    if (chains_run(cs, [&] { hipLaunchKernelGGL(k_chains_pair, dim3(c0->mom->grid_for((n + 1) / 2, 1)), dim3(BLOCK), 0, c0->stream, a, par, n, stat); })) return 1;
     return ro.close(n);
 }
 
@@ -552,13 +553,7 @@ int chains_hist_impl(dangx_ctx* const* ctxs, int nchains, int reg, int stat, int
     a.out = ro.dst; a.lo = m0->hists[reg].lo; a.hi = m0->hists[reg].hi; a.n = c0->dims.npix;
     a.K = cs.K; a.nbins = m0->hbins; a.bits = m0->hbits; a.stat = stat; a.nq = stat == 0 ? nq : 0;
     for (int j = 0; j < a.nq; ++j) a.q[j] = q[j];
-    if (chains_join(cs)) return 1;
-    {
-        Timed tm(c0, DANGX_K_CHAINS);
-        hipLaunchKernelGGL(k_chains_hist, dim3(c0->mom->grid_for(a.n, 1)), dim3(BLOCK), 0, c0->stream, a);
-        HIPCHK(c0, hipGetLastError());
-    }
-    if (chains_release(cs)) return 1;
+    if (chains_run(cs, [&] { hipLaunchKernelGGL(k_chains_hist, dim3(c0->mom->grid_for(a.n, 1)), dim3(BLOCK), 0, c0->stream, a); })) return 1;
     return ro.close(total);
 }
 
@@ -581,13 +576,7 @@ int chains_rank_impl(dangx_ctx* const* ctxs, int nchains, int reg, int stat, dou
         if (!a.rec[j]) return chains_missing(ctxs, j, "HIST(" + std::to_string(reg) + ")");
     }
     a.out = ro.dst; a.n = n; a.K = cs.K; a.nbins = m0->hbins; a.bits = m0->hbits; a.stat = stat;
-    if (chains_join(cs)) return 1;
-    {
-        Timed tm(c0, DANGX_K_CHAINS);
-        hipLaunchKernelGGL(k_chains_rank, dim3(c0->mom->grid_for(n, 1)), dim3(BLOCK), 0, c0->stream, a);
-        HIPCHK(c0, hipGetLastError());
-    }
-    if (chains_release(cs)) return 1;
+    if (chains_run(cs, [&] { hipLaunchKernelGGL(k_chains_rank, dim3(c0->mom->grid_for(n, 1)), dim3(BLOCK), 0, c0->stream, a); })) return 1;
     return ro.close(n);
 }
 
@@ -631,13 +620,7 @@ int chains_batches_impl(dangx_ctx* const* ctxs, int nchains, int reg, int stat, 
     }
     a.out = ro.dst; a.pitch = m0->bpitch; a.n = n;
     a.par = dx_batches_par(stat, first, ddof, p.L, p.nfull, p.partial, cs.K);
-    if (chains_join(cs)) return 1;
-    {
-        Timed tm(c0, DANGX_K_CHAINS);
-        hipLaunchKernelGGL(k_chains_batches, dim3(c0->mom->grid_for((n + 1) / 2, 1)), dim3(BLOCK), 0, c0->stream, a);
-        HIPCHK(c0, hipGetLastError());
-    }
-    if (chains_release(cs)) return 1;
+    if (chains_run(cs, [&] { hipLaunchKernelGGL(k_chains_batches, dim3(c0->mom->grid_for((n + 1) / 2, 1)), dim3(BLOCK), 0, c0->stream, a); })) return 1;
     return ro.close(n);
 }
 

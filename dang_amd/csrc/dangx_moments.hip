@@ -455,6 +455,30 @@ int need_live(dangx_ctx* ctx, const char* who) {
     return 0;
 }
 
+// The frame of a registration entry point `who` (dangx_moments_pairs / _hist / _signals / _batches).  reg_open: a context with
+// accumulators of its own that has accumulated nothing yet, and (tab given) the tables the dx_*_check functions take, from what
+// dangx_moments_begin recorded.  reg_close: everything new has been allocated into locals by now; wait for their fills (`wait`:
+// something was allocated) and name the entry on failure.  Only after it returns 0 does the caller move the locals in, so a
+// failure leaves the registration as it was.
+struct RegTables { int nind[MAXC] = {}, global[MAXC] = {}; };
+
+int reg_open(dangx_ctx* ctx, const char* who, RegTables* tab = nullptr) {
+    if (!ctx || need_live(ctx, who)) return 1;
+    const DxMoments* m = ctx->mom;
+    if (m->count != 0)
+        return fail(ctx, std::string("posterior moments: ") + who + " is legal only before the first dangx_moments_accumulate after dangx_moments_begin");
+    for (int l = 0; tab && l < ctx->dims.ncomp; ++l) {
+        tab->nind[l] = m->nind[l];
+        tab->global[l] = is_global_type(m->type[l]) ? 1 : 0;
+    }
+    return 0;
+}
+
+int reg_close(dangx_ctx* ctx, const char* who, DevStatus& st, bool wait) {
+    if (wait) st.sync(ctx->stream);
+    return st.ok() ? 0 : st.fail(ctx, (std::string(who) + ": ").c_str());
+}
+
 // the resident plane of a segment as it is now (adopted buffers may have been replaced since begin)
 const double* seg_plane(const dangx_ctx* ctx, const DxMoments::Seg& s) {
     const long long np = ctx->dims.npix;
@@ -669,17 +693,10 @@ int dangx_moments_begin(dangx_ctx* ctx, const int32_t* sel) {
 }
 
 int dangx_moments_pairs(dangx_ctx* ctx, int lag1, int npairs, const int32_t* pairs) {
-    if (!ctx || need_live(ctx, "dangx_moments_pairs")) return 1;
+    RegTables tab;
+    if (reg_open(ctx, "dangx_moments_pairs", &tab)) return 1;
     DxMoments* m = ctx->mom;
-    if (m->count != 0)
-        return fail(ctx, "posterior moments: dangx_moments_pairs is legal only before the first dangx_moments_accumulate after dangx_moments_begin");
-    const int ncomp = ctx->dims.ncomp;
-    int nind[MAXC] = {}, global[MAXC] = {};
-    for (int l = 0; l < ncomp; ++l) {
-        nind[l] = m->nind[l];
-        global[l] = is_global_type(m->type[l]) ? 1 : 0;
-    }
-    const std::string why = dx_pairs_check(npairs, pairs, ncomp, ctx->dims.nmaps, m->sel, nind, global);
+    const std::string why = dx_pairs_check(npairs, pairs, ctx->dims.ncomp, ctx->dims.nmaps, m->sel, tab.nind, tab.global);
     if (!why.empty()) return fail(ctx, "posterior moments: dangx_moments_pairs: " + why);
     std::vector<DxMoments::Pair> np;
     long long off = 0;
@@ -694,8 +711,7 @@ int dangx_moments_pairs(dangx_ctx* ctx, int lag1, int npairs, const int32_t* pai
         np.push_back(pr);
     }
     (void)hipSetDevice(ctx->device);
-    // everything new is allocated before anything old is dropped: a failure leaves the registration as it was
-    // (the new buffers are locals that free themselves, and are moved in only after the last call that can fail)
+    // everything new is allocated before anything old is dropped (reg_close): the new buffers are locals that free themselves
     DevBuf<double> lag, pc;
     DevBuf<LagSeg> d_lag;
     DevBuf<PairSeg> d_pairs;
@@ -708,8 +724,7 @@ int dangx_moments_pairs(dangx_ctx* ctx, int lag1, int npairs, const int32_t* pai
         pc.zeros((size_t)off, ctx->stream, st);
         d_pairs.alloc(np.size(), st);
     }
-    st.sync(ctx->stream);
-    if (!st.ok()) return st.fail(ctx, "dangx_moments_pairs: ");
+    if (reg_close(ctx, "dangx_moments_pairs", st, true)) return 1;
     m->lag = std::move(lag); m->d_lag = std::move(d_lag); m->pc = std::move(pc); m->d_pairs = std::move(d_pairs);
     m->lag1 = lag1 != 0;
     m->pairs = np;
@@ -934,16 +949,11 @@ int dangx_moments_get_pair(dangx_ctx* ctx, int pair, int stat, int ddof, double*
 }
 
 int dangx_moments_hist(dangx_ctx* ctx, int nreg, const int32_t* planes, const double* range, int nbins, int bits) {
-    if (!ctx || need_live(ctx, "dangx_moments_hist")) return 1;
+    RegTables tab;
+    if (reg_open(ctx, "dangx_moments_hist", &tab)) return 1;
     DxMoments* m = ctx->mom;
-    if (m->count != 0)
-        return fail(ctx, "posterior moments: dangx_moments_hist is legal only before the first dangx_moments_accumulate after dangx_moments_begin");
     const int ncomp = ctx->dims.ncomp;
-    int nind[MAXC] = {}, global[MAXC] = {};
-    for (int l = 0; l < ncomp; ++l) {
-        nind[l] = m->nind[l];
-        global[l] = is_global_type(m->type[l]) ? 1 : 0;
-    }
+    const int* nind = tab.nind;
     // the ranges with the defaults filled in: an index plane's is that index's uni_prior as the descriptor holds it now
     const int nr = std::max(0, std::min(nreg, DX_HIST_MAX));
     std::vector<double> rg(2 * (size_t)nr, 0.0);
@@ -960,7 +970,7 @@ int dangx_moments_hist(dangx_ctx* ctx, int nreg, const int32_t* planes, const do
             has[r] = 1;   // out of range: dx_hist_check names it
         }
     }
-    const std::string why = dx_hist_check(nreg, planes, rg.data(), has.data(), nbins, bits, ncomp, ctx->dims.nmaps, m->sel, nind, global);
+    const std::string why = dx_hist_check(nreg, planes, rg.data(), has.data(), nbins, bits, ncomp, ctx->dims.nmaps, m->sel, nind, tab.global);
     if (!why.empty()) return fail(ctx, "posterior moments: dangx_moments_hist: " + why);
     const long long np = ctx->dims.npix, words = dx_hist_words(nbins, bits);
     std::vector<DxMoments::Hist> nh;
@@ -972,16 +982,15 @@ int dangx_moments_hist(dangx_ctx* ctx, int nreg, const int32_t* planes, const do
         off += (np * words + 63) / 64 * 64;
     }
     (void)hipSetDevice(ctx->device);
-    // everything new is allocated before anything old is dropped: a failure leaves the registration as it was
+    // everything new is allocated before anything old is dropped (reg_close)
     DevBuf<uint32_t> hrec;
     DevBuf<HistSeg> d_hist;
     DevStatus st;
     if (!nh.empty()) {
         hrec.zeros((size_t)off, ctx->stream, st);
         d_hist.alloc(nh.size(), st);
-        st.sync(ctx->stream);
     }
-    if (!st.ok()) return st.fail(ctx, "dangx_moments_hist: ");
+    if (reg_close(ctx, "dangx_moments_hist", st, !nh.empty())) return 1;
     m->hrec = std::move(hrec); m->d_hist = std::move(d_hist);
     m->hists = nh;
     m->hbins = nbins; m->hbits = bits;
@@ -1031,10 +1040,8 @@ int dangx_moments_hist_stat(dangx_ctx* ctx, int reg, int stat, int nq, const dou
 }
 
 int dangx_moments_signals(dangx_ctx* ctx, int nsig, const int32_t* spec) {
-    if (!ctx || need_live(ctx, "dangx_moments_signals")) return 1;
+    if (reg_open(ctx, "dangx_moments_signals")) return 1;   // its tables come from the descriptors: signals do not depend on the selection
     DxMoments* m = ctx->mom;
-    if (m->count != 0)
-        return fail(ctx, "posterior moments: dangx_moments_signals is legal only before the first dangx_moments_accumulate after dangx_moments_begin");
     const int ncomp = ctx->dims.ncomp, nmaps = ctx->dims.nmaps;
     int set[MAXC] = {}, global[MAXC] = {};
     for (int l = 0; l < ncomp; ++l) {
@@ -1063,16 +1070,15 @@ int dangx_moments_signals(dangx_ctx* ctx, int nsig, const int32_t* spec) {
         ns.push_back(sg);
     }
     const long long half = off + (off & 1);   // even: the m2 half has the phases of the mean half
-    // everything new is allocated before anything old is dropped: a failure leaves the registration as it was
+    // everything new is allocated before anything old is dropped (reg_close)
     DevBuf<double> sacc;
     DevBuf<SigSeg> d_sig;
     DevStatus st;
     if (!ns.empty()) {
         sacc.zeros(2 * (size_t)half, ctx->stream, st);
         d_sig.alloc(plan.size(), st);
-        st.sync(ctx->stream);
     }
-    if (!st.ok()) return st.fail(ctx, "dangx_moments_signals: ");
+    if (reg_close(ctx, "dangx_moments_signals", st, !ns.empty())) return 1;
     m->sacc = std::move(sacc); m->d_sig = std::move(d_sig); m->sacc_half = half;
     m->sigs = ns;
     m->sig_plan = plan;
@@ -1106,17 +1112,10 @@ int dangx_moments_get_signal(dangx_ctx* ctx, int sig, int stat, int ddof, double
 }
 
 int dangx_moments_batches(dangx_ctx* ctx, int nreg, const int32_t* planes, int nbatch, int64_t batch_len) {
-    if (!ctx || need_live(ctx, "dangx_moments_batches")) return 1;
+    RegTables tab;
+    if (reg_open(ctx, "dangx_moments_batches", &tab)) return 1;
     DxMoments* m = ctx->mom;
-    if (m->count != 0)
-        return fail(ctx, "posterior moments: dangx_moments_batches is legal only before the first dangx_moments_accumulate after dangx_moments_begin");
-    const int ncomp = ctx->dims.ncomp;
-    int nind[MAXC] = {}, global[MAXC] = {};
-    for (int l = 0; l < ncomp; ++l) {
-        nind[l] = m->nind[l];
-        global[l] = is_global_type(m->type[l]) ? 1 : 0;
-    }
-    const std::string why = dx_batches_check(nreg, planes, nbatch, batch_len, ncomp, ctx->dims.nmaps, m->sel, nind, global);
+    const std::string why = dx_batches_check(nreg, planes, nbatch, batch_len, ctx->dims.ncomp, ctx->dims.nmaps, m->sel, tab.nind, tab.global);
     if (!why.empty()) return fail(ctx, "posterior moments: dangx_moments_batches: " + why);
     const long long pitch = ctx->dims.npix + (ctx->dims.npix & 1);   // even: every plane of a registration at the phase of its first
     std::vector<DxMoments::Batch> nb;
@@ -1129,16 +1128,15 @@ int dangx_moments_batches(dangx_ctx* ctx, int nreg, const int32_t* planes, int n
         off += 2LL * nbatch * pitch;
     }
     (void)hipSetDevice(ctx->device);
-    // everything new is allocated before anything old is dropped: a failure leaves the registration as it was
+    // everything new is allocated before anything old is dropped (reg_close)
     DevBuf<double> bacc;
     DevBuf<MomSeg> d_batch;
     DevStatus st;
     if (!nb.empty()) {
         bacc.zeros((size_t)off, ctx->stream, st);
         d_batch.alloc(nb.size() * (size_t)nbatch, st);
-        st.sync(ctx->stream);
     }
-    if (!st.ok()) return st.fail(ctx, "dangx_moments_batches: ");
+    if (reg_close(ctx, "dangx_moments_batches", st, !nb.empty())) return 1;
     m->bacc = std::move(bacc); m->d_batch = std::move(d_batch);
     m->batches = nb;
     m->nbatch = nb.empty() ? 0 : nbatch;
