@@ -1,8 +1,8 @@
 // dangx_core.hip -- the context behind the C ABI of include/dangx.h: creation, the host mirror of the model and its device copy
 // (sync_model: band constants, host-evaluated SEDs of spatially constant index maps, bandpass tables), the resident state maps,
 // the chi^2 / index-sum ring the sweeps leave their by-products in (chi_next / chi_flush), the CG group descriptors
-// (make_group), the host solvers of the parity and template paths (device_cg, device_schur), the small reduction / statistics /
-// unit-conversion entry points and the launch profile.  The sampling entry points live in dangx_entry.hip, the full-sky / coarse-
+// (make_group), the small reduction / statistics / unit-conversion entry points and the launch profile.  The two linear solvers
+// and the seams of their operators live in dangx_solve.hip, the sampling entry points in dangx_entry.hip, the full-sky / coarse-
 // Nside device side in dangx_coarse.hip, the sky-wide chains in dangx_sky.hip, the kernels next to their launchers.
 //
 // Design: one thread owns one (pixel, Stokes plane) unit -- the reference's global CG system is block diagonal
@@ -40,113 +40,6 @@ const char* dx_kernel_family(int kid) {
 // ======================================================================= kernels
 
 namespace {
-
-// eta(i) = rand_normal(0,1), src/dang_cg_mod.f90:256-262, from the keyed stream
-__global__ __launch_bounds__(BLOCK) void k_draw_eta(const Model* __restrict__ Mp, GroupArgs a, double* __restrict__ eta) {
-    const Model& M = *Mp;
-    const long long SN = (long long)flag_nplanes(a.flag) * M.npix;
-    const long long u = (long long)blockIdx.x * BLOCK + threadIdx.x;
-    if (u >= SN) return;
-    const int p = (int)(u / M.npix), i = (int)(u - (long long)p * M.npix), k = flag_map(a.flag, p);
-    double u1, u2;
-    uniform2(a.seed, a.stream, (unsigned long long)(M.pix0 + i), (uint32_t)k, u1, u2);
-    eta[u] = rand_normal(0.0, 1.0, u1, u2);
-}
-
-// pack / unpack between c%amplitude and x (initialize_x :1173-1282, unpack_amplitudes :1284-1396)
-__global__ __launch_bounds__(BLOCK) void k_pack(const Model* __restrict__ Mp, GroupArgs a, double* __restrict__ x, int unpack) {
-    const Model& M = *Mp;
-    const long long SN = (long long)flag_nplanes(a.flag) * M.npix;
-    const long long u = (long long)blockIdx.x * BLOCK + threadIdx.x;
-    if (u >= SN) return;
-    const int p = (int)(u / M.npix), i = (int)(u - (long long)p * M.npix), k = flag_map(a.flag, p);
-    for (int g = 0; g < a.ng; ++g) {
-        double* amp = M.comp[a.gc[g]].amp + (long long)(k - 1) * M.npix + i;
-        if (unpack) *amp = x[(long long)g * SN + u];
-        else x[(long long)g * SN + u] = *amp;
-    }
-}
-
-// CG vector updates (src/dang_cg_mod.f90:283-305) with block partials of sum(r*r)
-//  mode 0: r = b2 - q ; d = r                        -> partial sum(r*r)
-//  mode 1: x += alpha*d ; r -= alpha*q               -> partial sum(r*r)
-//  mode 2: d = r + beta*d
-//  mode 3: b2 = b + f
-// entries t >= ndot do not enter the partial sums (replicated global rows on the non-root ranks of a sharded run)
-__global__ __launch_bounds__(BLOCK) void k_cg_vec(int mode, long long n, long long ndot, double alpha, double* __restrict__ x,
-                                                  double* __restrict__ r, double* __restrict__ d,
-                                                  const double* __restrict__ q, const double* __restrict__ b2,
-                                                  double* __restrict__ partial) {
-    const long long t = (long long)blockIdx.x * BLOCK + threadIdx.x;
-    double rr = 0.0;
-    if (t < n) {
-        if (mode == 0) {
-            const double rv = b2[t] - q[t];
-            r[t] = rv; d[t] = rv; rr = (t < ndot) ? rv * rv : 0.0;
-        } else if (mode == 1) {
-            x[t] = x[t] + alpha * d[t];
-            const double rv = r[t] - alpha * q[t];
-            r[t] = rv; rr = (t < ndot) ? rv * rv : 0.0;
-        } else if (mode == 2) {
-            d[t] = r[t] + alpha * d[t];
-        } else {
-            x[t] = b2[t] + q[t];
-        }
-    }
-    if (partial) {
-        __shared__ double sh[BLOCK / 64];
-        for (int o = 32; o > 0; o >>= 1) rr += __shfl_down(rr, o, 64);
-        if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = rr;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double s = 0.0;
-            for (int w = 0; w < BLOCK / 64; ++w) s += sh[w];
-            partial[blockIdx.x] = s;
-        }
-    }
-}
-
-// block partials of sum(u*v)
-__global__ __launch_bounds__(BLOCK) void k_dot(const double* __restrict__ u, const double* __restrict__ v, long long n,
-                                               long long ndot, double* __restrict__ partial) {
-    __shared__ double sh[BLOCK / 64];
-    const long long t = (long long)blockIdx.x * BLOCK + threadIdx.x;
-    double s = (t < n && t < ndot) ? u[t] * v[t] : 0.0;
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double w = 0.0;
-        for (int q = 0; q < BLOCK / 64; ++q) w += sh[q];
-        partial[blockIdx.x] = w;
-    }
-}
-
-// block partials of sum((b-q)^2) [row 0] and sum(b^2) [row 1] over the diffuse entries t < ndiff of unmasked units
-// (the rows of masked units are zero in A and keep whatever b holds: not part of the solve)
-__global__ __launch_bounds__(BLOCK) void k_resid_norm(const Model* __restrict__ Mp, const double* __restrict__ b,
-                                                      const double* __restrict__ q, long long ndiff, long long SN,
-                                                      double* __restrict__ partial) {
-    __shared__ double sh[2][BLOCK / 64];
-    const Model& M = *Mp;
-    const long long t = (long long)blockIdx.x * BLOCK + threadIdx.x;
-    double rr = 0.0, bb = 0.0;
-    if (t < ndiff) {
-        const long long u = t % SN;
-        if (!is_masked(M.mask[u % M.npix])) {
-            const double r = b[t] - q[t];
-            rr = r * r; bb = b[t] * b[t];
-        }
-    }
-    for (int o = 32; o > 0; o >>= 1) { rr += __shfl_down(rr, o, 64); bb += __shfl_down(bb, o, 64); }
-    if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = rr; sh[1][threadIdx.x >> 6] = bb; }
-    __syncthreads();
-    if (threadIdx.x < 2) {
-        double v = 0.0;
-        for (int w = 0; w < BLOCK / 64; ++w) v += sh[threadIdx.x][w];
-        partial[(long long)threadIdx.x * gridDim.x + blockIdx.x] = v;
-    }
-}
 
 // deterministic second stage: out[0] = sum(partial[0..n)) in a fixed order
 __global__ __launch_bounds__(BLOCK) void k_reduce(const double* __restrict__ partial, long long n, double* __restrict__ out) {
@@ -451,18 +344,6 @@ __global__ __launch_bounds__(BLOCK) void k_qu_differ(const double* __restrict__ 
     }
 }
 
-// eval_sed(band, pix, map_n) over the shard (src/dang_component_mod.f90:778-813)
-__global__ __launch_bounds__(BLOCK) void k_eval_sed(const Model* __restrict__ Mp, int comp, int band, int map_n,
-                                                    double* __restrict__ out) {
-    const Model& M = *Mp;
-    const int i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= M.npix) return;
-    const Comp& c = M.comp[comp];
-    double t0, t1;
-    load_theta(M, c, i, map_n, t0, t1);
-    out[i] = comp_sed(M, c, i, map_n, band, sed_prep(c, t0, t1));
-}
-
 }  // namespace
 
 // ======================================================================= host side
@@ -479,24 +360,26 @@ void dx_reduce_rows_to(dangx_ctx* ctx, const double* partial, unsigned nblk, int
 namespace {
 
 
-// a2t(bp), src/dang_bp_mod.f90:211-243
-double host_a2t(const dangx_ctx* ctx, int j) {
-    const Band& b = ctx->hm.band[j];
-    double sum = 0.0, y;
-    if (b.n == 0) {
-        if (b.nu_c > 1e7f) y = (H_PLANCK * b.nu_c) / (K_B * ctx->hm.tcmb);
-        else y = (H_PLANCK * b.nu_c * 1e9) / (K_B * ctx->hm.tcmb);
-        sum = ((std::exp(y) - 1.0) * (std::exp(y) - 1.0)) / ((y * y) * std::exp(y));
-    } else {
-        for (int i = 0; i < b.n; ++i) {
-            const double nu = ctx->bp_nu0[b.off + i], tau = ctx->bp_tau0[b.off + i];
-            if (nu == 0.0) continue;
-            if (nu > 1e7f) y = (H_PLANCK * nu) / (K_B * ctx->hm.tcmb);
-            else y = (H_PLANCK * nu * 1e9) / (K_B * ctx->hm.tcmb);
-            sum = sum + tau * ((std::exp(y) - 1.0) * (std::exp(y) - 1.0)) / ((y * y) * std::exp(y));
-        }
+// the bandpass sum of the reference's unit conversions and SEDs: term(nu, tau) at (nu_c, 1) for a delta band, otherwise added up
+// over the band's samples (nu0, tau0) in their order; samples with nu0 == 0 are skipped.  A delta band's value is its one term:
+// the weight 1 changes no bit of it
+template <class F>
+double band_sum(const dangx_ctx* ctx, const Band& b, F&& term) {
+    if (b.n == 0) return term(b.nu_c, 1.0);
+    double sum = 0.0;
+    for (int i = 0; i < b.n; ++i) {
+        const double nu = ctx->bp_nu0[b.off + i];
+        if (nu != 0.0) sum = sum + term(nu, ctx->bp_tau0[b.off + i]);
     }
     return sum;
+}
+
+// a2t(bp), src/dang_bp_mod.f90:211-243
+double host_a2t(const dangx_ctx* ctx, int j) {
+    return band_sum(ctx, ctx->hm.band[j], [&](double nu, double tau) {
+        const double y = (nu > 1e7f) ? (H_PLANCK * nu) / (K_B * ctx->hm.tcmb) : (H_PLANCK * nu * 1e9) / (K_B * ctx->hm.tcmb);
+        return tau * ((std::exp(y) - 1.0) * (std::exp(y) - 1.0)) / ((y * y) * std::exp(y));
+    });
 }
 
 // compute_bnu_prime_RJ / compute_bnu_prime, src/dang_bp_mod.f90:160-179 (nu in Hz)
@@ -509,34 +392,17 @@ double host_bnu_prime(double nu, double tcmb) {
 // a2f(bp) [MJy/sr / uK_RJ], src/dang_bp_mod.f90:181-209.  `sum*1e14` multiplies by a SINGLE-precision literal: 1e14 is
 // not representable in real(4), the factor is 100000000376832 -- kept, it is what the reference's maps are scaled by
 double host_a2f(const dangx_ctx* ctx, int j) {
-    const Band& b = ctx->hm.band[j];
-    double sum = 0.0;
-    if (b.n == 0) {
-        sum = (b.nu_c > 1e7f) ? host_bnu_prime_RJ(b.nu_c) : host_bnu_prime_RJ(b.nu_c * 1e9);
-    } else {
-        for (int i = 0; i < b.n; ++i) {
-            const double nu = ctx->bp_nu0[b.off + i], tau = ctx->bp_tau0[b.off + i];
-            if (nu == 0.0) continue;
-            sum = sum + tau * ((nu > 1e7f) ? host_bnu_prime_RJ(nu) : host_bnu_prime_RJ(nu * 1e9));
-        }
-    }
+    const double sum = band_sum(ctx, ctx->hm.band[j], [](double nu, double tau) {
+        return tau * ((nu > 1e7f) ? host_bnu_prime_RJ(nu) : host_bnu_prime_RJ(nu * 1e9));
+    });
     return sum * (double)1e14f;
 }
 // f2t(bp) [uK_cmb / MJy sr-1], src/dang_bp_mod.f90:245-274
 double host_f2t(const dangx_ctx* ctx, int j) {
-    const Band& b = ctx->hm.band[j];
     const double T = ctx->hm.tcmb;
-    double sum = 0.0;
-    if (b.n == 0) {
-        sum = 1.0 / ((b.nu_c > 1e7f) ? host_bnu_prime(b.nu_c, T) : host_bnu_prime(b.nu_c * 1e9, T)) * 1.0e-14;
-    } else {
-        for (int i = 0; i < b.n; ++i) {
-            const double nu = ctx->bp_nu0[b.off + i], tau = ctx->bp_tau0[b.off + i];
-            if (nu == 0.0) continue;
-            sum = sum + tau / ((nu > 1e7f) ? host_bnu_prime(nu, T) : host_bnu_prime(nu * 1e9, T)) * 1.0e-14;
-        }
-    }
-    return sum;
+    return band_sum(ctx, ctx->hm.band[j], [T](double nu, double tau) {
+        return tau / ((nu > 1e7f) ? host_bnu_prime(nu, T) : host_bnu_prime(nu * 1e9, T)) * 1.0e-14;
+    });
 }
 
 // eval_sed for a delta bandpass on the host (src/dang_component_mod.f90:886-1040), used for components whose
@@ -574,11 +440,8 @@ double host_sed(const Comp& c, double nu, double cmb_cst, double th0, double th1
 double dx_host_band_sed(dangx_ctx* ctx, int comp, int j, double t0, double t1) {
     const Comp& c = ctx->hm.comp[comp];
     const Band& b = ctx->hm.band[j];
-    if (b.n == 0 || c.type == DANGX_CMB) return host_sed(c, b.nu_c, c.cst[j], t0, t1);
-    double sum = 0.0;
-    for (int q = 0; q < b.n; ++q)
-        if (ctx->bp_nu0[b.off + q] != 0.0) sum = sum + ctx->bp_tau0[b.off + q] * host_sed(c, ctx->bp_nu0[b.off + q], 0.0, t0, t1);
-    return sum;
+    if (c.type == DANGX_CMB) return host_sed(c, b.nu_c, c.cst[j], t0, t1);
+    return band_sum(ctx, b, [&](double nu, double tau) { return tau * host_sed(c, nu, 0.0, t0, t1); });
 }
 
 int sync_model(dangx_ctx* ctx) {
@@ -659,14 +522,7 @@ int sync_model(dangx_ctx* ctx) {
                 if ((cp >> k) & 1) {
                     c.const_planes |= 1 << k;
                     const double t0 = ctx->idx_val[l][k][0], t1 = ctx->idx_val[l][k][1];
-                    for (int j = 0; j < M.nbands; ++j) {
-                        const Band& b = M.band[j];
-                        if (b.n == 0 || c.type == DANGX_CMB) { c.csed[k][j] = host_sed(c, b.nu_c, c.cst[j], t0, t1); continue; }
-                        double sum = 0.0;
-                        for (int q = 0; q < b.n; ++q)
-                            if (ctx->bp_nu0[b.off + q] != 0.0) sum = sum + ctx->bp_tau0[b.off + q] * host_sed(c, ctx->bp_nu0[b.off + q], 0.0, t0, t1);
-                        c.csed[k][j] = sum;
-                    }
+                    for (int j = 0; j < M.nbands; ++j) c.csed[k][j] = dx_host_band_sed(ctx, l, j, t0, t1);
                 }
         }
     }
@@ -748,9 +604,10 @@ int chi_next(dangx_ctx* ctx, long long nblk, double** buf) {
 }
 
 int make_group(dangx_ctx* ctx, int group, int flag, GroupArgs& a) {
-    if (flag != DANGX_FLAG_T && flag != DANGX_FLAG_Q && flag != DANGX_FLAG_U && flag != DANGX_FLAG_QU)
-        return fail(ctx, "flag must be exactly one of T(1), Q(2), U(4), Q+U(8)");
+    PlaneSet ps;
+    if (plane_set_of(ctx, flag, ps)) return 1;
     if (ctx->dims.nmaps < 3 && flag != DANGX_FLAG_T) return fail(ctx, "polarisation flag needs nmaps == 3");
+    const unsigned planes = map_bits(ps.map_n);  // planes this (group, flag) works on
     std::memset(&a, 0, sizeof(a));
     a.flag = flag;
     for (int l = 0; l < ctx->hm.ncomp; ++l) {
@@ -765,11 +622,8 @@ int make_group(dangx_ctx* ctx, int group, int flag, GroupArgs& a) {
             if (a.nt > 0) return fail(ctx, "diffuse components must precede the global-amplitude ones in a CG group");
             if (a.ng >= MAXG) return fail(ctx, "too many components in CG group");
             a.gc[a.ng++] = l;
-        } else {
-            unsigned planes = 0;  // planes this (group, flag) works on
-            for (int pl = 0; pl < flag_planes_h(flag); ++pl)
-                planes |= 1u << (((flag & DANGX_FLAG_QU) ? 2 + pl : (flag & DANGX_FLAG_T) ? 1 : (flag & DANGX_FLAG_Q) ? 2 : 3) - 1);
-            if ((ctx->plane_nz[l] & planes) || ctx->desc[l].type == DANGX_TCMB || is_global_type(ctx->desc[l].type)) a.oc[a.no++] = l;  // all-zero plane: 0*sed, skipped
+        } else if ((ctx->plane_nz[l] & planes) || d.type == DANGX_TCMB || is_global_type(d.type)) {
+            a.oc[a.no++] = l;  // (all-zero plane: 0*sed, skipped)
         }
     }
     if (a.ng + a.nt == 0) return fail(ctx, "Woah there, number of CG components = 0 for CG group " + std::to_string(group));
@@ -786,44 +640,13 @@ int reduce_to_host(dangx_ctx* ctx, long long nblk, double* out) {
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return 0;
 }
-
-// global rows of x <-> c%template_amplitudes (initialize_x :1244-1279, unpack_amplitudes :1355-1393)
-void globals_to_x(dangx_ctx* ctx, const GroupArgs& a, std::vector<double>& xg) {
-    xg.assign(std::max(a.nglob, 1), 0.0);
-    const int k = (a.flag & DANGX_FLAG_QU) ? 2 : (a.flag & DANGX_FLAG_T) ? 1 : (a.flag & DANGX_FLAG_Q) ? 2 : 3;
-    for (int t = 0; t < a.nt; ++t) {
-        const int l = a.tc[t];
-        int lf = 0;
-        for (int j = 0; j < ctx->hm.nbands && lf < ctx->nfit[l]; ++j)
-            if ((ctx->corr_mask[l] >> j) & 1) xg[a.trow[t] + lf++] = ctx->tamp[l][k - 1][j];
-    }
-}
-void x_to_globals(dangx_ctx* ctx, const GroupArgs& a, const std::vector<double>& xg) {
-    const int k = (a.flag & DANGX_FLAG_QU) ? 2 : (a.flag & DANGX_FLAG_T) ? 1 : (a.flag & DANGX_FLAG_Q) ? 2 : 3;
-    for (int t = 0; t < a.nt; ++t) {
-        const int l = a.tc[t];
-        int lf = 0;
-        for (int j = 0; j < ctx->hm.nbands && lf < ctx->nfit[l]; ++j)
-            if ((ctx->corr_mask[l] >> j) & 1) {
-                const double v = xg[a.trow[t] + lf++];
-                if (ctx->desc[l].type == DANGX_TEMPLATE && (a.flag & DANGX_FLAG_QU)) {  // :1380-1382 one amplitude for Q and U
-                    ctx->tamp[l][1][j] = v; ctx->tamp[l][2][j] = v;
-                } else {
-                    ctx->tamp[l][k - 1][j] = v;
-                }
-            }
-        if (ctx->desc[l].type == DANGX_MONOPOLE)  // update_sky_model: self%offset = c%template_amplitudes(:,1), src/dang_data_mod.f90:357-361
-            for (int j = 0; j < ctx->hm.nbands; ++j) ctx->hm.offset[j] = ctx->tamp[l][0][j];
-    }
-    ctx->dirty = true;
-}
-
-// sum(a*b) over n entries -> host (deterministic two-stage reduction)
-int device_dot(dangx_ctx* ctx, const double* u, const double* v, long long n, long long ndot, double* out) {
-    const unsigned nblk = nblocks(n);
-    if (ensure_partial(ctx, nblk)) return 1;
-    hipLaunchKernelGGL(k_dot, dim3(nblk), dim3(BLOCK), 0, ctx->stream, u, v, n, ndot, ctx->partial);
-    return reduce_to_host(ctx, nblk, out);
+// sums of `rows` rows of block partials ([rows][nblk] in ctx->partial) -> host doubles, one block per row (deterministic order)
+int rows_to_host(dangx_ctx* ctx, long long nblk, int rows, double* out) {
+    hipLaunchKernelGGL(k_reduce_rows_final, dim3(rows), dim3(BLOCK), 0, ctx->stream, ctx->partial, nblk, rows, ctx->rows_out);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(out, ctx->rows_out, sizeof(double) * rows, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
 }
 
 // sum of host doubles over the ranks of a pixel-sharded run (dangx_set_allreduce); identity on a single rank
@@ -832,331 +655,6 @@ int rank_sum(dangx_ctx* ctx, double* buf, int64_t n) {
     if (ctx->allreduce(ctx->allreduce_user, buf, n)) return fail(ctx, "the all-reduce callback reported an error");
     return 0;
 }
-// the global rows at the tail of a device vector hold this rank's sums: make them the sums over all ranks
-int rank_sum_rows(dangx_ctx* ctx, double* tail_dev, int rows) {
-    if (!ctx->allreduce || rows <= 0) return 0;
-    std::vector<double> h(rows);
-    HIPCHK(ctx, hipMemcpyAsync(h.data(), tail_dev, sizeof(double) * rows, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (rank_sum(ctx, h.data(), rows)) return 1;
-    HIPCHK(ctx, hipMemcpyAsync(tail_dev, h.data(), sizeof(double) * rows, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return 0;
-}
-
-// cg_search on the device, src/dang_cg_mod.f90:179-324.  work[0]=x, [1]=r, [2]=d, [3]=q, [4]=b2, [5]=eta/b.
-// Groups with global-amplitude members use the mixed kernels; their vectors are [diffuse | global rows].
-int device_cg(dangx_ctx* ctx, const GroupArgs& a, int i_max, double converge, int* iters) {
-    const long long SN = (long long)flag_planes_h(a.flag) * ctx->hm.npix;
-    const long long n = SN * a.ng + a.nglob;
-    const bool mixed = a.nt > 0;
-    // pixel-sharded run: the diffuse entries are this rank's, the global rows are replicated (and summed over ranks
-    // wherever an operator produces them); dot products count the global rows on the root rank only
-    const long long ndot = ctx->is_root ? n : SN * a.ng;
-    if (ensure_work(ctx, n)) return 1;
-    if (ensure_partial(ctx, nblocks(n))) return 1;
-    double *x = ctx->work[0], *r = ctx->work[1], *d = ctx->work[2], *q = ctx->work[3], *b2 = ctx->work[4], *tmp = ctx->work[5];
-    hipStream_t st = ctx->stream;
-    auto Ax = [&](const double* in, double* out) -> int {
-        if (mixed ? dx_launch_Ax_mixed(ctx, a, SN, in, out) : dx_launch_Ax(ctx, a, SN, in, out, nullptr)) return 1;
-        return mixed ? rank_sum_rows(ctx, out + SN * a.ng, a.nglob) : 0;
-    };
-    // b = compute_rhs
-    if (mixed ? dx_launch_rhs_mixed(ctx, a, SN, tmp) : dx_launch_rhs(ctx, a, SN, tmp)) return 1;
-    if (mixed && rank_sum_rows(ctx, tmp + SN * a.ng, a.nglob)) return 1;
-    if (a.ml_mode == DANGX_ML_SAMPLE) {  // b2 = b + compute_sample_vector(eta)
-        hipLaunchKernelGGL(k_draw_eta, dim3(nblocks(SN)), dim3(BLOCK), 0, st, ctx->dm, a, r);
-        if (mixed ? dx_launch_sv_mixed(ctx, a, SN, r, q) : dx_launch_sample_vector(ctx, a, SN, r, q)) return 1;
-        if (mixed && rank_sum_rows(ctx, q + SN * a.ng, a.nglob)) return 1;
-        hipLaunchKernelGGL(k_cg_vec, dim3(nblocks(n)), dim3(BLOCK), 0, st, 3, n, n, 0.0, b2, nullptr, nullptr, q, tmp, nullptr);
-    } else {
-        HIPCHK(ctx, hipMemcpyAsync(b2, tmp, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st));
-    }
-    // x0 = current amplitudes (the reference keeps self%x; identical as amplitudes only change via unpack)
-    if (a.ng) hipLaunchKernelGGL(k_pack, dim3(nblocks(SN)), dim3(BLOCK), 0, st, ctx->dm, a, x, 0);
-    std::vector<double> xg;
-    if (mixed) {
-        globals_to_x(ctx, a, xg);
-        HIPCHK(ctx, hipMemcpyAsync(x + SN * a.ng, xg.data(), sizeof(double) * a.nglob, hipMemcpyHostToDevice, st));
-        HIPCHK(ctx, hipStreamSynchronize(st));
-    }
-    if (Ax(x, q)) return 1;
-    hipLaunchKernelGGL(k_cg_vec, dim3(nblocks(n)), dim3(BLOCK), 0, st, 0, n, ndot, 0.0, x, r, d, q, b2, ctx->partial);
-    double delta_new = 0.0, delta_old, dq = 0.0;
-    if (reduce_to_host(ctx, nblocks(n), &delta_new) || rank_sum(ctx, &delta_new, 1)) return 1;
-    int i = 1;
-    while (i < i_max && delta_new > converge) {
-        if (Ax(d, q)) return 1;
-        if (device_dot(ctx, d, q, n, ndot, &dq) || rank_sum(ctx, &dq, 1)) return 1;
-        const double alpha = delta_new / dq;
-        if (ensure_partial(ctx, nblocks(n))) return 1;
-        {
-            Timed t(ctx, DANGX_K_CG_VEC);
-            hipLaunchKernelGGL(k_cg_vec, dim3(nblocks(n)), dim3(BLOCK), 0, st, 1, n, ndot, alpha, x, r, d, q, b2, ctx->partial);
-        }
-        delta_old = delta_new;
-        if (reduce_to_host(ctx, nblocks(n), &delta_new) || rank_sum(ctx, &delta_new, 1)) return 1;
-        const double beta = delta_new / delta_old;
-        {
-            Timed t(ctx, DANGX_K_CG_VEC);
-            hipLaunchKernelGGL(k_cg_vec, dim3(nblocks(n)), dim3(BLOCK), 0, st, 2, n, n, beta, x, r, d, q, b2, nullptr);
-        }
-        i = i + 1;
-    }
-    if (a.ng) hipLaunchKernelGGL(k_pack, dim3(nblocks(SN)), dim3(BLOCK), 0, st, ctx->dm, a, x, 1);
-    if (mixed) {
-        HIPCHK(ctx, hipMemcpyAsync(xg.data(), x + SN * a.ng, sizeof(double) * a.nglob, hipMemcpyDeviceToHost, st));
-        HIPCHK(ctx, hipStreamSynchronize(st));
-        x_to_globals(ctx, a, xg);
-    }
-    if (iters) *iters = i;
-    return 0;
-}
-
-// Direct solve of a group with global-amplitude members: eliminate every (pixel, plane) block on the device
-// (pass 1), solve the nglob x nglob Schur system on the host, back-substitute per unit (pass 2).  The linear
-// system is the one cg_search iterates on (compute_rhs / compute_Ax / compute_sample_vector,
-// src/dang_cg_mod.f90:326-1096), quirks included; the answer is its exact solution instead of the iterate at i_max.
-// cs[0..nc): the contexts of this process that share the sky (shard order; nc = 1: dangx_amp_sample); as[r], SNs[r]: the
-// group as context r sees it.  Row sums are added over the contexts in shard order, then over the ranks (cs[0]'s callback);
-// the small system is solved once and every context gets the same global amplitudes.
-// defer: in, non-zero: the caller can run the back-substitution itself (together with the sweeps that follow: the plane-set kernel's
-// solve on the data minus the templates' new signal); out, non-zero: the new global amplitudes are in the model of every context
-// and pass 2 has NOT run -- granted only for a well-conditioned system, whose residual check is skipped (see below).
-int device_schur(dangx_ctx* const* cs, int nc, const GroupArgs* as, const long long* SNs, int64_t* n_not_spd, int* nullity, int* defer) {
-    dangx_ctx* ctx = cs[0];
-    const GroupArgs& a = as[0];
-    const int R = a.nglob, nb = ctx->hm.nbands;
-    auto each = [&](auto&& fn) -> int {  // fn(context, its group, its SN) on every context; the first error is the call's
-        for (int r = 0; r < nc; ++r)
-            if (fn(cs[r], as[r], SNs[r])) { if (cs[r] != ctx) ctx->err = cs[r]->err; return 1; }
-        return 0;
-    };
-    // rows_dev of every context -> host, added in shard order, then over the ranks
-    auto gather = [&](std::vector<double>& rows, int n) -> int {
-        std::vector<double> part((size_t)n);
-        std::fill(rows.begin(), rows.end(), 0.0);
-        for (int r = 0; r < nc; ++r) {
-            (void)hipSetDevice(cs[r]->device);
-            HIPCHK(ctx, hipMemcpyAsync(part.data(), cs[r]->work[0], sizeof(double) * n, hipMemcpyDeviceToHost, cs[r]->stream));
-            HIPCHK(ctx, hipStreamSynchronize(cs[r]->stream));
-            for (int q = 0; q < n; ++q) rows[q] += part[q];
-        }
-        return rank_sum(ctx, rows.data(), n);
-    };
-    auto set_globals = [&](const std::vector<double>& g) -> int {  // new global amplitudes + back-substitution everywhere
-        return each([&](dangx_ctx* c, const GroupArgs& ga, long long SN) -> int {
-            (void)hipSetDevice(c->device);
-            x_to_globals(c, ga, g);
-            return sync_model(c) || dx_launch_schur_pass2(c, ga, SN);
-        });
-    };
-    if (R > DX_MAX_ROWS) return fail(ctx, "more than 32 global amplitudes in one CG group: use DANGX_SOLVER_CG");
-    SchurArgs sa;
-    std::memset(&sa, 0, sizeof(sa));
-    sa.nrows = R;
-    for (int j = 0; j < MAXB; ++j) sa.bslot[j] = -1;
-    for (int t = 0; t < a.nt; ++t) {
-        const int l = a.tc[t];
-        int lf = 0;
-        for (int j = 0; j < nb && lf < ctx->nfit[l]; ++j)
-            if ((ctx->corr_mask[l] >> j) & 1) {
-                const int r = a.trow[t] + lf++;
-                sa.rt[r] = (unsigned char)t; sa.rj[r] = (unsigned char)j; sa.ftarget[r] = -1;
-            }
-    }
-    for (int j = 0; j < nb; ++j)
-        for (int r = 0; r < R; ++r)
-            if (sa.rj[r] == j && sa.bslot[j] < 0) sa.bslot[j] = (signed char)sa.nslots++;
-    int lrun = 0;  // the running row counter of compute_sample_vector (:970, :1057, :1071, :1094)
-    for (int j = 0; j < nb; ++j)
-        for (int t = 0; t < a.nt; ++t) {
-            const unsigned m = ctx->corr_mask[a.tc[t]];
-            if ((m >> j) & 1) {
-                int lt = 0;
-                for (int jj = 0; jj < j; ++jj) lt += (m >> jj) & 1;
-                if (lt < ctx->nfit[a.tc[t]] && lrun < R) sa.ftarget[a.trow[t] + lt] = (signed char)lrun;
-                ++lrun;
-            }
-        }
-    const int nrows = R * R + 3 * R;
-    if (each([&](dangx_ctx* c, const GroupArgs& ga, long long SN) -> int {  // enqueued on every device before any result is awaited
-            (void)hipSetDevice(c->device);
-            return ensure_work(c, std::max<long long>(nrows, 1)) || dx_launch_schur_pass1(c, ga, sa, SN, c->work[0]);
-        }))
-        return 1;
-    std::vector<double> rows(nrows);
-    if (gather(rows, nrows)) return 1;  // every context / rank then solves the same small system
-    unsigned long long bad_all = 0;
-    for (int r = 0; r < nc; ++r) {
-        unsigned long long bad = 0;
-        (void)hipSetDevice(cs[r]->device);
-        HIPCHK(ctx, hipMemcpyAsync(&bad, cs[r]->counters, sizeof(bad), hipMemcpyDeviceToHost, cs[r]->stream));
-        HIPCHK(ctx, hipStreamSynchronize(cs[r]->stream));
-        bad_all += bad;
-    }
-    if (n_not_spd) *n_not_spd = (int64_t)bad_all;
-    // S g = t (+ fluctuation sums).  S is not symmetric when a monopole is fitted (its row weight is 1, :857), so:
-    // Gaussian elimination, on the system equilibrated by G's diagonal (row amplitudes span ~1e-6 for hi_fit to ~1e2),
-    // for the CORRECTION to the current amplitudes, S d = t - S g0, with complete pivoting.  A remaining pivot at
-    // rounding level (1e-10 in units of G's diagonal, where 1 = nothing absorbed by the diffuse members) means the
-    // global rows are degenerate with the diffuse members -- a template fitted at every band beside a pixel-independent
-    // SED such as the CMB, or spatially constant index maps (the state a run starts from).  The normal equations stay
-    // consistent; the free directions keep their current value (d = 0 there), which is what the reference's CG does
-    // with them too (a Krylov iterate never moves along the null space).  nullity is reported through cg_iters.
-    std::vector<double> S(rows.begin(), rows.begin() + (size_t)R * R), t(rows.begin() + (size_t)R * R, rows.begin() + (size_t)R * R + R);
-    // fluctuation term of every row: the reference's through the running-counter mapping of compute_sample_vector, the textbook
-    // one (DANGX_FLUCT_CORRECT) on the natural rows
-    std::vector<double> fl(R, 0.0);
-    if (a.ml_mode == DANGX_ML_SAMPLE && a.fluct != DANGX_FLUCT_REFERENCE)
-        for (int r = 0; r < R; ++r) fl[r] = rows[(size_t)R * R + R + r];
-    else if (a.ml_mode == DANGX_ML_SAMPLE)
-        for (int r = 0; r < R; ++r)
-            if (sa.ftarget[r] >= 0) fl[sa.ftarget[r]] += rows[(size_t)R * R + R + r];
-    for (int r = 0; r < R; ++r) t[r] += fl[r];
-    std::vector<double> g0;
-    globals_to_x(ctx, a, g0);
-    std::vector<double> sc(R);
-    for (int r = 0; r < R; ++r) {
-        const double dg = std::fabs(rows[(size_t)R * R + 2 * R + r]);  // G[r][r] = sum_u w_r s_r / sigma^2, before elimination
-        if (!(dg > 0.0) || !std::isfinite(dg))
-            return fail(ctx, "global amplitude row " + std::to_string(r) + " of the CG group has no support (template zero or fully masked)");
-        sc[r] = 1.0 / std::sqrt(dg);
-    }
-    for (int r = 0; r < R; ++r) {
-        double v = t[r];
-        for (int k = 0; k < R; ++k) v -= S[(size_t)r * R + k] * g0[k];
-        t[r] = v;  // residual of the current amplitudes, as pass 1 sees it
-    }
-    for (int r = 0; r < R; ++r)
-        for (int k = 0; k < R; ++k) S[(size_t)r * R + k] *= sc[r] * sc[k];
-    // LU with complete pivoting, multipliers kept: rp / cp are the row / column permutations, rank the number of pivots
-    std::vector<int> rp(R), cp(R);
-    for (int c = 0; c < R; ++c) rp[c] = cp[c] = c;
-    int rank = 0;
-    for (int c = 0; c < R; ++c) {
-        int pr = c, pc = c;
-        double best = -1.0;
-        for (int r = c; r < R; ++r)
-            for (int k = c; k < R; ++k) {
-                const double v = std::fabs(S[(size_t)r * R + k]);
-                if (!std::isfinite(v)) return fail(ctx, "non-finite entry in the system of the global amplitudes");
-                if (v > best) { best = v; pr = r; pc = k; }
-            }
-        if (!(best > 1e-10)) break;
-        if (pr != c) {
-            for (int k = 0; k < R; ++k) std::swap(S[(size_t)pr * R + k], S[(size_t)c * R + k]);
-            std::swap(rp[pr], rp[c]);
-        }
-        if (pc != c) {
-            for (int r = 0; r < R; ++r) std::swap(S[(size_t)r * R + pc], S[(size_t)r * R + c]);
-            std::swap(cp[pc], cp[c]);
-        }
-        for (int r = c + 1; r < R; ++r) {
-            const double f = S[(size_t)r * R + c] / S[(size_t)c * R + c];
-            S[(size_t)r * R + c] = f;  // L below the diagonal
-            for (int k = c + 1; k < R; ++k) S[(size_t)r * R + k] -= f * S[(size_t)c * R + k];
-        }
-        ++rank;
-    }
-    // d = correction of the global amplitudes for a residual `res` of the (unscaled) global rows; free directions get 0
-    auto lu_solve = [&](const std::vector<double>& res, std::vector<double>& d) {
-        std::vector<double> y(R);
-        for (int r = 0; r < R; ++r) y[r] = res[rp[r]] * sc[rp[r]];
-        for (int r = 0; r < R; ++r)
-            for (int k = 0; k < std::min(r, rank); ++k) y[r] -= S[(size_t)r * R + k] * y[k];
-        std::vector<double> z(R, 0.0);
-        for (int r = rank - 1; r >= 0; --r) {
-            double v = y[r];
-            for (int k = r + 1; k < rank; ++k) v -= S[(size_t)r * R + k] * z[k];
-            z[r] = v / S[(size_t)r * R + r];
-        }
-        d.assign(R, 0.0);
-        for (int r = 0; r < rank; ++r) d[cp[r]] = z[r] * sc[cp[r]];
-    };
-    std::vector<double> d, g(R);
-    lu_solve(t, d);
-    for (int r = 0; r < R; ++r) g[r] = g0[r] + d[r];
-    if (nullity) *nullity = R - rank;
-    // A well-conditioned system needs no residual check: the entries of the equilibrated S are differences of per-unit terms of
-    // size <= 1 formed to a few ulp, so S is known to ~1e-15 absolute and the solution to ~1e-15 / (smallest pivot) -- the pivots
-    // of complete pivoting bound |S^-1| up to the growth factor of an R x R elimination.  With every pivot >= 1e-3 (the diffuse
-    // members absorb at most 99.9 % of any global row: a Q/U dust template beside synchrotron and dust; the near-degenerate fits
-    // -- a monopole beside the CMB -- have pivots of 1e-6 and below) the global rows' residual is <= 1e-12 of b without the
-    // check, which costs one more pass over the group's maps and a host round trip.  DANGX_SCHUR_CHECK=1 measures it always
-    // (tests/test_gpu_round4.py compares the two).
-    const char* chk = getenv("DANGX_SCHUR_CHECK");
-    double minpiv = 1.0;
-    for (int c = 0; c < rank; ++c) minpiv = std::min(minpiv, std::fabs(S[(size_t)c * R + c]));
-    // (Only for `template` members, whose amplitudes are of the size of the data -- tests/test_gpu_round4.py.  The bound is a backward
-    // error: relative to the size of a row's terms.  A monopole + hi_fit pair can sit at 1e-15 of its terms and 2e-9 of b with
-    // pivots of 1e-2, its amplitudes being 1e7 times the data -- seed 243 of a 300-seed run of tests/test_gpu_fuzz.py, where the
-    // measured figure is what the report must carry.  DANGX_SCHUR_SKIP=any extends the skip to every member type, for experiments.)
-    const char* skp = getenv("DANGX_SCHUR_SKIP");
-    bool templates_only = !(skp && skp[0] == 'a');
-    for (int t = 0; templates_only && t < a.nt; ++t) templates_only = ctx->desc[a.tc[t]].type == DANGX_TEMPLATE;
-    if (skp && skp[0] == 'a') templates_only = true;
-    const bool well = rank == R && minpiv >= 1e-3 && templates_only && !(chk && chk[0] == '1');
-    const bool deferred = well && defer && *defer;
-    if (defer) *defer = deferred ? 1 : 0;
-    if (deferred) {
-        if (each([&](dangx_ctx* c, const GroupArgs& ga, long long) -> int {
-                (void)hipSetDevice(c->device);
-                x_to_globals(c, ga, g);
-                return sync_model(c);
-            }))
-            return 1;
-    } else if (set_globals(g)) {
-        return 1;
-    }
-    if (well) {  // reported: the a-priori bound, no refinement step
-        const double bound = 16.0 * R * 2.220446049250313e-16 / minpiv;
-        for (int r = 0; r < nc; ++r) { cs[r]->schur_resid = bound; cs[r]->schur_backward = bound; cs[r]->schur_refine = 0; }
-        return 0;
-    }
-    // Residual check + iterative refinement.  Pass 1 forms S and t as sums of per-unit differences that cancel to the
-    // part of a global row the diffuse members do NOT absorb; when they absorb nearly all of it (a fitted monopole
-    // beside the CMB) S keeps only a few digits and S g = t is solved for a slightly wrong S.  The true residual of the
-    // global rows, r = b - A x evaluated directly at the new state (k_schur_resid: no elimination, no cancellation),
-    // drives the correction g += S^-1 r; the diffuse rows are re-solved exactly by pass 2.  The contraction factor is
-    // cond(S) * (relative error of S); the loop stops at 1e-12 of the row of b, or when a step no longer helps.
-    int refine = 0;
-    double prev = INFINITY, resid_b = 0.0, resid_bw = 0.0;
-    std::vector<double> rr(3 * R), res(R);
-    for (int step = 0; step <= 4; ++step) {
-        if (each([&](dangx_ctx* c, const GroupArgs& ga, long long SN) -> int {
-                (void)hipSetDevice(c->device);
-                return dx_launch_schur_resid(c, ga, sa, SN, c->work[0]);
-            }))
-            return 1;
-        if (gather(rr, 3 * R)) return 1;
-        double worst = 0.0, worst_bw = 0.0;
-        for (int r = 0; r < R; ++r) {
-            res[r] = rr[r] + fl[r];
-            const double brow = std::fabs(rr[R + r] + fl[r]);
-            // rows along a free (degenerate) direction cannot be reduced by the global amplitudes alone; they are
-            // consistent through the diffuse members, so their residual is reported like any other
-            worst = std::max(worst, std::fabs(res[r]) / std::max(brow, 1e-300));
-            worst_bw = std::max(worst_bw, std::fabs(res[r]) / std::max(rr[2 * R + r] + std::fabs(fl[r]), 1e-300));
-        }
-        if (step > 0 && !(worst < prev)) {  // the last correction did not help: take it back
-            for (int r = 0; r < R; ++r) g[r] -= d[r];
-            if (set_globals(g)) return 1;
-            refine -= 1;
-            break;
-        }
-        resid_b = prev = worst;
-        resid_bw = worst_bw;
-        if (worst <= 1e-12 || worst_bw <= 1e-15 || step == 4) break;
-        lu_solve(res, d);
-        for (int r = 0; r < R; ++r) g[r] += d[r];
-        if (set_globals(g)) return 1;
-        refine += 1;
-    }
-    for (int r = 0; r < nc; ++r) { cs[r]->schur_resid = resid_b; cs[r]->schur_backward = resid_bw; cs[r]->schur_refine = refine; }
-    return 0;
-}
-
 // host <-> device copy of `planes` maps of this shard.  The host side is either a packed [planes][npix] array or, after
 // dangx_set_host_stride, a window into full-sky arrays: plane q starts host_stride doubles after plane q-1.
 int copy_planes(dangx_ctx* ctx, void* dst, const void* src, size_t planes, bool to_device) {
@@ -1175,6 +673,25 @@ int copy_planes(dangx_ctx* ctx, void* dst, const void* src, size_t planes, bool 
 // element (plane q, pixel t) of a host map array under the current host layout
 inline double host_at(const dangx_ctx* ctx, const double* a, long long q, long long t) {
     return a[q * (ctx->host_stride > 0 ? ctx->host_stride : ctx->dims.npix) + t];
+}
+// whether pred holds for every pixel t >= from of plane q of a host map array (stops at the first that fails)
+template <class P>
+static bool plane_all(const dangx_ctx* ctx, const double* a, long long q, P&& pred, long long from = 0) {
+    for (long long t = from; t < ctx->dims.npix; ++t)
+        if (!pred(host_at(ctx, a, q, t))) return false;
+    return true;
+}
+// bit k: pred holds for every pixel of plane k of a host [nmaps][npix] array
+template <class P>
+static unsigned planes_where(const dangx_ctx* ctx, const double* a, P&& pred) {
+    unsigned bits = 0;
+    for (int k = 0; k < ctx->dims.nmaps; ++k)
+        if (plane_all(ctx, a, k, pred)) bits |= 1u << k;
+    return bits;
+}
+// ... and the planes that hold a non-zero value: those that are not zero everywhere
+static unsigned planes_nonzero(const dangx_ctx* ctx, const double* a) {
+    return ((1u << ctx->dims.nmaps) - 1u) & ~planes_where(ctx, a, [](double v) { return !(v != 0.0); });
 }
 
 int check_comp(dangx_ctx* ctx, int comp) {
@@ -1204,8 +721,6 @@ int ensure_state(dangx_ctx* ctx, int comp) {
 }
 
 // ======================================================================= C ABI
-
-static int seam_common(dangx_ctx* ctx, int group, int flag, GroupArgs& a, long long& SN, long long& n);
 
 extern "C" {
 
@@ -1411,10 +926,7 @@ int dangx_adopt_device_data(dangx_ctx* ctx, const double* sig, const double* rms
 int dangx_put_amplitude(dangx_ctx* ctx, int comp, const double* amp) {
     if (!ctx || !amp || check_comp(ctx, comp) || ensure_state(ctx, comp)) return 1;
     invalidate_chi(ctx);
-    ctx->plane_nz[comp] = 0;
-    for (int k = 0; k < ctx->dims.nmaps; ++k)
-        for (long long t = 0; t < ctx->dims.npix; ++t)
-            if (host_at(ctx, amp, k, t) != 0.0) { ctx->plane_nz[comp] |= 1u << k; break; }
+    ctx->plane_nz[comp] = planes_nonzero(ctx, amp);
     return copy_planes(ctx, ctx->amp[comp], amp, (size_t)ctx->dims.nmaps, true);
 }
 int dangx_get_amplitude(dangx_ctx* ctx, int comp, double* amp) {
@@ -1434,7 +946,7 @@ int dangx_put_indices(dangx_ctx* ctx, int comp, const double* ind) {
             for (int q = 0; q < ctx->desc[comp].nindices && cst; ++q) {
                 const long long pl = (long long)q * ctx->dims.nmaps + k;
                 const double m0 = host_at(ctx, ind, pl, 0);
-                for (long long t = 1; t < np; ++t) if (host_at(ctx, ind, pl, t) != m0) { cst = false; break; }
+                cst = plane_all(ctx, ind, pl, [m0](double v) { return !(v != m0); }, 1);
                 ctx->idx_val[comp][k][q] = m0;
             }
             if (cst) ctx->idx_const[comp] |= 1u << k;
@@ -1464,16 +976,8 @@ int dangx_set_template(dangx_ctx* ctx, int comp, const double* tmpl, const int32
     const size_t bytes = (size_t)ctx->dims.npix * ctx->dims.nmaps * sizeof(double);
     if (!ctx->tmpl[comp]) HIPCHK(ctx, hipMalloc(&ctx->tmpl[comp], bytes));
     if (copy_planes(ctx, ctx->tmpl[comp], tmpl, (size_t)ctx->dims.nmaps, true)) return 1;
-    ctx->tmpl_nz[comp] = 0;   // planes on which the template is identically zero carry none of its signal (a Q/U template on T)
-    for (int k = 0; k < ctx->dims.nmaps; ++k)
-        for (long long t = 0; t < ctx->dims.npix; ++t)
-            if (host_at(ctx, tmpl, k, t) != 0.0) { ctx->tmpl_nz[comp] |= 1u << k; break; }
-    ctx->tmpl_one[comp] = 0;
-    for (int k = 0; k < ctx->dims.nmaps; ++k) {
-        bool one = true;
-        for (long long t = 0; one && t < ctx->dims.npix; ++t) one = host_at(ctx, tmpl, k, t) == 1.0;
-        if (one) ctx->tmpl_one[comp] |= 1u << k;
-    }
+    ctx->tmpl_nz[comp] = planes_nonzero(ctx, tmpl);   // planes on which the template is identically zero carry none of its signal (a Q/U template on T)
+    ctx->tmpl_one[comp] = planes_where(ctx, tmpl, [](double v) { return v == 1.0; });
     ctx->corr_mask[comp] = mask; ctx->nfit[comp] = nfit;
     ctx->dirty = true;
     invalidate_chi(ctx);
@@ -1555,78 +1059,6 @@ void* dangx_indices_devptr(dangx_ctx* ctx, int comp) {
     return (ctx && comp >= 0 && comp < ctx->dims.ncomp && !ensure_state(ctx, comp)) ? ctx->idx[comp] : nullptr;
 }
 
-int64_t dangx_group_size(dangx_ctx* ctx, int group, int flag) {
-    GroupArgs a;
-    if (!ctx || make_group(ctx, group, flag, a)) return -1;
-    return (int64_t)a.ng * flag_planes_h(flag) * ctx->hm.npix + a.nglob;
-}
-
-int dangx_schur_info(dangx_ctx* ctx, double* rel_residual, int* refinements) {
-    if (!ctx) return 1;
-    if (rel_residual) { rel_residual[0] = ctx->schur_resid; rel_residual[1] = ctx->schur_backward; }
-    if (refinements) *refinements = ctx->schur_refine;
-    return 0;
-}
-
-int dangx_amp_residual(dangx_ctx* ctx, int group, int flag, int ml_mode, uint64_t seed, uint64_t stream, double* out) {
-    if (!ctx || !out) return 1;
-    (void)hipSetDevice(ctx->device);
-    if (ml_mode != DANGX_ML_SAMPLE && ml_mode != DANGX_ML_OPTIMIZE) return fail(ctx, "bad ml_mode");
-    GroupArgs a;
-    long long SN, n;
-    if (seam_common(ctx, group, flag, a, SN, n)) return 1;
-    a.ml_mode = ml_mode; a.fluct = DANGX_FLUCT_REFERENCE; a.seed = seed; a.stream = stream;
-    const bool mixed = a.nt > 0;
-    const long long ndiff = SN * a.ng;
-    double *x = ctx->work[0], *eta = ctx->work[1], *q = ctx->work[3], *b2 = ctx->work[4], *b = ctx->work[5];
-    hipStream_t st = ctx->stream;
-    if (mixed ? dx_launch_rhs_mixed(ctx, a, SN, b) : dx_launch_rhs(ctx, a, SN, b)) return 1;
-    if (mixed && rank_sum_rows(ctx, b + ndiff, a.nglob)) return 1;
-    if (ml_mode == DANGX_ML_SAMPLE) {
-        hipLaunchKernelGGL(k_draw_eta, dim3(nblocks(SN)), dim3(BLOCK), 0, st, ctx->dm, a, eta);
-        if (mixed ? dx_launch_sv_mixed(ctx, a, SN, eta, q) : dx_launch_sample_vector(ctx, a, SN, eta, q)) return 1;
-        if (mixed && rank_sum_rows(ctx, q + ndiff, a.nglob)) return 1;
-        hipLaunchKernelGGL(k_cg_vec, dim3(nblocks(n)), dim3(BLOCK), 0, st, 3, n, n, 0.0, b2, nullptr, nullptr, q, b, nullptr);
-    } else {
-        HIPCHK(ctx, hipMemcpyAsync(b2, b, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st));
-    }
-    if (a.ng) hipLaunchKernelGGL(k_pack, dim3(nblocks(SN)), dim3(BLOCK), 0, st, ctx->dm, a, x, 0);
-    std::vector<double> xg;
-    if (mixed) {
-        globals_to_x(ctx, a, xg);
-        HIPCHK(ctx, hipMemcpyAsync(x + ndiff, xg.data(), sizeof(double) * a.nglob, hipMemcpyHostToDevice, st));
-        HIPCHK(ctx, hipStreamSynchronize(st));
-    }
-    if (mixed ? dx_launch_Ax_mixed(ctx, a, SN, x, q) : dx_launch_Ax(ctx, a, SN, x, q, nullptr)) return 1;
-    if (mixed && rank_sum_rows(ctx, q + ndiff, a.nglob)) return 1;
-    double sums[2] = {0.0, 0.0};
-    if (ndiff > 0) {
-        const unsigned nblk = nblocks(ndiff);
-        if (ensure_partial(ctx, 2ll * nblk)) return 1;
-        hipLaunchKernelGGL(k_resid_norm, dim3(nblk), dim3(BLOCK), 0, st, ctx->dm, b2, q, ndiff, SN, ctx->partial);
-        hipLaunchKernelGGL(k_reduce_rows_final, dim3(2), dim3(BLOCK), 0, st, ctx->partial, (long long)nblk, 2, ctx->rows_out);
-        HIPCHK(ctx, hipGetLastError());
-        HIPCHK(ctx, hipMemcpyAsync(sums, ctx->rows_out, sizeof(sums), hipMemcpyDeviceToHost, st));
-        HIPCHK(ctx, hipStreamSynchronize(st));
-        if (rank_sum(ctx, sums, 2)) return 1;
-    }
-    double worst = 0.0;
-    if (a.nglob > 0) {
-        std::vector<double> bg(a.nglob), qg(a.nglob);
-        HIPCHK(ctx, hipMemcpyAsync(bg.data(), b2 + ndiff, sizeof(double) * a.nglob, hipMemcpyDeviceToHost, st));
-        HIPCHK(ctx, hipMemcpyAsync(qg.data(), q + ndiff, sizeof(double) * a.nglob, hipMemcpyDeviceToHost, st));
-        HIPCHK(ctx, hipStreamSynchronize(st));
-        for (int r = 0; r < a.nglob; ++r) {
-            const double res = bg[r] - qg[r];
-            sums[0] += res * res; sums[1] += bg[r] * bg[r];
-            worst = std::max(worst, std::fabs(res) / std::max(std::fabs(bg[r]), 1e-300));
-        }
-    }
-    out[0] = (sums[1] > 0.0) ? std::sqrt(sums[0] / sums[1]) : 0.0;
-    out[1] = worst;
-    return 0;
-}
-
 // local (this shard's) sum of c%indices(:, map_n, nind) over unmasked pixels and their number: mask_avg = sum / count
 int dangx_index_masked_sum(dangx_ctx* ctx, int comp, int nind, int map_n, double* sum, int64_t* count) {
     if (!ctx || !sum || !count || check_comp(ctx, comp)) return 1;
@@ -1637,11 +1069,8 @@ int dangx_index_masked_sum(dangx_ctx* ctx, int comp, int nind, int map_n, double
     const unsigned nblk = nblocks(ctx->hm.npix);
     if (ensure_partial(ctx, 2ll * nblk)) return 1;
     hipLaunchKernelGGL(k_index_masked_sum, dim3(nblk), dim3(BLOCK), 0, ctx->stream, ctx->dm, comp, nind, map_n, ctx->partial);
-    hipLaunchKernelGGL(k_reduce_rows_final, dim3(2), dim3(BLOCK), 0, ctx->stream, ctx->partial, (long long)nblk, 2, ctx->rows_out);
-    HIPCHK(ctx, hipGetLastError());
     double out[2] = {0.0, 0.0};
-    HIPCHK(ctx, hipMemcpyAsync(out, ctx->rows_out, sizeof(out), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (rows_to_host(ctx, nblk, 2, out)) return 1;
     *sum = out[0];
     *count = (int64_t)out[1];
     return 0;
@@ -1717,11 +1146,8 @@ int dangx_index_plain_sum(dangx_ctx* ctx, int comp, int nind, int map_n, double*
     const unsigned nblk = nblocks(ctx->hm.npix);
     if (ensure_partial(ctx, 2ll * nblk)) return 1;
     hipLaunchKernelGGL(k_index_plain_sum, dim3(nblk), dim3(BLOCK), 0, ctx->stream, ctx->dm, comp, nind, map_n, ctx->partial);
-    hipLaunchKernelGGL(k_reduce_rows_final, dim3(2), dim3(BLOCK), 0, ctx->stream, ctx->partial, (long long)nblk, 2, ctx->rows_out);
-    HIPCHK(ctx, hipGetLastError());
     double out[2] = {0.0, 0.0};
-    HIPCHK(ctx, hipMemcpyAsync(out, ctx->rows_out, sizeof(out), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (rows_to_host(ctx, nblk, 2, out)) return 1;
     *sum_index = out[0];
     *sum_mask = out[1];
     return 0;
@@ -1822,65 +1248,7 @@ int dangx_gain_sums(dangx_ctx* ctx, int band, double* out) {
     const unsigned nblk = nblocks(ctx->hm.npix);
     if (ensure_partial(ctx, 2ll * nblk)) return 1;
     hipLaunchKernelGGL(k_gain_rows, dim3(nblk), dim3(BLOCK), 0, ctx->stream, ctx->dm, band, ctx->partial);
-    hipLaunchKernelGGL(k_reduce_rows_final, dim3(1), dim3(BLOCK), 0, ctx->stream, ctx->partial, (long long)nblk, 2, ctx->rows_out);
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(out, ctx->rows_out, 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return 0;
-}
-
-// ---- secondary seams, host vectors ------------------------------------------------
-
-static int seam_common(dangx_ctx* ctx, int group, int flag, GroupArgs& a, long long& SN, long long& n) {
-    (void)hipSetDevice(ctx->device);
-    if (make_group(ctx, group, flag, a) || sync_model(ctx)) return 1;
-    SN = (long long)flag_planes_h(flag) * ctx->hm.npix;
-    n = SN * a.ng + a.nglob;
-    if (ensure_work(ctx, n)) return 1;
-    return 0;
-}
-
-int dangx_compute_rhs(dangx_ctx* ctx, int group, int flag, double* b) {
-    if (!ctx || !b) return 1;
-    GroupArgs a; long long SN, n;
-    if (seam_common(ctx, group, flag, a, SN, n)) return 1;
-    if (a.nt ? dx_launch_rhs_mixed(ctx, a, SN, ctx->work[0]) : dx_launch_rhs(ctx, a, SN, ctx->work[0])) return 1;
-    HIPCHK(ctx, hipMemcpyAsync(b, ctx->work[0], sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return 0;
-}
-
-int dangx_compute_Ax(dangx_ctx* ctx, int group, int flag, const double* x, double* res) {
-    if (!ctx || !x || !res) return 1;
-    GroupArgs a; long long SN, n;
-    if (seam_common(ctx, group, flag, a, SN, n)) return 1;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->work[0], x, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    if (a.nt ? dx_launch_Ax_mixed(ctx, a, SN, ctx->work[0], ctx->work[1]) : dx_launch_Ax(ctx, a, SN, ctx->work[0], ctx->work[1], nullptr)) return 1;
-    HIPCHK(ctx, hipMemcpyAsync(res, ctx->work[1], sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return 0;
-}
-
-int dangx_compute_sample_vector(dangx_ctx* ctx, int group, int flag, const double* eta, double* res) {
-    if (!ctx || !eta || !res) return 1;
-    GroupArgs a; long long SN, n;
-    if (seam_common(ctx, group, flag, a, SN, n)) return 1;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->work[0], eta, sizeof(double) * (size_t)SN, hipMemcpyHostToDevice, ctx->stream));
-    if (a.nt ? dx_launch_sv_mixed(ctx, a, SN, ctx->work[0], ctx->work[1]) : dx_launch_sample_vector(ctx, a, SN, ctx->work[0], ctx->work[1])) return 1;
-    HIPCHK(ctx, hipMemcpyAsync(res, ctx->work[1], sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return 0;
-}
-
-int dangx_eval_sed(dangx_ctx* ctx, int comp, int band, int map_n, double* out) {
-    if (!ctx || !out || check_comp(ctx, comp)) return 1;
-    (void)hipSetDevice(ctx->device);
-    if (band < 0 || band >= ctx->dims.nbands || map_n < 1 || map_n > ctx->dims.nmaps) return fail(ctx, "bad band/map");
-    if (sync_model(ctx) || ensure_work(ctx, ctx->hm.npix)) return 1;
-    hipLaunchKernelGGL(k_eval_sed, dim3(nblocks(ctx->hm.npix)), dim3(BLOCK), 0, ctx->stream, ctx->dm, comp, band, map_n, ctx->work[0]);
-    HIPCHK(ctx, hipMemcpyAsync(out, ctx->work[0], sizeof(double) * (size_t)ctx->hm.npix, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return 0;
+    return rows_to_host(ctx, nblk, 2, out);
 }
 
 // ---- profiling ---------------------------------------------------------------------

@@ -1,8 +1,10 @@
 // dx_host.h -- host-side context and launch-argument structs shared by the translation units of libdangx.so
-// (dangx_core.hip: context, model, chi^2 ring, host solvers, small kernels; dangx_entry.hip: the sampling entry points;
-// dangx_coarse.hip: full-sky / coarse-Nside device side; dangx_amp.hip: amplitude kernels of diffuse groups; dangx_mixed.hip /
-// dangx_schur.hip: groups with template-type members (mixed CG operators / direct Schur solve); dangx_mh.hip: LDS-form
-// Metropolis kernels; dangx_mhreg.hip: register-resident Metropolis kernels, compiled once per chain mode).
+// (dangx_core.hip: context, setters and getters, model, chi^2 ring, reductions, index sums, unit conversions, profile;
+// dangx_solve.hip: the two linear solvers, device_cg and device_schur, and the seams of their operators -- the host algebra of the
+// direct solve in dx_schur_host.h; dangx_entry.hip: the sampling entry points; dangx_coarse.hip: full-sky / coarse-Nside device
+// side; dangx_sky.hip: the sky-wide chains; dangx_amp.hip: amplitude kernels of diffuse groups; dangx_mixed.hip / dangx_schur.hip:
+// groups with template-type members (mixed CG operators / direct Schur solve); dangx_mh.hip: LDS-form Metropolis kernels;
+// dangx_mhreg.hip: register-resident Metropolis kernels, compiled once per chain mode).
 // The context holds state that outlives a call: the model, the buffers, and what is known about them (which cached chi^2 values and
 // index sums are valid, which planes carry a signal, which index maps are constant or equal on Q and U).  Nothing in it passes
 // arguments from one function of a call to another.  The small helpers every entry point shares live here too: flag -> planes
@@ -20,6 +22,7 @@
 
 #include "../../include/dangx.h"
 #include "dx_args.h"
+#include "dx_schur_host.h"
 
 struct DxMoments;   // posterior-moment accumulators (dx_moments_state.h: written by dangx_moments.hip, read by dangx_chains.hip)
 
@@ -237,7 +240,7 @@ void dx_reduce_rows_to(dangx_ctx* ctx, const double* partial, unsigned nblk, int
 constexpr int DX_RSTAGE = 128;
 void dx_reduce_two_stage(dangx_ctx* ctx, const double* partial, long long n, double* stage, double* out_dev);
 
-// ---- host helpers of dangx_core.hip used by the other translation units of the ABI
+// ---- host helpers of dangx_core.hip / dangx_solve.hip used by the other translation units of the ABI
 int sync_model(dangx_ctx* ctx);                 // host model -> device copy when something changed (constant-index rows, bandpass tables)
 int prof_collect(dangx_ctx* ctx);
 void dx_moments_free(dangx_ctx* ctx);           // dangx_moments.hip: release the posterior-moment accumulators
@@ -250,12 +253,13 @@ int dx_set_chi_after(dangx_ctx* ctx, int k, double chi);   // dangx_entry.hip
 int chi_flush(dangx_ctx* ctx);                  // reduce every pending launch's chi^2 / index-sum partials into chi_cache
 int chi_next(dangx_ctx* ctx, long long nblk, double** buf);
 int reduce_to_host(dangx_ctx* ctx, long long nblk, double* out);
+int rows_to_host(dangx_ctx* ctx, long long nblk, int rows, double* out);   // [rows][nblk] block partials in ctx->partial -> their sums
 int rank_sum(dangx_ctx* ctx, double* buf, int64_t n);
-int device_cg(dangx_ctx* ctx, const GroupArgs& a, int i_max, double converge, int* iters);
+int device_cg(dangx_ctx* ctx, const GroupArgs& a, int i_max, double converge, int* iters);   // dangx_solve.hip
 extern "C" int dx_fullsky_prepare_lazy(dangx_ctx* ctx, int comp, int map_n);   // dangx_fullsky_prepare without the staging pass (dangx_coarse.hip)
 extern "C" int dx_fullsky_coarse_model(dangx_ctx* ctx, int comp, int nind);   // DANGX_COARSE_DEGRADED: the coarse full-sky sums on the degraded amplitude (dangx_coarse.hip)
 double dx_host_band_sed(dangx_ctx* ctx, int comp, int j, double t0, double t1);   // eval_sed of a diffuse component, host side
-int device_schur(dangx_ctx* const* cs, int nc, const GroupArgs* as, const long long* SNs, int64_t* n_not_spd, int* nullity, int* defer = nullptr);
+int device_schur(dangx_ctx* const* cs, int nc, const GroupArgs* as, const long long* SNs, int64_t* n_not_spd, int* nullity, int* defer = nullptr);   // dangx_solve.hip
 // map_n of sample_index_mh (src/dang_sample_mod.f90:53-64) -> first and last map plane
 inline int map_planes(dangx_ctx* ctx, int map_n, int& s1, int& s2) {
     if (map_n == -1) { s1 = 2; s2 = 3; }
@@ -307,22 +311,12 @@ int dx_launch_amp(dangx_ctx* ctx, const GroupArgs& a, long long SN);
 int dx_launch_amp_reg(dangx_ctx* ctx, const GroupArgs& a, long long SN);
 int dx_launch_chisq_reg(dangx_ctx* ctx, int k, double* partial);  // dangx_ampreg.hip
 int dx_launch_amp_reg_templates(dangx_ctx* ctx, const GroupArgs& a, long long SN);  // pass 2 of a template group's Schur solve
-struct SchurArgs;
 int dx_launch_schur_resid_reg(dangx_ctx* ctx, const GroupArgs& a, const SchurArgs& sa, long long SN, double* rows_dev);  // its residual pass
 int dx_launch_schur_pass1_reg(dangx_ctx* ctx, const GroupArgs& a, const SchurArgs& sa, long long SN, double* rows_dev);  // its pass 1
 int dx_launch_rhs(dangx_ctx* ctx, const GroupArgs& a, long long SN, double* b);
 int dx_launch_Ax(dangx_ctx* ctx, const GroupArgs& a, long long SN, const double* x, double* res, double* part);
 int dx_launch_sample_vector(dangx_ctx* ctx, const GroupArgs& a, long long SN, const double* eta, double* res);
-// direct (Schur complement) solve of a group with global-amplitude members; rows <= DX_MAX_ROWS
-constexpr int DX_MAX_ROWS = 32;
-struct SchurArgs {
-    int nrows;
-    unsigned char rt[DX_MAX_ROWS], rj[DX_MAX_ROWS];  // row r <-> (global member rt[r], band rj[r])
-    signed char ftarget[DX_MAX_ROWS];                // row that receives row r's fluctuation sum (running counter of
-                                                     // compute_sample_vector, src/dang_cg_mod.f90:970-1094); -1 = dropped
-    signed char bslot[MAXB];                         // LDS slot of band j (-1: no global row at that band)
-    int nslots;
-};
+// direct (Schur complement) solve of a group with global-amplitude members (SchurArgs, DX_MAX_ROWS: dx_schur_host.h)
 int dx_launch_schur_pass1(dangx_ctx* ctx, const GroupArgs& a, const SchurArgs& sa, long long SN, double* rows_dev);
 int dx_launch_schur_pass2(dangx_ctx* ctx, const GroupArgs& a, long long SN);
 // rows_dev[0..R): global rows of b - A x at the current state (without the fluctuation term); [R..2R): those rows of b

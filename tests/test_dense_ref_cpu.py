@@ -13,6 +13,7 @@ from dang_amd import _lib as L
 import dense_ref as D
 import oracle_ffi as O
 from test_oracle_templates_cpu import add_globals
+from test_schur_host_cpu import host_solve, schur_exe  # noqa: F401  (schur_exe: the fixture that builds the stand-alone program)
 from util import make_case
 
 GLOBAL_TYPES = ("template", "monopole", "hi_fit")
@@ -218,9 +219,10 @@ def test_checker_sees_a_fluctuation_term_on_the_neighbouring_global_row():
 
 
 def host_lu(S, t, g0, diag, unscaled_row=None):
-    """The host solve of device_schur (dang_amd/csrc/dangx_core.hip) restated: the correction to g0 from the system equilibrated
-    by the global block's diagonal, LU with complete pivoting, pivots below 1e-10 left alone.  unscaled_row: that row of S misses
-    its 1/sqrt(diag) -- the equilibration half applied.  Returns (g, rank)."""
+    """The generator of the mutant below, not the code under test: the host solve of device_schur (dang_amd/csrc/dx_schur_host.h,
+    which tests/test_schur_host_cpu.py and the "whole" leg below run as it is) restated so that one step of it can be left out --
+    the correction to g0 from the system equilibrated by the global block's diagonal, LU with complete pivoting, pivots below 1e-10
+    left alone.  unscaled_row: that row of S misses its 1/sqrt(diag) -- the equilibration half applied.  Returns (g, rank)."""
     R = len(t)
     S = np.array(S, dtype=np.float64)
     sc = 1.0 / np.sqrt(np.abs(np.asarray(diag, dtype=np.float64)))
@@ -256,9 +258,11 @@ def host_lu(S, t, g0, diag, unscaled_row=None):
     return g0 + d, rank
 
 
-def test_checker_sees_a_half_applied_equilibration_of_the_host_solve():
-    """The host LU on the float64 Schur system, followed by the back-substitution, is within the bound; the same with the
-    equilibration of one row dropped from the matrix (but not from the right-hand side) is not."""
+def test_checker_sees_a_half_applied_equilibration_of_the_host_solve(schur_exe):
+    """The host LU of dx_schur_host.h (the real code, in its stand-alone program) on the float64 Schur system, followed by the
+    back-substitution, is within the bound; the restated solve with the equilibration of one row dropped from the matrix (but not
+    from the right-hand side) is not.  The restated solve without the mutation is the real one to within the bound's share of
+    every global row."""
     case, group, flag, ref = _well_posed("optimize")
     A, b, R = ref["A"], ref["b"], ref["nrows"]
     m = A.shape[0] - R
@@ -266,8 +270,11 @@ def test_checker_sees_a_half_applied_equilibration_of_the_host_solve():
     S = (A[m:, m:] - A[m:, :m].astype(D.LD) @ X[:, :R]).astype(np.float64)
     t = (b[m:] - A[m:, :m].astype(D.LD) @ X[:, R]).astype(np.float64)
     out = {}
-    for which, row in (("whole", None), ("half", 1)):
-        g, rank = host_lu(S, t, np.zeros(R), np.diag(A)[m:], unscaled_row=row)
+    real, real_rank, _ = host_solve(schur_exe, S, t, np.zeros(R), np.diag(A)[m:])
+    restated, restated_rank = host_lu(S, t, np.zeros(R), np.diag(A)[m:])
+    assert restated_rank == real_rank
+    assert (np.abs(restated - real) <= ref["bound"][m:].astype(np.float64)).all(), (restated, real)
+    for which, (g, rank) in (("whole", (real, real_rank)), ("half", host_lu(S, t, np.zeros(R), np.diag(A)[m:], unscaled_row=1))):
         assert rank == R
         x = np.concatenate([(X[:, R] - X[:, :R] @ g.astype(D.LD)), g.astype(D.LD)])
         out[which] = worst_ratio(x, ref)

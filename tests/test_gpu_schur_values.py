@@ -33,7 +33,7 @@ pytestmark = pytest.mark.gpu
 
 ML_MODES = ("optimize", "sample")
 SHARD_BOUNDS = (0, 37, 101, 192)          # Nside 4: three unequal shards, no boundary a multiple of 64
-# quoted from device_schur (dang_amd/csrc/dangx_core.hip): the switch on the smallest pivot, and the residual it promises
+# quoted from device_schur (dang_amd/csrc/dangx_solve.hip): the switch on the smallest pivot, and the residual it promises
 MINPIV_SWITCH, SKIP_RESIDUAL = 1e-3, 1e-12
 
 
