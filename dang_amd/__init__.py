@@ -11,7 +11,7 @@ from .api import (BandInfo, DangCGGroup, DangComps, DangData, DangParams, DangxE
                   sample_index_mh_fullsky, sample_spectral_parameters, stream_id, tune_perpixel, fusable_first_sweeps, plan_plane_sets, sky_amp_sample, sky_plane_set_sample)
 from .posterior import (default_moment_selection, moments_begin, moments_accumulate, posterior_maps,  # noqa: F401
                         default_moment_pairs, moments_pairs, posterior_pair_maps,
-                        default_hist_planes, moments_hist, posterior_quantile_maps,
+                        default_hist_planes, moments_hist, posterior_quantile_maps, hist_ranges_from_moments,
                         default_signal_specs, moments_signals, posterior_signal_maps,
                         chains_get, chains_get_template, chains_get_signal, chains_get_pair, chains_hist_stat, open_chain,
                         chains_posterior_maps, chains_pair_maps, chains_quantile_maps, chains_signal_maps, chains_hist_rank, chains_rank_maps,

@@ -34,13 +34,14 @@ MAX_PAIRS = 64
 HIST_STAT_CODES = {"quantile": 0, "mode": 1, "n": 2}
 RANK_STAT_CODES = {"bulk": 0, "folded": 1, "max": 2}
 MAX_HIST, MAX_HIST_Q = 32, 16
+HIST_SIGNAL = -1                          # planes[r] = (sig, HIST_SIGNAL, 0): a histogram that reads registered signal sig
 MAX_SIGNALS = 64
 MAX_CHAINS = 8
 CHAINS_STAT_CODES = {"mean": 0, "std": 1, "rhat": 2, "W": 3, "B": 4, "ess": 5}
 BATCH_STAT_CODES = {"mean": 0, "std": 1, "mcse": 2, "ess_bm": 3, "split_rhat": 4}
 MAX_BATCHES, MAX_BATCH_PLANES = 32, 32
-SEC_HEAD, SEC_PLANES, SEC_PAIR, SEC_HIST, SEC_SIGNAL, SEC_BATCHES = range(6)   # family of a section
-SECTION_NAMES = ("HEAD", "PLANES", "PAIR", "HIST", "SIGNAL", "BATCHES")
+SEC_HEAD, SEC_PLANES, SEC_PAIR, SEC_HIST, SEC_SIGNAL, SEC_BATCHES, SEC_HIST_RANGE = range(7)   # family of a section
+SECTION_NAMES = ("HEAD", "PLANES", "PAIR", "HIST", "SIGNAL", "BATCHES", "HIST_RANGE")
 # a PLANES section of pixel planes is equal parts: mean and m2, and with lag-1 tracking three more behind them (include/dangx.h)
 PLANES_MOMENT_PARTS, PLANES_LAG1_PARTS = 2, 5
 SECTION_HEAD_BYTES = 104
@@ -175,6 +176,10 @@ SYMBOLS = {
     "dangx_moments_hist_get_dev": (C.c_int, [_P, C.c_int, _P]),
     "dangx_moments_hist_stat": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "dangx_moments_hist_stat_dev": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "dangx_moments_hist_range_maps": (C.c_int, [_P, C.c_int, _P, _P]),
+    "dangx_moments_hist_range_maps_dev": (C.c_int, [_P, C.c_int, _P, _P]),
+    "dangx_moments_hist_range_get": (C.c_int, [_P, C.c_int, _P, _P]),
+    "dangx_moments_hist_range_get_dev": (C.c_int, [_P, C.c_int, _P, _P]),
     "dangx_moments_signals": (C.c_int, [_P, C.c_int, _P]),
     "dangx_moments_get_signal": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
     "dangx_moments_get_signal_dev": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),

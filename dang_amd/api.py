@@ -198,6 +198,11 @@ def _hist_stat_args(who, npix, reg, stat, q):
     return ((qa.size, npix) if st == 0 else (npix,)), (int(reg), st, qa.size, qp)
 
 
+def _is_range_maps(r):
+    """a histogram range given as a pair of per-pixel maps (arrays or tensors) rather than as two numbers"""
+    return r is not None and len(r) == 2 and (_is_torch(r[0]) or np.ndim(r[0]) >= 1)
+
+
 def _sec_family(family):
     return L.SECTION_NAMES.index(family) if isinstance(family, str) else int(family)
 
@@ -686,6 +691,7 @@ class Engine:
     def moments_begin(self, sel=None):
         """Start (or restart) accumulating: sel[l] = selection word of component l (include/dangx.h; None = every plane)."""
         self._clear_mirror()                                # dangx_moments_begin drops every registration made before it
+        self._moment_holder = False
         self._moment_pairs, self._moment_lag1 = [], False
         if sel is None:
             self._chk(self.lib.dangx_moments_begin(self.h, None))
@@ -749,27 +755,65 @@ class Engine:
         """Register per-pixel histograms after moments_begin and before the first moments_accumulate: planes = [(l, what, plane), ...]
         (what / plane as in moments_pairs), ranges = [(lo, hi) or None, ...] or None (None = the default: an index plane's
         uni_prior; an amplitude plane has none), nbins in {8, 16, 32, 64} counters of bits in {16, 32} per pixel, nbins * bits / 8
-        <= 128.  A second call replaces the first.  Definitions: include/dangx.h.
+        <= 128.  A ranges[r] may also be a pair of maps (lo, hi), arrays or torch tensors [npix] of this shard: a per-pixel
+        range -- a pixel whose bounds are NaN (a masked one), not finite or not hi > lo counts nothing and reads as NaN.  The
+        library copies the maps; moments_hist_range_get returns them.  A second call replaces the first.  Definitions:
+        include/dangx.h.  The mirror `_moment_hist` records the kind of every range ("kinds": 'global' | 'pixel'; a per-pixel
+        range's entry in "ranges" is None).  A planes[r] may be ("signal", s): the histogram reads registered signal s of
+        moments_signals (any kind, P included), filled by the signal launch itself; it has no default range.  The mirror holds it
+        as (s, -1, 0) in "planes" and as 'signal' in "sources" (else 'plane').
         The range this object reports for a default (`_moment_hist["ranges"]`, posterior_quantile_maps' "range") is the
         component's uni_prior as comp_desc() writes it into the descriptor -- what the library takes when the descriptor has not
         been replaced through dangx_set_component with other bounds since this Engine was built; pass explicit ranges otherwise."""
-        p = np.ascontiguousarray(np.asarray(list(planes), dtype=np.int32).reshape(-1, 3))
+        planes = [(int(pl[1]), L.HIST_SIGNAL, 0) if isinstance(pl[0], str) and pl[0] == "signal" else tuple(pl) for pl in planes]
+        p = np.ascontiguousarray(np.asarray(planes, dtype=np.int32).reshape(-1, 3))
         rp = None
         if ranges is not None:
             ranges = list(ranges)
             assert len(ranges) == p.shape[0]
-            rg = np.array([(np.nan, np.nan) if r is None else (float(r[0]), float(r[1])) for r in ranges], dtype=np.float64).reshape(-1, 2)
+            rg = np.array([(np.nan, np.nan) if r is None else (-np.inf, np.inf) if _is_range_maps(r) else (float(r[0]), float(r[1]))
+                           for r in ranges], dtype=np.float64).reshape(-1, 2)
             rp = np.ascontiguousarray(rg)
+        maps = {r: ranges[r] for r in range(p.shape[0]) if ranges is not None and _is_range_maps(ranges[r])}
         self._chk(self.lib.dangx_moments_hist(self.h, p.shape[0], p.ctypes.data if p.size else None,
                                               rp.ctypes.data if rp is not None and rp.size else None, int(nbins), int(bits)))
         eff = []
+        pixel = [r in maps or (rp is not None and rp[r, 0] == -np.inf and rp[r, 1] == np.inf) for r in range(p.shape[0])]
         for r, (l, what, k) in enumerate(p):
-            if rp is not None and not np.isnan(rp[r, 0]):
+            if pixel[r]:                                    # maps, or the library's own way to declare them (hand them in afterwards)
+                eff.append(None)
+            elif rp is not None and not np.isnan(rp[r, 0]):
                 eff.append((float(rp[r, 0]), float(rp[r, 1])))
             else:
                 up = comp_desc(self.component_list[l]).uni_prior[what - 1]      # the descriptor's own words
                 eff.append((float(up[0]), float(up[1])))
-        self._moment_hist = {"planes": [tuple(int(v) for v in r) for r in p], "ranges": eff, "nbins": int(nbins), "bits": int(bits)}
+        self._moment_hist = {"planes": [tuple(int(v) for v in r) for r in p], "ranges": eff, "nbins": int(nbins), "bits": int(bits),
+                             "kinds": ["pixel" if px else "global" for px in pixel],
+                             "sources": ["signal" if int(r[1]) == L.HIST_SIGNAL else "plane" for r in p]}
+        for r, (lo, hi) in maps.items():
+            self.moments_hist_range_maps(r, lo, hi)
+
+    def moments_hist_range_maps(self, reg, lo, hi):
+        """Hand in the per-pixel range of registration reg, which moments_hist declared with a pair of maps (or the library's
+        range (-inf, +inf)): lo, hi = arrays or torch tensors [npix] of this shard; cuda tensors go through the device form.
+        Legal before the first moments_accumulate; a second call replaces the first."""
+        dev = _is_torch(lo) and lo.is_cuda and _is_torch(hi) and hi.is_cuda
+        if dev:
+            import torch
+            lo, hi = (t.to(torch.float64).contiguous() for t in (lo, hi))
+            assert tuple(lo.shape) == tuple(hi.shape) == (self.npix,)
+            torch.cuda.current_stream(lo.device).synchronize()          # the maps exist before the context's stream copies them
+            self._chk(self.lib.dangx_moments_hist_range_maps_dev(self.h, int(reg), lo.data_ptr(), hi.data_ptr()))
+            return
+        lo, hi = (np.ascontiguousarray(t.cpu().numpy() if _is_torch(t) else t, dtype=np.float64) for t in (lo, hi))
+        assert lo.shape == hi.shape == (self.npix,)
+        self._chk(self.lib.dangx_moments_hist_range_maps(self.h, int(reg), lo.ctypes.data, hi.ctypes.data))
+
+    def moments_hist_range_get(self, reg, device=False):
+        """(lo, hi) of registration reg as [npix] maps of this shard: the maps of a per-pixel range as they were handed in, the
+        two numbers of a global range spread over the shard.  device=True: torch cuda tensors."""
+        lo, pl = _readout_dest(self, (self.npix,), device)
+        return lo, self._readout("dangx_moments_hist_range_get", (self.npix,), (int(reg), pl), device)
 
     def _hist_shape(self):
         h = _registration(self, "hist", None, "moments_hist")
@@ -873,6 +917,7 @@ class Engine:
         allocates no accumulators; sections put into it (moments_section_put) serve the chains_* read-outs, at any position of
         their list.  moments_accumulate and the single-chain read-outs refuse a holder.  Calling it again drops what is held."""
         self._chk(self.lib.dangx_moments_begin_like(self.h, like.h))
+        self._moment_holder = True
         import copy
         for name in MOMENT_ATTRS:
             setattr(self, name, copy.deepcopy(getattr(like, name, None)))

@@ -176,6 +176,17 @@ __global__ __launch_bounds__(BLOCK) void k_chains_hist(ChainsHistArgs a) {
     dx_hist_readout<unsigned long long>(a, [&](long long i, auto f) { chains_hist_walk(a, i, pieces, f); });
 }
 
+struct ChainsHistPxArgs : ChainsHistArgs {
+    const double* lo_map;   // [n]: the registration's range maps (chain 0's: the same in every chain) in place of lo, hi
+    const double* hi_map;
+};
+
+// k_chains_hist of a registration with per-pixel ranges (quantiles and the mode; N needs no range and goes through k_chains_hist)
+__global__ __launch_bounds__(BLOCK) void k_chains_hist_px(ChainsHistPxArgs a) {
+    const int pieces = dx_hist_words(a.nbins, a.bits) / 4;
+    dx_hist_readout_impl<true, unsigned long long>(a, [&](long long i, auto f) { chains_hist_walk(a, i, pieces, f); });
+}
+
 struct ChainsRankArgs {
     const uint32_t* rec[DX_CHAINS_MAX];
     double* out;          // [n]
@@ -525,11 +536,12 @@ int chains_hist_same(dangx_ctx* const* ctxs, int nchains, int reg) {
         bool same = reg < (int)m->hists.size() && m->hbins == m0->hbins && m->hbits == m0->hbits;
         if (same) {
             const auto &h = m->hists[reg], &h0 = m0->hists[reg];
-            same = same_plane(m->segs[h.seg], m0->segs[h0.seg]) && h.lo == h0.lo && h.hi == h0.hi;
+            same = h.sig == h0.sig && (h.sig >= 0 || same_plane(m->segs[h.seg], m0->segs[h0.seg])) && h.lo == h0.lo && h.hi == h0.hi && h.kind == h0.kind && h.sum == h0.sum;
         }
         if (!same)
             return chains_fail(ctxs, "chain " + std::to_string(k) + ": histogram registration " + std::to_string(reg) +
-                                         " is not the registration of chain 0 (plane, lo, hi, nbins and bits must agree)");
+                                         " is not the registration of chain 0 (plane, lo, hi, nbins and bits must agree, and with per-pixel "
+                                         "ranges the checksum of the range maps)");
     }
     return 0;
 }
@@ -553,6 +565,15 @@ int chains_hist_impl(dangx_ctx* const* ctxs, int nchains, int reg, int stat, int
     a.out = ro.dst; a.lo = m0->hists[reg].lo; a.hi = m0->hists[reg].hi; a.n = c0->dims.npix;
     a.K = cs.K; a.nbins = m0->hbins; a.bits = m0->hbits; a.stat = stat; a.nq = stat == 0 ? nq : 0;
     for (int j = 0; j < a.nq; ++j) a.q[j] = q[j];
+    const auto& h0 = m0->hists[reg];
+    if (h0.kind == DX_HIST_RANGE_PIXEL && stat != 2) {   // quantiles and the mode need the pixels' bounds (chain 0's maps); N does not
+        ChainsHistPxArgs ap{};
+        static_cast<ChainsHistArgs&>(ap) = a;
+        ap.lo_map = m0->range_lo(h0); ap.hi_map = m0->range_hi(h0);
+        if (!ap.lo_map) return chains_missing(ctxs, 0, "HIST_RANGE(" + std::to_string(reg) + ")");
+        if (chains_run(cs, [&] { hipLaunchKernelGGL(k_chains_hist_px, dim3(c0->mom->grid_for(a.n, 1)), dim3(BLOCK), 0, c0->stream, ap); })) return 1;
+        return ro.close(total);
+    }
     if (chains_run(cs, [&] { hipLaunchKernelGGL(k_chains_hist, dim3(c0->mom->grid_for(a.n, 1)), dim3(BLOCK), 0, c0->stream, a); })) return 1;
     return ro.close(total);
 }

@@ -29,6 +29,9 @@
 // registration) behind the moments': the thread that read a pixel's x loads, increments and stores the ONE 32-bit word holding the
 // bin -- no atomics, a pixel's record belongs to one thread -- and a sample outside the range touches no record.  k_hist_stat
 // reads a record as 16-byte pieces and leaves quantiles, the mode or the count of counted samples.  Nothing registered: no launch.
+// A registration may instead take its range per pixel from two f64 maps (dangx_moments_hist_range_maps): those registrations go
+// into one launch of k_moments_hist_px, which streams lo and hi beside x and forms the bin with the pixel's own bounds, and are
+// read by k_hist_stat_px; k_moments_hist and k_hist_stat stay what they were for the registrations with one range per shard.
 //
 // dangx_moments_signals adds the moments of component signals at a band (definitions in dx_signal_host.h): the sample
 // comp_signal(band, pix, plane) = amplitude * sed(indices) of a diffuse component -- what write_maps' output_fg maps hold
@@ -62,7 +65,7 @@
 #include <memory>
 
 static_assert(DX_MOM_MAX_PAIRS == DANGX_MAX_PAIRS, "dx_moments_host.h and include/dangx.h disagree");
-static_assert(DX_HIST_MAX == DANGX_MAX_HIST, "dx_hist_host.h and include/dangx.h disagree");
+static_assert(DX_HIST_MAX == DANGX_MAX_HIST && DX_HIST_SIGNAL == DANGX_HIST_SIGNAL, "dx_hist_host.h and include/dangx.h disagree");
 static_assert(DX_SIG_MAX == DANGX_MAX_SIGNALS, "dx_signal_host.h and include/dangx.h disagree");
 static_assert(DX_SEC_HEAD_BYTES == DANGX_SECTION_HEAD_BYTES, "dx_section_host.h and include/dangx.h disagree");
 static_assert(DX_BATCH_MAX == DANGX_MAX_BATCHES && DX_BATCH_MAX_PLANES == DANGX_MAX_BATCH_PLANES, "dx_batches_host.h and include/dangx.h disagree");
@@ -172,6 +175,31 @@ __global__ __launch_bounds__(BLOCK) void k_moments_hist(const HistSeg* __restric
               });
 }
 
+// hist_one with the pixel's own bounds (dx_hist_pixel_bin: the scale is one IEEE division per sample; an off pixel counts nothing)
+__device__ __forceinline__ void hist_one_px(const HistPxSeg& s, int words, long long i, double x, double lo, double hi) {
+    const int b = dx_hist_pixel_bin(x, lo, hi, s.nbins);
+    if (b < 0) return;
+    GU32* w = (GU32*)s.rec + i * words + dx_hist_word_of(b, s.bits);
+    *w = *w + dx_hist_one(b, s.bits);
+}
+
+// k_moments_hist for the registrations with per-pixel ranges (a launch of its own, only when there are any): lo and hi stream
+// beside x, 16 more bytes per pixel, as pairs where the three share their 16-byte phase (the library allocates the maps at the
+// phase of the segment's accumulators, which dangx_moments_begin lays out at the phase the chain's plane had then) and element by element otherwise
+__global__ __launch_bounds__(BLOCK) void k_moments_hist_px(const HistPxSeg* __restrict__ segs) {
+    const HistPxSeg s = segs[blockIdx.y];
+    const int words = dx_hist_words(s.nbins, s.bits);
+    const uintptr_t ax = addr(s.x);
+    const bool vec = (ax & 7) == 0 && (((ax ^ addr(s.lo)) | (ax ^ addr(s.hi))) & 15) == 0;
+    dx_stream(s.n, vec, ax, [&](long long i) { hist_one_px(s, words, i, s.x[i], s.lo[i], s.hi[i]); },
+              [&](long long i) {
+                  double x[2], lo[2], hi[2];
+                  ChV<2>::ld(s.x + i, x); ChV<2>::ld(s.lo + i, lo); ChV<2>::ld(s.hi + i, hi);
+                  hist_one_px(s, words, i, x[0], lo[0], hi[0]);
+                  hist_one_px(s, words, i + 1, x[1], lo[1], hi[1]);
+              });
+}
+
 typedef const SigSeg __attribute__((address_space(4))) * sig_kptr;   // the segment table through the scalar cache (dx_sed.h: kptr)
 
 // comp_sed for a registered signal.  Registration refuses the global-amplitude types, and the host puts a segment into the
@@ -198,7 +226,21 @@ __device__ __forceinline__ void put4(int e, double (&v)[4], double x) {
 // share their 16-byte phase (vec), the odd first / last element alone; element by element otherwise.  An item holds up to four
 // evaluation slots e = 2 * (plane of the class) + (half of the pair); every slot goes through the SAME code (the loops over e:
 // one copy of sed_prep and comp_sed in the kernel), so a result does not depend on which kind of item held its pixel.
-template <bool BP>
+// one sample y of an output into pixel i's record of the histogram that reads the output: hist_one's one-word read-modify-write,
+// the bin by the pixel's own bounds (dx_hist_pixel_bin; with one range for the shard lo and hi are that range in every pixel, and
+// the scale the same one IEEE division the host forms for k_moments_hist: the same integer)
+__device__ __forceinline__ void sig_hist_one(uint32_t* rec, int words, int nbins, int bits, long long i, double y, double lo, double hi) {
+    const int b = dx_hist_pixel_bin(y, lo, hi, nbins);
+    if (b < 0) return;
+    GU32* w = (GU32*)rec + i * words + dx_hist_word_of(b, bits);
+    *w = *w + dx_hist_one(b, bits);
+}
+
+// HIST: after the Welford update of an output the SAME value is binned into the record of the histogram registered on that output
+// (SigBand::rec, null = none).  <BP, false> is the kernel as it was and runs whenever no histogram reads a signal; with one, the
+// HIST form replaces it in the same launches: no further launch.  The histogram's own uniforms (words, nbins, bits) follow the
+// discipline below: parked in VGPRs, and the band's record pointer and range come by vector loads through sv.
+template <bool BP, bool HIST>
 __global__ __launch_bounds__(BLOCK) void k_moments_signal(const Model* __restrict__ Mp, const SigSeg* __restrict__ segs, double inv_n) {
     const Model& M = *Mp;
     const sig_kptr s = reinterpret_cast<sig_kptr>(reinterpret_cast<uintptr_t>(segs + blockIdx.y));
@@ -220,6 +262,9 @@ __global__ __launch_bounds__(BLOCK) void k_moments_signal(const Model* __restric
     asm volatile("" : "+v"(item_stride), "+v"(item_end), "+v"(pair_end), "+v"(i_head), "+v"(i_tail), "+v"(inv_n));
     asm volatile("" : "+v"(pa0), "+v"(pt00), "+v"(pt01), "+v"(pa1), "+v"(pt10), "+v"(pt11), "+v"(sv));
     asm volatile("" : "+v"(k0), "+v"(np2), "+v"(nb), "+v"(nind), "+v"(estep));
+    int hbins = HIST ? s->hbins : 0, hbits = HIST ? s->hbits : 0;
+    const SigHistBand* hv = segs[blockIdx.y].hb;
+    if (HIST) asm volatile("" : "+v"(hbins), "+v"(hbits), "+v"(hv));
     for (long long t = gid; t < item_end; t += item_stride) {
         const bool single = t >= pair_end;
         const long long i = !single ? i_head + 2 * t : !vec ? t : (t == pair_end && i_head) ? 0 : i_tail;   // the item's first pixel
@@ -279,6 +324,22 @@ __global__ __launch_bounds__(BLOCK) void k_moments_signal(const Model* __restric
                     welford(y1, m1, r1, inv_n);
                     *(GD2*)mp = dbl2{m0, m1}; *(GD2*)qp = dbl2{r0, r1};
                 }
+                if (HIST) {
+                    uint32_t* rec = hv[b].rec[o];
+                    if (rec) {
+                        const double *lp = hv[b].lo[o], *hp = hv[b].hi[o];
+                        const int words = dx_hist_words(hbins, hbits);
+                        double l0, l1, h0, h1;
+                        if (!lp) { l0 = l1 = hv[b].glo[o]; h0 = h1 = hv[b].ghi[o]; }
+                        else if (single) { l0 = l1 = lp[i]; h0 = h1 = hp[i]; }
+                        else {
+                            const dbl2 lv = *(const GD2*)(lp + i), hv = *(const GD2*)(hp + i);
+                            l0 = lv.x; l1 = lv.y; h0 = hv.x; h1 = hv.y;
+                        }
+                        sig_hist_one(rec, words, hbins, hbits, i, y0, l0, h0);
+                        if (!single) sig_hist_one(rec, words, hbins, hbits, i + 1, y1, l1, h1);
+                    }
+                }
             }
         }
     }
@@ -319,6 +380,18 @@ __global__ __launch_bounds__(BLOCK) void k_hist_stat(HistStatArgs a) {
     const GU4* __restrict__ rec = (const GU4*)a.rec;
     const int pieces = dx_hist_words(a.nbins, a.bits) / 4;
     dx_hist_readout<uint32_t>(a, [&](long long i, auto f) { hist_walk(rec, i, pieces, a.bits, f); });
+}
+
+struct HistStatPxArgs : HistStatArgs {
+    const double* lo_map;   // [n]: the registration's range maps in place of lo, hi
+    const double* hi_map;
+};
+
+// k_hist_stat of a registration with per-pixel ranges (quantiles and the mode; N needs no range and goes through k_hist_stat)
+__global__ __launch_bounds__(BLOCK) void k_hist_stat_px(HistStatPxArgs a) {
+    const GU4* __restrict__ rec = (const GU4*)a.rec;
+    const int pieces = dx_hist_words(a.nbins, a.bits) / 4;
+    dx_hist_readout_impl<true, uint32_t>(a, [&](long long i, auto f) { hist_walk(rec, i, pieces, a.bits, f); });
 }
 
 struct FinishLagArgs {
@@ -551,6 +624,7 @@ size_t sig_table(const dangx_ctx* ctx, const DxMoments* m, std::vector<SigSeg>& 
         s.n = np;
         s.comp = ps.comp; s.k0 = sig_k0(ps.cls); s.np = ps.cls == 0 ? 1 : 2; s.nb = ps.nb;
         s.nind = ctx->desc[ps.comp].nindices;
+        s.hbins = m->hbins; s.hbits = m->hbits;
         uintptr_t phase = 0, diff = 0;   // diff: bit 3 set when two addresses differ in their 16-byte phase
         bool first = true;
         auto see = [&](const double* q) {
@@ -569,6 +643,17 @@ size_t sig_table(const dangx_ctx* ctx, const DxMoments* m, std::vector<SigSeg>& 
                 sb.mean[o] = m->mean(m->sigs[sg]);
                 sb.m2[o] = m->m2(m->sigs[sg]);
                 see(sb.mean[o]); see(sb.m2[o]);
+                for (const auto& h : m->hists) {   // the histogram that reads this signal, if any
+                    if (h.sig != sg) continue;
+                    SigHistBand& sh = s.hb[b];
+                    sh.rec[o] = m->records(h);
+                    if (h.kind == DX_HIST_RANGE_PIXEL) {
+                        sh.lo[o] = m->range_lo(h); sh.hi[o] = m->range_hi(h);
+                        see(sh.lo[o]); see(sh.hi[o]);
+                    } else {
+                        sh.glo[o] = h.lo; sh.ghi[o] = h.hi;
+                    }
+                }
                 needp |= (o == 2) ? 3u : 1u << o;
             }
         }
@@ -747,6 +832,10 @@ int dangx_moments_accumulate(dangx_ctx* ctx) {
     if (!m->hists.empty()) {   // no counter ever wraps: refused before anything is touched
         const std::string why = dx_hist_limit_check(m->count + 1, m->hbits);
         if (!why.empty()) return fail(ctx, "posterior moments: dangx_moments_accumulate: " + why);
+        for (const auto& h : m->hists)
+            if (h.kind == DX_HIST_RANGE_PIXEL && !h.have_maps)
+                return fail(ctx, "posterior moments: dangx_moments_accumulate: histogram registration " + std::to_string(h.id) +
+                                     " declared per-pixel ranges and has no maps (dangx_moments_hist_range_maps was not called for it)");
     }
     (void)hipSetDevice(ctx->device);
     if (!m->sigs.empty() && sync_model(ctx)) return 1;   // the SEDs read the device model: current before anything is launched
@@ -777,11 +866,20 @@ int dangx_moments_accumulate(dangx_ctx* ctx) {
                 HIPCHK(ctx, hipMemcpyAsync(m->d_pairs, tp.data(), sizeof(PairSeg) * tp.size(), hipMemcpyHostToDevice, ctx->stream));
             }
             std::vector<HistSeg> th;
+            std::vector<HistPxSeg> thp;
             if (m->d_hist) {
-                for (const auto& h : m->hists)
-                    th.push_back(HistSeg{t[h.seg].x, m->records(h), h.lo, h.hi, dx_hist_scale(h.lo, h.hi, m->hbins), (long long)ctx->dims.npix,
-                                         m->hbins, m->hbits});
-                HIPCHK(ctx, hipMemcpyAsync(m->d_hist, th.data(), sizeof(HistSeg) * th.size(), hipMemcpyHostToDevice, ctx->stream));
+                for (const auto& h : m->hists) {
+                    if (h.sig >= 0) continue;   // a signal's histogram is filled by k_moments_signal (sig_table)
+                    if (h.kind == DX_HIST_RANGE_PIXEL)
+                        thp.push_back(HistPxSeg{t[h.seg].x, m->records(h), m->range_lo(h), m->range_hi(h), (long long)ctx->dims.npix, m->hbins, m->hbits});
+                    else
+                        th.push_back(HistSeg{t[h.seg].x, m->records(h), h.lo, h.hi, dx_hist_scale(h.lo, h.hi, m->hbins), (long long)ctx->dims.npix,
+                                             m->hbins, m->hbits});
+                }
+                if (!th.empty())
+                    HIPCHK(ctx, hipMemcpyAsync(m->d_hist, th.data(), sizeof(HistSeg) * th.size(), hipMemcpyHostToDevice, ctx->stream));
+                if (!thp.empty())
+                    HIPCHK(ctx, hipMemcpyAsync(m->d_histpx, thp.data(), sizeof(HistPxSeg) * thp.size(), hipMemcpyHostToDevice, ctx->stream));
             }
             std::vector<MomSeg> tb;
             if (m->d_batch) {   // every slot's row at once: moving on to the next slot needs no upload
@@ -809,10 +907,17 @@ int dangx_moments_accumulate(dangx_ctx* ctx) {
         HIPCHK(ctx, hipGetLastError());
     }
     if (!m->hists.empty()) {   // the histograms: a launch of their own, independent of the accumulators above
-        const unsigned nreg = (unsigned)m->hists.size();
-        Timed tm(ctx, DANGX_K_HIST);
-        hipLaunchKernelGGL(k_moments_hist, dim3(m->grid_for(pairs, nreg), nreg), dim3(BLOCK), 0, ctx->stream, (const HistSeg*)m->d_hist);
-        HIPCHK(ctx, hipGetLastError());
+        const unsigned npx = (unsigned)m->nhist_px, nreg = (unsigned)m->hists.size() - npx - (unsigned)m->nhist_sig;   // state planes only
+        if (nreg) {
+            Timed tm(ctx, DANGX_K_HIST);
+            hipLaunchKernelGGL(k_moments_hist, dim3(m->grid_for(pairs, nreg), nreg), dim3(BLOCK), 0, ctx->stream, (const HistSeg*)m->d_hist);
+            HIPCHK(ctx, hipGetLastError());
+        }
+        if (npx) {   // the registrations with per-pixel ranges: the form that streams lo and hi beside x
+            Timed tm(ctx, DANGX_K_HIST, 2);   // the profile tells the two forms apart by this mark
+            hipLaunchKernelGGL(k_moments_hist_px, dim3(m->grid_for(pairs, npx), npx), dim3(BLOCK), 0, ctx->stream, (const HistPxSeg*)m->d_histpx);
+            HIPCHK(ctx, hipGetLastError());
+        }
     }
     if (!m->sigs.empty()) {   // the component signals: a launch of their own, independent of everything above
         std::vector<SigSeg> t;
@@ -826,14 +931,17 @@ int dangx_moments_accumulate(dangx_ctx* ctx) {
         if (ndelta) {
             const unsigned nseg = (unsigned)ndelta;
             Timed tm(ctx, DANGX_K_SIGNAL);
-            hipLaunchKernelGGL(k_moments_signal<false>, dim3(m->grid_for(pairs, nseg), nseg), dim3(BLOCK), 0, ctx->stream, (const Model*)ctx->dm,
+            // a histogram reads a signal: the HIST form in place of the plain one, in the same launch
+            auto kern = m->nhist_sig ? k_moments_signal<false, true> : k_moments_signal<false, false>;
+            hipLaunchKernelGGL(kern, dim3(m->grid_for(pairs, nseg), nseg), dim3(BLOCK), 0, ctx->stream, (const Model*)ctx->dm,
                                (const SigSeg*)m->d_sig, inv_n);
             HIPCHK(ctx, hipGetLastError());
         }
         if (t.size() > ndelta) {   // segments with an integrated band: element by element
             const unsigned nseg = (unsigned)(t.size() - ndelta);
             Timed tm(ctx, DANGX_K_SIGNAL, 2);   // the profile tells the two forms apart by this mark
-            hipLaunchKernelGGL(k_moments_signal<true>, dim3(m->grid_for(ctx->dims.npix, nseg), nseg), dim3(BLOCK), 0, ctx->stream, (const Model*)ctx->dm,
+            auto kern = m->nhist_sig ? k_moments_signal<true, true> : k_moments_signal<true, false>;
+            hipLaunchKernelGGL(kern, dim3(m->grid_for(ctx->dims.npix, nseg), nseg), dim3(BLOCK), 0, ctx->stream, (const Model*)ctx->dm,
                                (const SigSeg*)(m->d_sig + ndelta), inv_n);
             HIPCHK(ctx, hipGetLastError());
         }
@@ -957,12 +1065,15 @@ int dangx_moments_hist(dangx_ctx* ctx, int nreg, const int32_t* planes, const do
     // the ranges with the defaults filled in: an index plane's is that index's uni_prior as the descriptor holds it now
     const int nr = std::max(0, std::min(nreg, DX_HIST_MAX));
     std::vector<double> rg(2 * (size_t)nr, 0.0);
-    std::vector<int> has(nr, 0);
+    std::vector<int> has(nr, 0), kind(nr, DX_HIST_RANGE_GLOBAL);
     for (int r = 0; planes && r < nr; ++r) {
         const int l = planes[3 * r], w = planes[3 * r + 1];
         if (range && !std::isnan(range[2 * r])) {
             rg[2 * r] = range[2 * r]; rg[2 * r + 1] = range[2 * r + 1];
             has[r] = 1;
+            kind[r] = dx_hist_range_kind(rg[2 * r], rg[2 * r + 1]);   // {-inf, +inf}: per-pixel maps follow (dangx_moments_hist_range_maps)
+        } else if (w == DX_HIST_SIGNAL) {
+            // a signal has no default range: dx_hist_check names it
         } else if (l >= 0 && l < ncomp && w >= 1 && w <= nind[l] && w <= DANGX_MAX_IND) {
             rg[2 * r] = ctx->desc[l].uni_prior[w - 1][0]; rg[2 * r + 1] = ctx->desc[l].uni_prior[w - 1][1];
             has[r] = 1;
@@ -970,28 +1081,50 @@ int dangx_moments_hist(dangx_ctx* ctx, int nreg, const int32_t* planes, const do
             has[r] = 1;   // out of range: dx_hist_check names it
         }
     }
-    const std::string why = dx_hist_check(nreg, planes, rg.data(), has.data(), nbins, bits, ncomp, ctx->dims.nmaps, m->sel, nind, tab.global);
+    const std::string why = dx_hist_check(nreg, planes, rg.data(), has.data(), nbins, bits, ncomp, ctx->dims.nmaps, m->sel, nind, tab.global, kind.data(),
+                                          (int)m->sigs.size());
     if (!why.empty()) return fail(ctx, "posterior moments: dangx_moments_hist: " + why);
     const long long np = ctx->dims.npix, words = dx_hist_words(nbins, bits);
+    const long long pitch = np + (np & 1);   // even: hi at the phase of lo
     std::vector<DxMoments::Hist> nh;
     long long off = 0;   // in 32-bit words; every registration's block starts at a multiple of 256 bytes
+    long long roff = 0;  // in doubles: the range maps of the per-pixel registrations, each pair at the phase of its segment's accumulators (Seg::off & 1), which dangx_moments_begin gave the phase of the chain's plane: the invariant k_moments_accum relies on too
+    int npx = 0, nhs = 0, nmaps_regs = 0;
     for (int r = 0; r < nreg; ++r) {
-        const int seg = m->find_seg(planes[3 * r], planes[3 * r + 1], planes[3 * r + 2]);
-        if (seg < 0) return fail(ctx, "posterior moments: dangx_moments_hist: registration " + std::to_string(r) + ": a plane that is not selected");
-        nh.push_back(DxMoments::Hist{seg, rg[2 * r], rg[2 * r + 1], off, r});
+        const bool signal = planes[3 * r + 1] == DX_HIST_SIGNAL;
+        const int seg = signal ? -1 : m->find_seg(planes[3 * r], planes[3 * r + 1], planes[3 * r + 2]);
+        if (!signal && seg < 0) return fail(ctx, "posterior moments: dangx_moments_hist: registration " + std::to_string(r) + ": a plane that is not selected");
+        DxMoments::Hist h{seg, rg[2 * r], rg[2 * r + 1], off, r};
+        h.kind = kind[r];
+        if (signal) { h.sig = planes[3 * r]; ++nhs; }
+        if (h.kind == DX_HIST_RANGE_PIXEL) {   // at the phase of what the kernel streams beside the maps: the accumulators of the plane or of the signal
+            if ((roff & 1) != ((signal ? m->sigs[h.sig].off : m->segs[seg].off) & 1)) ++roff;
+            h.roff = roff;
+            roff += 2 * pitch;
+            ++nmaps_regs;
+            if (!signal) ++npx;
+        }
+        nh.push_back(h);
         off += (np * words + 63) / 64 * 64;
     }
     (void)hipSetDevice(ctx->device);
     // everything new is allocated before anything old is dropped (reg_close)
     DevBuf<uint32_t> hrec;
     DevBuf<HistSeg> d_hist;
+    DevBuf<double> hrange;
+    DevBuf<HistPxSeg> d_histpx;
     DevStatus st;
     if (!nh.empty()) {
         hrec.zeros((size_t)off, ctx->stream, st);
         d_hist.alloc(nh.size(), st);
     }
+    if (nmaps_regs) hrange.zeros((size_t)roff, ctx->stream, st);
+    if (npx) d_histpx.alloc((size_t)npx, st);
     if (reg_close(ctx, "dangx_moments_hist", st, !nh.empty())) return 1;
     m->hrec = std::move(hrec); m->d_hist = std::move(d_hist);
+    m->hrange = std::move(hrange); m->d_histpx = std::move(d_histpx);
+    m->hpitch = pitch; m->nhist_px = npx; m->nhist_sig = nhs;
+    m->sig_table.clear();   // the signal table carries the records of the histograms that read signals
     m->hists = nh;
     m->hbins = nbins; m->hbits = bits;
     m->table.clear();   // the next accumulation uploads the tables
@@ -1026,10 +1159,98 @@ static int hist_stat_impl(dangx_ctx* ctx, int reg, int stat, int nq, const doubl
     a.nbins = m->hbins; a.bits = m->hbits; a.stat = stat; a.nq = stat == 0 ? nq : 0;
     for (int j = 0; j < a.nq; ++j) a.q[j] = q[j];
     const unsigned gx = std::max(1u, std::min(nblocks(a.n), 2048u));
-    hipLaunchKernelGGL(k_hist_stat, dim3(gx), dim3(BLOCK), 0, ctx->stream, a);
+    if (h.kind == DX_HIST_RANGE_PIXEL && stat != 2) {   // quantiles and the mode need the pixel's bounds; N does not
+        HistStatPxArgs ap{};
+        static_cast<HistStatArgs&>(ap) = a;
+        ap.lo_map = m->range_lo(h); ap.hi_map = m->range_hi(h);
+        if (!ap.lo_map) return fail(ctx, "posterior moments: dangx_moments_hist_stat: histogram registration " + std::to_string(reg) + " has no range maps");
+        hipLaunchKernelGGL(k_hist_stat_px, dim3(gx), dim3(BLOCK), 0, ctx->stream, ap);
+    } else {
+        hipLaunchKernelGGL(k_hist_stat, dim3(gx), dim3(BLOCK), 0, ctx->stream, a);
+    }
     HIPCHK(ctx, hipGetLastError());
     return ro.close(total);
 }
+
+// the checks of dangx_moments_hist_range_*: a registration of this context, whatever it has accumulated
+static int range_reg(dangx_ctx* ctx, const char* who, int reg) {
+    const DxMoments* m = ctx->mom;
+    if (reg < 0 || reg >= (int)m->hists.size())
+        return fail(ctx, std::string("posterior moments: ") + who + ": histogram registration out of range (" + std::to_string(m->hists.size()) + " registered)");
+    return 0;
+}
+
+// lo, hi: [npix] of this shard, host or device arrays.  The checksum is taken from the host arrays, or from a staged copy of the
+// device arrays (registration is not on the hot path); the library keeps its own copy.
+static int range_maps_impl(dangx_ctx* ctx, int reg, const double* lo, const double* hi, bool from_dev) {
+    const char* who = "dangx_moments_hist_range_maps";
+    if (!ctx || !lo || !hi || reg_open(ctx, who) || range_reg(ctx, who, reg)) return 1;
+    DxMoments* m = ctx->mom;
+    DxMoments::Hist& h = m->hists[reg];
+    if (h.kind != DX_HIST_RANGE_PIXEL)
+        return fail(ctx, std::string("posterior moments: ") + who + ": histogram registration " + std::to_string(reg) +
+                             " has a global range: it did not declare per-pixel maps (range {-inf, +inf} in dangx_moments_hist)");
+    (void)hipSetDevice(ctx->device);
+    const size_t np = (size_t)ctx->dims.npix, bytes = sizeof(double) * np;
+    std::vector<double> stage;
+    const double *hl = lo, *hh = hi;
+    if (from_dev) {
+        stage.resize(2 * np);
+        HIPCHK(ctx, hipMemcpyAsync(stage.data(), lo, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(stage.data() + np, hi, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        hl = stage.data(); hh = stage.data() + np;
+    }
+    const uint64_t sum = dx_hist_range_checksum(hl, hh, (long long)np);
+    double* dlo = m->hrange + h.roff;
+    HIPCHK(ctx, hipMemcpyAsync(dlo, hl, bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(dlo + m->hpitch, hh, bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // the caller's arrays and the staged copy are free again
+    h.have_maps = true;
+    h.sum = sum;
+    return 0;
+}
+
+// the maps of a per-pixel registration as they were handed in; the constants of a global one spread over the shard
+static int range_get_impl(dangx_ctx* ctx, int reg, double* lo, double* hi, bool to_dev) {
+    const char* who = "dangx_moments_hist_range_get";
+    if (!ctx || !lo || !hi || need(ctx) || range_reg(ctx, who, reg)) return 1;
+    const DxMoments* m = ctx->mom;
+    const DxMoments::Hist& h = m->hists[reg];
+    (void)hipSetDevice(ctx->device);
+    const size_t np = (size_t)ctx->dims.npix, bytes = sizeof(double) * np;
+    if (h.kind != DX_HIST_RANGE_PIXEL) {
+        if (!to_dev) {
+            std::fill(lo, lo + np, h.lo);
+            std::fill(hi, hi + np, h.hi);
+            return 0;
+        }
+        const std::vector<double> vl(np, h.lo), vh(np, h.hi);
+        HIPCHK(ctx, hipMemcpyAsync(lo, vl.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(hi, vh.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // the staged constants go with this call
+        return 0;
+    }
+    const double *dl = m->range_lo(h), *dh = m->range_hi(h);
+    if (!dl)
+        return fail(ctx, std::string("posterior moments: ") + who + ": histogram registration " + std::to_string(reg) +
+                             (m->holder ? ": section HIST_RANGE(" + std::to_string(reg) + ") was not put into this holder" : " has no range maps yet"));
+    const hipMemcpyKind kind = to_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    HIPCHK(ctx, hipMemcpyAsync(lo, dl, bytes, kind, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(hi, dh, bytes, kind, ctx->stream));
+    if (!to_dev) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+int dangx_moments_hist_range_maps(dangx_ctx* ctx, int reg, const double* lo, const double* hi) { return range_maps_impl(ctx, reg, lo, hi, false); }
+
+int dangx_moments_hist_range_maps_dev(dangx_ctx* ctx, int reg, const double* lo_dev, const double* hi_dev) {
+    return range_maps_impl(ctx, reg, lo_dev, hi_dev, true);
+}
+
+int dangx_moments_hist_range_get(dangx_ctx* ctx, int reg, double* lo, double* hi) { return range_get_impl(ctx, reg, lo, hi, false); }
+
+int dangx_moments_hist_range_get_dev(dangx_ctx* ctx, int reg, double* lo_dev, double* hi_dev) { return range_get_impl(ctx, reg, lo_dev, hi_dev, true); }
 
 int dangx_moments_hist_stat_dev(dangx_ctx* ctx, int reg, int stat, int nq, const double* q, double* out_dev) {
     return hist_stat_impl(ctx, reg, stat, nq, q, out_dev, false);
@@ -1042,6 +1263,10 @@ int dangx_moments_hist_stat(dangx_ctx* ctx, int reg, int stat, int nq, const dou
 int dangx_moments_signals(dangx_ctx* ctx, int nsig, const int32_t* spec) {
     if (reg_open(ctx, "dangx_moments_signals")) return 1;   // its tables come from the descriptors: signals do not depend on the selection
     DxMoments* m = ctx->mom;
+    for (const auto& h : m->hists)
+        if (h.sig >= 0)
+            return fail(ctx, "posterior moments: dangx_moments_signals: histogram registration " + std::to_string(h.id) + " reads signal " +
+                                 std::to_string(h.sig) + " of the present list: drop the histograms first (dangx_moments_hist with nreg = 0)");
     const int ncomp = ctx->dims.ncomp, nmaps = ctx->dims.nmaps;
     int set[MAXC] = {}, global[MAXC] = {};
     for (int l = 0; l < ncomp; ++l) {
@@ -1228,7 +1453,12 @@ static DxSecReg section_reg(const dangx_ctx* ctx, const DxMoments* m) {
     r.lag1 = m->lag1 ? 1 : 0;
     auto plane = [&](std::vector<int32_t>& v, int seg) { const auto& s = m->segs[seg]; v.push_back(s.comp); v.push_back(s.what); v.push_back(s.plane); };
     for (const auto& p : m->pairs) { plane(r.pairs, p.a); plane(r.pairs, p.b); }
-    for (const auto& h : m->hists) { plane(r.hist_planes, h.seg); r.hist_range.push_back(h.lo); r.hist_range.push_back(h.hi); }
+    for (const auto& h : m->hists) {
+        if (h.sig >= 0) { r.hist_planes.push_back(h.sig); r.hist_planes.push_back(DX_HIST_SIGNAL); r.hist_planes.push_back(0); }
+        else plane(r.hist_planes, h.seg);
+        r.hist_range.push_back(h.lo); r.hist_range.push_back(h.hi);
+        r.hist_kind.push_back(h.kind); r.hist_sum.push_back(h.sum);
+    }
     r.nbins = m->hbins; r.bits = m->hbits;
     for (const auto& s : m->sigs) { r.signals.push_back(s.comp); r.signals.push_back(s.band); r.signals.push_back(s.kind); }
     for (const auto& b : m->batches) plane(r.batch_planes, b.seg);
@@ -1278,8 +1508,15 @@ int section_shape(dangx_ctx* ctx, const char* who, int family, int a, int b, Sec
     case DX_SEC_HIST: if (range(m->hists.size(), "histogram registration")) return 1; sh.bytes = dx_section_hist_bytes(np, m->hbins, m->hbits); return 0;
     case DX_SEC_SIGNAL: if (range(m->sigs.size(), "signal index")) return 1; sh.bytes = dx_section_signal_bytes(np); return 0;
     case DX_SEC_BATCHES: if (range(m->batches.size(), "batch registration")) return 1; sh.bytes = dx_section_batches_bytes(np, m->nbatch); return 0;
+    case DX_SEC_HIST_RANGE:
+        if (range(m->hists.size(), "histogram registration")) return 1;
+        if (m->hists[a].kind != DX_HIST_RANGE_PIXEL)
+            return fail(ctx, std::string("posterior moments: ") + who + ": section " + section_name(family, a, b) + ": histogram registration " +
+                                 std::to_string(a) + " has a global range and no range maps");
+        sh.bytes = dx_section_hist_range_bytes(np);
+        return 0;
     }
-    return fail(ctx, std::string("posterior moments: ") + who + ": family must be 0 (HEAD) .. 5 (BATCHES)");
+    return fail(ctx, std::string("posterior moments: ") + who + ": family must be 0 (HEAD) .. 6 (HIST_RANGE)");
 }
 
 // a holder's buffer for a section of `bytes` payload bytes, and its planes entered into the tables
@@ -1326,6 +1563,7 @@ int holder_take(dangx_ctx* ctx, int family, int a, int b, const SecShape& sh, lo
     case DX_SEC_HIST: m->h_hist[a] = reinterpret_cast<uint32_t*>(h->buf.p); break;
     case DX_SEC_SIGNAL: m->h_sig[a].mean = base; m->h_sig[a].m2 = base + np; break;
     case DX_SEC_BATCHES: m->h_batch[a] = base; break;
+    case DX_SEC_HIST_RANGE: m->h_range[a] = base; break;
     }
     return 0;
 }
@@ -1361,6 +1599,12 @@ int section_runs(dangx_ctx* ctx, const char* who, int family, int a, int b, cons
             add(m->bmean(m->batches[a], t), 2LL * t * plane, plane);
             add(m->bm2(m->batches[a], t), (2LL * t + 1) * plane, plane);
         }
+        break;
+    case DX_SEC_HIST_RANGE:
+        if (!m->holder && !m->hists[a].have_maps)
+            return fail(ctx, std::string("posterior moments: ") + who + ": section " + section_name(family, a, b) + ": histogram registration " +
+                                 std::to_string(a) + " has no range maps yet (dangx_moments_hist_range_maps)");
+        add(m->range_lo(m->hists[a]), 0, plane); add(m->range_hi(m->hists[a]), plane, plane);
         break;
     }
     bool missing = !put && m->holder && family == DX_SEC_PLANES && sh.global && !m->h_rows[a];
@@ -1411,6 +1655,23 @@ int section_move(dangx_ctx* ctx, const char* who, int family, int a, int b, void
         return 0;
     }
     (void)hipSetDevice(ctx->device);
+    if (put && family == DX_SEC_HIST_RANGE) {   // the maps put are the registration's: checked before anything is written
+        const size_t np = (size_t)ctx->dims.npix;
+        std::vector<double> stage;
+        const double* v = static_cast<const double*>(user);
+        if (user_dev) {
+            stage.resize(2 * np);
+            HIPCHK(ctx, hipMemcpyAsync(stage.data(), user, (size_t)bytes, hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+            v = stage.data();
+        }
+        if (!m->holder && !m->hists[a].have_maps)
+            return fail(ctx, std::string("posterior moments: ") + who + ": section " + name + ": histogram registration " + std::to_string(a) +
+                                 " has no range maps yet (dangx_moments_hist_range_maps first: a put does not register them)");
+        if (dx_hist_range_checksum(v, v + np, (long long)np) != m->hists[a].sum)
+            return fail(ctx, std::string("posterior moments: ") + who + ": section " + name + ": the checksum of these maps is not that of histogram registration " +
+                                 std::to_string(a));
+    }
     if (put && m->holder && !sh.global && holder_take(ctx, family, a, b, sh, bytes)) return 1;
     std::vector<SecRun> runs;
     if (section_runs(ctx, who, family, a, b, sh, nparts, put, runs)) return 1;
@@ -1480,12 +1741,15 @@ int dangx_moments_begin_like(dangx_ctx* ctx, dangx_ctx* like) {
     std::memcpy(m->sel, o->sel, sizeof m->sel); std::memcpy(m->type, o->type, sizeof m->type); std::memcpy(m->nind, o->nind, sizeof m->nind);
     m->segs = o->segs; m->grid_target = o->grid_target;
     m->lag1 = o->lag1; m->pairs = o->pairs;
-    m->hists = o->hists; m->hbins = o->hbins; m->hbits = o->hbits;
+    m->hists = o->hists; m->hbins = o->hbins; m->hbits = o->hbits;   // range kind and checksum included; the maps come by a put of HIST_RANGE
+    for (auto& h : m->hists) { h.have_maps = false; h.roff = 0; }
+    m->nhist_px = o->nhist_px; m->nhist_sig = o->nhist_sig; m->hpitch = ctx->dims.npix;            // a section's payload is packed
     m->sigs = o->sigs; m->sig_plan = o->sig_plan;
     std::memcpy(m->sig_type, o->sig_type, sizeof m->sig_type); std::memcpy(m->sig_nind, o->sig_nind, sizeof m->sig_nind);
     std::memcpy(m->sig_used, o->sig_used, sizeof m->sig_used);
     m->batches = o->batches; m->nbatch = o->nbatch; m->batch_len = o->batch_len; m->bpitch = o->bpitch;
     m->h_seg.resize(m->segs.size()); m->h_pair.assign(m->pairs.size(), nullptr); m->h_hist.assign(m->hists.size(), nullptr);
+    m->h_range.assign(m->hists.size(), nullptr);
     m->h_sig.resize(m->sigs.size()); m->h_batch.assign(m->batches.size(), nullptr);
     dx_moments_free(ctx);   // whatever the context held or accumulated goes
     ctx->mom = m.release();

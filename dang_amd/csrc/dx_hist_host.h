@@ -1,5 +1,6 @@
 // dx_hist_host.h -- the definitions of the per-pixel posterior histograms (dangx_moments_hist, include/dangx.h): the bin of a
-// sample, the quantile walk, the mode, the counter limit and the check of a registration list.  k_moments_hist / k_hist_stat of
+// sample (with one range for the shard or with a range per pixel), the quantile walk, the mode, the counter limit and the check of
+// a registration list.  k_moments_hist / k_hist_stat of
 // dangx_moments.hip and every host-side check evaluate the SAME inline functions, and a stand-alone host program can include
 // this file without the HIP runtime.
 //
@@ -8,6 +9,7 @@
 #pragma once
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <string>
 
 #ifndef DX_HD
@@ -21,6 +23,7 @@
 #define DX_HIST_MAX 32          // == DANGX_MAX_HIST (include/dangx.h)
 #define DX_HIST_MAX_Q 16        // quantiles of one read-out
 #define DX_HIST_MAX_BYTES 128   // a record never crosses a 128-byte memory request
+#define DX_HIST_SIGNAL (-1)     // == DANGX_HIST_SIGNAL: planes[r] = {sig, DX_HIST_SIGNAL, 0} reads registered signal sig, not a state plane
 
 // x is counted iff it lies in the closed range: NaN fails both comparisons, +-inf one of them
 DX_HD bool dx_hist_counted(double x, double lo, double hi) { return x >= lo && x <= hi; }
@@ -79,6 +82,50 @@ DX_HD double dx_hist_mode_value(int best_b, double lo, double width) {
     return best_b < 0 ? (double)NAN : dx_hist_value(lo, width, (double)best_b + 0.5);
 }
 
+// ---- per-pixel ranges: a registration declared with range = {-inf, +inf} takes its bounds from two f64 maps lo[p], hi[p]
+// (dangx_moments_hist_range_maps).  Every rule above holds with that pixel's bounds; the scale is formed per sample, one IEEE division.
+
+#define DX_HIST_RANGE_GLOBAL 0   // one (lo, hi) for the whole shard
+#define DX_HIST_RANGE_PIXEL 1    // lo[p], hi[p]
+
+// range[r] = {-inf, +inf}: "per-pixel maps follow"
+inline int dx_hist_range_kind(double lo, double hi) {
+    return (std::isinf(lo) && lo < 0.0 && std::isinf(hi) && hi > 0.0) ? DX_HIST_RANGE_PIXEL : DX_HIST_RANGE_GLOBAL;
+}
+
+DX_HD double dx_hist_pixel_scale(double lo, double hi, int nbins) { return (double)nbins / (hi - lo); }
+
+// pixel p is ON: both bounds finite, hi > lo, and neither hi - lo nor nbins / (hi - lo) overflows -- what dx_hist_check asks of a
+// global range.  An off pixel (a masked one handed in as NaN is the normal case) counts nothing; its quantile and mode are NaN.
+DX_HD bool dx_hist_pixel_on(double lo, double hi, int nbins) {
+    return __builtin_isfinite(lo) && __builtin_isfinite(hi) && hi > lo && __builtin_isfinite(hi - lo) &&
+           __builtin_isfinite(dx_hist_pixel_scale(lo, hi, nbins));
+}
+
+// bin of sample x at a pixel with bounds lo, hi; -1: not counted (an off pixel, or x outside the closed range)
+DX_HD int dx_hist_pixel_bin(double x, double lo, double hi, int nbins) {
+    if (!dx_hist_pixel_on(lo, hi, nbins) || !dx_hist_counted(x, lo, hi)) return -1;
+    return dx_hist_bin(x, lo, dx_hist_pixel_scale(lo, hi, nbins), nbins);
+}
+
+// checksum of a pair of range maps: FNV-1a (64 bit) over the little-endian 64-bit words of lo[0..n) then hi[0..n).  Part of what
+// "the same registration" means between chains and between a saved run and the context it is loaded into.
+inline uint64_t dx_hist_range_checksum(const double* lo, const double* hi, long long n) {
+    uint64_t h = 0xcbf29ce484222325ull;
+    for (int part = 0; part < 2; ++part) {
+        const double* v = part == 0 ? lo : hi;
+        for (long long i = 0; i < n; ++i) {
+            uint64_t u;
+            std::memcpy(&u, &v[i], sizeof u);
+            for (int k = 0; k < 8; ++k) {
+                h ^= (u >> (8 * k)) & 0xffu;
+                h *= 0x100000001b3ull;
+            }
+        }
+    }
+    return h;
+}
+
 // the whole walks over one record in memory (host checks; k_hist_stat takes the same steps over 16-byte pieces)
 DX_HD unsigned long long dx_hist_total(const uint32_t* rec, int nbins, int bits) {
     unsigned long long n = 0;
@@ -115,9 +162,13 @@ inline std::string dx_hist_shape_check(int nbins, int bits) {
 
 // planes[r] = {comp, what, plane} and range[r] = {lo, hi} AFTER the defaults were filled in (has_range[r] == 0: an amplitude plane
 // that was given none) against the selection words sel[ncomp], nind[l] = indices of component l, global[l] != 0: template /
-// monopole / hi_fit member.  "" = fine, else the cause.
+// monopole / hi_fit member.  kind (optional): kind[r] == DX_HIST_RANGE_PIXEL: the registration takes per-pixel maps, range[r] is the
+// {-inf, +inf} that declared it and is not a pair of bounds.  nsig (optional, >= 0: the caller knows signal sources): the number of
+// signals registered now; planes[r] = {sig, DX_HIST_SIGNAL, 0} then reads signal sig, which has no default range.  "" = fine, else
+// the cause.
 inline std::string dx_hist_check(int nreg, const int32_t* planes, const double* range, const int* has_range, int nbins, int bits,
-                                 int ncomp, int nmaps, const int32_t* sel, const int* nind, const int* global) {
+                                 int ncomp, int nmaps, const int32_t* sel, const int* nind, const int* global, const int* kind = nullptr,
+                                 int nsig = -1) {
     if (nreg < 0) return "the number of registrations is negative";
     if (nreg > DX_HIST_MAX) return "more than DANGX_MAX_HIST (" + std::to_string(DX_HIST_MAX) + ") registrations";
     const std::string shape = dx_hist_shape_check(nbins, bits);
@@ -127,18 +178,28 @@ inline std::string dx_hist_check(int nreg, const int32_t* planes, const double* 
         const int32_t* p = planes + 3 * r;
         const std::string at = "registration " + std::to_string(r) + ": ";
         const int l = p[0], w = p[1], k = p[2];
+        const bool signal = nsig >= 0 && w == DX_HIST_SIGNAL;
+        if (signal) {
+            if (nsig == 0) return at + "a signal source, and no signals are registered (dangx_moments_signals comes first)";
+            if (l < 0 || l >= nsig) return at + "signal index out of range (" + std::to_string(nsig) + " signals registered)";
+            if (k != 0) return at + "the third word of a signal source must be 0";
+            if (!has_range[r]) return at + "a signal source has no default range: it needs an explicit range or range maps";
+        } else {
         if (l < 0 || l >= ncomp) return at + "component index out of range";
         if (w < 0 || w > nind[l]) return at + "what must be 0 (amplitude) or 1 + index number of the component";
         if (k < 0 || k >= nmaps) return at + "plane out of range";
         if (w == 0 && global[l]) return at + "a template / monopole / hi_fit amplitude is not a pixel plane";
         if (!((sel[l] >> (w == 0 ? k : 3 + 3 * (w - 1) + k)) & 1)) return at + "a plane that is not selected";
         if (!has_range[r]) return at + "an amplitude plane needs an explicit range";
-        const double lo = range[2 * r], hi = range[2 * r + 1];
-        if (!std::isfinite(lo) || !std::isfinite(hi)) return at + "a non-finite bound";
-        if (!(hi > lo)) return at + "the range needs hi > lo";
-        if (!std::isfinite(dx_hist_scale(lo, hi, nbins)) || !std::isfinite(hi - lo)) return at + "a non-finite bound (hi - lo overflows)";
+        }
+        if (!(kind && kind[r] == DX_HIST_RANGE_PIXEL)) {
+            const double lo = range[2 * r], hi = range[2 * r + 1];
+            if (!std::isfinite(lo) || !std::isfinite(hi)) return at + "a non-finite bound";
+            if (!(hi > lo)) return at + "the range needs hi > lo";
+            if (!std::isfinite(dx_hist_scale(lo, hi, nbins)) || !std::isfinite(hi - lo)) return at + "a non-finite bound (hi - lo overflows)";
+        }
         for (int o = 0; o < r; ++o)
-            if (planes[3 * o] == l && planes[3 * o + 1] == w && planes[3 * o + 2] == k) return at + "the same plane twice";
+            if (planes[3 * o] == l && planes[3 * o + 1] == w && planes[3 * o + 2] == k) return at + (signal ? "the same signal twice" : "the same plane twice");
     }
     return "";
 }

@@ -44,11 +44,32 @@ struct HistSeg {          // one registered histogram: the chain's plane (resolv
     int nbins, bits;
 };
 
+struct HistPxSeg {        // a registered histogram with per-pixel ranges: HistSeg with the two range maps in place of the constants
+    const double* x;
+    uint32_t* rec;
+    const double* lo;     // [n], the library's copy, at the 16-byte phase of the segment's accumulators (Seg::off & 1: the phase
+                          // the chain's plane had at dangx_moments_begin, which lays the accumulators out by it)
+    const double* hi;
+    long long n;
+    int nbins, bits;
+};
+
 struct SigBand {          // one band of a signal segment: the accumulators of its outputs (slot 0..2: T, or Q, U, P), null = not wanted
     double* mean[3];
     double* m2[3];
     int band;
     unsigned want;        // bit o: output slot o is registered
+};
+
+// The histograms that read the outputs of one band of a signal segment (k_moments_signal<BP, true> alone looks here; a table of
+// its own behind the bands, so that SigBand and what the plain form reads stay laid out as they were): per output slot the
+// records, null = none, and the range -- the maps lo[o], hi[o] at the phase of the output's accumulators, or with lo[o] == null
+// the two numbers glo[o], ghi[o]
+struct SigHistBand {
+    uint32_t* rec[3];
+    const double* lo[3];
+    const double* hi[3];
+    double glo[3], ghi[3];
 };
 
 struct SigSeg {           // a (component, plane class) with up to DX_SIG_SEG_BANDS bands; the chain's planes resolved at accumulate time
@@ -61,6 +82,8 @@ struct SigSeg {           // a (component, plane class) with up to DX_SIG_SEG_BA
     int comp, k0, np, nb; // k0: first plane (1-based) of the class, np: planes of the class (1: T, 2: Q+U)
     int vec, nind;        // nind: indices of the component (load_theta: an index beyond it is 0.0).  vec 0: element by element; 1 / 2: pairs of pixels, every plane read and every accumulator at 16-byte phase 0 / 8
     SigBand b[DX_SIG_SEG_BANDS];
+    SigHistBand hb[DX_SIG_SEG_BANDS];   // by band, as b
+    int hbins, hbits;     // the context's nbins and bits, for the outputs with a histogram
 };
 
 // ---- device memory that belongs to its holder: freed when the holder goes, handed on by move
@@ -125,11 +148,20 @@ struct DxMoments {
     DevBuf<PairSeg> d_pairs;
     double tm_prev[MAXC][3][MAXB] = {}, tm_first[MAXC][3][MAXB] = {}, tm_P[MAXC][3][MAXB] = {};
     // dangx_moments_hist
-    struct Hist { int seg; double lo, hi; long long off; int id = 0; };   // seg: index into segs; off: the records' first word in hrec; id: its index in hists
+    // seg: index into segs; off: the records' first word in hrec; id: its index in hists.  kind: DX_HIST_RANGE_* (dx_hist_host.h);
+    // a per-pixel registration keeps lo = -inf, hi = +inf (what declared it), its maps at roff in hrange once have_maps, and sum:
+    // their checksum
+    // a histogram of a registered signal: seg = -1 and sig = its index in sigs (else sig = -1)
+    struct Hist { int seg; double lo, hi; long long off; int id = 0; int kind = 0; long long roff = 0; bool have_maps = false; uint64_t sum = 0; int sig = -1; };
     std::vector<Hist> hists;
     int hbins = 0, hbits = 0;
     DevBuf<uint32_t> hrec;           // every registration's records, each block at a multiple of 256 bytes
-    DevBuf<HistSeg> d_hist;
+    DevBuf<HistSeg> d_hist;          // the global-range registrations, in registration order
+    DevBuf<double> hrange;           // per-pixel registrations: [lo: hpitch doubles | hi: hpitch doubles] each, at the phase of the segment's accumulators
+    long long hpitch = 0;            // doubles between lo and hi of a registration (live: npix rounded up to even; holder: npix, packed)
+    DevBuf<HistPxSeg> d_histpx;      // the per-pixel registrations, in registration order
+    int nhist_px = 0;                // how many registrations of state planes are per-pixel
+    int nhist_sig = 0;               // how many registrations read a signal (filled by k_moments_signal<BP, true>, no launch of their own)
     // dangx_moments_signals
     struct Sig { int comp, band, kind; long long off; int id = 0; };   // off: the signal's mean plane in sacc; id: its index in sigs
     std::vector<Sig> sigs;
@@ -169,6 +201,7 @@ struct DxMoments {
     std::vector<HeldSeg> h_seg;       // by Seg::id
     std::vector<double*> h_pair;      // by Pair::id
     std::vector<uint32_t*> h_hist;    // by Hist::id
+    std::vector<double*> h_range;     // by Hist::id: lo of a HIST_RANGE section put (hi follows at npix)
     std::vector<HeldSeg> h_sig;       // by Sig::id (mean, m2)
     std::vector<double*> h_batch;     // by Batch::id: batch 0's mean plane
     bool h_rows[MAXC] = {};           // the host rows tm_* of a template / monopole / hi_fit member were put
@@ -183,6 +216,8 @@ struct DxMoments {
     double* mean(const Sig& s) const { return holder ? h_sig[s.id].mean : sacc + s.off; }
     double* m2(const Sig& s) const { return holder ? h_sig[s.id].m2 : sacc + sacc_half + s.off; }
     uint32_t* records(const Hist& h) const { return holder ? h_hist[h.id] : hrec + h.off; }
+    double* range_lo(const Hist& h) const { return holder ? h_range[h.id] : (h.have_maps ? hrange + h.roff : nullptr); }   // null: no maps (yet)
+    double* range_hi(const Hist& h) const { double* p = range_lo(h); return p ? p + hpitch : nullptr; }
     double* bbase(const Batch& r) const { return holder ? h_batch[r.id] : bacc + r.off; }
     double* bmean(const Batch& r, int b) const { double* p = bbase(r); return p ? p + 2LL * b * bpitch : nullptr; }
     double* bm2(const Batch& r, int b) const { double* p = bbase(r); return p ? p + (2LL * b + 1) * bpitch : nullptr; }

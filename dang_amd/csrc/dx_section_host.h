@@ -10,18 +10,21 @@
 //   HIST    (reg, -)      [npix][nbins] counters of `bits` bits, as dangx_moments_hist_get lays them out
 //   SIGNAL  (sig, -)      mean, m2, each [npix] f64
 //   BATCHES (reg, -)      [nbatch][mean, m2][npix] f64
+//   HIST_RANGE (reg, -)   lo, hi, each [npix] f64: the range maps of a histogram registration with per-pixel ranges (only those have it)
 //
 // The fingerprint is FNV-1a (64 bit) over the registration written out as little-endian 64-bit words, in six groups that HEAD
 // carries one by one, so that a mismatch can be named: the shard (npix, pix0, nmaps), the selection (the selection words, type
 // and nindices of every selected component), the pairs (lag-1 flag and pair list), the histograms (planes, lo, hi as their bit
-// patterns, nbins, bits), the signals (specs) and the batches (planes, nbatch).  The overall value hashes the six.
+// patterns, nbins, bits; with a per-pixel range anywhere in the list also every registration's range kind and the checksum of its
+// maps -- a list of global ranges alone hashes as it always did), the signals (specs) and the batches (planes, nbatch).  The
+// overall value hashes the six.
 #pragma once
 #include <cstdint>
 #include <cstring>
 #include <string>
 #include <vector>
 
-enum { DX_SEC_HEAD = 0, DX_SEC_PLANES = 1, DX_SEC_PAIR = 2, DX_SEC_HIST = 3, DX_SEC_SIGNAL = 4, DX_SEC_BATCHES = 5, DX_SEC_FAMILIES = 6 };
+enum { DX_SEC_HEAD = 0, DX_SEC_PLANES = 1, DX_SEC_PAIR = 2, DX_SEC_HIST = 3, DX_SEC_SIGNAL = 4, DX_SEC_BATCHES = 5, DX_SEC_HIST_RANGE = 6, DX_SEC_FAMILIES = 7 };
 enum { DX_SEC_G_SHARD = 0, DX_SEC_G_SEL = 1, DX_SEC_G_PAIRS = 2, DX_SEC_G_HIST = 3, DX_SEC_G_SIGNALS = 4, DX_SEC_G_BATCHES = 5, DX_SEC_GROUPS = 6 };
 
 #define DX_SEC_VERSION 1u
@@ -29,7 +32,7 @@ enum { DX_SEC_G_SHARD = 0, DX_SEC_G_SEL = 1, DX_SEC_G_PAIRS = 2, DX_SEC_G_HIST =
 #define DX_SEC_HEAD_BYTES 104
 
 inline const char* dx_section_family_name(int family) {
-    static const char* const n[DX_SEC_FAMILIES] = {"HEAD", "PLANES", "PAIR", "HIST", "SIGNAL", "BATCHES"};
+    static const char* const n[DX_SEC_FAMILIES] = {"HEAD", "PLANES", "PAIR", "HIST", "SIGNAL", "BATCHES", "HIST_RANGE"};
     return family >= 0 && family < DX_SEC_FAMILIES ? n[family] : "?";
 }
 
@@ -40,7 +43,9 @@ struct DxSecReg {              // what a registration is made of
     int lag1 = 0;
     std::vector<int32_t> pairs;               // 6 per pair: {comp, what, plane} of a and of b
     std::vector<int32_t> hist_planes;         // 3 per registration
-    std::vector<double> hist_range;           // lo, hi per registration
+    std::vector<double> hist_range;           // lo, hi per registration ({-inf, +inf}: per-pixel maps)
+    std::vector<int32_t> hist_kind;           // range kind per registration (dx_hist_host.h); empty or all 0: global ranges only
+    std::vector<uint64_t> hist_sum;           // checksum of the range maps per registration (0 for a global range)
     int nbins = 0, bits = 0;
     std::vector<int32_t> signals;             // 3 per signal: {comp, band, kind}
     std::vector<int32_t> batch_planes;        // 3 per registration
@@ -92,6 +97,13 @@ inline void dx_section_groups(const DxSecReg& r, uint64_t (&g)[DX_SEC_GROUPS]) {
     d.num((long long)r.hist_range.size());
     for (double v : r.hist_range) d.real(v);
     d.num(r.hist_planes.empty() ? 0 : r.nbins); d.num(r.hist_planes.empty() ? 0 : r.bits);
+    bool per_pixel = false;
+    for (int32_t k : r.hist_kind) per_pixel = per_pixel || k != 0;
+    if (per_pixel) {   // only then: the group of a list of global ranges stays what it was
+        d.list(r.hist_kind);
+        d.num((long long)r.hist_sum.size());
+        for (uint64_t v : r.hist_sum) d.word(v);
+    }
     e.list(r.signals);
     f.list(r.batch_planes); f.num(r.batch_planes.empty() ? 0 : r.nbatch);
     g[0] = a.h; g[1] = b.h; g[2] = c.h; g[3] = d.h; g[4] = e.h; g[5] = f.h;
@@ -197,4 +209,5 @@ inline long long dx_section_pair_bytes(long long npix) { return npix * 8; }
 inline long long dx_section_hist_bytes(long long npix, int nbins, int bits) { return npix * nbins * (bits / 8); }
 inline long long dx_section_signal_bytes(long long npix) { return 2 * npix * 8; }
 inline long long dx_section_batches_bytes(long long npix, int nbatch) { return 2LL * nbatch * npix * 8; }
+inline long long dx_section_hist_range_bytes(long long npix) { return 2 * npix * 8; }
 inline long long dx_section_round256(long long bytes) { return (bytes + 255) / 256 * 256; }

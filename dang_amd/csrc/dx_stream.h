@@ -51,24 +51,36 @@ __device__ __forceinline__ void dx_stream(long long n, bool vec, uintptr_t phase
 // The read-out of histogram records (k_hist_stat: one chain's; k_chains_hist: the sum of several chains'): a lane walks its own
 // pixel's bins once for N and the mode, once more per quantile (those passes hit the cache).  a: the kernel's arguments (q, out,
 // lo, hi, n, nbins, stat, nq); walk(i, f): f(count, bin) per bin of pixel i in bin order until f says stop; CT: its count type.
-template <class CT, class Args, class Walk>
-__device__ __forceinline__ void dx_hist_readout(const Args& a, Walk walk) {
-    const double width = (a.hi - a.lo) / (double)a.nbins;
+// PX: the registration has per-pixel ranges -- a carries lo_map / hi_map [n] beside the rest, a lane takes its pixel's bounds
+// from them, and an off pixel (dx_hist_pixel_on) gives NaN for quantile and mode whatever its record holds.
+template <bool PX, class CT, class Args, class Walk>
+__device__ __forceinline__ void dx_hist_readout_impl(const Args& a, Walk walk) {
+    double lo = a.lo, width = (a.hi - a.lo) / (double)a.nbins;
     for (long long i = (long long)blockIdx.x * BLOCK + threadIdx.x; i < a.n; i += (long long)gridDim.x * BLOCK) {
+        bool on = true;
+        if constexpr (PX) {
+            const double hi = a.hi_map[i];
+            lo = a.lo_map[i];
+            on = dx_hist_pixel_on(lo, hi, a.nbins);
+            width = (hi - lo) / (double)a.nbins;
+        }
         unsigned long long N = 0;
         CT best_c = 0;
         int best_b = -1;
         walk(i, [&](CT c, int b) { N += c; dx_hist_mstep(c, b, best_c, best_b); return false; });
-        if (a.stat == 1) { a.out[i] = dx_hist_mode_value(best_b, a.lo, width); continue; }
+        if (a.stat == 1) { a.out[i] = dx_hist_mode_value(on ? best_b : -1, lo, width); continue; }
         if (a.stat == 2) { a.out[i] = (double)N; continue; }
         for (int j = 0; j < a.nq; ++j) {
             double val = (double)NAN;
-            if (N > 0) {
+            if (N > 0 && on) {
                 const double target = a.q[j] * (double)N;
                 unsigned long long cum = 0;
-                walk(i, [&](CT c, int b) { return dx_hist_qstep(c, b, target, cum, a.lo, width, val); });
+                walk(i, [&](CT c, int b) { return dx_hist_qstep(c, b, target, cum, lo, width, val); });
             }
             a.out[(long long)j * a.n + i] = val;
         }
     }
 }
+
+template <class CT, class Args, class Walk>
+__device__ __forceinline__ void dx_hist_readout(const Args& a, Walk walk) { dx_hist_readout_impl<false, CT>(a, walk); }

@@ -21,7 +21,7 @@ import numpy as np
 from . import _lib as L
 from . import api as _api
 from . import dist as _dist
-from .api import DangxError, Engine, _code, _ctx_array, _engines_of, _hist_stat_args, _is_torch, _readout_dest, _registration
+from .api import DangxError, Engine, _code, _ctx_array, _engines_of, _hist_stat_args, _is_range_maps, _is_torch, _readout_dest, _registration
 
 __all__ = ["GLOBAL_TYPES", "BATCH_STATS", "default_moment_selection", "default_moment_pairs", "default_hist_planes", "default_signal_specs",
            "moments_begin", "moments_accumulate", "moments_pairs", "moments_hist", "moments_signals", "moments_batches",
@@ -161,14 +161,83 @@ def default_hist_planes(dpar, component_list, sel):
 
 def moments_hist(dpar, ddata, planes=None, ranges=None, nbins=64, bits=16, engines=None):
     """dangx_moments_hist on every context of this process, after moments_begin and before the first moments_accumulate;
-    planes=None: default_hist_planes of the selection moments_begin made.  Returns the plane list."""
-    return _register("moments_hist", dpar, ddata, engines, planes, default_hist_planes, _int_tuple, ranges=ranges, nbins=nbins, bits=bits)
+    planes=None: default_hist_planes of the selection moments_begin made.  Returns the plane list.  A ranges[r] may be a pair of maps
+    (lo, hi) -- a per-pixel range, Engine.moments_hist -- over the whole pixel range of this process (the contexts' shards side by
+    side, as hist_ranges_from_moments returns them): every context is handed its slice by (pix0, npix).  Give every chain the same
+    maps: the read-outs over several chains refuse chains whose maps differ."""
+    engs = _engines_of(ddata, engines)
+    if ranges is None or not any(_is_range_maps(r) for r in ranges):
+        return _register("moments_hist", dpar, ddata, engs, planes, default_hist_planes, _hist_plane, ranges=ranges, nbins=nbins, bits=bits)
+    if planes is None:
+        planes = default_hist_planes(dpar, engs[0].component_list, _registration(engs[0], "sel", "moments_hist", "moments_begin"))
+    planes = [_hist_plane(p) for p in planes]
+    total = sum(e.npix for e in engs)
+    for e in engs:
+        e.moments_hist(planes, ranges=_slice_ranges(ranges, e.pix0 - engs[0].pix0, e.npix, total), nbins=nbins, bits=bits)
+    return planes
+
+
+def _hist_plane(p):
+    """a histogram's source as the library takes it: (l, what, plane), or ("signal", s) -> (s, HIST_SIGNAL, 0)"""
+    if isinstance(p[0], str) and p[0] == "signal":
+        return (int(p[1]), L.HIST_SIGNAL, 0)
+    return _int_tuple(p)
+
+
+def _slice_ranges(ranges, off, npix, total):
+    """ranges with every pair of maps over `total` pixels cut down to the `npix` pixels from `off` on; the rest as it is"""
+    out = []
+    for r in ranges:
+        if _is_range_maps(r):
+            if any(tuple(m.shape) != (total,) for m in r):
+                raise DangxError("moments_hist: a per-pixel range is a pair of maps over this process's %d pixels, not of shape %s and %s"
+                                 % (total, tuple(r[0].shape), tuple(r[1].shape)))
+            r = (r[0][off:off + npix], r[1][off:off + npix])
+        out.append(r)
+    return out
+
+
+def _ranges_from_mean_std(mean, std, nsigma, clip0=False):
+    """(mean - nsigma std, mean + nsigma std); NaN where std is 0 or not finite (a pixel that never moved: a masked one).  clip0
+    (a polarised intensity P, which is never negative): the lower bound is not below 0.  numpy arrays or torch tensors."""
+    xp = __import__("torch") if _is_torch(mean) else np
+    bad = ~(xp.isfinite(std) & (std > 0))
+    nan = xp.full_like(mean, float("nan"))
+    lo = mean - nsigma * std
+    if clip0:
+        lo = xp.where(lo < 0, xp.zeros_like(lo), lo)
+    return xp.where(bad, nan, lo), xp.where(bad, nan, mean + nsigma * std)
+
+
+def hist_ranges_from_moments(ddata, planes, nsigma=5.0, engines=None):
+    """Per-pixel histogram ranges from the accumulators a pilot stretch left behind: for every plane (l, what, plane) or signal
+    ("signal", s) of `planes` (the lower bound of a P signal clipped at 0)
+    the pair (mean - nsigma std, mean + nsigma std) as device tensors over this process's pixels (the contexts' shards side by
+    side), NaN where the standard deviation is 0 or not finite -- such a pixel counts nothing.  The planes must be selected in
+    the pilot's moments_begin.  Intended use: a pilot of some iterations with moments_begin / moments_accumulate, this call,
+    moments_begin again, then moments_hist(planes, ranges=these) -- with the same maps on every chain."""
+    import torch
+    engs = _engines_of(ddata, engines)
+    out, cache = [], {}
+    for l, what, k in (_hist_plane(p) for p in planes):
+        if what == L.HIST_SIGNAL:                        # ("signal", s): the signal's own moments; P is clipped at 0
+            mean = torch.cat([e.moments_get_signal(l, "mean", device=True) for e in engs])
+            std = torch.cat([e.moments_get_signal(l, "std", device=True) for e in engs])
+            out.append(_ranges_from_mean_std(mean, std, float(nsigma), clip0=_registration(engs[0], "signals", "hist_ranges_from_moments",
+                                                                                          "moments_signals")[l][2] == 3))
+            continue
+        if (l, what) not in cache:
+            cache[(l, what)] = [(e.moments_get(l, what, "mean", device=True), e.moments_get(l, what, "std", device=True)) for e in engs]
+        mean = torch.cat([m[k] for m, _ in cache[(l, what)]])
+        std = torch.cat([s[k] for _, s in cache[(l, what)]])
+        out.append(_ranges_from_mean_std(mean, std, float(nsigma)))
+    return out
 
 
 def posterior_quantile_maps(ddata, q=(0.16, 0.5, 0.84), masked_value=None, engines=None):
     """{(label, name, plane): {'q': [nq][npix], 'mode': [npix], 'n': [npix], 'range': (lo, hi), 'nbins'}} of the histograms
     moments_hist registered; names as posterior_maps' keys, planes 0-based.  Several contexts of this process: their shards side by
-    side.  masked_value: as in posterior_maps.  Raises when the contexts differ in sample count or registration."""
+    side.  For a per-pixel range, 'range' is the pair of maps (lo, hi), [npix] each, shards side by side.  masked_value: as in posterior_maps.  Raises when the contexts differ in sample count or registration."""
     return _build(HIST, "posterior_quantile_maps", _OneChain(ddata, engines), q=q, masked_value=masked_value)
 
 
@@ -414,6 +483,7 @@ class _Family:
     args: Callable                  # (item, statistic, options) -> the getters' arguments after the engine(s)
     head: Callable                  # (source, registration, item, options) -> the entry before its maps; None: the entry IS the one map
     rows: Callable = lambda e0, item: False     # the item is a template's [nmaps][nbands] rows: <getter>_template without `what`
+    own: Optional[Callable] = None              # item -> the sections the item owns; None: the first of `sections`
 
 
 def _named(stats):
@@ -436,11 +506,52 @@ def _plane_stats(src, o):
     return _named(_chains_stats(src.counts, all(_registration(e, "lag1") for col in src.shards for e in col)))
 
 
-def _hist_family(chains, checks, stats, args):
+def _hist_kind(reg, r):
+    """'global' or 'pixel': the range kind of registration r in the mirror `reg` (a mirror without kinds: global ranges)"""
+    kinds = reg.get("kinds")
+    return kinds[r] if kinds else "global"
+
+
+def _hist_range(src, reg, r, fetched):
+    """a registration's 'range': its two numbers, or for a per-pixel range the pair of maps, shards side by side -- read from the
+    first chain of each shard that has accumulators of its own (every chain holds the same maps).  A shard whose chains are all
+    holders: its first holder, when the family's statistics had HIST_RANGE fetched into it (`fetched`); otherwise nobody on this
+    side holds the maps -- the rank R-hat needs none and moves none -- and 'range' is None."""
+    if _hist_kind(reg, r) != "pixel":
+        return reg["ranges"][r]
+    owners = [next((e for e in col if not getattr(e, "_moment_holder", False)), col[0] if fetched else None) for col in src.shards]
+    if any(e is None for e in owners):
+        return None
+    parts = [e.moments_hist_range_get(r) for e in owners]
+    return tuple(np.concatenate([p[i] for p in parts]) for i in (0, 1))
+
+
+def _hist_key(e0, it):
+    """a state plane as posterior_maps names it plus the plane; a signal source as posterior_signal_maps keys it"""
+    l, what, k = it[1]
+    if what == L.HIST_SIGNAL:
+        c, band, kind = _registration(e0, "signals", "a histogram of a signal", "moments_signals")[l]
+        return (e0.component_list[c].label, e0.bands[band].label, L.SIGNAL_KINDS[kind])
+    return _plane_key(e0, l, what, k)
+
+
+_RANGE_STATS = ("quantile", "mode")      # the histogram statistics that need range values; N and the rank R-hat do not
+
+
+def _hist_sections(it, stats):
+    """HIST, and for a per-pixel range HIST_RANGE where a statistic needs its values (no statistics named: every section owned)"""
+    secs = [(L.SEC_HIST, it[0], 0, False)]
+    if it[2] == "pixel" and (not stats or any(s in _RANGE_STATS for s in stats)):
+        secs.append((L.SEC_HIST_RANGE, it[0], 0, False))
+    return secs
+
+
+def _hist_family(chains, checks, stats, args, ranged):
     return _Family("hist", "moments_hist", "histogram", "moments_hist_stat", chains, checks,
-                   items=lambda e0, reg: list(enumerate(reg["planes"])), key=lambda e0, it: _plane_key(e0, *it[1]),
-                   sections=lambda it, _: [(L.SEC_HIST, it[0], 0, False)], stats=lambda src, o: stats, args=args,
-                   head=lambda src, reg, it, o: {"range": reg["ranges"][it[0]], "nbins": reg["nbins"]})
+                   items=lambda e0, reg: [(r, p, _hist_kind(reg, r)) for r, p in enumerate(reg["planes"])], key=_hist_key,
+                   sections=_hist_sections, stats=lambda src, o: stats, args=args,
+                   head=lambda src, reg, it, o: {"range": _hist_range(src, reg, it[0], ranged), "nbins": reg["nbins"]},
+                   own=lambda it: _hist_sections(it, ()))
 
 
 _REGISTERED, _SAME = ("registered",), ("registered", "same")
@@ -455,9 +566,9 @@ PAIR = _Family("pairs", "moments_pairs", None, "moments_get_pair", "chains_get_p
                sections=lambda it, stats: [(L.SEC_PAIR, it[0], 0, False)] + sorted({(L.SEC_PLANES, l, what, False) for l, what, _ in it[1]}),
                stats=lambda src, o: [(None, o["stat"])], args=lambda it, stat, o: (it[0], stat, o["ddof"]), head=lambda *_: None)
 HIST = _hist_family("chains_hist_stat", (_SAME + ("counts",), _SAME), [("q", "quantile"), ("mode", "mode"), ("n", "n")],
-                    lambda it, stat, o: (it[0], stat, o["q"] if stat == "quantile" else None))
+                    lambda it, stat, o: (it[0], stat, o["q"] if stat == "quantile" else None), ranged=True)
 RANK = _hist_family("chains_hist_rank", ((), _SAME), [("rhat_rank", "bulk"), ("rhat_folded", "folded"), ("rhat_max", "max")],
-                    lambda it, stat, o: (it[0], stat))
+                    lambda it, stat, o: (it[0], stat), ranged=False)
 BATCHES = _Family("batches", "moments_batches", "batch", "moments_batches_get", "chains_batches_get",
                   (_SAME + ("counts", "first"), _SAME + ("equal", "first")),
                   items=lambda e0, reg: list(enumerate(reg["planes"])), key=lambda e0, it: _plane_key(e0, *it[1]),
@@ -479,7 +590,8 @@ def own_sections(e):
     for fam in (PLANES, PAIR, HIST, SIGNAL, BATCHES):
         reg = _registration(e, fam.reg, None, fam.call if fam is PLANES else None)
         if reg is not None:
-            out += [fam.sections(item, ())[0][:3] for item in fam.items(e, reg)]
+            for item in fam.items(e, reg):
+                out += [s[:3] for s in (fam.own(item) if fam.own else fam.sections(item, ())[:1])]
     return out
 
 
@@ -562,7 +674,8 @@ def chains_quantile_maps(chains, q=(0.16, 0.5, 0.84), masked_value=None):
 def chains_rank_maps(chains, masked_value=None):
     """The rank-normalised R-hat of every registered histogram plane over several chains: {'rhat_rank', 'rhat_folded', 'rhat_max',
     'range', 'nbins'} per plane (chains_hist_rank's 'bulk', 'folded' and 'max').  Shards side by side; masked_value as in
-    posterior_maps."""
+    posterior_maps.  The statistic needs no range values, so a per-pixel range's maps are not moved for it: 'range' is then the
+    pair of maps where a chain with accumulators of its own is at hand in every shard, and None where all are holders."""
     return _build(RANK, "chains_rank_maps", chains, masked_value=masked_value)
 
 

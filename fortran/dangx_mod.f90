@@ -594,6 +594,29 @@ module dangx_mod
        type(c_ptr), value :: ctx, q, out_dev
        integer(c_int), value :: reg, stat, nq
      end function
+     ! per-pixel ranges of histogram registration reg (0-based), declared in dangx_moments_hist with range(:, reg) = (-inf, +inf):
+     ! lo, hi = real(c_double)(0:npix-1) of this shard (NaN = an off pixel, which counts nothing); after dangx_moments_hist and
+     ! before the first dangx_moments_accumulate.  _get returns them (the constants of a global-range registration, spread out).
+     integer(c_int) function dangx_moments_hist_range_maps(ctx, reg, lo, hi) bind(C, name='dangx_moments_hist_range_maps')
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx, lo, hi
+       integer(c_int), value :: reg
+     end function
+     integer(c_int) function dangx_moments_hist_range_maps_dev(ctx, reg, lo_dev, hi_dev) bind(C, name='dangx_moments_hist_range_maps_dev')
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx, lo_dev, hi_dev
+       integer(c_int), value :: reg
+     end function
+     integer(c_int) function dangx_moments_hist_range_get(ctx, reg, lo, hi) bind(C, name='dangx_moments_hist_range_get')
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx, lo, hi
+       integer(c_int), value :: reg
+     end function
+     integer(c_int) function dangx_moments_hist_range_get_dev(ctx, reg, lo_dev, hi_dev) bind(C, name='dangx_moments_hist_range_get_dev')
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx, lo_dev, hi_dev
+       integer(c_int), value :: reg
+     end function
      ! moments of component signals at a band (eval_signal(band, pix, map) = amplitude * sed, what write_maps' output_fg maps hold):
      ! spec(3, nsig) = (comp, band, kind), 0-based as in C; kind 0, 1, 2 = plane T, Q, U, 3 = P = sqrt(Q**2 + U**2) (nmaps == 3).
      ! Only between dangx_moments_begin and the first dangx_moments_accumulate; template / monopole / hi_fit members are refused.

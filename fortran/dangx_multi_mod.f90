@@ -294,6 +294,19 @@ contains
     end do
   end subroutine dangx_sky_moments_hist
 
+  ! reg: 0-based, a registration declared with range (-inf, +inf); lo, hi: c_loc of full-sky (0:npix-1) arrays, of which every
+  ! context takes its pixel range.  After dangx_sky_moments_hist, before the first accumulate
+  subroutine dangx_sky_moments_hist_range_maps(sky, reg, lo, hi)
+    type(dangx_sky), intent(in) :: sky
+    integer, intent(in) :: reg
+    type(c_ptr), intent(in) :: lo, hi
+    integer :: r
+    do r = 1, sky%nctx
+       call dangx_check(sky%ctx(r), dangx_moments_hist_range_maps(sky%ctx(r), reg, at_pix(lo, sky%pix0(r)), at_pix(hi, sky%pix0(r))), &
+            'dangx_moments_hist_range_maps')
+    end do
+  end subroutine dangx_sky_moments_hist_range_maps
+
   ! reg: 0-based.  stat 0: the nq quantiles q into out = c_loc of a full-sky (0:npix-1, nq) array; 1: the mode, 2: the counted
   ! samples into a full-sky (0:npix-1) array.  A context writes its quantile rows packed, so with several contexts each row goes
   ! through a call of its own into that context's pixel range

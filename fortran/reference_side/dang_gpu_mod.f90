@@ -803,10 +803,15 @@ contains
   ! of `bits` bits, include/dangx.h) of every selected plane of every index the run samples (c%sample_index(j)), over that index's
   ! uni_prior -- as dang_amd.api.default_hist_planes: component order, then index, then plane.  Read with
   ! posterior_quantile_to_host_gpu / posterior_hist_n_to_host_gpu (reg = 1 .. gpu_post_nhist).
-  subroutine posterior_hist_gpu(dpar, nbins, bits)
+  ! per_pixel (optional, default .false.): every registration is declared with the range (-inf, +inf) instead, i.e. it takes
+  ! per-pixel range maps, which posterior_hist_range_gpu must hand in before the first sample.
+  subroutine posterior_hist_gpu(dpar, nbins, bits, per_pixel)
+    use, intrinsic :: ieee_arithmetic, only: ieee_value, ieee_negative_inf, ieee_positive_inf
     type(dang_params) :: dpar
     integer(i4b), intent(in) :: nbins, bits
+    logical(lgt), intent(in), optional :: per_pixel
     type(dang_comps), pointer :: cc
+    real(c_double), allocatable, target :: rg(:,:)
     integer(i4b) :: i, j, k, n, pass
     if (.not. allocated(gpu_post_sel)) then
        write(*,*) 'posterior_hist_gpu: posterior_begin_gpu was not called'
@@ -832,8 +837,30 @@ contains
        end if
     end do
     gpu_post_nhist = n
+    if (present(per_pixel)) then
+       if (per_pixel .and. n > 0) then
+          allocate(rg(2, n))
+          rg(1, :) = ieee_value(1.0_c_double, ieee_negative_inf)
+          rg(2, :) = ieee_value(1.0_c_double, ieee_positive_inf)
+          call dangx_sky_moments_hist(gpu_sky, n, gpu_post_hist, c_loc(rg), nbins, bits)
+          return
+       end if
+    end if
     call dangx_sky_moments_hist(gpu_sky, n, gpu_post_hist, c_null_ptr, nbins, bits)
   end subroutine posterior_hist_gpu
+
+  ! the per-pixel range of histogram `reg` (1-based, posterior_hist_gpu's order, registered with per_pixel): lo(0:npix-1),
+  ! hi(0:npix-1) over the full sky, of which this rank's contexts take their pixel ranges.  A pixel whose bounds are NaN (a masked
+  ! one), not finite or not hi > lo counts nothing and reads as NaN.  After posterior_hist_gpu, before the first sample is taken.
+  subroutine posterior_hist_range_gpu(reg, lo, hi)
+    integer(i4b), intent(in) :: reg
+    real(dp), intent(in), target :: lo(0:), hi(0:)
+    if (reg < 1 .or. reg > gpu_post_nhist) then
+       write(*,*) 'posterior_hist_range_gpu: registration out of range', reg, gpu_post_nhist
+       stop 1
+    end if
+    call dangx_sky_moments_hist_range_maps(gpu_sky, reg - 1, c_loc(lo), c_loc(hi))
+  end subroutine posterior_hist_range_gpu
 
   ! the quantiles q(:) (each inside (0, 1), at most 16) of histogram `reg` (1-based, posterior_hist_gpu's order) into
   ! out(0:npix-1, size(q)); under MPI every rank fills its pixel range and the ranges are merged as rank_window merges a plane.

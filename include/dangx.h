@@ -545,6 +545,20 @@ int dangx_moments_get_pair_dev(dangx_ctx *ctx, int pair, int stat, int ddof, dou
  *     c_b > 0 && cum + c_b >= target gives lo + ((hi - lo) / nbins) * (b + (target - cum) / c_b); N = 0 gives NaN.  The value lies
  *     in the closed bin that holds the ceil(q N)-th smallest counted sample.
  *   mode: the centre of the fullest bin, the lowest on ties; N = 0 gives NaN.
+ *   per-pixel range: a registration declared with range[r] = {-inf, +inf} takes two f64 maps lo[p], hi[p] over this shard's pixels
+ *     (dangx_moments_hist_range_maps; the library copies them and owns the copy).  Pixel p is ON when lo[p] and hi[p] are finite,
+ *     hi[p] > lo[p], and neither hi[p] - lo[p] nor nbins / (hi[p] - lo[p]) overflows; for an on pixel every rule above holds with
+ *     that pixel's bounds, scale_p = (double)nbins / (hi[p] - lo[p]) being one IEEE division.  An off pixel counts nothing: its
+ *     N = 0, its quantile and mode are NaN.  Handing in masked pixels as NaN is the normal case, not an error.  The checksum of a
+ *     pair of maps -- FNV-1a (64 bit) over the little-endian words of lo[0..npix) then hi[0..npix) -- is part of the registration
+ *     wherever registrations are compared (the HEAD fingerprint below, the read-outs over several chains).
+ *   source: planes[r] = {comp, what, plane} reads a plane of the chain's state; planes[r] = {sig, DANGX_HIST_SIGNAL, 0} reads
+ *     registered signal sig of the current dangx_moments_signals list (any kind, P included): the sample is the value
+ *     k_moments_signal feeds to its Welford update, bit for bit, binned by that kernel itself behind the update (its HIST form takes
+ *     the place of the plain one in the same launches; no histogram reads a signal: the plain form runs, as before).  A signal has
+ *     no default range: it needs a global one or maps.  Further errors of dangx_moments_hist: a signal source while no signals are
+ *     registered, sig out of range, the same signal twice, a signal without any range.  dangx_moments_signals refuses, by name, to
+ *     replace the signal list while a histogram reads a signal: drop the histograms first (nreg = 0).
  * dangx_moments_hist: range[r] = {lo, hi}; range == NULL or a NaN lo = the default, which an index plane has (that index's uni_prior
  *   in the descriptor at registration time: the chain never leaves it, src/dang_sample_mod.f90:415) and an amplitude plane has not.
  *   Legal after dangx_moments_begin and before the first dangx_moments_accumulate, independent of dangx_moments_pairs (either order,
@@ -553,17 +567,29 @@ int dangx_moments_get_pair_dev(dangx_ctx *ctx, int pair, int stat, int ddof, dou
  *   (not a pixel plane), a bad nbins or bits or a record over 128 bytes, hi <= lo or a non-finite bound, an amplitude plane
  *   without a range, nreg > DANGX_MAX_HIST, the same plane twice, a failed allocation (nbins * bits / 8 bytes per pixel and
  *   registration).  With histograms registered dangx_moments_accumulate fails before touching anything, naming the limit, when the
- *   new count would exceed 2^bits - 1: no counter ever wraps or saturates.
+ *   new count would exceed 2^bits - 1: no counter ever wraps or saturates.  range[r] = {-inf, +inf} declares a per-pixel range
+ *   (any other non-finite bound stays an error); dangx_moments_accumulate then fails before touching anything, naming the
+ *   registration, until its maps were handed in.
+ * dangx_moments_hist_range_maps: lo, hi = host arrays [npix] of this shard for registration reg; legal after dangx_moments_hist and
+ *   before the first dangx_moments_accumulate, only for a registration declared with {-inf, +inf}; a second call replaces the
+ *   first.  dangx_moments_hist_range_get returns the maps; for a global-range registration it fills them with its constants.
+ *   k_moments_hist takes the global-range registrations as before; the per-pixel ones go into one launch of a second form of
+ *   it that streams lo and hi beside x (16 bytes more per pixel and sample, 16 * npix bytes of maps per registration).
  * dangx_moments_hist_get: the raw records [npix][nbins] of this shard as uint16_t (bits 16) or uint32_t (bits 32).
  * dangx_moments_hist_stat: stat 0 = the nq quantiles q[0..nq) as out[nq][npix] (1 <= nq <= 16, every q strictly inside (0, 1));
  *   stat 1 = the mode, stat 2 = N as f64 (out[npix]; nq and q ignored).  Errors: reg out of range, no sample accumulated, a bad stat.
  * The _dev forms write a device array of this shard, asynchronously on the context's stream. */
 #define DANGX_MAX_HIST 32
+#define DANGX_HIST_SIGNAL (-1)
 int dangx_moments_hist(dangx_ctx *ctx, int nreg, const int32_t *planes, const double *range, int nbins, int bits);
 int dangx_moments_hist_get(dangx_ctx *ctx, int reg, void *counts);
 int dangx_moments_hist_get_dev(dangx_ctx *ctx, int reg, void *counts_dev);
 int dangx_moments_hist_stat(dangx_ctx *ctx, int reg, int stat, int nq, const double *q, double *out);
 int dangx_moments_hist_stat_dev(dangx_ctx *ctx, int reg, int stat, int nq, const double *q, double *out_dev);
+int dangx_moments_hist_range_maps(dangx_ctx *ctx, int reg, const double *lo, const double *hi);
+int dangx_moments_hist_range_maps_dev(dangx_ctx *ctx, int reg, const double *lo_dev, const double *hi_dev);
+int dangx_moments_hist_range_get(dangx_ctx *ctx, int reg, double *lo, double *hi);
+int dangx_moments_hist_range_get_dev(dangx_ctx *ctx, int reg, double *lo_dev, double *hi_dev);
 /* Moments of component signals at a band, accumulated on the same samples (k_moments_signal: a launch of its own per accumulation, and a second one for the signals at bandpass-integrated bands,
  * only when something is registered): what write_maps' output_fg maps hold (c%eval_signal(band, pix, map),
  * src/dang_data_mod.f90:596-617) and scripts/make_mean_maps.py averages -- nonlinear in the sampled amplitude and indices, so
@@ -584,8 +610,8 @@ int dangx_moments_hist_stat_dev(dangx_ctx *ctx, int reg, int stat, int nq, const
  * dangx_moments_get_signal: stat 0 = mean, 1 = standard deviation sqrt(m2 / (n - ddof)); out: [npix] of this shard.  Errors: sig
  *   out of range, n = 0, a bad stat, stat = 1 with n - ddof <= 0.  The _dev form writes a device array, asynchronously on the
  *   context's stream.
- * Not covered: the polarisation angle (a circular statistic), lag-1 / pairs / histograms of signals, frequencies that are not
- * bands of the model. */
+ * Histograms of signals: dangx_moments_hist with a signal source (above).  Not covered: the polarisation angle (a circular
+ * statistic), lag-1 / pairs of signals, frequencies that are not bands of the model. */
 #define DANGX_MAX_SIGNALS 64
 int dangx_moments_signals(dangx_ctx *ctx, int nsig, const int32_t *spec);
 int dangx_moments_get_signal(dangx_ctx *ctx, int sig, int stat, int ddof, double *out);
@@ -633,8 +659,9 @@ int dangx_moments_batches_raw_dev(dangx_ctx *ctx, int reg, int batch, double *me
  *                                    the current batch length, the full batches, the fill of the open batch and a 64-bit
  *                                    fingerprint of the registration, with one 64-bit value per part of it: the shard (npix,
  *                                    pix0, nmaps); the selection words with type and nindices of the selected components; the
- *                                    lag-1 flag and the pair list; the histogram planes with lo, hi, nbins, bits; the signal
- *                                    specs; the batch planes with nbatch
+ *                                    lag-1 flag and the pair list; the histogram planes with lo, hi, nbins, bits (and, once a
+ *                                    registration has a per-pixel range, every range kind and map checksum: a list of global
+ *                                    ranges hashes as it always did); the signal specs; the batch planes with nbatch
  *   family 1 PLANES  (comp, what)    parts mean, m2 (then prev, first, P when lag-1 is tracked), each [selected planes in T, Q, U
  *                                    order][npix] f64; for a template / monopole / hi_fit member (what 0) its host rows in the
  *                                    same part order, each [selected planes][nbands]
@@ -642,6 +669,13 @@ int dangx_moments_batches_raw_dev(dangx_ctx *ctx, int reg, int batch, double *me
  *   family 3 HIST    (reg, -)        the records as the raw histogram getter lays them out
  *   family 4 SIGNAL  (sig, -)        mean, m2, each [npix] f64
  *   family 5 BATCHES (reg, -)        [nbatch][mean, m2][npix] f64
+ *   family 6 HIST_RANGE (reg, -)     lo, hi, each [npix] f64: the range maps of a histogram registration with a per-pixel range.
+ *                                    Asking for it of a global-range registration is an error.  A put is refused unless the
+ *                                    checksum of its maps is the registration's (on a live context: make the registration and
+ *                                    hand in the maps first); a holder takes range kind and checksum over from `like` and
+ *                                    receives the maps by this put.  Quantile and mode read-outs over several chains take
+ *                                    the maps from ctxs[0] and name this section when a holder there lacks it; N and the
+ *                                    rank R-hat need no range values and do not ask for it.
  * _section_bytes: the payload's size.  _section_get / _put: host arrays, returning after the copy; the _dev forms take device
  * arrays and are asynchronous on the context's stream (the host rows of a template / monopole / hi_fit member: the call waits).
  * Transport is one copy per plane; no kernel is launched.  Every get and put checks `bytes` against _section_bytes.

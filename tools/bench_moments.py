@@ -3,7 +3,7 @@
 iterations of the C3 model: blocks of iterations without and with accumulation after every iteration, alternating in one process;
 then the k_moments kernel time from the profile and its bandwidth in algorithmic bytes (5 x 8 B per selected element) against the
 6.29 TB/s measured copy ceiling of the MI355X.
-    python3 tools/bench_moments.py [nside=1024] [steps per block=10] [rounds=5] [--lag1] [--pairs default] [--hist [nbins=64]] [--signals [--bandpass]] [--chains K [--samples N]] [--batches NB] [--sections]
+    python3 tools/bench_moments.py [nside=1024] [steps per block=10] [rounds=5] [--lag1] [--pairs default] [--hist [nbins=64] [--range-maps | --signals]] [--signals [--bandpass]] [--chains K [--samples N]] [--batches NB] [--sections]
 --lag1 / --pairs default: after the above, `rounds` alternating rounds of `steps` accumulations each of (a) the plain accumulate,
 (b) with lag-1 tracking (k_moments_accum_lag: 10 x 8 B per selected element) and (c) with the default pairs (k_moments_pairs: 6 x 8 B
 per pair element, timed apart from the mean launch that follows it); per launch the algorithmic bytes, the achieved bytes/s and
@@ -12,6 +12,13 @@ their ratio to (a) in the same round.
 default index planes, at nbins and at 16 bins; per launch the line-granular traffic -- 8 B of x plus the record's 128-byte request
 read and written once per counted pixel -- its bytes/s and the ratio to
 (a)'s algorithmic bytes/s in the same round; then the read-out of three quantiles of one plane and the records' memory.
+--hist --range-maps: in every round also (p) the same planes registered with per-pixel ranges -- maps that hold every plane's
+default bounds in every pixel, so that the same pixels are counted -- which go through the form of the launch that streams lo and
+hi beside x (k_moments_hist_px): 16 B more per pixel and plane; its time over (h)'s of the same round against the byte ratio.
+--hist --signals: histograms that read the default signals (one range per signal, from a pilot of three iterations), filled by the
+HIST form of the signal launch itself: alternating rounds of (s) the plain signal launch, (h) the scalar-range k_moments_hist launch
+over as many index planes as there are signals and (f) the fused launch; (f) against (s) + (h), what an unfused form would cost at
+best.  Nothing else of --hist or --signals is run.
 --signals: alternating rounds of (a) the plain accumulate and (s) the signal launch (k_moments_signal) on the default signals; per
 launch the algorithmic bytes -- per segment (amplitude planes + index planes read + 4 x outputs) x 8 B x pixels -- its bytes/s and
 the ratio to (a)'s in the same round.
@@ -384,10 +391,16 @@ if want_lag1 or want_pairs:
             print("%s / (a): median %.3f (spread %.3f .. %.3f); target >= 0.9" % (name, float(np.median(res[key])), min(res[key]), max(res[key])))
 
 
-def hist_launches(nbins, bits=16):
-    """(ms per k_moments_hist launch, ms per plain k_moments launch beside it, registrations, counted pixels per launch, read-out ms)"""
+def hist_launches(nbins, bits=16, range_maps=False):
+    """(ms per k_moments_hist launch, ms per plain k_moments launch beside it, registrations, counted pixels per launch, read-out ms);
+    range_maps: every plane's default bounds as a pair of per-pixel maps (the launch that streams them)"""
     da.moments_begin(dpar, ddata, sel=sel)
-    hp = da.moments_hist(dpar, ddata, nbins=nbins, bits=bits)
+    ranges = None
+    if range_maps:
+        hp = da.default_hist_planes(dpar, comps, sel)
+        one = torch.ones(meta["npix"], dtype=torch.float64, device=dev)
+        ranges = [(one * float(comps[l].uni_prior[w - 1][0]), one * float(comps[l].uni_prior[w - 1][1])) for l, w, k in hp]
+    hp = da.moments_hist(dpar, ddata, ranges=ranges, nbins=nbins, bits=bits)
     da.moments_accumulate(ddata)   # table upload
     eng.profile(True)
     for _ in range(steps):
@@ -404,10 +417,11 @@ def hist_launches(nbins, bits=16):
             len(hp), counted, (t1 - t0) * 1e3)
 
 
-if hist_bins:
+if hist_bins and "--signals" not in sys.argv:
     npx = meta["npix"]
     forms = [hist_bins] + ([16] if hist_bins != 16 else [])
     ratios = {nb: [] for nb in forms}
+    px_ratios = []
     for r in range(rounds):
         a_ms = launches("plain")[0]
         a_bw = 5 * 8 * planes * npx / a_ms * 1e-9
@@ -420,9 +434,20 @@ if hist_bins:
             line += "; (h) %d bins x 16 bit on %d planes %.3f ms, %.2f GB line-granular (%.0f counted pixels) -> %.2f TB/s = %.3f of (a)" \
                     "; k_moments beside it %.3f ms; 3 quantiles of one plane %.3f ms" % (nb, nreg, h_ms, traffic * 1e-9, counted, h_bw,
                                                                                        h_bw / a_bw, m_ms, q_ms)
+            if "--range-maps" in sys.argv and nb == hist_bins:
+                p_ms, _, _, p_counted, pq_ms = hist_launches(nb, range_maps=True)
+                p_traffic = traffic + 16.0 * nreg * npx
+                px_ratios.append((p_ms / h_ms, p_traffic / traffic))
+                line += "; (p) per-pixel ranges %.3f ms, %.2f GB (%.0f counted pixels) = %.3f of (h)'s time at %.3f of its bytes; 3 quantiles %.3f ms" \
+                        % (p_ms, p_traffic * 1e-9, p_counted, p_ms / h_ms, p_traffic / traffic, pq_ms)
         print(line)
     for nb in forms:
         print("(h) %d bins / (a): median %.3f (spread %.3f .. %.3f)" % (nb, float(np.median(ratios[nb])), min(ratios[nb]), max(ratios[nb])))
+    if px_ratios:
+        t = [a for a, b in px_ratios]
+        byte = float(np.median([b for a, b in px_ratios]))
+        print("(p) / (h) time: median %.3f (spread %.3f .. %.3f); byte ratio %.3f; bound byte ratio x 1.10 = %.3f"
+              % (float(np.median(t)), min(t), max(t), byte, 1.10 * byte))
     nreg = len(da.default_hist_planes(dpar, comps, sel))
     print("records: %d B x %d pixels x %d planes = %.2f GB at %d bins x 16 bit" % (hist_bins * 2, npx, nreg, hist_bins * 2.0 * npx * nreg * 1e-9, hist_bins))
     da.moments_begin(dpar, ddata, sel=sel)   # drops the records
@@ -451,7 +476,51 @@ def signal_launches():
     return prof["k_signal"]["total_ms"] / prof["k_signal"]["launches"], prof["k_moments"]["total_ms"] / prof["k_moments"]["launches"], specs
 
 
-if "--signals" in sys.argv:
+if "--signals" in sys.argv and hist_bins:
+    npx = meta["npix"]
+    da.moments_begin(dpar, ddata, sel=sel)
+    specs = da.moments_signals(dpar, ddata)
+    for it in range(1001, 1004):                      # the pilot: three samples of the signals
+        da.gibbs_iteration(dpar, ddata, it)
+        da.moments_accumulate(ddata)
+    sources = [("signal", s) for s in range(len(specs))]
+    inf = float("inf")
+    granges = [(float(torch.nan_to_num(lo, nan=inf).min()), float(torch.nan_to_num(hi, nan=-inf).max()))
+               for lo, hi in da.hist_ranges_from_moments(ddata, sources, nsigma=5.0)]
+    hp_n = da.default_hist_planes(dpar, comps, sel)[:len(specs)]
+    assert len(hp_n) == len(specs), "fewer default index planes than default signals"
+
+    def timed(register, family):
+        da.moments_begin(dpar, ddata, sel=sel)
+        nreg = register()
+        da.moments_accumulate(ddata)   # table upload
+        eng.profile(True)
+        for _ in range(steps):
+            da.moments_accumulate(ddata)
+        prof = eng.profile_get()
+        eng.profile(False)
+        counted = sum(float(eng.moments_hist_stat(r, "n", device=True).sum()) for r in range(nreg)) / (steps + 1)
+        return prof[family]["total_ms"] / prof[family]["launches"], counted
+
+    def reg_fused():
+        da.moments_signals(dpar, ddata)
+        da.moments_hist(dpar, ddata, planes=sources, ranges=granges, nbins=hist_bins, bits=16)
+        return len(sources)
+
+    res = []
+    for r in range(rounds):
+        s_ms = signal_launches()[0]
+        h_ms, h_counted = timed(lambda: len(da.moments_hist(dpar, ddata, planes=hp_n, nbins=hist_bins, bits=16)), "k_hist")
+        f_ms, f_counted = timed(reg_fused, "k_signal")
+        res.append(f_ms / (s_ms + h_ms))
+        print("round %d: (s) %d signals %.3f ms; (h) k_moments_hist, %d bins x 16 bit on %d planes %.3f ms (%.0f counted pixels); (f) the fused "
+              "signal-histogram launch %.3f ms (%.0f counted pixels) = %.3f of (s) + (h) = %.3f ms"
+              % (r + 1, len(specs), s_ms, hist_bins, len(hp_n), h_ms, h_counted, f_ms, f_counted, f_ms / (s_ms + h_ms), s_ms + h_ms))
+    print("(f) / ((s) + (h)): median %.3f (spread %.3f .. %.3f); must not exceed 1" % (float(np.median(res)), min(res), max(res)))
+    print("records: %d B x %d pixels x %d signals = %.2f GB at %d bins x 16 bit" % (hist_bins * 2, npx, len(specs), hist_bins * 2.0 * npx * len(specs) * 1e-9, hist_bins))
+    da.moments_begin(dpar, ddata, sel=sel)
+
+if "--signals" in sys.argv and not hist_bins:
     npx = meta["npix"]
     ratios = []
     for r in range(rounds):
