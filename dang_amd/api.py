@@ -175,8 +175,8 @@ def _code(codes, stat):
 
 # The Python mirror of what the library has registered on a context, one attribute per registration call: the selection words of
 # moments_begin, then what moments_pairs (the pair list and its lag-1 flag), moments_hist, moments_signals and moments_batches
-# registered.  Plain attributes (tests and stand-in engines set and delete them); this tuple is the one list of them.
-MOMENT_ATTRS = ("_moment_sel", "_moment_pairs", "_moment_lag1", "_moment_hist", "_moment_signals", "_moment_batches")
+# registered, and last the angle list of moments_angles.  Plain attributes (tests and stand-in engines set and delete them); this tuple is the one list of them.
+MOMENT_ATTRS = ("_moment_sel", "_moment_pairs", "_moment_lag1", "_moment_hist", "_moment_signals", "_moment_batches", "_moment_angles")
 
 
 def _registration(e, name, who=None, call=None):
@@ -846,6 +846,24 @@ class Engine:
         """Mean ('mean' / 0) or standard deviation ('std' / 1, sqrt(m2 / (n - ddof))) of registered signal s as [npix].
         device=True: a torch cuda tensor filled on the device."""
         return self._readout("dangx_moments_get_signal", (self.npix,), (int(s), _code(L.STAT_CODES, stat), int(ddof)), device, out)
+
+    def moments_angles(self, specs):
+        """Register posterior polarisation angles after moments_begin and before the first moments_accumulate: specs = [(l, band),
+        ...], the angle psi = atan2(U, Q) / 2 of the signal of component l at that band, accumulated as the running mean of
+        (cos 2psi, sin 2psi) of every sample (a circular statistic; no sign convention is applied to the model's Q, U).  nmaps == 3
+        only.  Independent of the selection and of moments_pairs / _hist / _signals / _batches; a second call replaces the first.
+        Definitions: include/dangx.h."""
+        sp = [(int(l), int(j)) for l, j in specs]
+        p = np.ascontiguousarray(np.asarray(sp, dtype=np.int32).reshape(-1, 2))
+        self._chk(self.lib.dangx_moments_angles(self.h, p.shape[0], p.ctypes.data if p.size else None))
+        self._moment_angles = sp
+
+    def moments_get_angle(self, a, stat, device=False, out=None):
+        """Read-out of registered angle a as [npix]: 'psi' / 0 = the circular mean 0.5 atan2(Sbar, Cbar) in [-pi/2, pi/2], 'psi_std'
+        / 1 = the circular standard deviation 0.5 sqrt(-2 log R) in radians, 'R' / 2 = the mean resultant length (clamped to 1),
+        'C' / 3 and 'S' / 4 = the accumulated means of cos 2psi and sin 2psi.  NaN where a sample had Q = U = 0.  device=True: a
+        torch cuda tensor filled on the device."""
+        return self._readout("dangx_moments_get_angle", (self.npix,), (int(a), _code(L.ANGLE_STAT_CODES, stat)), device, out)
 
     def moments_batches(self, planes, nbatch=16, batch_len=1):
         """Register batched accumulators after moments_begin and before the first moments_accumulate: planes = [(l, what, plane),

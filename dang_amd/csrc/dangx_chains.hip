@@ -1,10 +1,12 @@
 // dangx_chains.hip -- dangx_chains_*: read-outs over the accumulators of SEVERAL chains of one device (definitions in dx_chains_host.h).  Nothing here
-// touches an accumulator, a chain or a cache: five read-only kernels combine the per-chain planes and write only the map asked for.
+// touches an accumulator, a chain or a cache: six read-only kernels combine the per-chain planes and write only the map asked for.
 //   k_chains_batches  the batched accumulators (dx_batches_host.h): every chain's slots in one pass from one base pointer per chain.
 //   k_chains_stat  planes and signals (blockIdx.y = plane, up to three): pooled mean / std, R-hat, W, B/n read K x (mean, m2) --
 //                  a stat that does not use one of the two does not load it -- and write one f64: at most (2 K + 1) x 8 B per
 //                  element; the pooled ESS reads K x (mean, m2, prev, first, P), (5 K + 1) x 8 B.
 //   k_chains_pair  one pair: K x (mean_a, mean_b, C) for the covariance, + K x (m2_a, m2_b) for the correlation.
+//   k_chains_angle one polarisation angle (dx_angle_host.h): K x (Cbar, Sbar) pooled by the sample counts and read as one chain's, or
+//                  the circular std of the K mean directions; (2 K + 1) x 8 B per element.
 //   k_chains_hist  a lane sums its pixel's K records piece by piece in 64-bit integers and takes k_hist_stat's steps on the sums.
 //   k_chains_rank  the rank-normalised / folded R-hat of the binned traces (dx_rank_host.h): a lane walks its pixel's K records for
 //                  the pooled total, once more for the scores and the K running (n, mean, m2), and for the fold a third time by
@@ -23,6 +25,7 @@
 #include "dx_stream.h"
 
 static_assert(DX_CHAINS_MAX == DANGX_MAX_CHAINS, "dx_chains_host.h and include/dangx.h disagree");
+static_assert(DX_ANG_MAX_CHAINS == DX_CHAINS_MAX, "dx_angle_host.h and dx_chains_host.h disagree");
 
 namespace {
 
@@ -133,6 +136,41 @@ __global__ __launch_bounds__(BLOCK) void k_chains_pair(ChainsPairArgs a, DxChain
     // element by element where the two planes (or a chain's adopted buffers) are at different 16-byte phases
     dx_stream(n, (diff & 15) == 0, ao, [&](long long i) { chains_pair_item<1>(a, par, stat, i); },
               [&](long long i) { chains_pair_item<2>(a, par, stat, i); });
+}
+
+struct ChainsAngleArgs {
+    const double* C[DX_CHAINS_MAX];
+    const double* S[DX_CHAINS_MAX];
+    double* out;
+};
+
+template <int V>
+__device__ __forceinline__ void chains_angle_item(const ChainsAngleArgs& a, const DxAngPar& par, int stat, long long i) {
+    double C[V][DX_CHAINS_MAX] = {}, S[V][DX_CHAINS_MAX] = {};
+    dx_chains_each<0>(par.K, [&](auto kc) {
+        constexpr int k = decltype(kc)::value;
+        double vc[V], vs[V];
+        ChV<V>::ld(a.C[k] + i, vc); ChV<V>::ld(a.S[k] + i, vs);
+#pragma unroll
+        for (int e = 0; e < V; ++e) { C[e][k] = vc[e]; S[e][k] = vs[e]; }
+    });
+    double r[V];
+#pragma unroll
+    for (int e = 0; e < V; ++e) r[e] = dx_angle_chains_stat(stat, par, C[e], S[e]);
+    ChV<V>::st(a.out + i, r);
+}
+
+// the polarisation angle over several chains (dx_angle_host.h): the chains' Cbar, Sbar pooled by their sample counts and read as
+// one chain's, or (stat 5) the circular std of the chains' mean directions
+__global__ __launch_bounds__(BLOCK) void k_chains_angle(ChainsAngleArgs a, DxAngPar par, long long n, int stat) {
+    const uintptr_t ao = addr(a.out);
+    uintptr_t diff = ao & 7;
+    dx_chains_each<0>(par.K, [&](auto kc) {
+        constexpr int k = decltype(kc)::value;
+        diff |= (ao ^ addr(a.C[k])) | (ao ^ addr(a.S[k]));
+    });
+    dx_stream(n, (diff & 15) == 0, ao, [&](long long i) { chains_angle_item<1>(a, par, stat, i); },
+              [&](long long i) { chains_angle_item<2>(a, par, stat, i); });
 }
 
 struct ChainsHistArgs {
@@ -488,6 +526,38 @@ int chains_signal_impl(dangx_ctx* const* ctxs, int nchains, int sig, int stat, i
     return ro.close(n);
 }
 
+int chains_angle_impl(dangx_ctx* const* ctxs, int nchains, int ang, int stat, double* out, bool to_host) {
+    if (!ctxs || !ctxs[0] || !out) return 1;
+    ChainSet cs{};
+    if (chains_open(ctxs, nchains, cs)) return 1;
+    const std::string why = dx_angle_stat_check(stat, nchains);
+    if (!why.empty()) return chains_fail(ctxs, why);
+    const auto& a0 = ctxs[0]->mom->angs;
+    if (ang < 0 || ang >= (int)a0.size())
+        return chains_fail(ctxs, "chain 0: angle index out of range (" + std::to_string(a0.size()) + " angles registered)");
+    for (int k = 1; k < nchains; ++k) {
+        const auto& ak = ctxs[k]->mom->angs;
+        if (ang >= (int)ak.size() || ak[ang].comp != a0[ang].comp || ak[ang].band != a0[ang].band)
+            return chains_fail(ctxs, "chain " + std::to_string(k) + ": angle " + std::to_string(ang) + " is not the registration of chain 0");
+    }
+    dangx_ctx* c0 = ctxs[0];
+    (void)hipSetDevice(c0->device);
+    const long long n = c0->dims.npix;
+    ReadOut ro{c0, out, to_host};
+    if (ro.open(sizeof(double) * (size_t)n)) return 1;
+    ChainsAngleArgs a{};
+    for (int j = 0; j < cs.K; ++j) {
+        const DxMoments* m = ctxs[j]->mom;
+        a.C[j] = m->angC(m->angs[ang]);
+        a.S[j] = m->angS(m->angs[ang]);
+        if (!a.C[j] || !a.S[j]) return chains_missing(ctxs, j, "ANGLE(" + std::to_string(ang) + ")");
+    }
+    a.out = ro.dst;
+    const DxAngPar par = dx_angle_par(cs.K, cs.cnt);
+    if (chains_run(cs, [&] { hipLaunchKernelGGL(k_chains_angle, dim3(c0->mom->grid_for((n + 1) / 2, 1)), dim3(BLOCK), 0, c0->stream, a, par, n, stat); })) return 1;
+    return ro.close(n);
+}
+
 int chains_pair_impl(dangx_ctx* const* ctxs, int nchains, int pair, int stat, int ddof, double* out, bool to_host) {
     if (!ctxs || !ctxs[0] || !out) return 1;
     ChainSet cs{};
@@ -707,6 +777,14 @@ int dangx_chains_get_signal_dev(dangx_ctx* const* ctxs, int nchains, int sig, in
 
 int dangx_chains_get_signal(dangx_ctx* const* ctxs, int nchains, int sig, int stat, int ddof, double* out) {
     return chains_signal_impl(ctxs, nchains, sig, stat, ddof, out, true);
+}
+
+int dangx_chains_get_angle_dev(dangx_ctx* const* ctxs, int nchains, int ang, int stat, double* out_dev) {
+    return chains_angle_impl(ctxs, nchains, ang, stat, out_dev, false);
+}
+
+int dangx_chains_get_angle(dangx_ctx* const* ctxs, int nchains, int ang, int stat, double* out) {
+    return chains_angle_impl(ctxs, nchains, ang, stat, out, true);
 }
 
 int dangx_chains_get_pair_dev(dangx_ctx* const* ctxs, int nchains, int pair, int stat, int ddof, double* out_dev) {

@@ -41,6 +41,12 @@
 // and updates the f64 mean / m2 planes of every registered output of every band of the segment.  Segments with an integrated
 // band go to a second launch of the kernel's BP form (the streaming form carries no bandpass code).  Nothing registered: no launch.
 //
+// dangx_moments_angles adds the posterior polarisation angle of a component's signal at a band (definitions in dx_angle_host.h):
+// a circular statistic, so what is accumulated is the running mean of (cos 2psi, sin 2psi) = (sQ, sU) / P of the signals' own
+// rounded samples, two f64 planes per angle.  k_moments_angle is a launch of its own behind the signals' (blockIdx.y = segment: a
+// component with up to 8 bands; a second launch of the BP form for segments with an integrated band); k_angle_finish reads the
+// circular mean, the circular standard deviation and the mean resultant length off the two planes.  Nothing registered: no launch.
+//
 // dangx_moments_batches adds batched accumulators of registered pixel planes (definitions in dx_batches_host.h): nbatch slots of
 // (mean, m2) per plane in an allocation of the library's own.  An accumulation adds ONE launch of k_moments_accum behind the
 // others, on the table row of the slot the sample belongs to (inv_n = 1 / its number within the slot); when every slot is full
@@ -67,6 +73,7 @@
 static_assert(DX_MOM_MAX_PAIRS == DANGX_MAX_PAIRS, "dx_moments_host.h and include/dangx.h disagree");
 static_assert(DX_HIST_MAX == DANGX_MAX_HIST && DX_HIST_SIGNAL == DANGX_HIST_SIGNAL, "dx_hist_host.h and include/dangx.h disagree");
 static_assert(DX_SIG_MAX == DANGX_MAX_SIGNALS, "dx_signal_host.h and include/dangx.h disagree");
+static_assert(DX_ANG_MAX == DANGX_MAX_ANGLES && DX_ANG_MAX_CHAINS == DANGX_MAX_CHAINS, "dx_angle_host.h and include/dangx.h disagree");
 static_assert(DX_SEC_HEAD_BYTES == DANGX_SECTION_HEAD_BYTES, "dx_section_host.h and include/dangx.h disagree");
 static_assert(DX_BATCH_MAX == DANGX_MAX_BATCHES && DX_BATCH_MAX_PLANES == DANGX_MAX_BATCH_PLANES, "dx_batches_host.h and include/dangx.h disagree");
 
@@ -343,6 +350,88 @@ __global__ __launch_bounds__(BLOCK) void k_moments_signal(const Model* __restric
             }
         }
     }
+}
+
+typedef const AngSeg __attribute__((address_space(4))) * ang_kptr;   // the segment table through the scalar cache, as sig_kptr
+
+// blockIdx.y = segment: a component with up to DX_ANG_SEG_BANDS bands.  One sample of every registered angle: the running means
+// of (c, s) = (sQ, sU) / P (dx_angle_cs), sQ and sU formed exactly as k_moments_signal forms its kinds 1 and 2 -- the same
+// sed_prep, sig_sed<BP> and dx_signal_product on the same values.  The item loop is k_moments_signal's with the class fixed to
+// Q+U (four evaluation slots e = 2 * (0: Q, 1: U) + (half of the pair)): pairs of pixels where every plane read and both
+// accumulators share their 16-byte phase, the odd first / last element alone, element by element otherwise; every slot goes
+// through the same code, so a result does not depend on which kind of item held its pixel.  The register discipline is that
+// kernel's too: the scalar file belongs to comp_sed's band constants, this kernel's own uniforms are parked in VGPRs.
+template <bool BP>
+__global__ __launch_bounds__(BLOCK) void k_moments_angle(const Model* __restrict__ Mp, const AngSeg* __restrict__ segs, double inv_n) {
+    const Model& M = *Mp;
+    const ang_kptr s = reinterpret_cast<ang_kptr>(reinterpret_cast<uintptr_t>(segs + blockIdx.y));
+    const Comp& c = M.comp[s->comp];
+    const long long n = s->n;
+    const long long gid = (long long)blockIdx.x * BLOCK + threadIdx.x, stride = (long long)gridDim.x * BLOCK;
+    const int vec = BP ? 0 : s->vec;   // segments with an integrated band: issue bound, element by element
+    const long long head = (vec == 2 && n > 0) ? 1 : 0;
+    const long long npair = vec ? (n - head) / 2 : 0, tail = head + 2 * npair;   // tail < n: one element after the last pair
+    const long long nitems = vec ? npair + head + (tail < n ? 1 : 0) : n;
+    int nb = s->nb, nind = s->nind, estep = vec ? 1 : 2;   // estep: the odd slots of an element-by-element item are not evaluated
+    long long item_stride = stride, item_end = nitems, pair_end = npair, i_head = head, i_tail = tail;
+    const double *pa0 = s->src[0][0], *pt00 = s->src[0][1], *pt01 = s->src[0][2];
+    const double *pa1 = s->src[1][0], *pt10 = s->src[1][1], *pt11 = s->src[1][2];
+    const AngBand* sv = segs[blockIdx.y].b;
+    asm volatile("" : "+v"(item_stride), "+v"(item_end), "+v"(pair_end), "+v"(i_head), "+v"(i_tail), "+v"(inv_n));
+    asm volatile("" : "+v"(pa0), "+v"(pt00), "+v"(pt01), "+v"(pa1), "+v"(pt10), "+v"(pt11), "+v"(sv));
+    asm volatile("" : "+v"(nb), "+v"(nind), "+v"(estep));
+    for (long long t = gid; t < item_end; t += item_stride) {
+        const bool single = t >= pair_end;
+        const long long i = !single ? i_head + 2 * t : !vec ? t : (t == pair_end && i_head) ? 0 : i_tail;   // the item's first pixel
+        double a[4] = {0.0, 0.0, 0.0, 0.0}, t0[4] = {0.0, 0.0, 0.0, 0.0}, t1[4] = {0.0, 0.0, 0.0, 0.0};
+        if (single) {
+            a[0] = pa0[i]; t0[0] = pt00[i]; t1[0] = pt01[i];
+            a[2] = pa1[i]; t0[2] = pt10[i]; t1[2] = pt11[i];
+        } else {
+            dbl2 v = *(const GD2*)(pa0 + i); a[0] = v.x; a[1] = v.y;
+            v = *(const GD2*)(pt00 + i); t0[0] = v.x; t0[1] = v.y;
+            v = *(const GD2*)(pt01 + i); t1[0] = v.x; t1[1] = v.y;
+            v = *(const GD2*)(pa1 + i); a[2] = v.x; a[3] = v.y;
+            v = *(const GD2*)(pt10 + i); t0[2] = v.x; t0[3] = v.y;
+            v = *(const GD2*)(pt11 + i); t1[2] = v.x; t1[3] = v.y;
+        }
+        double q0[4] = {0.0, 0.0, 0.0, 0.0}, q1[4] = {0.0, 0.0, 0.0, 0.0}, q2[4] = {0.0, 0.0, 0.0, 0.0};   // the slots' Prep
+#pragma nounroll
+        for (int e = 0; e < 4; e += uni(estep)) {
+            const Prep pr = sed_prep(c, nind > 0 ? sel4(e, t0[0], t0[1], t0[2], t0[3]) : 0.0, nind > 1 ? sel4(e, t1[0], t1[1], t1[2], t1[3]) : 0.0);
+            put4(e, q0, pr.p0); put4(e, q1, pr.p1); put4(e, q2, pr.p2);
+        }
+        for (int b = 0; b < uni(nb); ++b) {
+            const int band = uni(sv[b].band);
+            double x[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma nounroll
+            for (int e = 0; e < 4; e += uni(estep)) {
+                const Prep pr = {sel4(e, q0[0], q0[1], q0[2], q0[3]), sel4(e, q1[0], q1[1], q1[2], q1[3]), sel4(e, q2[0], q2[1], q2[2], q2[3])};
+                const double sed = sig_sed<BP>(M, c, (int)i + (single ? 0 : (e & 1)), 2 + (e >> 1), band, pr);   // never a pixel past the item
+                put4(e, x, dx_signal_product(sel4(e, a[0], a[1], a[2], a[3]), sed));
+            }
+            double c0, s0, c1, s1;
+            dx_angle_cs(x[0], x[2], c0, s0);
+            dx_angle_cs(x[1], x[3], c1, s1);   // the second half of a pair; of a single element 0 / 0, never stored
+            double* cp = sv[b].C + i;
+            double* sp = sv[b].S + i;
+            if (single) {
+                *cp = dx_angle_mean(c0, *cp, inv_n);
+                *sp = dx_angle_mean(s0, *sp, inv_n);
+            } else {
+                const dbl2 mc = *(GD2*)cp, ms = *(GD2*)sp;
+                *(GD2*)cp = dbl2{dx_angle_mean(c0, mc.x, inv_n), dx_angle_mean(c1, mc.y, inv_n)};
+                *(GD2*)sp = dbl2{dx_angle_mean(s0, ms.x, inv_n), dx_angle_mean(s1, ms.y, inv_n)};
+            }
+        }
+    }
+}
+
+// one chain's read-out: out = dx_angle_stat(stat, Cbar, Sbar)
+__global__ __launch_bounds__(BLOCK) void k_angle_finish(const double* __restrict__ C, const double* __restrict__ S, double* __restrict__ out,
+                                                        long long n, int stat) {
+    for (long long i = (long long)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * BLOCK)
+        out[i] = dx_angle_stat(stat, C[i], S[i]);
 }
 
 struct HistStatArgs {
@@ -673,6 +762,54 @@ size_t sig_table(const dangx_ctx* ctx, const DxMoments* m, std::vector<SigSeg>& 
     return ndelta;
 }
 
+// the device table of the registered angles for the chain's planes as they are now: delta-band segments first
+// (k_moments_angle<false>), then those with an integrated band; returns the number of the first kind
+size_t ang_table(const dangx_ctx* ctx, const DxMoments* m, std::vector<AngSeg>& t) {
+    const long long np = ctx->dims.npix;
+    const int nmaps = ctx->dims.nmaps;
+    t.clear();
+    size_t ndelta = 0;
+    for (int pass = 0; pass < 2; ++pass)
+    for (const DxAngSeg& ps : m->ang_plan) {
+        bool bp = false;
+        for (int b = 0; b < ps.nb; ++b) bp = bp || ctx->hm.band[ps.band[b]].n != 0;
+        if (bp != (pass == 1)) continue;
+        if (!bp) ++ndelta;
+        AngSeg s;
+        std::memset(&s, 0, sizeof s);   // the tables are compared as bytes
+        s.amp = ctx->amp[ps.comp];
+        s.idx = ctx->idx[ps.comp];
+        s.n = np;
+        s.comp = ps.comp; s.nb = ps.nb;
+        s.nind = ctx->desc[ps.comp].nindices;
+        uintptr_t phase = 0, diff = 0;   // diff: bit 3 set when two addresses differ in their 16-byte phase
+        bool first = true;
+        auto see = [&](const double* q) {
+            const uintptr_t a = reinterpret_cast<uintptr_t>(q);
+            if (first) { phase = a; first = false; }
+            diff |= (a ^ phase) & 15;
+        };
+        for (int b = 0; b < ps.nb; ++b) {
+            const auto& ag = m->angs[ps.ang[b]];
+            s.b[b].band = ps.band[b];
+            s.b[b].C = m->angC(ag);
+            s.b[b].S = m->angS(ag);
+            see(s.b[b].C); see(s.b[b].S);
+        }
+        for (int k = 0; k < 2; ++k) {
+            const long long plane = 1 + k;   // Q, U
+            for (int q = 0; q < 3; ++q) {
+                const bool has = q == 0 || q - 1 < s.nind;
+                s.src[k][q] = !has ? s.amp + plane * np : q == 0 ? s.amp + plane * np : s.idx + ((long long)(q - 1) * nmaps + plane) * np;
+                see(s.src[k][q]);
+            }
+        }
+        s.vec = diff ? 0 : ((phase & 15) ? 2 : 1);
+        t.push_back(s);
+    }
+    return ndelta;
+}
+
 // finish of one plane pair (mean, m2) into dst [npix]
 int finish_plane(dangx_ctx* ctx, const double* mean, const double* m2, int stat, double dn, double* dst) {
     FinishArgs a{};
@@ -829,6 +966,9 @@ int dangx_moments_accumulate(dangx_ctx* ctx) {
     for (int l = 0; l < ctx->dims.ncomp; ++l)
         if (m->sig_used[l] && (!ctx->comp_set[l] || ctx->desc[l].type != m->sig_type[l] || ctx->desc[l].nindices != m->sig_nind[l]))
             return fail(ctx, "posterior moments: component " + std::to_string(l) + " changed type or nindices since dangx_moments_signals");
+    for (int l = 0; l < ctx->dims.ncomp; ++l)
+        if (m->ang_used[l] && (!ctx->comp_set[l] || ctx->desc[l].type != m->ang_type[l] || ctx->desc[l].nindices != m->ang_nind[l]))
+            return fail(ctx, "posterior moments: component " + std::to_string(l) + " changed type or nindices since dangx_moments_angles");
     if (!m->hists.empty()) {   // no counter ever wraps: refused before anything is touched
         const std::string why = dx_hist_limit_check(m->count + 1, m->hbits);
         if (!why.empty()) return fail(ctx, "posterior moments: dangx_moments_accumulate: " + why);
@@ -838,7 +978,7 @@ int dangx_moments_accumulate(dangx_ctx* ctx) {
                                      " declared per-pixel ranges and has no maps (dangx_moments_hist_range_maps was not called for it)");
     }
     (void)hipSetDevice(ctx->device);
-    if (!m->sigs.empty() && sync_model(ctx)) return 1;   // the SEDs read the device model: current before anything is launched
+    if ((!m->sigs.empty() || !m->angs.empty()) && sync_model(ctx)) return 1;   // the SEDs read the device model: current before anything is launched
     const double inv_n = 1.0 / (double)(m->count + 1);
     const long long pairs = (ctx->dims.npix + 1) / 2;   // the items of a launch that strides over pairs of pixels
     if (!m->segs.empty()) {
@@ -943,6 +1083,30 @@ int dangx_moments_accumulate(dangx_ctx* ctx) {
             auto kern = m->nhist_sig ? k_moments_signal<true, true> : k_moments_signal<true, false>;
             hipLaunchKernelGGL(kern, dim3(m->grid_for(ctx->dims.npix, nseg), nseg), dim3(BLOCK), 0, ctx->stream, (const Model*)ctx->dm,
                                (const SigSeg*)(m->d_sig + ndelta), inv_n);
+            HIPCHK(ctx, hipGetLastError());
+        }
+    }
+    if (!m->angs.empty()) {   // the polarisation angles: a launch of their own behind the signals', independent of everything above
+        std::vector<AngSeg> t;
+        const size_t ndelta = ang_table(ctx, m, t);
+        const bool same = t.size() == m->ang_table.size() && std::memcmp(t.data(), m->ang_table.data(), sizeof(AngSeg) * t.size()) == 0;
+        if (!same) {   // first accumulation, a component's buffers adopted again or a band's bandpass replaced: one upload (and a host wait)
+            HIPCHK(ctx, hipMemcpyAsync(m->d_ang, t.data(), sizeof(AngSeg) * t.size(), hipMemcpyHostToDevice, ctx->stream));
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+            m->ang_table = t;
+        }
+        if (ndelta) {
+            const unsigned nseg = (unsigned)ndelta;
+            Timed tm(ctx, DANGX_K_ANGLE);
+            hipLaunchKernelGGL(k_moments_angle<false>, dim3(m->grid_for(pairs, nseg), nseg), dim3(BLOCK), 0, ctx->stream, (const Model*)ctx->dm,
+                               (const AngSeg*)m->d_ang, inv_n);
+            HIPCHK(ctx, hipGetLastError());
+        }
+        if (t.size() > ndelta) {   // segments with an integrated band: element by element
+            const unsigned nseg = (unsigned)(t.size() - ndelta);
+            Timed tm(ctx, DANGX_K_ANGLE, 2);   // the profile tells the two forms apart by this mark
+            hipLaunchKernelGGL(k_moments_angle<true>, dim3(m->grid_for(ctx->dims.npix, nseg), nseg), dim3(BLOCK), 0, ctx->stream,
+                               (const Model*)ctx->dm, (const AngSeg*)(m->d_ang + ndelta), inv_n);
             HIPCHK(ctx, hipGetLastError());
         }
     }
@@ -1336,6 +1500,82 @@ int dangx_moments_get_signal(dangx_ctx* ctx, int sig, int stat, int ddof, double
     return get_signal_impl(ctx, sig, stat, ddof, out, true);
 }
 
+int dangx_moments_angles(dangx_ctx* ctx, int nang, const int32_t* spec) {
+    if (reg_open(ctx, "dangx_moments_angles")) return 1;   // its tables come from the descriptors: angles do not depend on the selection
+    DxMoments* m = ctx->mom;
+    const int ncomp = ctx->dims.ncomp;
+    int set[MAXC] = {}, global[MAXC] = {}, tcmb[MAXC] = {};
+    for (int l = 0; l < ncomp; ++l) {
+        set[l] = ctx->comp_set[l] ? 1 : 0;
+        global[l] = is_global_type(ctx->desc[l].type) ? 1 : 0;
+        tcmb[l] = ctx->desc[l].type == DANGX_TCMB ? 1 : 0;
+    }
+    const std::string why = dx_angle_check(nang, spec, ncomp, ctx->dims.nbands, ctx->dims.nmaps, set, global, tcmb);
+    if (!why.empty()) return fail(ctx, "posterior moments: dangx_moments_angles: " + why);
+    (void)hipSetDevice(ctx->device);
+    bool used[MAXC] = {};
+    for (int a = 0; a < nang; ++a) used[spec[2 * a]] = true;
+    for (int l = 0; l < ncomp; ++l)   // the chain's maps exist from here on (what dangx_get_amplitude does on first use)
+        if (used[l] && ensure_state(ctx, l)) return 1;
+    const std::vector<DxAngSeg> plan = dx_angle_plan(nang, spec, ncomp, ctx->dims.nbands);
+    // accumulators: both planes of an angle at the 16-byte phase of the component's Q plane, so that the streams line up
+    std::vector<DxMoments::Ang> na;
+    long long off = 0;
+    for (int a = 0; a < nang; ++a) {
+        DxMoments::Ang ag{spec[2 * a], spec[2 * a + 1], 0};
+        const double* plane = ctx->amp[ag.comp] + (long long)ctx->dims.npix;
+        const long long phase = (long long)((reinterpret_cast<uintptr_t>(plane) >> 3) & 1);
+        if ((off & 1) != phase) ++off;
+        ag.off = off;
+        ag.id = a;
+        off += ctx->dims.npix;
+        na.push_back(ag);
+    }
+    const long long half = off + (off & 1);   // even: the Sbar half has the phases of the Cbar half
+    // everything new is allocated before anything old is dropped (reg_close)
+    DevBuf<double> aacc;
+    DevBuf<AngSeg> d_ang;
+    DevStatus st;
+    if (!na.empty()) {
+        aacc.zeros(2 * (size_t)half, ctx->stream, st);
+        d_ang.alloc(plan.size(), st);
+    }
+    if (reg_close(ctx, "dangx_moments_angles", st, !na.empty())) return 1;
+    m->aacc = std::move(aacc); m->d_ang = std::move(d_ang); m->aacc_half = half;
+    m->angs = na;
+    m->ang_plan = plan;
+    m->ang_table.clear();   // the next accumulation uploads the table
+    for (int l = 0; l < MAXC; ++l) {
+        m->ang_used[l] = l < ncomp && used[l];
+        m->ang_type[l] = m->ang_used[l] ? ctx->desc[l].type : 0;
+        m->ang_nind[l] = m->ang_used[l] ? ctx->desc[l].nindices : 0;
+    }
+    return 0;
+}
+
+static int get_angle_impl(dangx_ctx* ctx, int ang, int stat, double* out, bool to_host) {
+    if (!ctx || !out || need_live(ctx, "dangx_moments_get_angle")) return 1;
+    const DxMoments* m = ctx->mom;
+    if (ang < 0 || ang >= (int)m->angs.size())
+        return fail(ctx, "posterior moments: angle index out of range (" + std::to_string(m->angs.size()) + " angles registered)");
+    const std::string why = dx_angle_stat_check(stat, 1);
+    if (!why.empty()) return fail(ctx, "posterior moments: " + why);
+    if (count_check(ctx, nullptr, 0)) return 1;
+    (void)hipSetDevice(ctx->device);
+    const long long np = ctx->dims.npix;
+    ReadOut ro{ctx, out, to_host};
+    if (ro.open(sizeof(double) * (size_t)np)) return 1;
+    const auto& a = m->angs[ang];
+    const unsigned gx = std::max(1u, std::min(nblocks(np), 1024u));
+    hipLaunchKernelGGL(k_angle_finish, dim3(gx), dim3(BLOCK), 0, ctx->stream, (const double*)m->angC(a), (const double*)m->angS(a), ro.dst, np, stat);
+    HIPCHK(ctx, hipGetLastError());
+    return ro.close(np);
+}
+
+int dangx_moments_get_angle_dev(dangx_ctx* ctx, int ang, int stat, double* out_dev) { return get_angle_impl(ctx, ang, stat, out_dev, false); }
+
+int dangx_moments_get_angle(dangx_ctx* ctx, int ang, int stat, double* out) { return get_angle_impl(ctx, ang, stat, out, true); }
+
 int dangx_moments_batches(dangx_ctx* ctx, int nreg, const int32_t* planes, int nbatch, int64_t batch_len) {
     RegTables tab;
     if (reg_open(ctx, "dangx_moments_batches", &tab)) return 1;
@@ -1461,6 +1701,7 @@ static DxSecReg section_reg(const dangx_ctx* ctx, const DxMoments* m) {
     }
     r.nbins = m->hbins; r.bits = m->hbits;
     for (const auto& s : m->sigs) { r.signals.push_back(s.comp); r.signals.push_back(s.band); r.signals.push_back(s.kind); }
+    for (const auto& a : m->angs) { r.angles.push_back(a.comp); r.angles.push_back(a.band); }
     for (const auto& b : m->batches) plane(r.batch_planes, b.seg);
     r.nbatch = m->nbatch;
     return r;
@@ -1515,8 +1756,13 @@ int section_shape(dangx_ctx* ctx, const char* who, int family, int a, int b, Sec
                                  std::to_string(a) + " has a global range and no range maps");
         sh.bytes = dx_section_hist_range_bytes(np);
         return 0;
+    case DX_SEC_ANGLE:
+        if (m->angs.empty()) break;   // a context without angles has the families it always had
+        if (range(m->angs.size(), "angle index")) return 1;
+        sh.bytes = dx_section_angle_bytes(np);
+        return 0;
     }
-    return fail(ctx, std::string("posterior moments: ") + who + ": family must be 0 (HEAD) .. 6 (HIST_RANGE)");
+    return fail(ctx, std::string("posterior moments: ") + who + ": family must be 0 (HEAD) .. 6 (HIST_RANGE), or 7 (ANGLE) where angles are registered");
 }
 
 // a holder's buffer for a section of `bytes` payload bytes, and its planes entered into the tables
@@ -1564,6 +1810,7 @@ int holder_take(dangx_ctx* ctx, int family, int a, int b, const SecShape& sh, lo
     case DX_SEC_SIGNAL: m->h_sig[a].mean = base; m->h_sig[a].m2 = base + np; break;
     case DX_SEC_BATCHES: m->h_batch[a] = base; break;
     case DX_SEC_HIST_RANGE: m->h_range[a] = base; break;
+    case DX_SEC_ANGLE: m->h_ang[a].mean = base; m->h_ang[a].m2 = base + np; break;
     }
     return 0;
 }
@@ -1606,6 +1853,7 @@ int section_runs(dangx_ctx* ctx, const char* who, int family, int a, int b, cons
                                  std::to_string(a) + " has no range maps yet (dangx_moments_hist_range_maps)");
         add(m->range_lo(m->hists[a]), 0, plane); add(m->range_hi(m->hists[a]), plane, plane);
         break;
+    case DX_SEC_ANGLE: add(m->angC(m->angs[a]), 0, plane); add(m->angS(m->angs[a]), plane, plane); break;
     }
     bool missing = !put && m->holder && family == DX_SEC_PLANES && sh.global && !m->h_rows[a];
     for (const SecRun& r : runs) missing = missing || (!r.dev && !r.host);
@@ -1732,7 +1980,7 @@ int dangx_moments_begin_like(dangx_ctx* ctx, dangx_ctx* like) {
         ctx->dims.ncomp != like->dims.ncomp || ctx->dims.nbands != like->dims.nbands)
         return fail(ctx, "posterior moments: dangx_moments_begin_like: the contexts differ in npix / pix0 / nmaps / ncomp / nbands");
     for (int l = 0; l < ctx->dims.ncomp; ++l)
-        if ((o->sel[l] || o->sig_used[l]) && (!ctx->comp_set[l] || ctx->desc[l].type != like->desc[l].type || ctx->desc[l].nindices != like->desc[l].nindices))
+        if ((o->sel[l] || o->sig_used[l] || o->ang_used[l]) && (!ctx->comp_set[l] || ctx->desc[l].type != like->desc[l].type || ctx->desc[l].nindices != like->desc[l].nindices))
             return fail(ctx, "posterior moments: dangx_moments_begin_like: component " + std::to_string(l) + " is not the other context's");
     (void)hipSetDevice(ctx->device);
     if (ctx->mom) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // no launch may still read what is dropped
@@ -1747,10 +1995,13 @@ int dangx_moments_begin_like(dangx_ctx* ctx, dangx_ctx* like) {
     m->sigs = o->sigs; m->sig_plan = o->sig_plan;
     std::memcpy(m->sig_type, o->sig_type, sizeof m->sig_type); std::memcpy(m->sig_nind, o->sig_nind, sizeof m->sig_nind);
     std::memcpy(m->sig_used, o->sig_used, sizeof m->sig_used);
+    m->angs = o->angs; m->ang_plan = o->ang_plan;
+    std::memcpy(m->ang_type, o->ang_type, sizeof m->ang_type); std::memcpy(m->ang_nind, o->ang_nind, sizeof m->ang_nind);
+    std::memcpy(m->ang_used, o->ang_used, sizeof m->ang_used);
     m->batches = o->batches; m->nbatch = o->nbatch; m->batch_len = o->batch_len; m->bpitch = o->bpitch;
     m->h_seg.resize(m->segs.size()); m->h_pair.assign(m->pairs.size(), nullptr); m->h_hist.assign(m->hists.size(), nullptr);
     m->h_range.assign(m->hists.size(), nullptr);
-    m->h_sig.resize(m->sigs.size()); m->h_batch.assign(m->batches.size(), nullptr);
+    m->h_sig.resize(m->sigs.size()); m->h_batch.assign(m->batches.size(), nullptr); m->h_ang.resize(m->angs.size());
     dx_moments_free(ctx);   // whatever the context held or accumulated goes
     ctx->mom = m.release();
     return 0;

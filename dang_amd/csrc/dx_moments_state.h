@@ -4,6 +4,7 @@
 #pragma once
 #include "dx_host.h"
 #include "dx_signal_host.h"
+#include "dx_angle_host.h"
 
 #include <cstdint>
 #include <utility>
@@ -84,6 +85,25 @@ struct SigSeg {           // a (component, plane class) with up to DX_SIG_SEG_BA
     SigBand b[DX_SIG_SEG_BANDS];
     SigHistBand hb[DX_SIG_SEG_BANDS];   // by band, as b
     int hbins, hbits;     // the context's nbins and bits, for the outputs with a histogram
+};
+
+struct AngBand {          // one band of an angle segment: the two accumulators of the angle registered there
+    double* C;
+    double* S;
+    int band;
+    int pad_;
+};
+
+struct AngSeg {           // a component with up to DX_ANG_SEG_BANDS bands; the chain's planes resolved at accumulate time
+    const double* amp;    // the component's [nmaps][npix]: what the table is compared by
+    const double* idx;    // the component's [nind][nmaps][npix]
+    // src[k][0..2]: the amplitude and the two index planes of plane Q (k = 0) and U (k = 1).  An index plane the component does
+    // not have points at the amplitude plane, which IS read: the load hits the cache and its value is never used
+    const double* src[2][3];
+    long long n;
+    int comp, nb;
+    int vec, nind;        // as SigSeg's
+    AngBand b[DX_ANG_SEG_BANDS];
 };
 
 // ---- device memory that belongs to its holder: freed when the holder goes, handed on by move
@@ -172,6 +192,16 @@ struct DxMoments {
     DevBuf<SigSeg> d_sig;
     DevBuf<double> sacc;             // [mean: sacc_half doubles | m2: sacc_half doubles]
     long long sacc_half = 0;
+    // dangx_moments_angles
+    struct Ang { int comp, band; long long off; int id = 0; };   // off: the angle's Cbar plane in aacc; id: its index in angs
+    std::vector<Ang> angs;
+    std::vector<DxAngSeg> ang_plan;
+    int ang_type[MAXC] = {}, ang_nind[MAXC] = {};   // shape key of the registered components at registration
+    bool ang_used[MAXC] = {};
+    std::vector<AngSeg> ang_table;   // the table as last uploaded
+    DevBuf<AngSeg> d_ang;
+    DevBuf<double> aacc;             // [Cbar: aacc_half doubles | Sbar: aacc_half doubles], every plane at the phase of the component's Q plane
+    long long aacc_half = 0;
     // dangx_moments_batches: [reg][batch][mean | m2][bpitch] in bacc, every plane at the 16-byte phase of its segment's main
     // accumulator (bpitch is even, so a registration's planes share the phase of its first)
     struct Batch { int seg; long long off; int id = 0; };   // seg: index into segs; off: batch 0's mean plane in bacc; id: its index in batches
@@ -204,6 +234,7 @@ struct DxMoments {
     std::vector<double*> h_range;     // by Hist::id: lo of a HIST_RANGE section put (hi follows at npix)
     std::vector<HeldSeg> h_sig;       // by Sig::id (mean, m2)
     std::vector<double*> h_batch;     // by Batch::id: batch 0's mean plane
+    std::vector<HeldSeg> h_ang;       // by Ang::id (mean: Cbar, m2: Sbar)
     bool h_rows[MAXC] = {};           // the host rows tm_* of a template / monopole / hi_fit member were put
 
     // where things are
@@ -215,6 +246,8 @@ struct DxMoments {
     double* C(const Pair& p) const { return holder ? h_pair[p.id] : pc + p.off; }
     double* mean(const Sig& s) const { return holder ? h_sig[s.id].mean : sacc + s.off; }
     double* m2(const Sig& s) const { return holder ? h_sig[s.id].m2 : sacc + sacc_half + s.off; }
+    double* angC(const Ang& a) const { return holder ? h_ang[a.id].mean : aacc + a.off; }
+    double* angS(const Ang& a) const { return holder ? h_ang[a.id].m2 : aacc + aacc_half + a.off; }
     uint32_t* records(const Hist& h) const { return holder ? h_hist[h.id] : hrec + h.off; }
     double* range_lo(const Hist& h) const { return holder ? h_range[h.id] : (h.have_maps ? hrange + h.roff : nullptr); }   // null: no maps (yet)
     double* range_hi(const Hist& h) const { double* p = range_lo(h); return p ? p + hpitch : nullptr; }

@@ -11,20 +11,22 @@
 //   SIGNAL  (sig, -)      mean, m2, each [npix] f64
 //   BATCHES (reg, -)      [nbatch][mean, m2][npix] f64
 //   HIST_RANGE (reg, -)   lo, hi, each [npix] f64: the range maps of a histogram registration with per-pixel ranges (only those have it)
+//   ANGLE   (ang, -)      Cbar, Sbar, each [npix] f64 (dx_angle_host.h)
 //
 // The fingerprint is FNV-1a (64 bit) over the registration written out as little-endian 64-bit words, in six groups that HEAD
 // carries one by one, so that a mismatch can be named: the shard (npix, pix0, nmaps), the selection (the selection words, type
 // and nindices of every selected component), the pairs (lag-1 flag and pair list), the histograms (planes, lo, hi as their bit
 // patterns, nbins, bits; with a per-pixel range anywhere in the list also every registration's range kind and the checksum of its
-// maps -- a list of global ranges alone hashes as it always did), the signals (specs) and the batches (planes, nbatch).  The
-// overall value hashes the six.
+// maps -- a list of global ranges alone hashes as it always did), the signals (specs; with an angle registered also the angle
+// specs -- a registration without angles hashes as it always did) and the batches (planes, nbatch).  The overall value hashes
+// the six.
 #pragma once
 #include <cstdint>
 #include <cstring>
 #include <string>
 #include <vector>
 
-enum { DX_SEC_HEAD = 0, DX_SEC_PLANES = 1, DX_SEC_PAIR = 2, DX_SEC_HIST = 3, DX_SEC_SIGNAL = 4, DX_SEC_BATCHES = 5, DX_SEC_HIST_RANGE = 6, DX_SEC_FAMILIES = 7 };
+enum { DX_SEC_HEAD = 0, DX_SEC_PLANES = 1, DX_SEC_PAIR = 2, DX_SEC_HIST = 3, DX_SEC_SIGNAL = 4, DX_SEC_BATCHES = 5, DX_SEC_HIST_RANGE = 6, DX_SEC_ANGLE = 7, DX_SEC_FAMILIES = 8 };
 enum { DX_SEC_G_SHARD = 0, DX_SEC_G_SEL = 1, DX_SEC_G_PAIRS = 2, DX_SEC_G_HIST = 3, DX_SEC_G_SIGNALS = 4, DX_SEC_G_BATCHES = 5, DX_SEC_GROUPS = 6 };
 
 #define DX_SEC_VERSION 1u
@@ -32,7 +34,7 @@ enum { DX_SEC_G_SHARD = 0, DX_SEC_G_SEL = 1, DX_SEC_G_PAIRS = 2, DX_SEC_G_HIST =
 #define DX_SEC_HEAD_BYTES 104
 
 inline const char* dx_section_family_name(int family) {
-    static const char* const n[DX_SEC_FAMILIES] = {"HEAD", "PLANES", "PAIR", "HIST", "SIGNAL", "BATCHES", "HIST_RANGE"};
+    static const char* const n[DX_SEC_FAMILIES] = {"HEAD", "PLANES", "PAIR", "HIST", "SIGNAL", "BATCHES", "HIST_RANGE", "ANGLE"};
     return family >= 0 && family < DX_SEC_FAMILIES ? n[family] : "?";
 }
 
@@ -48,6 +50,7 @@ struct DxSecReg {              // what a registration is made of
     std::vector<uint64_t> hist_sum;           // checksum of the range maps per registration (0 for a global range)
     int nbins = 0, bits = 0;
     std::vector<int32_t> signals;             // 3 per signal: {comp, band, kind}
+    std::vector<int32_t> angles;              // 2 per angle: {comp, band}; hashed into the signals' group, and only when not empty
     std::vector<int32_t> batch_planes;        // 3 per registration
     int nbatch = 0;
 };
@@ -105,6 +108,7 @@ inline void dx_section_groups(const DxSecReg& r, uint64_t (&g)[DX_SEC_GROUPS]) {
         for (uint64_t v : r.hist_sum) d.word(v);
     }
     e.list(r.signals);
+    if (!r.angles.empty()) e.list(r.angles);   // only then: the group of a registration without angles stays what it was
     f.list(r.batch_planes); f.num(r.batch_planes.empty() ? 0 : r.nbatch);
     g[0] = a.h; g[1] = b.h; g[2] = c.h; g[3] = d.h; g[4] = e.h; g[5] = f.h;
 }
@@ -184,7 +188,7 @@ inline std::string dx_section_head_unpack(const unsigned char* in, size_t bytes,
 inline std::string dx_section_head_diff(const DxSecHead& got, const DxSecHead& own) {
     static const char* const what[DX_SEC_GROUPS] = {
         "the shard (npix, pix0 or nmaps)", "the selection (selection words, type or nindices of a selected component)",
-        "the pair list", "the histogram registrations (planes, lo / hi range, nbins or bits)", "the signal registrations",
+        "the pair list", "the histogram registrations (planes, lo / hi range, nbins or bits)", "the signal or angle registrations",
         "the batch registrations (planes)"};
     std::string why;
     auto add = [&](const std::string& s) { why += (why.empty() ? "" : "; ") + s; };
@@ -210,4 +214,5 @@ inline long long dx_section_hist_bytes(long long npix, int nbins, int bits) { re
 inline long long dx_section_signal_bytes(long long npix) { return 2 * npix * 8; }
 inline long long dx_section_batches_bytes(long long npix, int nbatch) { return 2LL * nbatch * npix * 8; }
 inline long long dx_section_hist_range_bytes(long long npix) { return 2 * npix * 8; }
+inline long long dx_section_angle_bytes(long long npix) { return 2 * npix * 8; }
 inline long long dx_section_round256(long long bytes) { return (bytes + 255) / 256 * 256; }

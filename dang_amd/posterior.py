@@ -6,7 +6,7 @@ Those are ONE builder (_build) driven by two descriptions:
 
   a source   what a *_maps call reads its chains through: one chain of this process (_OneChain), several (_LocalChains), or
              the chains of every rank of a process group (DistChains); all with shards, counts, fetch, batches_info, finish, here
-  a family   what is read (FAMILIES: planes, pair, hist, rank, batches, signal): its registration, how an item becomes a key,
+  a family   what is read (FAMILIES: planes, pair, hist, rank, batches, signal, angle): its registration, how an item becomes a key,
              which sections it owns, which statistics are available, its two thin getters and the checks each form makes
 
 Chains of other processes (dist_chains) and save / restore (moments_save, moments_load) are thin layers over the sections of the
@@ -321,6 +321,33 @@ def posterior_signal_maps(ddata, ddof=0, masked_value=None, engines=None):
     return _build(SIGNAL, "posterior_signal_maps", _OneChain(ddata, engines), ddof=ddof, masked_value=masked_value)
 
 
+def default_angle_specs(dpar, component_list, bands):
+    """[(l, band), ...] for moments_angles: one angle for every polarised intensity (l, band, P) of default_signal_specs -- the
+    components whose Q and U amplitudes are both sampled and that have a sampled index, at the band nearest their nu_ref.
+    Pure Python."""
+    return [(l, band) for l, band, kind in default_signal_specs(dpar, component_list, bands) if kind == 3]
+
+
+def moments_angles(dpar, ddata, specs=None, engines=None):
+    """dangx_moments_angles on every context of this process, after moments_begin and before the first moments_accumulate;
+    specs=None: default_angle_specs of the run.  Returns the spec list [(l, band), ...]."""
+    engs = _engines_of(ddata, engines)
+    if specs is None:
+        specs = default_angle_specs(dpar, engs[0].component_list, engs[0].bands)
+    specs = [(int(l), int(j)) for l, j in specs]
+    for e in engs:
+        e.moments_angles(specs)
+    return specs
+
+
+def posterior_angle_maps(ddata, masked_value=None, engines=None):
+    """{(component label, band label): {'n', 'psi', 'psi_std', 'R'}} of the angles moments_angles registered, as host arrays
+    [npix]: the circular mean of the polarisation angle psi = atan2(U, Q) / 2 in [-pi/2, pi/2] (the model's own Q, U: no sign
+    convention is applied), its circular standard deviation in radians and the mean resultant length.  Several contexts of this
+    process: their shards side by side.  masked_value: as in posterior_maps."""
+    return _build(ANGLE, "posterior_angle_maps", _OneChain(ddata, engines), masked_value=masked_value)
+
+
 # --------------------------------------------------------------------------- several chains: R-hat and pooled summaries
 # dangx_chains_* (include/dangx.h): the accumulators of K chains of one device are combined on the device and only the map asked
 # for is written.  `engines` below is one Engine per chain (the same shard of each); a "chain" of the map functions is a ddata
@@ -360,6 +387,13 @@ def chains_get_template(engines, l, stat, ddof=0, out=None):
 def chains_get_signal(engines, s, stat, ddof=0, device=False, out=None):
     """chains_get's statistics 'mean', 'std', 'rhat', 'W', 'B' of registered signal s (the same registration in every chain), [npix]."""
     return _chains_readout(engines, "dangx_chains_get_signal", (engines[0].npix,), (int(s), _code(L.CHAINS_STAT_CODES, stat), int(ddof)), device, out)
+
+
+def chains_get_angle(engines, a, stat, device=False, out=None):
+    """Engine.moments_get_angle's statistics of registered angle a (the same registration in every chain) on the chains' (Cbar,
+    Sbar) pooled by their sample counts -- unequal counts allowed -- and 'between' / 5: the circular standard deviation of the
+    chains' mean directions, to set beside 'psi_std' (there is no standard circular R-hat); [npix]."""
+    return _chains_readout(engines, "dangx_chains_get_angle", (engines[0].npix,), (int(a), _code(L.ANGLE_STAT_CODES, stat)), device, out)
 
 
 def chains_get_pair(engines, p, stat, ddof=0, device=False, out=None):
@@ -581,13 +615,19 @@ SIGNAL = _Family("signals", "moments_signals", "signal", "moments_get_signal", "
                  sections=lambda it, stats: [(L.SEC_SIGNAL, it[0], 0, False)],
                  stats=lambda src, o: _named(_chains_stats(src.counts, False) if src.pooled else ("mean", "std")),
                  args=lambda it, stat, o: (it[0], stat, o["ddof"]), head=_count_head)
-FAMILIES = {"planes": PLANES, "pair": PAIR, "hist": HIST, "rank": RANK, "batches": BATCHES, "signal": SIGNAL}
+ANGLE = _Family("angles", "moments_angles", "angle", "moments_get_angle", "chains_get_angle", (_SAME + ("counts",), _SAME),
+                items=lambda e0, specs: list(enumerate(specs)),
+                key=lambda e0, it: (e0.component_list[it[1][0]].label, e0.bands[it[1][1]].label),
+                sections=lambda it, stats: [(L.SEC_ANGLE, it[0], 0, False)],
+                stats=lambda src, o: _named(("psi", "psi_std", "R") + (("between",) if src.pooled else ())),
+                args=lambda it, stat, o: (it[0], stat), head=_count_head)
+FAMILIES = {"planes": PLANES, "pair": PAIR, "hist": HIST, "rank": RANK, "batches": BATCHES, "signal": SIGNAL, "angle": ANGLE}
 
 
 def own_sections(e):
     """Engine.moments_sections: the section every registered item of engine e owns, in the order moments_save writes them"""
     out = []
-    for fam in (PLANES, PAIR, HIST, SIGNAL, BATCHES):
+    for fam in (PLANES, PAIR, HIST, SIGNAL, BATCHES, ANGLE):
         reg = _registration(e, fam.reg, None, fam.call if fam is PLANES else None)
         if reg is not None:
             for item in fam.items(e, reg):
@@ -618,7 +658,8 @@ def _build(fam, who, chains, masked_value=None, **o):
             _batch_first_check(who, o["info"], o["first"])
     if src.pooled:
         # through dang_amd.api, where these names have always been replaced by stand-ins; it hands back this module's own otherwise
-        get = lambda col, suffix, args: getattr(_api, fam.chains + suffix)(col, *args)
+        # (a name outside __all__, which api does not carry, is taken here)
+        get = lambda col, suffix, args: (getattr(_api, fam.chains + suffix, None) or globals()[fam.chains + suffix])(col, *args)
     else:
         get = lambda col, suffix, args: getattr(col[0], fam.single + suffix)(*args)
     stats = fam.stats(src, o)
@@ -693,6 +734,12 @@ def chains_batch_maps(chains, first=0, ddof=0, masked_value=None):
     return _build(BATCHES, "chains_batch_maps", chains, first=first, ddof=ddof, masked_value=masked_value)
 
 
+def chains_angle_maps(chains, masked_value=None):
+    """posterior_angle_maps over several chains (or dist_chains' object): {'n', 'nchains', 'psi', 'psi_std', 'R', 'between'} per
+    registered angle -- the first three of the pooled (Cbar, Sbar), 'between' the circular std of the chains' mean directions."""
+    return _build(ANGLE, "chains_angle_maps", chains, masked_value=masked_value)
+
+
 def chains_signal_maps(chains, ddof=0, masked_value=None):
     """posterior_signal_maps over several chains: {'n', 'nchains', 'mean', 'std', 'rhat', 'W', 'B'} per registered signal."""
     return _build(SIGNAL, "chains_signal_maps", chains, ddof=ddof, masked_value=masked_value)
@@ -706,7 +753,7 @@ def chains_signal_maps(chains, ddof=0, masked_value=None):
 
 _HEAD_STRUCT = struct.Struct("<IIqiiqiiqQ6Q")
 _HEAD_GROUPS = ("the shard (npix, pix0 or nmaps)", "the selection (selection words, type or nindices of a selected component)",
-                "the pair list", "the histogram registrations (planes, lo / hi range, nbins or bits)", "the signal registrations",
+                "the pair list", "the histogram registrations (planes, lo / hi range, nbins or bits)", "the signal or angle registrations",
                 "the batch registrations (planes)")
 
 
@@ -894,7 +941,7 @@ class DistChains:
 def dist_chains(chains, group=None, dst=0):
     """The chains of every rank of `group` (None: the default process group) as ONE set: every rank passes its local chain or
     chains (each a ddata, or the list of that chain's shard engines), and the object returned is accepted by chains_posterior_maps,
-    chains_pair_maps, chains_quantile_maps, chains_rank_maps, chains_batch_maps and chains_signal_maps in place of the list.  Those
+    chains_pair_maps, chains_quantile_maps, chains_rank_maps, chains_batch_maps, chains_signal_maps and chains_angle_maps in place of the list.  Those
     calls are then collective -- every rank of the group makes the same call -- and return the maps on rank `dst` of the group and
     None elsewhere; dst=None: on every rank.  The chain order is rank order, and list order within a rank; 2 to 8 chains in all.
     The ranks of one group hold the same pixel range (a sharded run makes one group per shard).  A rank whose registration, shard

@@ -636,6 +636,26 @@ module dangx_mod
        type(c_ptr), value :: ctx, out_dev
        integer(c_int), value :: sig, stat, ddof
      end function
+     ! posterior polarisation angle psi = atan2(U, Q) / 2 of a component's signal at a band, a circular statistic: spec(2, nang) =
+     ! (comp, band), 0-based as in C (nmaps == 3).  Only between dangx_moments_begin and the first dangx_moments_accumulate;
+     ! template / monopole / hi_fit members and T_cmb components are refused.
+     integer(c_int) function dangx_moments_angles(ctx, nang, spec) bind(C, name='dangx_moments_angles')
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx, spec              ! spec: integer(c_int32_t)(2, nang) or c_null_ptr
+       integer(c_int), value :: nang
+     end function
+     ! ang: 0-based; stat: 0 = circular mean, 1 = circular std (radians), 2 = mean resultant length, 3 = mean cos 2psi, 4 = mean
+     ! sin 2psi; out: (0:npix-1) of this shard
+     integer(c_int) function dangx_moments_get_angle(ctx, ang, stat, out) bind(C, name='dangx_moments_get_angle')
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx, out
+       integer(c_int), value :: ang, stat
+     end function
+     integer(c_int) function dangx_moments_get_angle_dev(ctx, ang, stat, out_dev) bind(C, name='dangx_moments_get_angle_dev')
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx, out_dev
+       integer(c_int), value :: ang, stat
+     end function
      ! batched accumulators: planes(3, nreg) = (comp, what, plane), 0-based as in C; nbatch even, 2..32 batches of initially
      ! batch_len samples, merged pairwise in place when all are full.  Only between dangx_moments_begin and the first
      ! dangx_moments_accumulate.  stat: 0 = mean, 1 = std (ddof), 2 = MCSE, 3 = batch-means ESS, 4 = split R-hat, the first
@@ -677,7 +697,7 @@ module dangx_mod
        integer(c_int), value :: reg, batch
      end function
      ! sections of the accumulator state in their packed layout (include/dangx.h): family 0 = HEAD (host forms only), 1 = PLANES
-     ! (a = comp, b = what), 2 = PAIR, 3 = HIST, 4 = SIGNAL, 5 = BATCHES (a = index, b ignored); bytes as _section_bytes gives them
+     ! (a = comp, b = what), 2 = PAIR, 3 = HIST, 4 = SIGNAL, 5 = BATCHES, 7 = ANGLE (a = index, b ignored); bytes as _section_bytes gives them
      integer(c_int) function dangx_moments_section_bytes(ctx, family, a, b, bytes) bind(C, name='dangx_moments_section_bytes')
        import :: c_int, c_ptr, c_int64_t
        type(c_ptr), value :: ctx
@@ -758,6 +778,20 @@ module dangx_mod
        import :: c_int, c_ptr
        type(c_ptr), intent(in) :: ctxs(*)
        integer(c_int), value :: nchains, sig, stat, ddof
+       type(c_ptr), value :: out_dev
+     end function
+     ! stat: dangx_moments_get_angle's 0..4 on the chains' pooled (Cbar, Sbar), 5 = the circular std of the chains' mean directions
+     integer(c_int) function dangx_chains_get_angle(ctxs, nchains, ang, stat, out) bind(C, name='dangx_chains_get_angle')
+       import :: c_int, c_ptr
+       type(c_ptr), intent(in) :: ctxs(*)
+       integer(c_int), value :: nchains, ang, stat
+       type(c_ptr), value :: out
+     end function
+     integer(c_int) function dangx_chains_get_angle_dev(ctxs, nchains, ang, stat, out_dev) &
+          bind(C, name='dangx_chains_get_angle_dev')
+       import :: c_int, c_ptr
+       type(c_ptr), intent(in) :: ctxs(*)
+       integer(c_int), value :: nchains, ang, stat
        type(c_ptr), value :: out_dev
      end function
      ! stat: 0 = covariance (ddof), 1 = correlation

@@ -371,6 +371,33 @@ contains
     end do
   end subroutine dangx_sky_moments_get_signal
 
+  ! posterior polarisation angles spec(2, nang) = (comp, band), 0-based as in include/dangx.h, on every context: after
+  ! dangx_sky_moments_begin, before the first accumulate
+  subroutine dangx_sky_moments_angles(sky, nang, spec)
+    type(dangx_sky), intent(in) :: sky
+    integer, intent(in) :: nang
+    integer(c_int32_t), intent(in), target :: spec(:,:)
+    type(c_ptr) :: p
+    integer :: r
+    p = c_null_ptr
+    if (nang > 0) p = c_loc(spec)
+    do r = 1, sky%nctx
+       call dangx_check(sky%ctx(r), dangx_moments_angles(sky%ctx(r), nang, p), 'dangx_moments_angles')
+    end do
+  end subroutine dangx_sky_moments_angles
+
+  ! ang: 0-based; stat 0 = circular mean, 1 = circular std, 2 = mean resultant length, 3 / 4 = mean cos / sin 2psi; out: c_loc of a
+  ! full-sky (0:npix-1) array, every context fills its pixel range
+  subroutine dangx_sky_moments_get_angle(sky, ang, stat, out)
+    type(dangx_sky), intent(in) :: sky
+    integer, intent(in) :: ang, stat
+    type(c_ptr), intent(in) :: out
+    integer :: r
+    do r = 1, sky%nctx
+       call dangx_check(sky%ctx(r), dangx_moments_get_angle(sky%ctx(r), ang, stat, at_pix(out, sky%pix0(r))), 'dangx_moments_get_angle')
+    end do
+  end subroutine dangx_sky_moments_get_angle
+
   function dangx_sky_moments_count(sky) result(n)
     type(dangx_sky), intent(in) :: sky
     integer(c_int64_t) :: n, m

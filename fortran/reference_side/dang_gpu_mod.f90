@@ -47,6 +47,8 @@ module dang_gpu_mod
   integer(i4b) :: gpu_post_nhist = 0
   integer(c_int32_t), allocatable, target :: gpu_post_sig(:,:)     ! posterior_signal_gpu's signals (3, gpu_post_nsig) = (comp, band, kind), 0-based as in C
   integer(i4b) :: gpu_post_nsig = 0
+  integer(c_int32_t), allocatable, target :: gpu_post_ang(:,:)     ! posterior_angle_gpu's angles (2, gpu_post_nang) = (comp, band), 0-based as in C
+  integer(i4b) :: gpu_post_nang = 0
 
 contains
 
@@ -733,6 +735,7 @@ contains
     gpu_post_npairs = 0
     gpu_post_nhist = 0
     gpu_post_nsig = 0
+    gpu_post_nang = 0
   end subroutine posterior_begin_gpu
 
   ! after posterior_begin_gpu, before the first posterior_accumulate_gpu that takes a sample: the second-order summaries.  lag1:
@@ -975,6 +978,70 @@ contains
     call rank_window(w, 1, .false.)
     out(0:npix-1) = w(:, 1)
   end subroutine posterior_signal_to_host_gpu
+
+  ! after posterior_begin_gpu, before the first posterior_accumulate_gpu that takes a sample: the posterior polarisation angle psi =
+  ! atan2(U, Q) / 2 of component signals, a circular statistic -- as dang_amd.default_angle_specs: one angle for every P that
+  ! posterior_signal_gpu's rule registers, i.e. every component that is no template / monopole / hi_fit, whose amplitude is
+  ! sampled on both Q and U and that has at least one sampled index, at the band whose nu_c is nearest its nu_ref (the lowest
+  ! band on ties).  Component order.  Read with posterior_angle_to_host_gpu (ang = 1 .. gpu_post_nang).
+  subroutine posterior_angle_gpu(dpar)
+    type(dang_params) :: dpar
+    type(dang_comps), pointer :: cc
+    integer(i4b) :: i, j, n, pass, band
+    real(dp) :: ref, nu, d, dbest
+    if (.not. allocated(gpu_post_sel)) then
+       write(*,*) 'posterior_angle_gpu: posterior_begin_gpu was not called'
+       stop 1
+    end if
+    do pass = 1, 2                                    ! count, then fill
+       n = 0
+       do i = 1, ncomp
+          cc => component_list(i)%p
+          if (trim(cc%type) == 'template' .or. trim(cc%type) == 'monopole' .or. trim(cc%type) == 'hi_fit') cycle
+          if (.not. cc%sample_amplitude) cycle
+          if (cc%nindices < 1) cycle
+          if (.not. any(cc%sample_index(1:cc%nindices))) cycle
+          if (iand(gpu_post_sel(i), 6) /= 6) cycle
+          ref = cc%nu_ref
+          if (ref < 1.d7) ref = ref*1.d9             ! Hz, src/dang_param_mod.f90:571-573
+          band = 1; dbest = huge(1.d0)
+          do j = 1, nbands
+             nu = bp(j)%nu_c
+             if (nu < 1.d9) nu = nu*1.d9             ! Hz, src/dang_bp_mod.f90:35-37
+             d = abs(nu - ref)
+             if (d < dbest) then
+                dbest = d; band = j
+             end if
+          end do
+          n = n + 1
+          if (pass == 2) gpu_post_ang(:, n) = int([i-1, band-1], c_int32_t)
+       end do
+       if (pass == 1) then
+          if (allocated(gpu_post_ang)) deallocate(gpu_post_ang)
+          allocate(gpu_post_ang(2, max(n, 1))); gpu_post_ang = 0
+       end if
+    end do
+    gpu_post_nang = n
+    call dangx_sky_moments_angles(gpu_sky, n, gpu_post_ang)
+  end subroutine posterior_angle_gpu
+
+  ! circular mean (stat = 0), circular standard deviation in radians (1) or mean resultant length (2) map of angle `ang` (1-based,
+  ! posterior_angle_gpu's order) into out(0:npix-1); under MPI every rank fills its pixel range and the ranges are merged as
+  ! rank_window merges a plane
+  subroutine posterior_angle_to_host_gpu(ang, stat, out)
+    integer(i4b), intent(in) :: ang, stat
+    real(dp), intent(inout), target :: out(0:)
+    real(dp), allocatable, target :: w(:,:)
+    if (ang < 1 .or. ang > gpu_post_nang) then
+       write(*,*) 'posterior_angle_to_host_gpu: angle out of range', ang, gpu_post_nang
+       stop 1
+    end if
+    allocate(w(0:npix-1, 1))
+    call rank_window(w, 1, .true.)
+    call dangx_sky_moments_get_angle(gpu_sky, ang - 1, stat, c_loc(w))
+    call rank_window(w, 1, .false.)
+    out(0:npix-1) = w(:, 1)
+  end subroutine posterior_angle_to_host_gpu
 
   ! after write_data_gpu in the loop: one sample of the current state, every thin-th iteration after burn_in.  Enqueued on every
   ! context's stream behind the iteration's launches: the host does not wait

@@ -77,7 +77,8 @@ enum {
     DANGX_K_CG_AX = 4, DANGX_K_CG_VEC = 5, DANGX_K_AMP_INDEX = 6, DANGX_K_MOMENTS = 7, DANGX_K_HIST = 8, DANGX_K_SIGNAL = 9,
     DANGX_K_CHAINS = 10,   /* the read-outs over several chains (dangx_chains_*): nothing else is ever counted here */
     DANGX_K_BATCH = 11,    /* the batched accumulators (dangx_moments_batches): one launch per accumulation, one more per merge */
-    DANGX_K_COUNT = 12
+    DANGX_K_ANGLE = 12,    /* the polarisation-angle accumulators (dangx_moments_angles): one launch per accumulation, two with an integrated band */
+    DANGX_K_COUNT = 13
 };
 
 typedef struct dangx_ctx dangx_ctx;
@@ -610,12 +611,45 @@ int dangx_moments_hist_range_get_dev(dangx_ctx *ctx, int reg, double *lo_dev, do
  * dangx_moments_get_signal: stat 0 = mean, 1 = standard deviation sqrt(m2 / (n - ddof)); out: [npix] of this shard.  Errors: sig
  *   out of range, n = 0, a bad stat, stat = 1 with n - ddof <= 0.  The _dev form writes a device array, asynchronously on the
  *   context's stream.
- * Histograms of signals: dangx_moments_hist with a signal source (above).  Not covered: the polarisation angle (a circular
- * statistic), lag-1 / pairs of signals, frequencies that are not bands of the model. */
+ * Histograms of signals: dangx_moments_hist with a signal source (above).  The polarisation angle of a signal is a circular
+ * statistic with accumulators of its own: dangx_moments_angles (below).  Not covered: lag-1 / pairs of signals, frequencies
+ * that are not bands of the model. */
 #define DANGX_MAX_SIGNALS 64
 int dangx_moments_signals(dangx_ctx *ctx, int nsig, const int32_t *spec);
 int dangx_moments_get_signal(dangx_ctx *ctx, int sig, int stat, int ddof, double *out);
 int dangx_moments_get_signal_dev(dangx_ctx *ctx, int sig, int stat, int ddof, double *out_dev);
+/* Posterior polarisation angle psi = atan2(U, Q) / 2 of a component's signal at a band, as a CIRCULAR statistic: the arithmetic
+ * mean of psi samples is wrong wherever the posterior straddles +-pi/2 (two samples at +85 and -85 degrees average to 0, not to
+ * 90).  Accumulated on the same samples by k_moments_angle, a launch of its own behind the signals' (a second one for the angles
+ * at bandpass-integrated bands), only when something is registered.  Definitions (dang_amd/csrc/dx_angle_host.h):
+ *   spec[a] = {comp, band}.  Per sample and pixel sQ, sU are exactly the rounded samples of signal kinds 1 and 2 of that
+ *     (comp, band), P = sqrt(sQ * sQ + sU * sU) as kind 3 forms it, c = sQ / P = cos 2 psi, s = sU / P = sin 2 psi (two IEEE
+ *     divisions).  P == 0 gives NaN and NaN stays: nothing is skipped.  No sign convention is applied: the angle is that of the
+ *     Q, U maps as the model holds them.
+ *   accumulators: two f64 planes per angle, Cbar and Sbar, the running means m = fma(x - m, 1/n, m) of c and s.
+ *   stat 0  circular mean  0.5 * atan2(Sbar, Cbar), in [-pi/2, pi/2]
+ *   stat 1  circular standard deviation of psi in radians  0.5 * sqrt(-2 * log(Rbar)); +inf where Rbar == 0; exactly 0 where
+ *           Rbar >= 1 - 5 * 2^-53, the rounding of a unit vector's length (a chain that never moved reads 0, not 7.45e-9)
+ *   stat 2  mean resultant length Rbar = min(1, sqrt(Cbar^2 + Sbar^2)); the clamp makes the std of a chain that never moved 0
+ *   stat 3, 4  Cbar, Sbar as they are.  NaN propagates through every stat.
+ * dangx_moments_angles: legal after dangx_moments_begin and before the first dangx_moments_accumulate, independent of
+ *   dangx_moments_pairs / _hist / _signals / _batches and of the selection words; a second call replaces the first (nang = 0:
+ *   none), dangx_moments_begin / _end drop it, dangx_moments_begin_like copies it into the holder.  Errors (nothing changes):
+ *   count > 0, nmaps != 3, comp / band out of range, an unset component, a template / monopole / hi_fit member, a T_cmb
+ *   component (its signal is a bare SED and has no direction), the same angle twice, nang > DANGX_MAX_ANGLES, a failed allocation.
+ * dangx_moments_get_angle: out [npix] of this shard.  Errors: ang out of range, n = 0, a bad stat (5 needs several chains).
+ * dangx_chains_get_angle (rules of dangx_chains_* below): pooled Cbar = sum_k (n_k / N) Cbar_k in list order, Sbar likewise
+ *   (unequal counts allowed); stats 0-4 on the pooled pair; stat 5 = BETWEEN, the circular std of the chains' mean directions:
+ *   u_k = (Cbar_k, Sbar_k) / sqrt(Cbar_k^2 + Sbar_k^2), (Cb, Sb) = (sum_k u_k) / K in list order, R_b = min(1, sqrt(Cb^2 +
+ *   Sb^2)), result 0.5 * sqrt(-2 log R_b): what to set beside stat 1 to see chains sitting at different angles.  There is no
+ *   circular R-hat: none is standard.
+ * The section of an angle is family 7 ANGLE (below).  The _dev forms write device arrays asynchronously.
+ * Not covered: histograms, quantiles and batches of an angle, a circular R-hat, debiasing of P, signals at frequencies that are
+ * not bands of the model. */
+#define DANGX_MAX_ANGLES 64
+int dangx_moments_angles(dangx_ctx *ctx, int nang, const int32_t *spec);
+int dangx_moments_get_angle(dangx_ctx *ctx, int ang, int stat, double *out);
+int dangx_moments_get_angle_dev(dangx_ctx *ctx, int ang, int stat, double *out_dev);
 /* Batched accumulators of registered pixel planes: the run cut into nbatch consecutive batches of L samples, each with its own
  * (mean, m2), so that burn-in can be discarded AFTER the run and one chain gets a batch-means Monte-Carlo error, a model-free
  * effective sample size and split R-hat.  One launch of k_moments_accum's update per accumulation (DANGX_K_BATCH) behind the
@@ -661,7 +695,9 @@ int dangx_moments_batches_raw_dev(dangx_ctx *ctx, int reg, int batch, double *me
  *                                    pix0, nmaps); the selection words with type and nindices of the selected components; the
  *                                    lag-1 flag and the pair list; the histogram planes with lo, hi, nbins, bits (and, once a
  *                                    registration has a per-pixel range, every range kind and map checksum: a list of global
- *                                    ranges hashes as it always did); the signal specs; the batch planes with nbatch
+ *                                    ranges hashes as it always did); the signal specs (and, only when angles are registered,
+ *                                    the angle specs: a registration without angles hashes as it always did); the batch planes
+ *                                    with nbatch
  *   family 1 PLANES  (comp, what)    parts mean, m2 (then prev, first, P when lag-1 is tracked), each [selected planes in T, Q, U
  *                                    order][npix] f64; for a template / monopole / hi_fit member (what 0) its host rows in the
  *                                    same part order, each [selected planes][nbands]
@@ -676,6 +712,7 @@ int dangx_moments_batches_raw_dev(dangx_ctx *ctx, int reg, int batch, double *me
  *                                    receives the maps by this put.  Quantile and mode read-outs over several chains take
  *                                    the maps from ctxs[0] and name this section when a holder there lacks it; N and the
  *                                    rank R-hat need no range values and do not ask for it.
+ *   family 7 ANGLE   (ang, -)        Cbar, Sbar, each [npix] f64
  * _section_bytes: the payload's size.  _section_get / _put: host arrays, returning after the copy; the _dev forms take device
  * arrays and are asynchronous on the context's stream (the host rows of a template / monopole / hi_fit member: the call waits).
  * Transport is one copy per plane; no kernel is launched.  Every get and put checks `bytes` against _section_bytes.
@@ -685,7 +722,7 @@ int dangx_moments_batches_raw_dev(dangx_ctx *ctx, int reg, int batch, double *me
  * product uses the restored prev, the pair terms the restored means, the batch schedule the restored batch length and fill, the
  * histogram limit the restored count.
  * dangx_moments_begin_like makes ctx a HOLDER: it takes over the registrations of `like` (selection, pairs / lag-1 flag,
- * histograms, signals, batches; the two contexts must agree in npix / pix0 / nmaps / ncomp / nbands and in the components
+ * histograms, signals, angles, batches; the two contexts must agree in npix / pix0 / nmaps / ncomp / nbands and in the components
  * concerned) and allocates NO accumulators; whatever ctx accumulated or held before is dropped.  A section's device memory
  * (its payload rounded up to 256 bytes; batches at the plane pitch of a live context) is allocated when it is first put.  A
  * holder with lag-1 also takes a PLANES payload of the first two parts (mean, m2) alone.  The read-outs over several chains
@@ -720,7 +757,7 @@ int dangx_moments_end(dangx_ctx *ctx);
  *   pooled pair term C += C_k + d_a d_b (n n_k / n'); covariance = C / (N - ddof), correlation = C / sqrt(M_a M_b).
  *   pooled histogram: bin b = sum_k c_{k,b} in 64-bit integers; N, quantiles and mode by dangx_moments_hist_stat's rules on them.
  * stat of dangx_chains_get / _get_template: 0 = pooled mean, 1 = pooled std, 2 = R-hat, 3 = W, 4 = B/n, 5 = pooled ESS;
- *   of _get_signal: 0-4; of _get_pair: 0 = covariance, 1 = correlation; of _hist_stat: as dangx_moments_hist_stat.
+ *   of _get_signal: 0-4; of _get_angle: dangx_moments_angles' 0-5; of _get_pair: 0 = covariance, 1 = correlation; of _hist_stat: as dangx_moments_hist_stat.
  * Host forms write host arrays laid out as the single-chain getters lay them out and return after the copy; _dev forms write a
  * packed device array asynchronously.  The kernel runs on ctxs[0]'s stream: before it every other chain's stream records an
  * event that stream waits on, after it that stream records an event the other streams wait on, so a following
@@ -736,6 +773,8 @@ int dangx_chains_get_dev(dangx_ctx *const *ctxs, int nchains, int comp, int what
 int dangx_chains_get_template(dangx_ctx *const *ctxs, int nchains, int comp, int stat, int ddof, double *ta);
 int dangx_chains_get_signal(dangx_ctx *const *ctxs, int nchains, int sig, int stat, int ddof, double *out);
 int dangx_chains_get_signal_dev(dangx_ctx *const *ctxs, int nchains, int sig, int stat, int ddof, double *out_dev);
+int dangx_chains_get_angle(dangx_ctx *const *ctxs, int nchains, int ang, int stat, double *out);
+int dangx_chains_get_angle_dev(dangx_ctx *const *ctxs, int nchains, int ang, int stat, double *out_dev);
 int dangx_chains_get_pair(dangx_ctx *const *ctxs, int nchains, int pair, int stat, int ddof, double *out);
 int dangx_chains_get_pair_dev(dangx_ctx *const *ctxs, int nchains, int pair, int stat, int ddof, double *out_dev);
 int dangx_chains_hist_stat(dangx_ctx *const *ctxs, int nchains, int reg, int stat, int nq, const double *q, double *out);

@@ -3,7 +3,7 @@
 iterations of the C3 model: blocks of iterations without and with accumulation after every iteration, alternating in one process;
 then the k_moments kernel time from the profile and its bandwidth in algorithmic bytes (5 x 8 B per selected element) against the
 6.29 TB/s measured copy ceiling of the MI355X.
-    python3 tools/bench_moments.py [nside=1024] [steps per block=10] [rounds=5] [--lag1] [--pairs default] [--hist [nbins=64] [--range-maps | --signals]] [--signals [--bandpass]] [--chains K [--samples N]] [--batches NB] [--sections]
+    python3 tools/bench_moments.py [nside=1024] [steps per block=10] [rounds=5] [--lag1] [--pairs default] [--hist [nbins=64] [--range-maps | --signals]] [--signals [--bandpass]] [--chains K [--samples N]] [--batches NB] [--sections] [--angles]
 --lag1 / --pairs default: after the above, `rounds` alternating rounds of `steps` accumulations each of (a) the plain accumulate,
 (b) with lag-1 tracking (k_moments_accum_lag: 10 x 8 B per selected element) and (c) with the default pairs (k_moments_pairs: 6 x 8 B
 per pair element, timed apart from the mean launch that follows it); per launch the algorithmic bytes, the achieved bytes/s and
@@ -42,7 +42,12 @@ merges the next 3 NB + 1 accumulations cause.  Nothing else of the above is run.
 --sections: one chain with lag-1 and one histogram plane (64 bins x 16 bit); three alternating rounds in one process of (c) a plain
 hipMemcpyAsync device to device, (s) the same on a stream of its own, (g) dangx_moments_section_get_dev and (p) _put_dev into a
 holder, of the same bytes: the histogram's records (one copy) and a PLANES section (one copy per plane and part); `steps` copies
-per timing, wall time around a device synchronisation.  Nothing else of the above is run."""
+per timing, wall time around a device synchronisation.  Nothing else of the above is run.
+--angles: the polarisation-angle launch (k_moments_angle) on the default angles against the signal launch (k_moments_signal) on the
+{Q, U, P} signals of the same (component, band): `rounds` alternating rounds in one process of `steps` accumulations each with (s)
+the signals alone and (g) the angles alone registered, an empty selection, after two Gibbs iterations; per launch the time, the
+algorithmic bytes -- per component the Q and U amplitude and index planes read once, and per output two accumulator planes read and
+written -- and their bytes/s; then (g) / (s) over the rounds.  Nothing else of the above is run."""
 import os
 import sys
 import time
@@ -106,6 +111,43 @@ if want_bandpass:
         eng.profile(False)
         print("round %d: bandpass form, %d signals at integrated bands of 9 samples: %.3f ms per launch (%d launches)"
               % (r + 1, len(specs), prof["total_ms"] / prof["launches"], prof["launches"]))
+    sys.exit(0)
+if "--angles" in sys.argv:
+    npx = meta["npix"]
+    for it in (1, 2):
+        da.gibbs_iteration(dpar, ddata, it, want_counts=False)
+    angles = da.default_angle_specs(dpar, comps, bands)
+    sigs = [(l, j, k) for l, j in angles for k in (1, 2, 3)]
+    none = np.zeros(len(comps), dtype=np.int32)
+    src = sum(2 * (1 + comps[l].nindices) for l in sorted({l for l, j in angles}))      # Q and U: amplitude + index planes
+    g_planes, s_planes = src + 4 * len(angles), src + 4 * len(sigs)
+
+    def per_launch(register, family):
+        da.moments_begin(dpar, ddata, sel=none)
+        register()
+        da.moments_accumulate(ddata)   # table upload
+        eng.profile(True)
+        for _ in range(steps):
+            da.moments_accumulate(ddata)
+        prof = eng.profile_get()
+        eng.profile(False)
+        assert set(prof) == {family}, prof
+        return prof[family]["total_ms"] / prof[family]["launches"]
+
+    print("C3 at Nside %d, %d pixels: angles %s; (s) k_moments_signal on their %d {Q, U, P} signals, %d planes of 8 B per pixel; (g) "
+          "k_moments_angle, %d planes" % (nside, npx, [(comps[l].label, bands[j].label) for l, j in angles], len(sigs), s_planes, g_planes))
+    s_all, g_all = [], []
+    for r in range(rounds):
+        s_ms = per_launch(lambda: da.moments_signals(dpar, ddata, specs=sigs), "k_signal")
+        g_ms = per_launch(lambda: da.moments_angles(dpar, ddata, specs=angles), "k_angle")
+        s_all.append(s_ms)
+        g_all.append(g_ms)
+        print("round %d: (s) %.3f ms, %.2f GB algorithmic -> %.2f TB/s; (g) %.3f ms, %.2f GB -> %.2f TB/s; (g) / (s) = %.3f"
+              % (r + 1, s_ms, 8e-9 * s_planes * npx, 8e-9 * s_planes * npx / s_ms, g_ms, 8e-9 * g_planes * npx, 8e-9 * g_planes * npx / g_ms,
+                 g_ms / s_ms))
+    print("(s) median %.3f ms (spread %.3f .. %.3f); (g) median %.3f ms (spread %.3f .. %.3f); target: (g) <= (s) within the spread"
+          % (float(np.median(s_all)), min(s_all), max(s_all), float(np.median(g_all)), min(g_all), max(g_all)))
+    print("accumulators: 16 B x %d pixels x %d angles = %.2f GB" % (npx, len(angles), 16.0 * npx * len(angles) * 1e-9))
     sys.exit(0)
 if "--sections" in sys.argv:
     import ctypes
