@@ -14,6 +14,7 @@ from .posterior import (default_moment_selection, moments_begin, moments_accumul
                         default_hist_planes, moments_hist, posterior_quantile_maps, hist_ranges_from_moments,
                         default_signal_specs, moments_signals, posterior_signal_maps,
                         default_angle_specs, moments_angles, posterior_angle_maps, chains_get_angle, chains_angle_maps,
+                        default_fit_specs, moments_fit, posterior_fit_maps, chains_get_fit, chains_fit_maps,
                         chains_get, chains_get_template, chains_get_signal, chains_get_pair, chains_hist_stat, open_chain,
                         chains_posterior_maps, chains_pair_maps, chains_quantile_maps, chains_signal_maps, chains_hist_rank, chains_rank_maps,
                         moments_batches, posterior_batch_maps, chains_batches_get, chains_batch_maps,

@@ -24,10 +24,10 @@ COARSE_REFERENCE, COARSE_DEGRADED = 0, 1
 COARSE_MODEL_CODES = {"reference": COARSE_REFERENCE, "degraded": COARSE_DEGRADED}
 A2T, A2F, F2T = 0, 1, 2
 UNIT_CODES = {"uK_RJ": 0, "uK_cmb": 1, "MJy/sr": 2}
-K_AMP_DIRECT, K_INDEX_MH, K_SKY_CHISQ, K_REDUCE, K_CG_AX, K_CG_VEC, K_AMP_INDEX, K_MOMENTS, K_HIST, K_SIGNAL, K_CHAINS, K_BATCH, K_ANGLE = range(13)
+K_AMP_DIRECT, K_INDEX_MH, K_SKY_CHISQ, K_REDUCE, K_CG_AX, K_CG_VEC, K_AMP_INDEX, K_MOMENTS, K_HIST, K_SIGNAL, K_CHAINS, K_BATCH, K_ANGLE, K_FIT = range(14)
 KERNEL_NAMES = {K_AMP_DIRECT: "k_amp_direct", K_INDEX_MH: "k_index_mh", K_SKY_CHISQ: "k_sky_chisq",
                 K_REDUCE: "k_reduce", K_CG_AX: "k_Ax", K_CG_VEC: "k_cg_vec", K_AMP_INDEX: "k_amp_index", K_MOMENTS: "k_moments",
-                K_HIST: "k_hist", K_SIGNAL: "k_signal", K_CHAINS: "k_chains", K_BATCH: "k_batch", K_ANGLE: "k_angle"}
+                K_HIST: "k_hist", K_SIGNAL: "k_signal", K_CHAINS: "k_chains", K_BATCH: "k_batch", K_ANGLE: "k_angle", K_FIT: "k_fit"}
 STAT_CODES = {"mean": 0, "std": 1, "rho1": 2, "ess": 3}
 PAIR_STAT_CODES = {"cov": 0, "corr": 1}
 MAX_PAIRS = 64
@@ -44,7 +44,11 @@ CHAINS_STAT_CODES = {"mean": 0, "std": 1, "rhat": 2, "W": 3, "B": 4, "ess": 5}
 BATCH_STAT_CODES = {"mean": 0, "std": 1, "mcse": 2, "ess_bm": 3, "split_rhat": 4}
 MAX_BATCHES, MAX_BATCH_PLANES = 32, 32
 SEC_HEAD, SEC_PLANES, SEC_PAIR, SEC_HIST, SEC_SIGNAL, SEC_BATCHES, SEC_HIST_RANGE, SEC_ANGLE = range(8)   # family of a section
-SECTION_NAMES = ("HEAD", "PLANES", "PAIR", "HIST", "SIGNAL", "BATCHES", "HIST_RANGE", "ANGLE")
+SECTION_NAMES = ("HEAD", "PLANES", "PAIR", "HIST", "SIGNAL", "BATCHES", "HIST_RANGE", "ANGLE")   # the families every context has
+SEC_FIT = 8                               # ... and behind them the family only a context with fit items has (moments_fit)
+SECTION_NAMES_ALL = SECTION_NAMES + ("FIT",)
+MAX_FIT = 128
+FIT_KINDS = ("residual", "chisq")         # what 0, 1 of a fit spec (what, band, plane); band -1 for 'chisq'
 # a PLANES section of pixel planes is equal parts: mean and m2, and with lag-1 tracking three more behind them (include/dangx.h)
 PLANES_MOMENT_PARTS, PLANES_LAG1_PARTS = 2, 5
 SECTION_HEAD_BYTES = 104
@@ -189,6 +193,9 @@ SYMBOLS = {
     "dangx_moments_angles": (C.c_int, [_P, C.c_int, _P]),
     "dangx_moments_get_angle": (C.c_int, [_P, C.c_int, C.c_int, _P]),
     "dangx_moments_get_angle_dev": (C.c_int, [_P, C.c_int, C.c_int, _P]),
+    "dangx_moments_fit": (C.c_int, [_P, C.c_int, _P]),
+    "dangx_moments_get_fit": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
+    "dangx_moments_get_fit_dev": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
     "dangx_moments_end": (C.c_int, [_P]),
     "dangx_moments_batches": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int64]),
     "dangx_moments_batches_info": (C.c_int, [_P, _P, _P, _P]),
@@ -210,6 +217,8 @@ SYMBOLS = {
     "dangx_chains_get_template": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "dangx_chains_get_signal": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "dangx_chains_get_signal_dev": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "dangx_chains_get_fit": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "dangx_chains_get_fit_dev": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "dangx_chains_get_angle": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int, C.c_int, _P]),
     "dangx_chains_get_angle_dev": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int, C.c_int, _P]),
     "dangx_chains_get_pair": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, _P]),

@@ -175,8 +175,8 @@ def _code(codes, stat):
 
 # The Python mirror of what the library has registered on a context, one attribute per registration call: the selection words of
 # moments_begin, then what moments_pairs (the pair list and its lag-1 flag), moments_hist, moments_signals and moments_batches
-# registered, and last the angle list of moments_angles.  Plain attributes (tests and stand-in engines set and delete them); this tuple is the one list of them.
-MOMENT_ATTRS = ("_moment_sel", "_moment_pairs", "_moment_lag1", "_moment_hist", "_moment_signals", "_moment_batches", "_moment_angles")
+# registered, the fit items of moments_fit, and last the angle list of moments_angles.  Plain attributes (tests and stand-in engines set and delete them); this tuple is the one list of them.
+MOMENT_ATTRS = ("_moment_sel", "_moment_pairs", "_moment_lag1", "_moment_hist", "_moment_signals", "_moment_batches", "_moment_fit", "_moment_angles")
 
 
 def _registration(e, name, who=None, call=None):
@@ -204,7 +204,7 @@ def _is_range_maps(r):
 
 
 def _sec_family(family):
-    return L.SECTION_NAMES.index(family) if isinstance(family, str) else int(family)
+    return L.SECTION_NAMES_ALL.index(family) if isinstance(family, str) else int(family)
 
 
 def _sec_buffer(x, device):
@@ -865,6 +865,22 @@ class Engine:
         torch cuda tensor filled on the device."""
         return self._readout("dangx_moments_get_angle", (self.npix,), (int(a), _code(L.ANGLE_STAT_CODES, stat)), device, out)
 
+    def moments_fit(self, specs):
+        """Register goodness-of-fit items after moments_begin and before the first moments_accumulate: specs = [(what, band, plane),
+        ...], what 0 / 'residual' = the residual of that band on plane 0, 1, 2 ('T' / 'Q' / 'U' accepted), what 1 / 'chisq' = the
+        chi^2 map of the plane (band -1; ('chisq', plane) is accepted too).  Units are the model's: the division by a band's unit
+        conversion that write_maps applies stays with the caller.  Independent of the selection and of every other
+        registration; a second call replaces the first.  Definitions: include/dangx.h."""
+        sp = [fit_spec(s) for s in specs]
+        p = np.ascontiguousarray(np.asarray(sp, dtype=np.int32).reshape(-1, 3))
+        self._chk(self.lib.dangx_moments_fit(self.h, p.shape[0], p.ctypes.data if p.size else None))
+        self._moment_fit = sp
+
+    def moments_get_fit(self, i, stat, ddof=0, device=False, out=None):
+        """Mean ('mean' / 0) or standard deviation ('std' / 1, sqrt(m2 / (n - ddof))) of registered fit item i as [npix]; a chi^2
+        item reads 0 at masked pixels.  device=True: a torch cuda tensor filled on the device."""
+        return self._readout("dangx_moments_get_fit", (self.npix,), (int(i), _code(L.STAT_CODES, stat), int(ddof)), device, out)
+
     def moments_batches(self, planes, nbatch=16, batch_len=1):
         """Register batched accumulators after moments_begin and before the first moments_accumulate: planes = [(l, what, plane),
         ...] as in moments_hist, nbatch (even, 2..32) batches of initially batch_len samples, each with its own (mean, m2); when
@@ -970,6 +986,17 @@ class Engine:
                 if n.value:
                     out[(name, pl) if pl else name] = {"total_ms": ms.value, "launches": n.value, "avg_ms": ms.value / n.value}
         return out
+
+
+def fit_spec(s):
+    """A fit item as the library takes it, (what, band, plane): 'residual' / 'chisq' and 'T' / 'Q' / 'U' accepted, and ('chisq',
+    plane) for ('chisq', -1, plane)"""
+    s = tuple(s)
+    if len(s) == 2:
+        s = (s[0], -1, s[1])
+    what, band, plane = s
+    return (L.FIT_KINDS.index(what) if isinstance(what, str) else int(what), int(band),
+            L.SIGNAL_KINDS[:3].index(plane) if isinstance(plane, str) else int(plane))
 
 
 def coarse_model_codes(c: DangComps):

@@ -526,6 +526,39 @@ int chains_signal_impl(dangx_ctx* const* ctxs, int nchains, int sig, int stat, i
     return ro.close(n);
 }
 
+// a fit item (dangx_moments_fit) over the chains: the signals' read-out on the item's (mean, m2)
+int chains_fit_impl(dangx_ctx* const* ctxs, int nchains, int item, int stat, int ddof, double* out, bool to_host) {
+    if (!ctxs || !ctxs[0] || !out) return 1;
+    ChainSet cs{};
+    if (chains_open(ctxs, nchains, cs)) return 1;
+    if (stat < DX_CH_MEAN || stat > DX_CH_BN)
+        return chains_fail(ctxs, "the stat of a fit item must be 0 (pooled mean), 1 (pooled std), 2 (R-hat), 3 (W) or 4 (B/n)");
+    const auto& f0 = ctxs[0]->mom->fits;
+    if (item < 0 || item >= (int)f0.size())
+        return chains_fail(ctxs, "chain 0: fit item out of range (" + std::to_string(f0.size()) + " fit items registered)");
+    for (int k = 1; k < nchains; ++k) {
+        const auto& fk = ctxs[k]->mom->fits;
+        if (item >= (int)fk.size() || fk[item].what != f0[item].what || fk[item].band != f0[item].band || fk[item].plane != f0[item].plane)
+            return chains_fail(ctxs, "chain " + std::to_string(k) + ": fit item " + std::to_string(item) + " is not the registration of chain 0");
+    }
+    if (chains_counts(cs, stat, ddof, false)) return 1;
+    dangx_ctx* c0 = ctxs[0];
+    (void)hipSetDevice(c0->device);
+    const long long n = c0->dims.npix;
+    ReadOut ro{c0, out, to_host};
+    if (ro.open(sizeof(double) * (size_t)n)) return 1;
+    ChainsArgs a{};
+    for (int j = 0; j < cs.K; ++j) {
+        const DxMoments* m = ctxs[j]->mom;
+        a.mean[0][j] = m->mean(m->fits[item]);
+        a.m2[0][j] = m->m2(m->fits[item]);
+        if (!a.mean[0][j]) return chains_missing(ctxs, j, "FIT(" + std::to_string(item) + ")");
+    }
+    a.out[0] = ro.dst;
+    if (chains_launch(cs, a, 1, stat, ddof)) return 1;
+    return ro.close(n);
+}
+
 int chains_angle_impl(dangx_ctx* const* ctxs, int nchains, int ang, int stat, double* out, bool to_host) {
     if (!ctxs || !ctxs[0] || !out) return 1;
     ChainSet cs{};
@@ -777,6 +810,14 @@ int dangx_chains_get_signal_dev(dangx_ctx* const* ctxs, int nchains, int sig, in
 
 int dangx_chains_get_signal(dangx_ctx* const* ctxs, int nchains, int sig, int stat, int ddof, double* out) {
     return chains_signal_impl(ctxs, nchains, sig, stat, ddof, out, true);
+}
+
+int dangx_chains_get_fit_dev(dangx_ctx* const* ctxs, int nchains, int item, int stat, int ddof, double* out_dev) {
+    return chains_fit_impl(ctxs, nchains, item, stat, ddof, out_dev, false);
+}
+
+int dangx_chains_get_fit(dangx_ctx* const* ctxs, int nchains, int item, int stat, int ddof, double* out) {
+    return chains_fit_impl(ctxs, nchains, item, stat, ddof, out, true);
 }
 
 int dangx_chains_get_angle_dev(dangx_ctx* const* ctxs, int nchains, int ang, int stat, double* out_dev) {

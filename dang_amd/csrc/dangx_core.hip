@@ -32,7 +32,7 @@ const DxRoctx& dx_roctx() {
 const char* dx_kernel_family(int kid) {
     static const char* const names[DANGX_K_COUNT] = {"dangx:amplitude_solve", "dangx:index_sweep", "dangx:sky_chisq", "dangx:reduce",
                                                      "dangx:cg_Ax", "dangx:cg_vec", "dangx:solve+sweeps", "dangx:moments", "dangx:hist",
-                                                     "dangx:signal", "dangx:chains", "dangx:batches", "dangx:angle"};
+                                                     "dangx:signal", "dangx:chains", "dangx:batches", "dangx:angle", "dangx:fit"};
     return (kid >= 0 && kid < DANGX_K_COUNT) ? names[kid] : "dangx:?";
 }
 

@@ -53,8 +53,14 @@
 // k_batches_merge first folds the slots pairwise in place and the batch length doubles.  k_batches_stat reads the slots in one
 // pass with running values (discarded burn-in, MCSE, batch-means ESS, split R-hat).  Nothing registered: no launch.
 //
+// dangx_moments_fit adds the goodness-of-fit maps write_maps leaves beside the components (definitions in dx_fit_host.h): the
+// residual at a (band, plane) and the chi^2 map of a plane, quadratic in all sampled parameters at once and so not derivable from
+// any other accumulator.  k_moments_fit is ONE launch of its own behind the others (blockIdx.y = plane with an item, at most
+// three): a thread builds a pixel's sky column over all bands in LDS, walks the bands once and updates the f64 mean / m2 planes of
+// the registered residuals and of the chi^2 map -- no copy of the residual exists in memory.  Nothing registered: no launch.
+//
 // dangx_moments_section_* read and write one section of all this state in a packed layout (dx_section_host.h: HEAD, the planes of a
-// (component, what), a pair, a histogram, a signal, a batch registration) with one hipMemcpyAsync per plane and no kernel, and
+// (component, what), a pair, a histogram, a signal, a batch registration, an angle, a fit item) with one hipMemcpyAsync per plane and no kernel, and
 // dangx_moments_begin_like makes a context a HOLDER of sections put into it, which the read-outs over several chains accept in
 // place of a live chain: what saving / restoring a run and chains in other processes are made of.
 //
@@ -74,6 +80,7 @@ static_assert(DX_MOM_MAX_PAIRS == DANGX_MAX_PAIRS, "dx_moments_host.h and includ
 static_assert(DX_HIST_MAX == DANGX_MAX_HIST && DX_HIST_SIGNAL == DANGX_HIST_SIGNAL, "dx_hist_host.h and include/dangx.h disagree");
 static_assert(DX_SIG_MAX == DANGX_MAX_SIGNALS, "dx_signal_host.h and include/dangx.h disagree");
 static_assert(DX_ANG_MAX == DANGX_MAX_ANGLES && DX_ANG_MAX_CHAINS == DANGX_MAX_CHAINS, "dx_angle_host.h and include/dangx.h disagree");
+static_assert(DX_FIT_MAX == DANGX_MAX_FIT, "dx_fit_host.h and include/dangx.h disagree");
 static_assert(DX_SEC_HEAD_BYTES == DANGX_SECTION_HEAD_BYTES, "dx_section_host.h and include/dangx.h disagree");
 static_assert(DX_BATCH_MAX == DANGX_MAX_BATCHES && DX_BATCH_MAX_PLANES == DANGX_MAX_BATCH_PLANES, "dx_batches_host.h and include/dangx.h disagree");
 
@@ -423,6 +430,63 @@ __global__ __launch_bounds__(BLOCK) void k_moments_angle(const Model* __restrict
                 *(GD2*)cp = dbl2{dx_angle_mean(c0, mc.x, inv_n), dx_angle_mean(c1, mc.y, inv_n)};
                 *(GD2*)sp = dbl2{dx_angle_mean(s0, ms.x, inv_n), dx_angle_mean(s1, ms.y, inv_n)};
             }
+        }
+    }
+}
+
+// blockIdx.y = segment: a plane with at least one fit item (at most three).  One sample of every registered residual and of the
+// plane's chi^2 map, fused: a thread owns a pixel, builds the plane's sky column over all bands once in LDS ([nb][blockDim.x], as
+// k_sky_chisq does -- nb is a run-time number) with load_theta / sed_prep / comp_sed of every component, then walks the bands once:
+// the residual and the chi^2 term of the band (dx_fit_host.h's expressions), Welford's update of the band's residual item where
+// one is registered, and at the end the update of the chi^2 item at an unmasked pixel.  Every data plane is read once, rms only
+// where chi^2 is wanted, and no residual ever lies in memory outside the accumulators.  The accesses are 8 bytes per lane,
+// consecutive over the wave (512-byte runs), at any alignment of the caller's buffers: a pixel's result does not depend on the
+// shard it is in or on the phase of an adopted buffer.  The accumulator pointers are wave-uniform table entries indexed by the
+// band: scalar loads, no register array.  4 waves per SIMD are asked for, as k_sky_chisq asks: left to itself the allocator sits at
+// 127 registers, one short of dropping to 3 waves with any small change of the SED helpers.
+__global__ __launch_bounds__(BLOCK, 4) void k_moments_fit(const Model* __restrict__ Mp, const FitSeg* __restrict__ segs, double inv_n) {
+    extern __shared__ double fit_col[];   // [nb][BS]
+    const Model& M = *Mp;
+    const FitSeg& s = segs[blockIdx.y];
+    const int BS = blockDim.x, tid = threadIdx.x;
+    const int npix = M.npix, nb = M.nbands, plane = s.plane, k = plane + 1;
+    const bool want_chi = s.chi_mean != nullptr;
+    for (long long i0 = (long long)blockIdx.x * BS; i0 < npix; i0 += (long long)gridDim.x * BS) {
+        if (i0 + tid >= npix) continue;   // no barrier below: a column belongs to its thread
+        const int i = (int)i0 + tid;
+        for (int j = 0; j < nb; ++j) fit_col[j * BS + tid] = 0.0;
+        for (int l = 0; l < M.ncomp; ++l) {
+            const Comp& c = M.comp[l];
+            if (c.type == DANGX_MONOPOLE) continue;   // lives in the band offsets (src/dang_data_mod.f90:357-361)
+            const double amp = c.amp[(long long)plane * npix + i];
+            double t0, t1;
+            load_theta(M, c, i, k, t0, t1);
+            const Prep pr = sed_prep(c, t0, t1);
+            for (int j = 0; j < nb; ++j) {
+                const double sed = comp_sed(M, c, i, k, j, pr);
+                // comp_signal with the product rounded: the bare sed for T_cmb, template_amplitudes * sed for the global types
+                const double x = (c.type == DANGX_TCMB) ? sed : dx_fit_product(is_global_type(c.type) ? c.tamp[plane][j] : amp, sed);
+                fit_col[j * BS + tid] = dx_fit_sky_add(fit_col[j * BS + tid], x);
+            }
+        }
+        const bool chi_here = want_chi && !is_masked(M.mask[i]);
+        double chi = 0.0;
+        for (int j = 0; j < nb; ++j) {
+            const long long q = ((long long)j * M.nmaps + plane) * npix + i;
+            const double r = dx_fit_residual(plane, M.sig[q], M.offset[j], M.gain[j], fit_col[j * BS + tid]);
+            if (chi_here) chi = dx_fit_chi_add(chi, dx_fit_chi_term(r, M.rms[q]));
+            double* mp = s.rmean[j];
+            if (mp) {
+                double* qp = s.rm2[j];
+                double m = mp[i], v = qp[i];
+                welford(r, m, v, inv_n);
+                mp[i] = m; qp[i] = v;
+            }
+        }
+        if (chi_here) {
+            double m = s.chi_mean[i], v = s.chi_m2[i];
+            welford(dx_fit_chisq(chi, nb), m, v, inv_n);
+            s.chi_mean[i] = m; s.chi_m2[i] = v;
         }
     }
 }
@@ -810,6 +874,20 @@ size_t ang_table(const dangx_ctx* ctx, const DxMoments* m, std::vector<AngSeg>& 
     return ndelta;
 }
 
+// the device table of the registered fit items: one segment per plane with items
+void fit_table(const DxMoments* m, std::vector<FitSeg>& t) {
+    t.clear();
+    for (const DxFitSeg& ps : m->fit_plan) {
+        FitSeg s;
+        std::memset(&s, 0, sizeof s);   // the tables are compared as bytes
+        s.plane = ps.plane;
+        if (ps.chi >= 0) { s.chi_mean = m->mean(m->fits[ps.chi]); s.chi_m2 = m->m2(m->fits[ps.chi]); }
+        for (size_t j = 0; j < ps.res.size() && j < (size_t)MAXB; ++j)
+            if (ps.res[j] >= 0) { s.rmean[j] = m->mean(m->fits[ps.res[j]]); s.rm2[j] = m->m2(m->fits[ps.res[j]]); }
+        t.push_back(s);
+    }
+}
+
 // finish of one plane pair (mean, m2) into dst [npix]
 int finish_plane(dangx_ctx* ctx, const double* mean, const double* m2, int stat, double dn, double* dst) {
     FinishArgs a{};
@@ -978,7 +1056,7 @@ int dangx_moments_accumulate(dangx_ctx* ctx) {
                                      " declared per-pixel ranges and has no maps (dangx_moments_hist_range_maps was not called for it)");
     }
     (void)hipSetDevice(ctx->device);
-    if ((!m->sigs.empty() || !m->angs.empty()) && sync_model(ctx)) return 1;   // the SEDs read the device model: current before anything is launched
+    if ((!m->sigs.empty() || !m->angs.empty() || !m->fits.empty()) && sync_model(ctx)) return 1;   // the SEDs read the device model: current before anything is launched
     const double inv_n = 1.0 / (double)(m->count + 1);
     const long long pairs = (ctx->dims.npix + 1) / 2;   // the items of a launch that strides over pairs of pixels
     if (!m->segs.empty()) {
@@ -1109,6 +1187,24 @@ int dangx_moments_accumulate(dangx_ctx* ctx) {
                                (const Model*)ctx->dm, (const AngSeg*)(m->d_ang + ndelta), inv_n);
             HIPCHK(ctx, hipGetLastError());
         }
+    }
+    if (!m->fits.empty()) {   // the residuals and chi^2 maps: one launch of their own, independent of everything above
+        std::vector<FitSeg> t;
+        fit_table(m, t);
+        const bool same = t.size() == m->fit_table.size() && std::memcmp(t.data(), m->fit_table.data(), sizeof(FitSeg) * t.size()) == 0;
+        if (!same) {   // first accumulation: one upload (and a host wait); the chain's planes come through the device model
+            HIPCHK(ctx, hipMemcpyAsync(m->d_fit, t.data(), sizeof(FitSeg) * t.size(), hipMemcpyHostToDevice, ctx->stream));
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+            m->fit_table = t;
+        }
+        int bs = BLOCK;   // the sky column [nbands][bs] within 32 KiB of LDS, as the launch of k_sky_chisq sizes it
+        while (bs > 64 && (size_t)ctx->hm.nbands * bs * sizeof(double) > 32 * 1024) bs >>= 1;
+        const unsigned nseg = (unsigned)t.size();
+        const unsigned gx = std::max(1u, std::min(nblocks(ctx->dims.npix, bs), (m->grid_target * (unsigned)(BLOCK / bs) + nseg - 1) / nseg));
+        Timed tm(ctx, DANGX_K_FIT);
+        hipLaunchKernelGGL(k_moments_fit, dim3(gx, nseg), dim3(bs), (size_t)ctx->hm.nbands * bs * sizeof(double), ctx->stream,
+                           (const Model*)ctx->dm, (const FitSeg*)m->d_fit, inv_n);
+        HIPCHK(ctx, hipGetLastError());
     }
     if (!m->batches.empty()) {   // the batched accumulators: k_moments_accum on the row of the slot this sample belongs to
         const unsigned nreg = (unsigned)m->batches.size(), gx = m->grid_for(pairs, nreg);
@@ -1576,6 +1672,56 @@ int dangx_moments_get_angle_dev(dangx_ctx* ctx, int ang, int stat, double* out_d
 
 int dangx_moments_get_angle(dangx_ctx* ctx, int ang, int stat, double* out) { return get_angle_impl(ctx, ang, stat, out, true); }
 
+int dangx_moments_fit(dangx_ctx* ctx, int nfit, const int32_t* spec) {
+    if (reg_open(ctx, "dangx_moments_fit")) return 1;   // every component enters the residual: nothing to look up in the selection
+    DxMoments* m = ctx->mom;
+    const std::string why = dx_fit_check(nfit, spec, ctx->dims.nbands, ctx->dims.nmaps);
+    if (!why.empty()) return fail(ctx, "posterior moments: dangx_moments_fit: " + why);
+    (void)hipSetDevice(ctx->device);
+    const std::vector<DxFitSeg> plan = dx_fit_plan(nfit, spec, ctx->dims.nbands);
+    std::vector<DxMoments::Fit> nf;
+    for (int i = 0; i < nfit; ++i) nf.push_back(DxMoments::Fit{spec[3 * i], spec[3 * i + 1], spec[3 * i + 2], (long long)i * ctx->dims.npix, i});
+    const long long half = (long long)nfit * ctx->dims.npix;
+    // everything new is allocated before anything old is dropped (reg_close)
+    DevBuf<double> facc;
+    DevBuf<FitSeg> d_fit;
+    DevStatus st;
+    if (!nf.empty()) {
+        facc.zeros(2 * (size_t)half, ctx->stream, st);
+        d_fit.alloc(plan.size(), st);
+    }
+    if (reg_close(ctx, "dangx_moments_fit", st, !nf.empty())) return 1;
+    m->facc = std::move(facc); m->d_fit = std::move(d_fit); m->facc_half = half;
+    m->fits = nf;
+    m->fit_plan = plan;
+    m->fit_table.clear();   // the next accumulation uploads the table
+    return 0;
+}
+
+static int get_fit_impl(dangx_ctx* ctx, int item, int stat, int ddof, double* out, bool to_host) {
+    if (!ctx || !out || need_live(ctx, "dangx_moments_get_fit")) return 1;
+    const DxMoments* m = ctx->mom;
+    if (item < 0 || item >= (int)m->fits.size())
+        return fail(ctx, "posterior moments: fit item out of range (" + std::to_string(m->fits.size()) + " fit items registered)");
+    if (stat != 0 && stat != 1) return fail(ctx, "posterior moments: the stat of a fit item must be 0 (mean) or 1 (standard deviation)");
+    if (count_check(ctx, stat == 1 ? "standard deviation" : nullptr, ddof)) return 1;
+    (void)hipSetDevice(ctx->device);
+    const long long np = ctx->dims.npix;
+    ReadOut ro{ctx, out, to_host};
+    if (ro.open(sizeof(double) * (size_t)np)) return 1;
+    const auto& f = m->fits[item];
+    if (finish_plane(ctx, m->mean(f), m->m2(f), stat, (double)(m->count - ddof), ro.dst)) return 1;
+    return ro.close(np);
+}
+
+int dangx_moments_get_fit_dev(dangx_ctx* ctx, int item, int stat, int ddof, double* out_dev) {
+    return get_fit_impl(ctx, item, stat, ddof, out_dev, false);
+}
+
+int dangx_moments_get_fit(dangx_ctx* ctx, int item, int stat, int ddof, double* out) {
+    return get_fit_impl(ctx, item, stat, ddof, out, true);
+}
+
 int dangx_moments_batches(dangx_ctx* ctx, int nreg, const int32_t* planes, int nbatch, int64_t batch_len) {
     RegTables tab;
     if (reg_open(ctx, "dangx_moments_batches", &tab)) return 1;
@@ -1702,6 +1848,7 @@ static DxSecReg section_reg(const dangx_ctx* ctx, const DxMoments* m) {
     r.nbins = m->hbins; r.bits = m->hbits;
     for (const auto& s : m->sigs) { r.signals.push_back(s.comp); r.signals.push_back(s.band); r.signals.push_back(s.kind); }
     for (const auto& a : m->angs) { r.angles.push_back(a.comp); r.angles.push_back(a.band); }
+    for (const auto& f : m->fits) { r.fit.push_back(f.what); r.fit.push_back(f.band); r.fit.push_back(f.plane); }
     for (const auto& b : m->batches) plane(r.batch_planes, b.seg);
     r.nbatch = m->nbatch;
     return r;
@@ -1761,8 +1908,13 @@ int section_shape(dangx_ctx* ctx, const char* who, int family, int a, int b, Sec
         if (range(m->angs.size(), "angle index")) return 1;
         sh.bytes = dx_section_angle_bytes(np);
         return 0;
+    case DX_SEC_FIT:
+        if (m->fits.empty()) break;   // likewise
+        if (range(m->fits.size(), "fit item")) return 1;
+        sh.bytes = dx_section_fit_bytes(np);
+        return 0;
     }
-    return fail(ctx, std::string("posterior moments: ") + who + ": family must be 0 (HEAD) .. 6 (HIST_RANGE), or 7 (ANGLE) where angles are registered");
+    return fail(ctx, std::string("posterior moments: ") + who + ": family must be 0 (HEAD) .. 6 (HIST_RANGE), or 7 (ANGLE) where angles are registered, or 8 (FIT) where fit items are");
 }
 
 // a holder's buffer for a section of `bytes` payload bytes, and its planes entered into the tables
@@ -1811,6 +1963,7 @@ int holder_take(dangx_ctx* ctx, int family, int a, int b, const SecShape& sh, lo
     case DX_SEC_BATCHES: m->h_batch[a] = base; break;
     case DX_SEC_HIST_RANGE: m->h_range[a] = base; break;
     case DX_SEC_ANGLE: m->h_ang[a].mean = base; m->h_ang[a].m2 = base + np; break;
+    case DX_SEC_FIT: m->h_fit[a].mean = base; m->h_fit[a].m2 = base + np; break;
     }
     return 0;
 }
@@ -1854,6 +2007,7 @@ int section_runs(dangx_ctx* ctx, const char* who, int family, int a, int b, cons
         add(m->range_lo(m->hists[a]), 0, plane); add(m->range_hi(m->hists[a]), plane, plane);
         break;
     case DX_SEC_ANGLE: add(m->angC(m->angs[a]), 0, plane); add(m->angS(m->angs[a]), plane, plane); break;
+    case DX_SEC_FIT: add(m->mean(m->fits[a]), 0, plane); add(m->m2(m->fits[a]), plane, plane); break;
     }
     bool missing = !put && m->holder && family == DX_SEC_PLANES && sh.global && !m->h_rows[a];
     for (const SecRun& r : runs) missing = missing || (!r.dev && !r.host);
@@ -1998,10 +2152,12 @@ int dangx_moments_begin_like(dangx_ctx* ctx, dangx_ctx* like) {
     m->angs = o->angs; m->ang_plan = o->ang_plan;
     std::memcpy(m->ang_type, o->ang_type, sizeof m->ang_type); std::memcpy(m->ang_nind, o->ang_nind, sizeof m->ang_nind);
     std::memcpy(m->ang_used, o->ang_used, sizeof m->ang_used);
+    m->fits = o->fits; m->fit_plan = o->fit_plan;
     m->batches = o->batches; m->nbatch = o->nbatch; m->batch_len = o->batch_len; m->bpitch = o->bpitch;
     m->h_seg.resize(m->segs.size()); m->h_pair.assign(m->pairs.size(), nullptr); m->h_hist.assign(m->hists.size(), nullptr);
     m->h_range.assign(m->hists.size(), nullptr);
     m->h_sig.resize(m->sigs.size()); m->h_batch.assign(m->batches.size(), nullptr); m->h_ang.resize(m->angs.size());
+    m->h_fit.resize(m->fits.size());
     dx_moments_free(ctx);   // whatever the context held or accumulated goes
     ctx->mom = m.release();
     return 0;

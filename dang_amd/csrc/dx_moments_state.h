@@ -5,6 +5,7 @@
 #include "dx_host.h"
 #include "dx_signal_host.h"
 #include "dx_angle_host.h"
+#include "dx_fit_host.h"
 
 #include <cstdint>
 #include <utility>
@@ -106,6 +107,15 @@ struct AngSeg {           // a component with up to DX_ANG_SEG_BANDS bands; the 
     AngBand b[DX_ANG_SEG_BANDS];
 };
 
+struct FitSeg {           // a plane with fit items (dx_fit_host.h): the accumulators of its chi^2 map and of its bands' residuals, null = not registered
+    double* chi_mean;
+    double* chi_m2;
+    double* rmean[MAXB];  // by band
+    double* rm2[MAXB];
+    int plane;            // 0-based
+    int pad_;
+};
+
 // ---- device memory that belongs to its holder: freed when the holder goes, handed on by move
 
 struct DevStatus {        // the first HIP call of a sequence that failed (`what` names it); later calls of the sequence do nothing
@@ -202,6 +212,14 @@ struct DxMoments {
     DevBuf<AngSeg> d_ang;
     DevBuf<double> aacc;             // [Cbar: aacc_half doubles | Sbar: aacc_half doubles], every plane at the phase of the component's Q plane
     long long aacc_half = 0;
+    // dangx_moments_fit
+    struct Fit { int what, band, plane; long long off; int id = 0; };   // off: the item's mean plane in facc; id: its index in fits
+    std::vector<Fit> fits;
+    std::vector<DxFitSeg> fit_plan;
+    std::vector<FitSeg> fit_table;   // the table as last uploaded
+    DevBuf<FitSeg> d_fit;
+    DevBuf<double> facc;             // [mean: facc_half doubles | m2: facc_half doubles]; k_moments_fit goes pixel by pixel: no phase to keep
+    long long facc_half = 0;
     // dangx_moments_batches: [reg][batch][mean | m2][bpitch] in bacc, every plane at the 16-byte phase of its segment's main
     // accumulator (bpitch is even, so a registration's planes share the phase of its first)
     struct Batch { int seg; long long off; int id = 0; };   // seg: index into segs; off: batch 0's mean plane in bacc; id: its index in batches
@@ -235,6 +253,7 @@ struct DxMoments {
     std::vector<HeldSeg> h_sig;       // by Sig::id (mean, m2)
     std::vector<double*> h_batch;     // by Batch::id: batch 0's mean plane
     std::vector<HeldSeg> h_ang;       // by Ang::id (mean: Cbar, m2: Sbar)
+    std::vector<HeldSeg> h_fit;       // by Fit::id (mean, m2)
     bool h_rows[MAXC] = {};           // the host rows tm_* of a template / monopole / hi_fit member were put
 
     // where things are
@@ -248,6 +267,8 @@ struct DxMoments {
     double* m2(const Sig& s) const { return holder ? h_sig[s.id].m2 : sacc + sacc_half + s.off; }
     double* angC(const Ang& a) const { return holder ? h_ang[a.id].mean : aacc + a.off; }
     double* angS(const Ang& a) const { return holder ? h_ang[a.id].m2 : aacc + aacc_half + a.off; }
+    double* mean(const Fit& f) const { return holder ? h_fit[f.id].mean : facc + f.off; }
+    double* m2(const Fit& f) const { return holder ? h_fit[f.id].m2 : facc + facc_half + f.off; }
     uint32_t* records(const Hist& h) const { return holder ? h_hist[h.id] : hrec + h.off; }
     double* range_lo(const Hist& h) const { return holder ? h_range[h.id] : (h.have_maps ? hrange + h.roff : nullptr); }   // null: no maps (yet)
     double* range_hi(const Hist& h) const { double* p = range_lo(h); return p ? p + hpitch : nullptr; }

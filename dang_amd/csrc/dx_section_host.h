@@ -12,13 +12,15 @@
 //   BATCHES (reg, -)      [nbatch][mean, m2][npix] f64
 //   HIST_RANGE (reg, -)   lo, hi, each [npix] f64: the range maps of a histogram registration with per-pixel ranges (only those have it)
 //   ANGLE   (ang, -)      Cbar, Sbar, each [npix] f64 (dx_angle_host.h)
+//   FIT     (item, -)     mean, m2, each [npix] f64 (dx_fit_host.h): family DX_SEC_FIT = 8, which exists only in a context with fit
+//                         items -- DX_SEC_FAMILIES counts the families every context has
 //
 // The fingerprint is FNV-1a (64 bit) over the registration written out as little-endian 64-bit words, in six groups that HEAD
 // carries one by one, so that a mismatch can be named: the shard (npix, pix0, nmaps), the selection (the selection words, type
 // and nindices of every selected component), the pairs (lag-1 flag and pair list), the histograms (planes, lo, hi as their bit
 // patterns, nbins, bits; with a per-pixel range anywhere in the list also every registration's range kind and the checksum of its
 // maps -- a list of global ranges alone hashes as it always did), the signals (specs; with an angle registered also the angle
-// specs -- a registration without angles hashes as it always did) and the batches (planes, nbatch).  The overall value hashes
+// specs, and with a fit item registered the fit specs -- a registration without angles / fit items hashes as it always did) and the batches (planes, nbatch).  The overall value hashes
 // the six.
 #pragma once
 #include <cstdint>
@@ -27,6 +29,7 @@
 #include <vector>
 
 enum { DX_SEC_HEAD = 0, DX_SEC_PLANES = 1, DX_SEC_PAIR = 2, DX_SEC_HIST = 3, DX_SEC_SIGNAL = 4, DX_SEC_BATCHES = 5, DX_SEC_HIST_RANGE = 6, DX_SEC_ANGLE = 7, DX_SEC_FAMILIES = 8 };
+enum { DX_SEC_FIT = 8 };   // behind the families every context has
 enum { DX_SEC_G_SHARD = 0, DX_SEC_G_SEL = 1, DX_SEC_G_PAIRS = 2, DX_SEC_G_HIST = 3, DX_SEC_G_SIGNALS = 4, DX_SEC_G_BATCHES = 5, DX_SEC_GROUPS = 6 };
 
 #define DX_SEC_VERSION 1u
@@ -35,6 +38,7 @@ enum { DX_SEC_G_SHARD = 0, DX_SEC_G_SEL = 1, DX_SEC_G_PAIRS = 2, DX_SEC_G_HIST =
 
 inline const char* dx_section_family_name(int family) {
     static const char* const n[DX_SEC_FAMILIES] = {"HEAD", "PLANES", "PAIR", "HIST", "SIGNAL", "BATCHES", "HIST_RANGE", "ANGLE"};
+    if (family == DX_SEC_FIT) return "FIT";
     return family >= 0 && family < DX_SEC_FAMILIES ? n[family] : "?";
 }
 
@@ -51,6 +55,7 @@ struct DxSecReg {              // what a registration is made of
     int nbins = 0, bits = 0;
     std::vector<int32_t> signals;             // 3 per signal: {comp, band, kind}
     std::vector<int32_t> angles;              // 2 per angle: {comp, band}; hashed into the signals' group, and only when not empty
+    std::vector<int32_t> fit;                 // 3 per fit item: {what, band, plane}; hashed into the signals' group behind a marker word, and only when not empty
     std::vector<int32_t> batch_planes;        // 3 per registration
     int nbatch = 0;
 };
@@ -109,6 +114,10 @@ inline void dx_section_groups(const DxSecReg& r, uint64_t (&g)[DX_SEC_GROUPS]) {
     }
     e.list(r.signals);
     if (!r.angles.empty()) e.list(r.angles);   // only then: the group of a registration without angles stays what it was
+    if (!r.fit.empty()) {                      // likewise; the marker keeps a fit list apart from an angle list of the same numbers
+        e.word(0x544946ull);                   // "FIT"
+        e.list(r.fit);
+    }
     f.list(r.batch_planes); f.num(r.batch_planes.empty() ? 0 : r.nbatch);
     g[0] = a.h; g[1] = b.h; g[2] = c.h; g[3] = d.h; g[4] = e.h; g[5] = f.h;
 }
@@ -188,7 +197,7 @@ inline std::string dx_section_head_unpack(const unsigned char* in, size_t bytes,
 inline std::string dx_section_head_diff(const DxSecHead& got, const DxSecHead& own) {
     static const char* const what[DX_SEC_GROUPS] = {
         "the shard (npix, pix0 or nmaps)", "the selection (selection words, type or nindices of a selected component)",
-        "the pair list", "the histogram registrations (planes, lo / hi range, nbins or bits)", "the signal or angle registrations",
+        "the pair list", "the histogram registrations (planes, lo / hi range, nbins or bits)", "the fit items, signal or angle registrations",
         "the batch registrations (planes)"};
     std::string why;
     auto add = [&](const std::string& s) { why += (why.empty() ? "" : "; ") + s; };
@@ -215,4 +224,5 @@ inline long long dx_section_signal_bytes(long long npix) { return 2 * npix * 8; 
 inline long long dx_section_batches_bytes(long long npix, int nbatch) { return 2LL * nbatch * npix * 8; }
 inline long long dx_section_hist_range_bytes(long long npix) { return 2 * npix * 8; }
 inline long long dx_section_angle_bytes(long long npix) { return 2 * npix * 8; }
+inline long long dx_section_fit_bytes(long long npix) { return 2 * npix * 8; }
 inline long long dx_section_round256(long long bytes) { return (bytes + 255) / 256 * 256; }

@@ -62,14 +62,16 @@ def write_problem(path, dpar, ddata, comps, meta, niter, nsample=None, seed=None
                 f.write(np.ones(nmaps, dtype="<f8").tobytes())          # c%temp_norm
 
 
-def read_result(path, comps, meta, maps=True, posterior=False, pairs=False, hist=False, signal=False, angle=False):
+def read_result(path, comps, meta, maps=True, posterior=False, pairs=False, hist=False, signal=False, angle=False, fit=False):
     """posterior: the run had DANG_POSTERIOR set -- res["post"] = {"n", "mean", "std"}, each of mean / std a dict of "amp", "ind",
     "tamp" lists laid out as the state's.  pairs: it had DANG_POSTERIOR_PAIRS set as well -- res["post"] also holds "rho1" and
     "ess" (laid out like "mean") and "corr", the [npairs][npix] correlation maps in posterior_pairs_gpu's order.  hist: it had
     DANG_POSTERIOR_HIST set -- res["post"]["hist"] = [{"q": [3][npix] (0.16 / 0.5 / 0.84), "n": [npix]}, ...] in
     posterior_hist_gpu's order.  signal: it had DANG_POSTERIOR_SIGNAL set -- res["post"]["signal"] = [{"spec": (comp, band, kind),
     "mean": [npix], "std": [npix]}, ...] in posterior_signal_gpu's order.  angle: it had DANG_POSTERIOR_ANGLE set --
-    res["post"]["angle"] = [{"spec": (comp, band), "psi": [npix], "psi_std": [npix], "R": [npix]}, ...] in posterior_angle_gpu's order."""
+    res["post"]["angle"] = [{"spec": (comp, band), "psi": [npix], "psi_std": [npix], "R": [npix]}, ...] in posterior_angle_gpu's order.
+    fit: it had DANG_POSTERIOR_FIT set -- res["post"]["fit"] = [{"spec": (what, band, plane), "mean": [npix], "std": [npix]}, ...] in
+    posterior_fit_gpu's order."""
     npix, nb, nmaps = meta["npix"], meta["nbands"], meta["nmaps"]
     out = np.fromfile(path, dtype="<f8")
     res = dict(chisq=out[0], tcmb=out[1], secs=out[2], gain=out[3:3 + nb], offset=out[3 + nb:3 + 2 * nb])
@@ -133,18 +135,27 @@ def read_result(path, comps, meta, maps=True, posterior=False, pairs=False, hist
                 res["post"]["angle"].append({"spec": tuple(int(v) for v in out[p:p + 2]), "psi": out[p + 2:p + 2 + npix],
                                              "psi_std": out[p + 2 + npix:p + 2 + 2 * npix], "R": out[p + 2 + 2 * npix:p + 2 + 3 * npix]})
                 p += 2 + 3 * npix
+        if fit:
+            nfit = int(out[p])
+            p += 1
+            res["post"]["fit"] = []
+            for _ in range(nfit):
+                res["post"]["fit"].append({"spec": tuple(int(v) for v in out[p:p + 3]), "mean": out[p + 3:p + 3 + npix],
+                                           "std": out[p + 3 + npix:p + 3 + 2 * npix]})
+                p += 3 + 2 * npix
     assert p == out.size, (p, out.size)
     return res
 
 
 def run(problem, result, nctx=1, mode="twocall", tile=1, timeout=900, posterior=None, pairs=False, hist=None, signal=False,
-        fluct_mode="reference", angle=False):
+        fluct_mode="reference", angle=False, fit=False):
     """Run the driver; returns its stdout.  Raises when flang is absent or the run fails (no fallback).
     posterior=(burn_in, thin): accumulate the posterior moments (DANG_POSTERIOR) and append them to the result file.
     pairs (with posterior): also the lag-1 and default pair statistics (DANG_POSTERIOR_PAIRS=1), appended after them.
     hist=nbins (with posterior): also the default per-pixel histograms (DANG_POSTERIOR_HIST=nbins), their quantiles appended behind them.
     signal (with posterior): also the default component signals (DANG_POSTERIOR_SIGNAL=1), their mean and std appended behind them.
-    angle (with posterior): also the default polarisation angles (DANG_POSTERIOR_ANGLE=1), their circular mean, std and R appended last.
+    angle (with posterior): also the default polarisation angles (DANG_POSTERIOR_ANGLE=1), their circular mean, std and R appended behind them.
+    fit (with posterior): also the default goodness-of-fit items (DANG_POSTERIOR_FIT=1), their mean and std appended last.
     fluct_mode: 'correct' runs the amplitude solves with the textbook fluctuation term (DANG_FLUCT=correct -> gpu_fluct_mode)."""
     exe = _build.build_reference_drive()
     if exe is None:
@@ -168,6 +179,8 @@ def run(problem, result, nctx=1, mode="twocall", tile=1, timeout=900, posterior=
             env["DANG_POSTERIOR_SIGNAL"] = "1"
         if angle:
             env["DANG_POSTERIOR_ANGLE"] = "1"
+        if fit:
+            env["DANG_POSTERIOR_FIT"] = "1"
     r = subprocess.run([exe, problem, result, str(nctx), mode, str(tile)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
                        text=True, timeout=timeout, env=env)
     if r.returncode != 0 or "dang_gpu_drive ok" not in r.stdout:

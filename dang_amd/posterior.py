@@ -6,7 +6,7 @@ Those are ONE builder (_build) driven by two descriptions:
 
   a source   what a *_maps call reads its chains through: one chain of this process (_OneChain), several (_LocalChains), or
              the chains of every rank of a process group (DistChains); all with shards, counts, fetch, batches_info, finish, here
-  a family   what is read (FAMILIES: planes, pair, hist, rank, batches, signal, angle): its registration, how an item becomes a key,
+  a family   what is read (FAMILIES: planes, pair, hist, rank, batches, signal, angle, fit): its registration, how an item becomes a key,
              which sections it owns, which statistics are available, its two thin getters and the checks each form makes
 
 Chains of other processes (dist_chains) and save / restore (moments_save, moments_load) are thin layers over the sections of the
@@ -348,6 +348,45 @@ def posterior_angle_maps(ddata, masked_value=None, engines=None):
     return _build(ANGLE, "posterior_angle_maps", _OneChain(ddata, engines), masked_value=masked_value)
 
 
+def default_fit_specs(dpar, component_list, bands, nmaps=3):
+    """[(what, band, plane), ...] for moments_fit: for every plane below `nmaps` named by a pol_flag of a CG group that samples a
+    component (a group some component with sample_amplitude belongs to), the chi^2 map of the plane (1, -1, plane) and then the
+    residual of every band (0, band, plane), bands ascending; planes ascending.  16 bytes per pixel and item: at full resolution
+    register fewer.  Pure Python."""
+    planes = 0
+    for g in dpar.cg_groups:
+        if any(c.sample_amplitude and c.cg_group == g.cg_group for c in component_list):
+            for f in g.pol_flag:
+                planes |= _flag_planes(f)
+    specs = []
+    for k in range(min(3, int(nmaps))):            # a flag that names a plane the model lacks adds nothing, as posterior_fit_gpu's loop over nmaps
+        if (planes >> k) & 1:
+            specs.append((1, -1, k))
+            specs += [(0, j, k) for j in range(len(bands))]
+    return specs
+
+
+def moments_fit(dpar, ddata, specs=None, engines=None):
+    """dangx_moments_fit on every context of this process, after moments_begin and before the first moments_accumulate;
+    specs=None: default_fit_specs of the run.  'residual' / 'chisq' and 'T' / 'Q' / 'U' are accepted in specs.  Returns the spec
+    list [(what, band, plane), ...]."""
+    engs = _engines_of(ddata, engines)
+    if specs is None:
+        specs = default_fit_specs(dpar, engs[0].component_list, engs[0].bands, nmaps=engs[0].nmaps)
+    specs = [_api.fit_spec(s) for s in specs]
+    for e in engs:
+        e.moments_fit(specs)
+    return specs
+
+
+def posterior_fit_maps(ddata, ddof=0, masked_value=None, engines=None):
+    """{('residual', band label, 'T' | 'Q' | 'U') or ('chisq', 'T' | 'Q' | 'U'): {'mean', 'std', 'n'}} of the items moments_fit
+    registered, as host arrays [npix] in the model's units (the residual of a band not divided by its unit conversion; a chi^2 map
+    reads 0 at masked pixels).  Several contexts of this process: their shards side by side.  masked_value: as in posterior_maps.
+    The std of the sky model at a band is the residual's std, its mean the (calibrated) data minus the residual's mean."""
+    return _build(FIT, "posterior_fit_maps", _OneChain(ddata, engines), ddof=ddof, masked_value=masked_value)
+
+
 # --------------------------------------------------------------------------- several chains: R-hat and pooled summaries
 # dangx_chains_* (include/dangx.h): the accumulators of K chains of one device are combined on the device and only the map asked
 # for is written.  `engines` below is one Engine per chain (the same shard of each); a "chain" of the map functions is a ddata
@@ -387,6 +426,11 @@ def chains_get_template(engines, l, stat, ddof=0, out=None):
 def chains_get_signal(engines, s, stat, ddof=0, device=False, out=None):
     """chains_get's statistics 'mean', 'std', 'rhat', 'W', 'B' of registered signal s (the same registration in every chain), [npix]."""
     return _chains_readout(engines, "dangx_chains_get_signal", (engines[0].npix,), (int(s), _code(L.CHAINS_STAT_CODES, stat), int(ddof)), device, out)
+
+
+def chains_get_fit(engines, i, stat, ddof=0, device=False, out=None):
+    """chains_get's statistics 'mean', 'std', 'rhat', 'W', 'B' of registered fit item i (the same registration in every chain), [npix]."""
+    return _chains_readout(engines, "dangx_chains_get_fit", (engines[0].npix,), (int(i), _code(L.CHAINS_STAT_CODES, stat), int(ddof)), device, out)
 
 
 def chains_get_angle(engines, a, stat, device=False, out=None):
@@ -621,13 +665,25 @@ ANGLE = _Family("angles", "moments_angles", "angle", "moments_get_angle", "chain
                 sections=lambda it, stats: [(L.SEC_ANGLE, it[0], 0, False)],
                 stats=lambda src, o: _named(("psi", "psi_std", "R") + (("between",) if src.pooled else ())),
                 args=lambda it, stat, o: (it[0], stat), head=_count_head)
-FAMILIES = {"planes": PLANES, "pair": PAIR, "hist": HIST, "rank": RANK, "batches": BATCHES, "signal": SIGNAL, "angle": ANGLE}
+def _fit_key(e0, it):
+    what, band, plane = it[1]
+    if what == 1:
+        return ("chisq", L.SIGNAL_KINDS[plane])
+    return ("residual", e0.bands[band].label, L.SIGNAL_KINDS[plane])
+
+
+FIT = _Family("fit", "moments_fit", "fit", "moments_get_fit", "chains_get_fit", (_SAME + ("counts",), _SAME),
+              items=lambda e0, specs: list(enumerate(specs)), key=_fit_key,
+              sections=lambda it, stats: [(L.SEC_FIT, it[0], 0, False)],
+              stats=lambda src, o: _named(_chains_stats(src.counts, False) if src.pooled else ("mean", "std")),
+              args=lambda it, stat, o: (it[0], stat, o["ddof"]), head=_count_head)
+FAMILIES = {"planes": PLANES, "pair": PAIR, "hist": HIST, "rank": RANK, "batches": BATCHES, "signal": SIGNAL, "angle": ANGLE, "fit": FIT}
 
 
 def own_sections(e):
     """Engine.moments_sections: the section every registered item of engine e owns, in the order moments_save writes them"""
     out = []
-    for fam in (PLANES, PAIR, HIST, SIGNAL, BATCHES, ANGLE):
+    for fam in (PLANES, PAIR, HIST, SIGNAL, BATCHES, ANGLE, FIT):
         reg = _registration(e, fam.reg, None, fam.call if fam is PLANES else None)
         if reg is not None:
             for item in fam.items(e, reg):
@@ -740,6 +796,12 @@ def chains_angle_maps(chains, masked_value=None):
     return _build(ANGLE, "chains_angle_maps", chains, masked_value=masked_value)
 
 
+def chains_fit_maps(chains, ddof=0, masked_value=None):
+    """posterior_fit_maps over several chains (or dist_chains' object): {'n', 'nchains', 'mean', 'std', 'rhat', 'W', 'B'} per
+    registered fit item."""
+    return _build(FIT, "chains_fit_maps", chains, ddof=ddof, masked_value=masked_value)
+
+
 def chains_signal_maps(chains, ddof=0, masked_value=None):
     """posterior_signal_maps over several chains: {'n', 'nchains', 'mean', 'std', 'rhat', 'W', 'B'} per registered signal."""
     return _build(SIGNAL, "chains_signal_maps", chains, ddof=ddof, masked_value=masked_value)
@@ -753,7 +815,7 @@ def chains_signal_maps(chains, ddof=0, masked_value=None):
 
 _HEAD_STRUCT = struct.Struct("<IIqiiqiiqQ6Q")
 _HEAD_GROUPS = ("the shard (npix, pix0 or nmaps)", "the selection (selection words, type or nindices of a selected component)",
-                "the pair list", "the histogram registrations (planes, lo / hi range, nbins or bits)", "the signal or angle registrations",
+                "the pair list", "the histogram registrations (planes, lo / hi range, nbins or bits)", "the fit items, signal or angle registrations",
                 "the batch registrations (planes)")
 
 
@@ -1027,7 +1089,7 @@ def moments_load(ddata, path, engines=None):
             for fam, a, b, _, off, n in index[1:]:
                 if n != e.moments_section_bytes(fam, a, b):
                     raise DangxError("moments_load: %s: section %s(%d, %d) is %d bytes, the engine's %d" % (
-                        fn, L.SECTION_NAMES[fam], a, b, n, e.moments_section_bytes(fam, a, b)))
+                        fn, L.SECTION_NAMES_ALL[fam], a, b, n, e.moments_section_bytes(fam, a, b)))
             e.moments_section_put(L.SEC_HEAD, 0, 0, head)        # the library checks the fingerprint once more
             for fam, a, b, _, off, n in index[1:]:
                 f.seek(off)

@@ -656,6 +656,25 @@ module dangx_mod
        type(c_ptr), value :: ctx, out_dev
        integer(c_int), value :: ang, stat
      end function
+     ! goodness-of-fit maps: spec(3, nfit) = (what, band, plane), 0-based as in C; what 0 = the residual of that band on plane
+     ! 0, 1, 2 = T, Q, U, what 1 = the chi**2 map of the plane (band = -1).  In the model's units: the division by conversion(j) that
+     ! write_maps applies stays with the caller.  Only between dangx_moments_begin and the first dangx_moments_accumulate.
+     integer(c_int) function dangx_moments_fit(ctx, nfit, spec) bind(C, name='dangx_moments_fit')
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx, spec              ! spec: integer(c_int32_t)(3, nfit) or c_null_ptr
+       integer(c_int), value :: nfit
+     end function
+     ! item: 0-based; stat: 0 = mean, 1 = std with ddof; out: (0:npix-1) of this shard
+     integer(c_int) function dangx_moments_get_fit(ctx, item, stat, ddof, out) bind(C, name='dangx_moments_get_fit')
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx, out
+       integer(c_int), value :: item, stat, ddof
+     end function
+     integer(c_int) function dangx_moments_get_fit_dev(ctx, item, stat, ddof, out_dev) bind(C, name='dangx_moments_get_fit_dev')
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx, out_dev
+       integer(c_int), value :: item, stat, ddof
+     end function
      ! batched accumulators: planes(3, nreg) = (comp, what, plane), 0-based as in C; nbatch even, 2..32 batches of initially
      ! batch_len samples, merged pairwise in place when all are full.  Only between dangx_moments_begin and the first
      ! dangx_moments_accumulate.  stat: 0 = mean, 1 = std (ddof), 2 = MCSE, 3 = batch-means ESS, 4 = split R-hat, the first
@@ -778,6 +797,20 @@ module dangx_mod
        import :: c_int, c_ptr
        type(c_ptr), intent(in) :: ctxs(*)
        integer(c_int), value :: nchains, sig, stat, ddof
+       type(c_ptr), value :: out_dev
+     end function
+     ! a fit item over the chains: stat 0..4 as for a signal
+     integer(c_int) function dangx_chains_get_fit(ctxs, nchains, item, stat, ddof, out) bind(C, name='dangx_chains_get_fit')
+       import :: c_int, c_ptr
+       type(c_ptr), intent(in) :: ctxs(*)
+       integer(c_int), value :: nchains, item, stat, ddof
+       type(c_ptr), value :: out
+     end function
+     integer(c_int) function dangx_chains_get_fit_dev(ctxs, nchains, item, stat, ddof, out_dev) &
+          bind(C, name='dangx_chains_get_fit_dev')
+       import :: c_int, c_ptr
+       type(c_ptr), intent(in) :: ctxs(*)
+       integer(c_int), value :: nchains, item, stat, ddof
        type(c_ptr), value :: out_dev
      end function
      ! stat: dangx_moments_get_angle's 0..4 on the chains' pooled (Cbar, Sbar), 5 = the circular std of the chains' mean directions

@@ -398,6 +398,33 @@ contains
     end do
   end subroutine dangx_sky_moments_get_angle
 
+  ! goodness-of-fit items spec(3, nfit) = (what, band, plane), 0-based as in include/dangx.h (what 0 = the residual at a band, 1 =
+  ! the chi**2 map with band = -1), on every context: after dangx_sky_moments_begin, before the first accumulate
+  subroutine dangx_sky_moments_fit(sky, nfit, spec)
+    type(dangx_sky), intent(in) :: sky
+    integer, intent(in) :: nfit
+    integer(c_int32_t), intent(in), target :: spec(:,:)
+    type(c_ptr) :: p
+    integer :: r
+    p = c_null_ptr
+    if (nfit > 0) p = c_loc(spec)
+    do r = 1, sky%nctx
+       call dangx_check(sky%ctx(r), dangx_moments_fit(sky%ctx(r), nfit, p), 'dangx_moments_fit')
+    end do
+  end subroutine dangx_sky_moments_fit
+
+  ! item: 0-based; stat 0 = mean, 1 = standard deviation with ddof; out: c_loc of a full-sky (0:npix-1) array, every context fills
+  ! its pixel range
+  subroutine dangx_sky_moments_get_fit(sky, item, stat, ddof, out)
+    type(dangx_sky), intent(in) :: sky
+    integer, intent(in) :: item, stat, ddof
+    type(c_ptr), intent(in) :: out
+    integer :: r
+    do r = 1, sky%nctx
+       call dangx_check(sky%ctx(r), dangx_moments_get_fit(sky%ctx(r), item, stat, ddof, at_pix(out, sky%pix0(r))), 'dangx_moments_get_fit')
+    end do
+  end subroutine dangx_sky_moments_get_fit
+
   function dangx_sky_moments_count(sky) result(n)
     type(dangx_sky), intent(in) :: sky
     integer(c_int64_t) :: n, m

@@ -30,6 +30,9 @@
 ! DANG_POSTERIOR_ANGLE=1 beside DANG_POSTERIOR: posterior_angle_gpu(dpar) after posterior_begin_gpu, and behind everything else the
 ! number of angles and per angle its (comp, band), its circular mean, circular standard deviation and mean resultant length.
 ! Without it the result file is what the other switches give.
+! DANG_POSTERIOR_FIT=1 beside DANG_POSTERIOR: posterior_fit_gpu(dpar) after posterior_begin_gpu, and behind everything else the
+! number of fit items and per item its (what, band, plane), its mean and its standard deviation (ddof 0).  Without it the result
+! file is what the other switches give.
 ! DANG_FLUCT=correct: gpu_fluct_mode = DANGX_FLUCT_CORRECT, the amplitude solves draw with the textbook fluctuation term (one
 ! normal per band); unset or anything else: the reference's term, as before.
 subroutine mpi_allreduce(sendbuf, recvbuf, count, datatype, op, comm, ierror)
@@ -65,9 +68,9 @@ program dang_gpu_drive
   character(len=512) :: fin, fout, arg, mode
   integer :: u, i, j, l, k, npix0, niter, ngroups, nctx, tile, t, it_first
   integer :: post_burn, post_thin, post_len, post_stat
-  logical :: post, post_pairs, post_hist, post_sig, post_ang
+  logical :: post, post_pairs, post_hist, post_sig, post_ang, post_fit
   integer :: hist_bins
-  real(c_double), allocatable :: pair_map(:), q_map(:,:), n_map(:), sig_map(:), ang_map(:)
+  real(c_double), allocatable :: pair_map(:), q_map(:,:), n_map(:), sig_map(:), ang_map(:), fit_map(:)
   integer(i8b) :: c0, c1, crate
   real(dp) :: secs
 
@@ -189,6 +192,9 @@ program dang_gpu_drive
   call get_environment_variable('DANG_POSTERIOR_ANGLE', arg, post_len)
   post_ang = post .and. post_len > 0
   if (post_ang) call posterior_angle_gpu(dpar)
+  call get_environment_variable('DANG_POSTERIOR_FIT', arg, post_len)
+  post_fit = post .and. post_len > 0
+  if (post_fit) call posterior_fit_gpu(dpar)
   secs = 0.d0; it_first = 3
   do iter = 1, niter
      if (iter == it_first + 1) then                       ! time iterations it_first+1 .. niter: the first two full ones warm up (index maps that start spatially constant take the generic launches once, kernels specialised at run time are compiled on first use)
@@ -283,6 +289,17 @@ program dang_gpu_drive
               call posterior_angle_to_host_gpu(i, post_stat, ang_map)
               write(u) ang_map
            end do
+        end do
+     end if
+     if (post_fit) then
+        write(u) real(gpu_post_nfit, c_double)
+        allocate(fit_map(0:npix-1))
+        do i = 1, gpu_post_nfit
+           write(u) real(gpu_post_fit(:, i), c_double)
+           call posterior_fit_to_host_gpu(i, 0, 0, fit_map)
+           write(u) fit_map
+           call posterior_fit_to_host_gpu(i, 1, 0, fit_map)
+           write(u) fit_map
         end do
      end if
   end if

@@ -49,6 +49,8 @@ module dang_gpu_mod
   integer(i4b) :: gpu_post_nsig = 0
   integer(c_int32_t), allocatable, target :: gpu_post_ang(:,:)     ! posterior_angle_gpu's angles (2, gpu_post_nang) = (comp, band), 0-based as in C
   integer(i4b) :: gpu_post_nang = 0
+  integer(c_int32_t), allocatable, target :: gpu_post_fit(:,:)     ! posterior_fit_gpu's items (3, gpu_post_nfit) = (what, band, plane), 0-based as in C
+  integer(i4b) :: gpu_post_nfit = 0
 
 contains
 
@@ -736,6 +738,7 @@ contains
     gpu_post_nhist = 0
     gpu_post_nsig = 0
     gpu_post_nang = 0
+    gpu_post_nfit = 0
   end subroutine posterior_begin_gpu
 
   ! after posterior_begin_gpu, before the first posterior_accumulate_gpu that takes a sample: the second-order summaries.  lag1:
@@ -1042,6 +1045,68 @@ contains
     call rank_window(w, 1, .false.)
     out(0:npix-1) = w(:, 1)
   end subroutine posterior_angle_to_host_gpu
+
+  ! after posterior_begin_gpu, before the first posterior_accumulate_gpu that takes a sample: mean and standard deviation of the
+  ! goodness-of-fit maps write_maps leaves beside the components (src/dang_data_mod.f90:619-634, 656-662) and
+  ! scripts/make_mean_maps.py averages -- as dang_amd.default_fit_specs: for every plane named by a pol_flag of a CG group that
+  ! samples a component, the chi**2 map of the plane (what 1, band -1) and then the residual of every band (what 0), bands
+  ! ascending; planes ascending.  In the model's units: the division by ddata%conversion(j) that write_maps applies to a residual
+  ! stays with the caller.  16 bytes per pixel and item.  Read with posterior_fit_to_host_gpu (item = 1 .. gpu_post_nfit).
+  subroutine posterior_fit_gpu(dpar)
+    type(dang_params) :: dpar
+    integer(i4b) :: i, j, k, g, n, pass, planes
+    logical :: sampled
+    if (.not. allocated(gpu_post_sel)) then
+       write(*,*) 'posterior_fit_gpu: posterior_begin_gpu was not called'
+       stop 1
+    end if
+    planes = 0
+    do g = 1, ncg_groups
+       sampled = .false.
+       do i = 1, ncomp
+          if (component_list(i)%p%sample_amplitude .and. component_list(i)%p%cg_group == cg_groups(g)%p%cg_group) sampled = .true.
+       end do
+       if (.not. sampled) cycle
+       do k = 1, cg_groups(g)%p%nflag
+          planes = ior(planes, flag_plane_bits(cg_groups(g)%p%pol_flag(k)))
+       end do
+    end do
+    do pass = 1, 2                                    ! count, then fill
+       n = 0
+       do k = 0, nmaps - 1
+          if (.not. btest(planes, k)) cycle
+          n = n + 1
+          if (pass == 2) gpu_post_fit(:, n) = int([1, -1, k], c_int32_t)
+          do j = 1, nbands
+             n = n + 1
+             if (pass == 2) gpu_post_fit(:, n) = int([0, j-1, k], c_int32_t)
+          end do
+       end do
+       if (pass == 1) then
+          if (allocated(gpu_post_fit)) deallocate(gpu_post_fit)
+          allocate(gpu_post_fit(3, max(n, 1))); gpu_post_fit = 0
+       end if
+    end do
+    gpu_post_nfit = n
+    call dangx_sky_moments_fit(gpu_sky, n, gpu_post_fit)
+  end subroutine posterior_fit_gpu
+
+  ! mean (stat = 0) or standard deviation (stat = 1, with ddof) map of fit item `item` (1-based, posterior_fit_gpu's order) into
+  ! out(0:npix-1); under MPI every rank fills its pixel range and the ranges are merged as rank_window merges a plane
+  subroutine posterior_fit_to_host_gpu(item, stat, ddof, out)
+    integer(i4b), intent(in) :: item, stat, ddof
+    real(dp), intent(inout), target :: out(0:)
+    real(dp), allocatable, target :: w(:,:)
+    if (item < 1 .or. item > gpu_post_nfit) then
+       write(*,*) 'posterior_fit_to_host_gpu: fit item out of range', item, gpu_post_nfit
+       stop 1
+    end if
+    allocate(w(0:npix-1, 1))
+    call rank_window(w, 1, .true.)
+    call dangx_sky_moments_get_fit(gpu_sky, item - 1, stat, ddof, c_loc(w))
+    call rank_window(w, 1, .false.)
+    out(0:npix-1) = w(:, 1)
+  end subroutine posterior_fit_to_host_gpu
 
   ! after write_data_gpu in the loop: one sample of the current state, every thin-th iteration after burn_in.  Enqueued on every
   ! context's stream behind the iteration's launches: the host does not wait

@@ -78,7 +78,8 @@ enum {
     DANGX_K_CHAINS = 10,   /* the read-outs over several chains (dangx_chains_*): nothing else is ever counted here */
     DANGX_K_BATCH = 11,    /* the batched accumulators (dangx_moments_batches): one launch per accumulation, one more per merge */
     DANGX_K_ANGLE = 12,    /* the polarisation-angle accumulators (dangx_moments_angles): one launch per accumulation, two with an integrated band */
-    DANGX_K_COUNT = 13
+    DANGX_K_FIT = 13,      /* the goodness-of-fit accumulators (dangx_moments_fit): one launch per accumulation */
+    DANGX_K_COUNT = 14
 };
 
 typedef struct dangx_ctx dangx_ctx;
@@ -650,6 +651,36 @@ int dangx_moments_get_signal_dev(dangx_ctx *ctx, int sig, int stat, int ddof, do
 int dangx_moments_angles(dangx_ctx *ctx, int nang, const int32_t *spec);
 int dangx_moments_get_angle(dangx_ctx *ctx, int ang, int stat, double *out);
 int dangx_moments_get_angle_dev(dangx_ctx *ctx, int ang, int stat, double *out_dev);
+/* Goodness-of-fit maps, accumulated on the same samples: the residual at a (band, plane) and the chi^2 map of a plane -- what
+ * write_maps writes as <band>_residual_k*.fits and chisq_k*.fits (src/dang_data_mod.f90:619-634, 656-662) and
+ * scripts/make_mean_maps.py averages into <band>_residual_mean.fits and chisq_mean.fits.  chi^2 is quadratic in all sampled
+ * parameters at once, so neither it nor the std of a residual follows from any other accumulator.  k_moments_fit is ONE launch
+ * per accumulation behind the others (DANGX_K_FIT), only when something is registered; no copy of the residual exists in memory.
+ * Definitions (dang_amd/csrc/dx_fit_host.h):
+ *   spec[i] = {what, band, plane}, plane 0, 1, 2 = T, Q, U; what 0 = the residual at `band`, what 1 = the chi^2 map (band = -1).
+ *   one sample at a pixel, in update_sky_model + compute_chisq's expressions as dangx_sky_model_chisq evaluates them:
+ *     x_c(j) = the ROUNDED product amplitude * sed of a diffuse member, template_amplitudes * sed of a template / hi_fit member,
+ *     the bare sed of T_cmb (a monopole lives in the band offset); sky_j = their sum in component order from 0.0;
+ *     r_j = (sig - offset_j) / gain_j - sky_j on T, sig - sky_j on Q, U, at EVERY pixel, masked ones included;
+ *     chi^2 = (sum_j (r_j r_j) / (rms_j rms_j)) / nbands over ALL bands in band order, whichever residuals are registered, at
+ *     unmasked pixels only (plane T's mask): at a masked pixel nothing is accumulated and mean and std read 0, as the
+ *     reference's chi_map.  NaN / inf propagate; nothing else is skipped (no amp == 0 shortcut).
+ *   Units are the model's (uK_RJ): the division by conversion(j) that write_maps applies to a residual stays with the caller.
+ *   The update is k_moments_accum's on two f64 planes per item of the library's own: 16 B * npix per item (everything at the C3
+ *   workload: 33 items = 6.6 GB; at C5: 63 items = 50 GB -- register what is looked at).
+ * dangx_moments_fit: legal after dangx_moments_begin and before the first dangx_moments_accumulate, independent of every other
+ *   registration and of the selection words; a second call replaces the first (nfit = 0: none), dangx_moments_begin / _end drop
+ *   it, dangx_moments_begin_like copies it into the holder.  Errors (nothing changes, the item is named): count > 0, what / band /
+ *   plane out of range, chi^2 with band != -1, a plane the model lacks, the same item twice, nfit > DANGX_MAX_FIT, a failed
+ *   allocation.  No component type is refused: the residual involves all of them.
+ * dangx_moments_get_fit: stat 0 = mean, 1 = standard deviation sqrt(m2 / (n - ddof)); out [npix] of this shard.
+ * dangx_chains_get_fit: rules and statistics of dangx_chains_get_signal.  The section of an item is family 8 FIT (below).
+ * A sky-model map is data' - residual with data' fixed, so its std is the residual's std and its mean data' minus the residual's.
+ * The global reduced chi^2 trace is dangx_chisq_current.  Not covered: histograms / quantiles, batches, lag-1 or pairs of fit items. */
+#define DANGX_MAX_FIT 128
+int dangx_moments_fit(dangx_ctx *ctx, int nfit, const int32_t *spec);
+int dangx_moments_get_fit(dangx_ctx *ctx, int item, int stat, int ddof, double *out);
+int dangx_moments_get_fit_dev(dangx_ctx *ctx, int item, int stat, int ddof, double *out_dev);
 /* Batched accumulators of registered pixel planes: the run cut into nbatch consecutive batches of L samples, each with its own
  * (mean, m2), so that burn-in can be discarded AFTER the run and one chain gets a batch-means Monte-Carlo error, a model-free
  * effective sample size and split R-hat.  One launch of k_moments_accum's update per accumulation (DANGX_K_BATCH) behind the
@@ -713,6 +744,9 @@ int dangx_moments_batches_raw_dev(dangx_ctx *ctx, int reg, int batch, double *me
  *                                    the maps from ctxs[0] and name this section when a holder there lacks it; N and the
  *                                    rank R-hat need no range values and do not ask for it.
  *   family 7 ANGLE   (ang, -)        Cbar, Sbar, each [npix] f64
+ *   family 8 FIT     (item, -)       mean, m2, each [npix] f64 (only a context with fit items has it; their specs enter the
+ *                                    fingerprint's signal part only when there are any: a registration without them hashes and
+ *                                    saves as it always did)
  * _section_bytes: the payload's size.  _section_get / _put: host arrays, returning after the copy; the _dev forms take device
  * arrays and are asynchronous on the context's stream (the host rows of a template / monopole / hi_fit member: the call waits).
  * Transport is one copy per plane; no kernel is launched.  Every get and put checks `bytes` against _section_bytes.
@@ -722,7 +756,7 @@ int dangx_moments_batches_raw_dev(dangx_ctx *ctx, int reg, int batch, double *me
  * product uses the restored prev, the pair terms the restored means, the batch schedule the restored batch length and fill, the
  * histogram limit the restored count.
  * dangx_moments_begin_like makes ctx a HOLDER: it takes over the registrations of `like` (selection, pairs / lag-1 flag,
- * histograms, signals, angles, batches; the two contexts must agree in npix / pix0 / nmaps / ncomp / nbands and in the components
+ * histograms, signals, angles, fit items, batches; the two contexts must agree in npix / pix0 / nmaps / ncomp / nbands and in the components
  * concerned) and allocates NO accumulators; whatever ctx accumulated or held before is dropped.  A section's device memory
  * (its payload rounded up to 256 bytes; batches at the plane pitch of a live context) is allocated when it is first put.  A
  * holder with lag-1 also takes a PLANES payload of the first two parts (mean, m2) alone.  The read-outs over several chains
@@ -773,6 +807,8 @@ int dangx_chains_get_dev(dangx_ctx *const *ctxs, int nchains, int comp, int what
 int dangx_chains_get_template(dangx_ctx *const *ctxs, int nchains, int comp, int stat, int ddof, double *ta);
 int dangx_chains_get_signal(dangx_ctx *const *ctxs, int nchains, int sig, int stat, int ddof, double *out);
 int dangx_chains_get_signal_dev(dangx_ctx *const *ctxs, int nchains, int sig, int stat, int ddof, double *out_dev);
+int dangx_chains_get_fit(dangx_ctx *const *ctxs, int nchains, int item, int stat, int ddof, double *out);
+int dangx_chains_get_fit_dev(dangx_ctx *const *ctxs, int nchains, int item, int stat, int ddof, double *out_dev);
 int dangx_chains_get_angle(dangx_ctx *const *ctxs, int nchains, int ang, int stat, double *out);
 int dangx_chains_get_angle_dev(dangx_ctx *const *ctxs, int nchains, int ang, int stat, double *out_dev);
 int dangx_chains_get_pair(dangx_ctx *const *ctxs, int nchains, int pair, int stat, int ddof, double *out);

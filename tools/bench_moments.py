@@ -3,7 +3,7 @@
 iterations of the C3 model: blocks of iterations without and with accumulation after every iteration, alternating in one process;
 then the k_moments kernel time from the profile and its bandwidth in algorithmic bytes (5 x 8 B per selected element) against the
 6.29 TB/s measured copy ceiling of the MI355X.
-    python3 tools/bench_moments.py [nside=1024] [steps per block=10] [rounds=5] [--lag1] [--pairs default] [--hist [nbins=64] [--range-maps | --signals]] [--signals [--bandpass]] [--chains K [--samples N]] [--batches NB] [--sections] [--angles]
+    python3 tools/bench_moments.py [nside=1024] [steps per block=10] [rounds=5] [--lag1] [--pairs default] [--hist [nbins=64] [--range-maps | --signals]] [--signals [--bandpass]] [--chains K [--samples N]] [--batches NB] [--sections] [--angles] [--fit]
 --lag1 / --pairs default: after the above, `rounds` alternating rounds of `steps` accumulations each of (a) the plain accumulate,
 (b) with lag-1 tracking (k_moments_accum_lag: 10 x 8 B per selected element) and (c) with the default pairs (k_moments_pairs: 6 x 8 B
 per pair element, timed apart from the mean launch that follows it); per launch the algorithmic bytes, the achieved bytes/s and
@@ -47,7 +47,13 @@ per timing, wall time around a device synchronisation.  Nothing else of the abov
 {Q, U, P} signals of the same (component, band): `rounds` alternating rounds in one process of `steps` accumulations each with (s)
 the signals alone and (g) the angles alone registered, an empty selection, after two Gibbs iterations; per launch the time, the
 algorithmic bytes -- per component the Q and U amplitude and index planes read once, and per output two accumulator planes read and
-written -- and their bytes/s; then (g) / (s) over the rounds.  Nothing else of the above is run."""
+written -- and their bytes/s; then (g) / (s) over the rounds.  Nothing else of the above is run.
+--fit: the goodness-of-fit launch (k_moments_fit) on the default fit items (every plane's chi^2 map and every band's residual)
+against the plain accumulate: `rounds` alternating rounds in one process of `steps` accumulations each with (a) the default
+selection alone and (f) the fit items alone registered, after two Gibbs iterations; per launch the time, the algorithmic bytes --
+per plane data and rms of every band, every component's amplitude and index planes, the mask, and 32 B per item -- their bytes/s
+and (f)'s rate over (a)'s; then whole iterations with an accumulation after each, without and with the fit items.  Nothing else of
+the above is run."""
 import os
 import sys
 import time
@@ -148,6 +154,69 @@ if "--angles" in sys.argv:
     print("(s) median %.3f ms (spread %.3f .. %.3f); (g) median %.3f ms (spread %.3f .. %.3f); target: (g) <= (s) within the spread"
           % (float(np.median(s_all)), min(s_all), max(s_all), float(np.median(g_all)), min(g_all), max(g_all)))
     print("accumulators: 16 B x %d pixels x %d angles = %.2f GB" % (npx, len(angles), 16.0 * npx * len(angles) * 1e-9))
+    sys.exit(0)
+if "--fit" in sys.argv:
+    npx, nb = meta["npix"], meta["nbands"]
+    for it in (1, 2):
+        da.gibbs_iteration(dpar, ddata, it, want_counts=False)
+    fit = da.default_fit_specs(dpar, comps, bands)
+    none = np.zeros(len(comps), dtype=np.int32)
+    sel = da.default_moment_selection(dpar, comps)
+    a_planes = 5 * sum(bin(int(w)).count("1") for w in sel)
+    state = sum(1 + c.nindices for c in comps)          # every component's amplitude and index planes are read on every plane
+    fit_planes = sorted({k for _, _, k in fit})
+    f_bytes = sum(16 * nb + 8 * state + 8 + 32 * sum(1 for s in fit if s[2] == k) for k in fit_planes)
+
+    def per_launch(register, family):
+        register()
+        da.moments_accumulate(ddata)   # table upload
+        eng.profile(True)
+        for _ in range(steps):
+            da.moments_accumulate(ddata)
+        prof = eng.profile_get()
+        eng.profile(False)
+        assert set(prof) == {family}, prof
+        return prof[family]["total_ms"] / prof[family]["launches"]
+
+    def fit_only():
+        da.moments_begin(dpar, ddata, sel=none)
+        da.moments_fit(dpar, ddata, specs=fit)
+
+    print("C3 at Nside %d, %d pixels, %d bands: (a) k_moments_accum on the default selection, %d x 8 B per pixel; (f) k_moments_fit on the "
+          "default %d items (%d planes): %d B per pixel = data + rms %d, state %d, mask %d, items %d"
+          % (nside, npx, nb, a_planes, len(fit), len(fit_planes), f_bytes, 16 * nb * len(fit_planes), 8 * state * len(fit_planes),
+             8 * len(fit_planes), 32 * len(fit)))
+    a_all, f_all, ratio = [], [], []
+    for r in range(rounds):
+        a_ms = per_launch(lambda: da.moments_begin(dpar, ddata), "k_moments")
+        f_ms = per_launch(fit_only, "k_fit")
+        a_bw, f_bw = 8e-9 * a_planes * npx / a_ms, 1e-9 * f_bytes * npx / f_ms
+        a_all.append(a_ms); f_all.append(f_ms); ratio.append(f_bw / a_bw)
+        print("round %d: (a) %.3f ms, %.2f GB algorithmic -> %.2f TB/s; (f) %.3f ms, %.2f GB -> %.2f TB/s = %.3f of (a)"
+              % (r + 1, a_ms, 8e-9 * a_planes * npx, a_bw, f_ms, 1e-9 * f_bytes * npx, f_bw, f_bw / a_bw))
+    print("(a) median %.3f ms (spread %.3f .. %.3f); (f) median %.3f ms (spread %.3f .. %.3f); (f) / (a) per byte: median %.3f (spread %.3f .. %.3f)"
+          % (float(np.median(a_all)), min(a_all), max(a_all), float(np.median(f_all)), min(f_all), max(f_all), float(np.median(ratio)),
+             min(ratio), max(ratio)))
+    # whole iterations: the default selection accumulated after every iteration, without and with the fit items, alternating
+    it = 2
+    walls = {False: [], True: []}
+    for r in range(rounds):
+        for with_fit in (False, True):
+            da.moments_begin(dpar, ddata)
+            if with_fit:
+                da.moments_fit(dpar, ddata, specs=fit)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                it += 1
+                da.gibbs_iteration(dpar, ddata, it, want_counts=False)
+                da.moments_accumulate(ddata)
+            torch.cuda.synchronize()
+            walls[with_fit].append((time.perf_counter() - t0) / steps * 1e3)
+        print("round %d: iteration + accumulate %.2f ms without, %.2f ms with the fit items" % (r + 1, walls[False][-1], walls[True][-1]))
+    print("per iteration: median %.2f ms without, %.2f ms with (+%.2f ms)" % (float(np.median(walls[False])), float(np.median(walls[True])),
+                                                                           float(np.median(walls[True])) - float(np.median(walls[False]))))
+    print("accumulators: 16 B x %d pixels x %d items = %.2f GB" % (npx, len(fit), 16.0 * npx * len(fit) * 1e-9))
     sys.exit(0)
 if "--sections" in sys.argv:
     import ctypes
